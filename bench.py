@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Contract benchmark: whole-shard STARK proofs on MI355X through libzkhip's C ABI.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks are the launcher's; started
    plainly, bench.py spawns its N rank processes itself BEFORE anything in the parent touches the GPU)
 
@@ -61,6 +61,30 @@ def _spawn_ranks(n):
     raise SystemExit(rc)
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6            # --dump-outputs stays under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> numpy array as the timed path returned it.  Written as out_dir/<name>.npy in float32 when every value is an
+    integer below 2^24 (exact), else float64; beyond DUMP_LIMIT_BYTES in all, each array is cut to a fixed, seeded sample of its
+    elements (the same positions in every run), written beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        exact32 = (a.dtype.kind in "bu" and a.dtype.itemsize <= 2) or a.dtype == np.float32
+        conv[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    for name, a in conv.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, DUMP_LIMIT_BYTES * a.nbytes // total // (a.itemsize + 8))     # this array's share of the limit, values + float64 indices
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, size=keep, replace=False)).astype(np.int64)
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,7 +128,12 @@ def main():
     ap.add_argument("--no-batch64", action="store_true", help="skip the 64-transcript batch (BASELINE configs[2]) measured beside the headline")
     ap.add_argument("--cpu-log-n", type=int, default=20, help="rows of the bounded CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline (0: min(cores, 64))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0: the proof bytes) as "
+                         "DIR/<name>.npy in float32, so that two builds can be compared output for output (the inputs are seeded)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.logical_devices:
         if not args.one_process:
@@ -401,6 +430,9 @@ def main():
         if sorted(digests) != expect:
             raise SystemExit("shard coverage broken: %d digests for %d distinct shards" % (len(digests), len(expect)))
         del proofs
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"proof": last})
 
     # the library's own multi-GPU entry on the same shards (one process, device list [this GPU]): the path a ZkProver::prove binds
     # (INTEGRATION.md 2), measured beside the rank-per-GPU path whenever this rank is alone on the node

@@ -88,10 +88,8 @@ def test_config2_host_traces_all_visible_devices(ctx, oracle):
     _lib.load().zkhip_release_cached_contexts()
 
 
-@pytest.mark.skipif(_lib.device_count() < 2, reason="needs two GPUs in one process")
-def test_multi_device_device_traces_live_where_the_shard_is_dealt(oracle):
+def _device_traces_live_where_the_shard_is_dealt(O):
     from zktls_amd.device import Context
-    O = oracle
     log_n, width, n_shards = 14, 64, 6
     devs = [0, 1]
     ctxs = {d: Context(d) for d in devs}
@@ -106,6 +104,37 @@ def test_multi_device_device_traces_live_where_the_shard_is_dealt(oracle):
     for c in ctxs.values():
         c.close()
     _lib.load().zkhip_release_cached_contexts()
+
+
+# the body above in a fresh process on two LOGICAL devices of one GPU (the A/B build, ZKHIP_LOGICAL_DEVICES=2: every allocation remembers the
+# logical device of its context, so a trace away from where its shard is dealt is refused by ordinal, as two physical GPUs refuse it)
+_LOGICAL_CHILD = """
+import os, sys
+sys.path[:0] = [os.path.join(sys.argv[1], "tools"), os.path.join(sys.argv[1], "tests"), sys.argv[1]]
+import _ab
+import oracle_lib as O
+from zktls_amd import _lib
+assert _lib.device_count() == 2, "the A/B library does not report two logical devices"
+O.build()
+O.set_threads(min(8, os.cpu_count() or 1))
+import test_gpu_configs as T
+T._device_traces_live_where_the_shard_is_dealt(O)
+print("two devices: six shards dealt where their traces live, bytes equal to the oracle's")
+"""
+
+
+def test_multi_device_device_traces_live_where_the_shard_is_dealt(oracle):
+    """device traces generated where zkhip_shard_device deals their shards, proven over the device list [0, 1], bytes against the oracle:
+    on two GPUs in this process; on a box with one, in a child process over two logical devices of it (the parent never loads the A/B build)"""
+    if _lib.device_count() >= 2:
+        _device_traces_live_where_the_shard_is_dealt(oracle)
+        return
+    import subprocess
+    import sys
+    env = dict(os.environ, ZKHIP_LOGICAL_DEVICES="2")
+    p = subprocess.run([sys.executable, "-c", _LOGICAL_CHILD, ROOT], env=env, cwd=ROOT, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    assert b"two devices: six shards dealt where their traces live" in p.stdout
 
 
 class Plan(C.Structure):

@@ -97,10 +97,11 @@ def test_dry_run_of_the_eight_gpu_configuration_on_logical_devices():
     assert r["verified"] is True and r["value"] > 0
 
 
-def test_dry_run_of_eight_ranks_sharing_the_one_gpu():
-    """the rank-per-GPU path at world size 8 (gloo collectives: RCCL refuses several ranks on one device): dealing, seed broadcast, max-over-ranks
-    timing and the digest gather with eight processes; blocking waits by default for N >= 4"""
-    r = run_bench("--gpus", "8", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64", timeout=1500)
-    assert r["n_gpus"] == 8 and r["rccl_world_size"] == 8 and r["share_gpu_test_mode"] is True and r["collective_backend"] == "gloo"
-    assert r["shards_proven"] == 16 and r["distinct_shards_proven"] == 16 and r["shard_digests_gathered"] == 16
+def test_dry_run_of_four_ranks_sharing_the_one_gpu():
+    """the rank-per-GPU path at world size 4 (gloo collectives: RCCL refuses several ranks on one device): dealing, seed broadcast, max-over-ranks
+    timing and the digest gather with four processes; blocking waits by default for N >= 4.  Four ranks and this process keep the number of
+    processes with the GPU open at five; world size 8 runs on the CPU (tests/test_shards_gloo_cpu.py::test_eight_rank_shard_parallel)."""
+    r = run_bench("--gpus", "4", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64", timeout=1500)
+    assert r["n_gpus"] == 4 and r["rccl_world_size"] == 4 and r["share_gpu_test_mode"] is True and r["collective_backend"] == "gloo"
+    assert r["shards_proven"] == 8 and r["distinct_shards_proven"] == 8 and r["shard_digests_gathered"] == 8
     assert r["host_wait"] == "block" and r["verified"] is True and r["value"] > 0

@@ -103,8 +103,13 @@ def test_pointer_arguments_stay_pointers():
 
 def test_cli_patch_applies_to_the_reference_tree_when_present(tmp_path):
     """integration/rust/cli-hip-backend.patch (types.rs:12-18, prove.rs:66-112, Cargo.toml:30-41) must apply
-    cleanly to the reference's four files; the reference tree exists only in the build container, so elsewhere the check is
-    that the patch names those four files and adds the Hip variants."""
+    cleanly to the reference's four files.  The reference tree is not part of this repository: tests/golden/reference/
+    cli_patch_preimage.json records, per file, its line count and the SHA-256 of the lines every hunk replaces, taken from the
+    reference at the revision the patch targets.  Each hunk's pre-image must hash to the recorded value at its stated position
+    (so it applies with no offset and no fuzz), and `patch -F0 --dry-run` must accept the patch on files of the recorded length
+    with those pre-images in place."""
+    import hashlib
+    import json
     import shutil
     import subprocess
     patch = os.path.join(ROOT, "integration", "rust", "cli-hip-backend.patch")
@@ -112,12 +117,37 @@ def test_cli_patch_applies_to_the_reference_tree_when_present(tmp_path):
     files = re.findall(r"^\+\+\+ b/(\S+)", text, flags=re.M)
     assert files == ["Cargo.toml", "bins/zktls/Cargo.toml", "bins/zktls/src/commands/types.rs", "bins/zktls/src/commands/prove.rs"]
     assert "Prover::Hip | Prover::HipR0" in text and 'hip-backend = ["zktls-guest-prover-hip"]' in text
-    ref = "/root/reference"
-    if not os.path.isdir(ref) or shutil.which("patch") is None:
-        return
+    pre = json.load(open(os.path.join(ROOT, "tests", "golden", "reference", "cli_patch_preimage.json")))
+    assert sorted(pre) == sorted(files)
+    # the pre-image of every hunk (context and removed lines), by file
+    hunks, cur, h = {f: [] for f in files}, None, None
+    for ln in text.split("\n"):
+        m = re.match(r"^\+\+\+ b/(\S+)", ln)
+        if m:
+            cur, h = m.group(1), None
+            continue
+        m = re.match(r"^@@ -(\d+)(?:,(\d+))? \+\d+(?:,\d+)? @@", ln)
+        if m and cur is not None:
+            h = {"old_start": int(m.group(1)), "old_lines": int(m.group(2) or 1), "pre": []}
+            hunks[cur].append(h)
+            continue
+        if h is not None and ln[:1] in (" ", "-") and not ln.startswith("--- "):
+            h["pre"].append(ln[1:])
     for f in files:
+        rec = pre[f]
+        assert [(x["old_start"], x["old_lines"]) for x in hunks[f]] == [(x["old_start"], x["old_lines"]) for x in rec["hunks"]], f
+        body = ["# line %d (not touched by the patch)" % (i + 1) for i in range(rec["lines"])]
+        for x, r in zip(hunks[f], rec["hunks"]):
+            assert len(x["pre"]) == x["old_lines"], "%s: hunk at %d: header says %d old lines, body has %d" % (f, x["old_start"], x["old_lines"], len(x["pre"]))
+            assert x["old_start"] - 1 + x["old_lines"] <= rec["lines"], "%s: hunk at %d runs past the file's end" % (f, x["old_start"])
+            assert hashlib.sha256(("\n".join(x["pre"]) + "\n").encode()).hexdigest() == r["sha256"], \
+                "%s: hunk at %d no longer matches the reference's lines %d-%d" % (f, x["old_start"], x["old_start"], x["old_start"] + x["old_lines"] - 1)
+            body[x["old_start"] - 1:x["old_start"] - 1 + x["old_lines"]] = x["pre"]
         dst = tmp_path / f
         dst.parent.mkdir(parents=True, exist_ok=True)
-        shutil.copy(os.path.join(ref, f), dst)
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", patch], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        dst.write_text("\n".join(body) + "\n")
+    if shutil.which("patch") is None:
+        return
+    r = subprocess.run(["patch", "-p1", "-F0", "--dry-run", "-i", patch], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0, r.stdout.decode()
+    assert b"offset" not in r.stdout and b"fuzz" not in r.stdout, r.stdout.decode()

@@ -55,6 +55,28 @@ def test_two_rank_shard_parallel(total):
     assert m0 == m1 and sorted(m0) == list(range(total))
 
 
+def test_eight_rank_shard_parallel():
+    """the same at world size 8 (bench.py --gpus 8): 16 shards, two per rank, every one proven exactly once; the dealing, seed broadcast,
+    max-over-ranks timing and digest gather over eight gloo processes"""
+    world, total = 8, 16
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, total, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=300) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert [r[0] for r in res] == list(range(world))
+    assert all(r[1] == [11 + i for i in range(8)] for r in res)
+    assert sorted(sum((r[2] for r in res), [])) == list(range(total))
+    assert all(r[2] == [r[0], r[0] + world] for r in res)
+    assert all(r[3] == float(world) for r in res)
+    assert all(r[4] == res[0][4] for r in res) and sorted(res[0][4]) == list(range(total))
+
+
 def _worker_real(rank, world, port, total, q):
     """the payload is a real proof: oracle-proven tiny shards, verified by libzkhip's host verifier"""
     import sys

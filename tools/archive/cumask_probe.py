@@ -1,7 +1,7 @@
 """exploration: CU-masked streams (hipExtStreamCreateWithCUMask).  (1) how does the leaf-hash time scale with the mask (which
 bits are which CUs)?  (2) with the chip split between a 'hash' stream and a 'memory' stream, do the LDE and the hashing overlap?"""
 import ctypes as C, sys, time, threading
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context
 hip = C.CDLL("libamdhip64.so")
 hip.hipSetDevice(0)

@@ -1,5 +1,5 @@
 import ctypes as C, os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context
 hip = C.CDLL("libamdhip64.so")
 ctx = Context(0)

@@ -1,6 +1,6 @@
 """exploration: leaf-hash kernel duration inside a proof vs alone (run under rocprofv3 --kernel-trace)"""
 import sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context
 from zktls_amd._lib import Params
 ctx = Context(0)

@@ -1,6 +1,6 @@
 """exploration: does the relative placement of source and destination matter for the strided NTT pass?"""
 import ctypes as C, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context, DeviceBuffer
 hip = C.CDLL("libamdhip64.so")
 ctx = Context(0)

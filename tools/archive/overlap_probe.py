@@ -1,6 +1,6 @@
 """exploration: do a VALU-bound kernel (Poseidon2 leaves) and a memory-bound one (coset LDE) overlap when issued from two streams?"""
 import sys, time, threading
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context
 w, log_n = 256, 20
 c1, c2 = Context(0), Context(0)

@@ -3,7 +3,7 @@
 The "reserved room" variant quoted in DESIGN.md section 7 additionally launched the leaf kernel with 1024 threads and 81 KiB of
 dynamic LDS per workgroup through a temporary launch knob that was not kept."""
 import ctypes as C, sys, time, threading
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from zktls_amd.device import Context
 hip = C.CDLL("libamdhip64.so")
 hip.hipSetDevice(0)

@@ -1,6 +1,6 @@
 """exploration: zkhip_prove_shards (the C-ABI batch entry) on 8 shards of 2^20 x 256, wall time per shard for several in_flight values"""
 import sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context, prove_shards
 from zktls_amd._lib import Params
 ctx = Context(0)

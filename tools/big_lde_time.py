@@ -1,7 +1,7 @@
 """The trace LDE above 2^20 rows: 2^21 x 256 and 2^22 x 128, blowup 2, HIP events around back-to-back LDEs.
 Run under `rocprofv3 --kernel-trace --stats` for the per-kernel averages (every launch of the run is a full-width one)."""
 import ctypes as C, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context
 hip = C.CDLL("libamdhip64.so")
 ctx = Context(0)

@@ -1,6 +1,6 @@
 """exploration: a few back-to-back leaf hashings of a 2^21 x 256 matrix (run under rocprofv3 --pmc ... for the counters)"""
 import sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context
 ctx = Context(0)
 w, log_n = 256, 21

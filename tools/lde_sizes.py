@@ -1,6 +1,6 @@
 """exploration: coset LDE (blowup 2) time per size, 256 columns: relative efficiency of the tile heights"""
 import ctypes as C, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context
 hip = C.CDLL("libamdhip64.so")
 ctx = Context(0)

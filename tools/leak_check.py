@@ -1,6 +1,6 @@
 """exploration: device memory must come back when a Context (and the buffers allocated through it) is closed"""
 import sys, ctypes as C
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context
 from zktls_amd._lib import Params
 hip = C.CDLL("libamdhip64.so")

@@ -1,6 +1,6 @@
 """exploration: device memory in use across repeated zkhip_prove_shards calls (cached internal contexts) and after releasing the cache"""
 import ctypes as C, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context, prove_shards
 from zktls_amd._lib import Params, load
 hip = C.CDLL("libamdhip64.so")

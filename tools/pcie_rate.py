@@ -1,6 +1,6 @@
 """exploration: PCIe-inclusive shard rate through zkhip_prove_shard_host (pageable and pinned host memory)"""
 import sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 import numpy as np, torch
 from zktls_amd.device import Context
 from zktls_amd._lib import Params

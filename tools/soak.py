@@ -1,6 +1,6 @@
 """exploration: many proofs on concurrent contexts; every proof must verify and repeat byte for byte"""
 import sys, threading, hashlib
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from zktls_amd.device import Context, verify_shard, verify_chips
 from zktls_amd._lib import Params
 errors = []
