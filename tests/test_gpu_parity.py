@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+from field_edges import EDGE_WORDS, assert_canonical, edge_canonical
+
 pytestmark = pytest.mark.gpu
 
 P = 2013265921
@@ -195,19 +197,38 @@ def test_poseidon2_extreme_states(ctx, oracle):
     buf = ctx.from_numpy(st)
     ctx.poseidon2_permute(buf)
     got = buf.download().reshape(-1, 16)
-    assert (got < P).all()
+    assert_canonical(buf)
     for i in range(st.shape[0]):
         assert (got[i] == oracle.poseidon2(st[i])).all(), i
+    # the same patterns as device WORDS: from_numpy above stores x R mod P, so apart from 0 none of those values is an edge word
+    # on the device; from_raw puts exactly these words there
+    words = np.stack([np.full(16, v, dtype=np.uint32) for v in EDGE_WORDS] +
+                     [np.where(np.arange(16) % 2 == 0, a, b).astype(np.uint32) for a in EDGE_WORDS for b in EDGE_WORDS] +
+                     [rng.choice(EDGE_WORDS, 16).astype(np.uint32) for _ in range(512)])
+    buf = ctx.from_raw(words)
+    ctx.poseidon2_permute(buf)
+    assert_canonical(buf)
+    got = buf.download().reshape(-1, 16)
+    st = edge_canonical(words)
+    for i in range(st.shape[0]):
+        assert (got[i] == oracle.poseidon2(st[i])).all(), words[i].tolist()
 
 
-@pytest.mark.parametrize("fill", [0, 1, P - 1, (P + 1) // 2])
+# canonical fills (1 and P - 1 are the Montgomery words R1 and P - R1 on the device), then fills whose DEVICE words are the other
+# edge words (field_edges.edge_canonical: 1 and P - 1 as words, the centered() boundary, P/2, 2^30)
+@pytest.mark.parametrize("fill", [0, 1, P - 1, (P + 1) // 2] +
+                         [int(edge_canonical([w])[0]) for w in (1, P - 1, (P + 1) // 2, P // 2, 1 << 30)])
 def test_hash_rows_and_p24_commit_of_constant_matrices(ctx, oracle, fill):
     m = np.full((256, 40), fill, dtype=np.uint32)
-    got = ctx.hash_rows([(ctx.from_numpy(m), 40)], 256).download().reshape(-1, 8)
+    d = ctx.hash_rows([(ctx.from_numpy(m), 40)], 256)
+    got = d.download().reshape(-1, 8)
     assert (got == oracle.hash_rows([m])).all()
+    assert_canonical(d)
     cm = np.ascontiguousarray(m[:, :24].T)                      # column-major [cols][rows]
-    got24 = ctx.merkle_commit_p24_colmajor(ctx.from_numpy(cm), 24, 8).download().reshape(-1, 8)
+    d24 = ctx.merkle_commit_p24_colmajor(ctx.from_numpy(cm), 24, 8)
+    got24 = d24.download().reshape(-1, 8)
     assert (got24 == oracle.merkle_tree_p24_colmajor(cm)).all()
+    assert_canonical(d24)
 
 
 @pytest.mark.parametrize("height,widths", [(64, [8]), (300, [5]), (1024, [16]), (1024, [20]), (257, [1]), (512, [3, 9]), (128, [8, 8, 4, 1])])
