@@ -41,6 +41,28 @@ int zkhip_prove_merkle_paths(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t ro
                              const uint32_t root[8], const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
 int zkhip_verify_merkle_paths(const uint8_t* proof, size_t len, const uint32_t root[8], size_t n_paths, const zkhip_params* prm, int* reason);
 
+/* The same chip for RISC Zero-shape commitments: the width-24 Poseidon2 permutation (rate 16, overwrite-mode sponge from the zero state,
+ * digest = state[0..8]; parent = permute(l || r || 0^8)[0..8]) -- the hash of zkhip_prove_segment, of every prover given hash_width = 24 and
+ * of zkhip_merkle_commit_p24_colmajor.  One row = one width-24 permutation of the tables in effect (ZKHIP_P24CHIP_WIDTH = 540 columns,
+ * degree <= 3); the flag columns are the width-16 chip's, plus three group flags for a partial last sponge block: opened rows are a multiple
+ * of 4 wide, so a leaf's last block absorbs 4, 8, 12 or 16 values and the rate words it does not absorb carry over (zero on a leaf's first
+ * row, the previous output on a later one).  Public values: root[8], count.  zkhip_p24chip_air writes the constraint program (it follows
+ * the width-24 tables: reload it after zkhip_load_poseidon2_params with a width-24 file).  zkhip_p24chip_gen_merkle_trace fills a device
+ * trace of 2^log_n rows (ld >= 540 and a multiple of 4, 16-byte aligned): with row_width = 0 leaves[p][8] is a leaf digest; with row_width
+ * a positive multiple of 4 (up to 1024) leaves[p][row_width] is the OPENED ROW and the path starts with ceil(row_width / 16) sponge rows;
+ * siblings, indices and roots as above.  zkhip_prove_merkle_paths_p24 / zkhip_verify_merkle_paths_p24: as the width-16 entries (paths that
+ * do not end in root are refused before anything is proven; the verifier needs no GPU and reads the trace height from the proof).  Any
+ * proof shape is accepted, the SP1 default and the RISC Zero shape (log_blowup 2, log_fold 4, hash_width 24) among them.  Not yet: lookup
+ * or bus variants of this chip, and its use inside the recursion machines. */
+#define ZKHIP_P24CHIP_WIDTH 540
+size_t zkhip_p24chip_air(uint32_t* program, size_t cap_words);
+int zkhip_p24chip_gen_merkle_trace(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t row_width, const uint32_t* siblings, const uint32_t* indices, size_t n_paths,
+                                   int depth, int log_n, uint32_t* d_trace, size_t ld, uint32_t* roots);
+size_t zkhip_merkle_paths_p24_proof_size(size_t n_paths, int depth, uint32_t row_width, const zkhip_params* prm);
+int zkhip_prove_merkle_paths_p24(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t row_width, const uint32_t* siblings, const uint32_t* indices, size_t n_paths,
+                                 int depth, const uint32_t root[8], const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_merkle_paths_p24(const uint8_t* proof, size_t len, const uint32_t root[8], size_t n_paths, const zkhip_params* prm, int* reason);
+
 /* ---- a first step of recursion: the FRI part of a shard proof checked INSIDE a proof (second half).  The reference's
  * hot call is client.prove(.., SP1ProofMode::Groth16) (crates/guest-prover-sp1/src/sp1.rs:116): core -> compress -> shrink -> wrap, and
  * compress verifies shard proofs in-circuit (sp1-recursion, reference Cargo.lock:6172 ff.; RISC Zero lift -> join, prover.rs:90).

@@ -47,6 +47,7 @@ EXPORTS = [
     "zkhip_fri_indices_program", "zkhip_fri_indices_key", "zkhip_fri_indices_proof_size", "zkhip_prove_fri_indices", "zkhip_verify_fri_indices",
     "zkhip_prove_fri_indices_batch", "zkhip_fri_view_all",
     "zkhip_p2chip_air", "zkhip_p2chip_gen_merkle_trace", "zkhip_merkle_paths_proof_size", "zkhip_prove_merkle_paths", "zkhip_verify_merkle_paths",
+    "zkhip_p24chip_air", "zkhip_p24chip_gen_merkle_trace", "zkhip_merkle_paths_p24_proof_size", "zkhip_prove_merkle_paths_p24", "zkhip_verify_merkle_paths_p24",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -317,6 +318,13 @@ def load():
     L.zkhip_merkle_paths_proof_size.argtypes = [C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Params)]
     L.zkhip_prove_merkle_paths.argtypes = [C.c_void_p, u32p, C.c_uint32, u32p, u32p, C.c_size_t, C.c_int, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
     L.zkhip_verify_merkle_paths.argtypes = [u8p, C.c_size_t, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int)]
+    L.zkhip_p24chip_air.restype = C.c_size_t
+    L.zkhip_p24chip_air.argtypes = [u32p, C.c_size_t]
+    L.zkhip_p24chip_gen_merkle_trace.argtypes = [C.c_void_p, u32p, C.c_uint32, u32p, u32p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, u32p]
+    L.zkhip_merkle_paths_p24_proof_size.restype = C.c_size_t
+    L.zkhip_merkle_paths_p24_proof_size.argtypes = [C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Params)]
+    L.zkhip_prove_merkle_paths_p24.argtypes = [C.c_void_p, u32p, C.c_uint32, u32p, u32p, C.c_size_t, C.c_int, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_merkle_paths_p24.argtypes = [u8p, C.c_size_t, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int)]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -13,6 +13,7 @@
 #include "poseidon2.cuh"
 #include "kernels.h"
 #include "batch.h"
+#include "p24chip.h"
 #include "p2chip.h"
 
 namespace zk {
@@ -1224,6 +1225,133 @@ hipError_t launch_p2chip_layer_paths(const p2chip::LayerPathsArgs& a, hipStream_
 hipError_t launch_p2chip_merkle(const p2chip::MerkleTraceArgs& a, hipStream_t s) {
     const uint64_t lanes = a.n_paths + (a.rows - a.n_paths * ((uint64_t)a.row_width / 8 + a.depth));
     ZK_LAUNCH(p2chip_merkle_kernel, p2chip_merkle_kernel_batch, p2chip_merkle_kernel_bargs, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ trace of the width-24 Poseidon2 chip (p24chip.h)
+// One row = one width-24 permutation with every intermediate the chip's constraints name (poseidon2_chip.cpp), on the width-24 constants of
+// the tables in effect (P24K: the constants behind zkhip_merkle_commit_p24_colmajor).  The columns are laid out in the order they are
+// produced, each section on a 16-byte boundary: a lane writes its row front to back with 16-byte stores (135 per row).
+__device__ __forceinline__ void p24chip_store4(uint32_t* t, uint32_t col, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    *reinterpret_cast<uint4*>(t + col) = make_uint4(a, b, c, d);
+}
+__device__ __forceinline__ void p24chip_store24(uint32_t* t, uint32_t col, const uint32_t v[24]) {
+#pragma unroll
+    for (int i = 0; i < 24; i += 4) p24chip_store4(t, col + i, v[i], v[i + 1], v[i + 2], v[i + 3]);
+}
+// groups: rate-word groups 4..8, 8..12, 12..16 absorbed by a sponge row (0..3; 0 on every other row)
+__device__ void p24chip_fill_row(uint32_t* t, const uint32_t in[24], uint32_t bit, uint32_t ch, uint32_t end, uint32_t cnt, uint32_t spg, uint32_t ss,
+                                 uint32_t groups, uint32_t out[24]) {
+    using namespace p24chip;
+    uint32_t s[24];
+#pragma unroll
+    for (int i = 0; i < 24; i++) s[i] = in[i];
+    p24chip_store24(t, IN, s);
+    p24_external_linear_dev(s);
+    p24chip_store24(t, S0, s);
+    auto external_round = [&](uint32_t r) {
+        uint32_t x3[24];
+#pragma unroll
+        for (int i = 0; i < 24; i++) {
+            const uint32_t y = fadd(s[i], P24K.ext_rc[r][i]);
+            x3[i] = fmul(fmul(y, y), y);
+            s[i] = fmul(fmul(x3[i], x3[i]), y);
+        }
+        p24chip_store24(t, x3e(r), x3);
+        p24_external_linear_dev(s);
+        p24chip_store24(t, oute(r), s);
+    };
+#pragma unroll 1
+    for (uint32_t r = 0; r < 4; r++) external_round(r);
+    // internal rounds: three columns each (63, then the unused column 303), flushed four at a time
+    uint32_t w[4];
+#pragma unroll
+    for (int r = 0; r < 21; r++) {
+        const uint32_t y = fadd(s[0], P24K.int_rc[r]);
+        const uint32_t x3 = fmul(fmul(y, y), y);
+        w[(3 * r) & 3] = s[0];
+        if (((3 * r) & 3) == 3) p24chip_store4(t, s0p(0) + 3 * r - 3, w[0], w[1], w[2], w[3]);
+        w[(3 * r + 1) & 3] = x3;
+        if (((3 * r + 1) & 3) == 3) p24chip_store4(t, s0p(0) + 3 * r + 1 - 3, w[0], w[1], w[2], w[3]);
+        s[0] = fmul(fmul(x3, x3), y);
+        w[(3 * r + 2) & 3] = s[0];
+        if (((3 * r + 2) & 3) == 3) p24chip_store4(t, s0p(0) + 3 * r + 2 - 3, w[0], w[1], w[2], w[3]);
+        uint32_t sum = 0u;
+#pragma unroll
+        for (int i = 0; i < 24; i++) sum = fadd(sum, s[i]);
+#pragma unroll
+        for (int i = 0; i < 24; i++) s[i] = fadd(fmul(s[i], P24K.diag[i]), sum);
+    }
+    p24chip_store4(t, SPARE - 3, w[0], w[1], w[2], 0u);
+    p24chip_store24(t, SP, s);
+#pragma unroll 1
+    for (uint32_t r = 4; r < 8; r++) external_round(r);
+#pragma unroll
+    for (int j = 0; j < 8; j += 4)
+        p24chip_store4(t, D + j, bit ? in[8 + j] : in[j], bit ? in[9 + j] : in[1 + j], bit ? in[10 + j] : in[2 + j], bit ? in[11 + j] : in[3 + j]);
+    const uint32_t one = MONTY_R1;
+    p24chip_store4(t, BIT, bit ? one : 0u, ch ? one : 0u, end ? one : 0u, to_monty(cnt));
+    p24chip_store4(t, SPG, spg ? one : 0u, ss ? one : 0u, groups >= 1 ? one : 0u, groups >= 2 ? one : 0u);
+    p24chip_store4(t, G(3), groups >= 3 ? one : 0u, spg && groups < 1 ? one : 0u, spg && groups < 2 ? one : 0u, spg && groups < 3 ? one : 0u);
+#pragma unroll
+    for (int j = 0; j < 24; j++) out[j] = s[j];
+}
+static_assert(p24chip::BIT % 4 == 0 && p24chip::SPG == p24chip::BIT + 4 && p24chip::G(3) == p24chip::SPG + 4 && p24chip::C(1) == p24chip::G(3) + 1,
+              "p24chip_fill_row writes the flag columns four at a time");
+static_assert(p24chip::s0p(0) % 4 == 0 && p24chip::SPARE % 4 == 3 && p24chip::SP % 4 == 0 && p24chip::D % 4 == 0, "p24chip_fill_row: 16-byte sections");
+// one lane per path (its rows are a serial chain): the sponge rows over the opened row (16 values a row, the last block 4, 8, 12 or 16), then
+// one compression row per level; the lanes behind the paths fill the padding rows (permutations of the zero state, no flags) side by side
+__device__ __forceinline__ void p24chip_merkle_kernel_body(const p24chip::MerkleTraceArgs& a) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t sponge_rows = (a.row_width + 15) / 16;
+    const uint64_t per_path = (uint64_t)sponge_rows + a.depth, path_rows = a.n_paths * per_path;
+    uint32_t out[24], in[24];
+    if (p < a.n_paths) {
+        uint32_t* t = a.trace + p * per_path * a.ld;
+#pragma unroll
+        for (int j = 0; j < 24; j++) out[j] = 0u;
+        if (sponge_rows) {                                       // the leaf: overwrite-mode sponge from the zero state
+            const uint32_t* vals = a.leaves + p * a.row_width;
+            for (uint32_t k = 0; k < sponge_rows; k++, t += a.ld) {
+                const uint32_t n = a.row_width - 16 * k < 16 ? a.row_width - 16 * k : 16u;
+#pragma unroll
+                for (int j = 0; j < 24; j++) in[j] = (uint32_t)j < n ? to_monty(vals[16 * k + j]) : out[j];
+                p24chip_fill_row(t, in, 0u, 0u, 0u, (uint32_t)p, k ? 1u : 0u, k ? 0u : 1u, n / 4 - 1, out);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++) out[j] = to_monty(a.leaves[8 * p + j]);
+        }
+        const uint32_t index = a.indices[p];
+        for (uint32_t lvl = 0; lvl < a.depth; lvl++, t += a.ld) {
+            const uint32_t bit = (index >> lvl) & 1u;
+            const uint32_t* sib = a.siblings + 8 * (p * a.depth + lvl);
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t sv = to_monty(sib[j]);
+                in[j] = bit ? sv : out[j];
+                in[8 + j] = bit ? out[j] : sv;
+                in[16 + j] = 0u;
+            }
+            const uint32_t end = lvl + 1 == a.depth ? 1u : 0u;
+            p24chip_fill_row(t, in, bit, (lvl || sponge_rows) ? 1u : 0u, end, (uint32_t)p + end, 0u, 0u, 0u, out);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) a.roots[8 * p + j] = from_monty(out[j]);
+        return;
+    }
+    const uint64_t row = path_rows + (p - a.n_paths);
+    if (row >= a.rows) return;
+#pragma unroll
+    for (int j = 0; j < 24; j++) in[j] = 0u;
+    p24chip_fill_row(a.trace + row * a.ld, in, 0u, 0u, 0u, (uint32_t)a.n_paths, 0u, 0u, 0u, out);
+}
+__global__ void __launch_bounds__(64) p24chip_merkle_kernel(p24chip::MerkleTraceArgs a) { p24chip_merkle_kernel_body(a); }
+struct p24chip_merkle_kernel_bargs { p24chip::MerkleTraceArgs a; static p24chip_merkle_kernel_bargs make(p24chip::MerkleTraceArgs a) { return p24chip_merkle_kernel_bargs{a}; } };
+__global__ void __launch_bounds__(64) p24chip_merkle_kernel_batch(const p24chip_merkle_kernel_bargs* __restrict__ zk_arr) { const p24chip_merkle_kernel_bargs& zk_b = zk_arr[blockIdx.z]; p24chip_merkle_kernel_body(zk_b.a); }
+hipError_t launch_p24chip_merkle(const p24chip::MerkleTraceArgs& a, hipStream_t s) {
+    const uint64_t lanes = a.n_paths + (a.rows - a.n_paths * (((uint64_t)a.row_width + 15) / 16 + a.depth));
+    ZK_LAUNCH(p24chip_merkle_kernel, p24chip_merkle_kernel_batch, p24chip_merkle_kernel_bargs, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,0 +1,42 @@
+// p24chip.h -- column layout of the width-24 Poseidon2 permutation chip (poseidon2_chip.cpp, its width-24 part: the constraint program and
+// the C entries; hash.hip: the on-device trace generator).  One row = one width-24 permutation (RISC Zero's shape: 8 full + 21 partial
+// rounds); the columns are laid out in the order the permutation produces them, and every section starts on a 16-byte boundary, so that a
+// lane writes its row with 16-byte stores of consecutive columns.
+#pragma once
+#include <cstdint>
+
+namespace zk {
+namespace p24chip {
+
+constexpr uint32_t IN = 0, S0 = 24, SPARE = 303, SP = 304, D = 520, BIT = 528, CH = 529, END = 530, CNT = 531, SPG = 532, SS = 533,
+                   WIDTH = 540, N_PUBLIC = 9;
+// external round r: cubes of the round's input + constant, then the state after the round; rounds 0..3 sit before the internal rounds,
+// rounds 4..7 after SP
+constexpr uint32_t x3e(uint32_t r) { return r < 4 ? 48 + 48 * r : 328 + 48 * (r - 4); }
+constexpr uint32_t oute(uint32_t r) { return x3e(r) + 24; }
+constexpr uint32_t s0p(uint32_t r) { return 240 + 3 * r; }      // internal round r: element 0 before the S-box,
+constexpr uint32_t x3p(uint32_t r) { return 241 + 3 * r; }      // its cube,
+constexpr uint32_t sbp(uint32_t r) { return 242 + 3 * r; }      // its seventh power (column 303 after the 21st round is unused)
+constexpr uint32_t ext_input(uint32_t r) { return r == 0 ? S0 : (r == 4 ? SP : oute(r - 1)); }
+// partial blocks: G(k), k = 1..3, = rate words 4k .. 4k + 4 are absorbed (words 0..4 always are); C(k) = SPG (1 - G(k)) = those words
+// carry over from the previous row's output
+constexpr uint32_t G(uint32_t k) { return 533 + k; }
+constexpr uint32_t C(uint32_t k) { return 536 + k; }
+static_assert(C(3) + 1 == WIDTH && WIDTH % 4 == 0, "p24chip layout");
+static_assert(oute(7) + 24 == D && sbp(20) + 1 == SPARE, "p24chip layout");
+
+// path p = rows [p (ceil(row_width / 16) + depth), ...): the sponge rows over its opened row (none when row_width = 0: the leaf digest is
+// given), then depth compression rows; leaves / siblings / indices are canonical words already on the device
+struct MerkleTraceArgs {
+    const uint32_t* leaves;      // [n_paths][8] digests, or [n_paths][row_width] opened rows
+    uint32_t row_width;          // 0, or a multiple of 4
+    const uint32_t* siblings;    // [n_paths][depth][8]
+    const uint32_t* indices;     // [n_paths]: bit l = the node is a right child at level l
+    uint64_t n_paths, rows;
+    uint32_t depth;
+    uint32_t* trace; uint64_t ld;   // [rows][ld], Montgomery; 16-byte aligned, ld % 4 == 0
+    uint32_t* roots;             // [n_paths][8], canonical
+};
+
+}  // namespace p24chip
+}  // namespace zk

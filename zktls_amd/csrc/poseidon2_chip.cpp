@@ -27,6 +27,7 @@
 
 #include "air.h"
 #include "context.h"
+#include "p24chip.h"
 #include "p2chip.h"
 
 namespace zk {
@@ -69,6 +70,62 @@ Terms linear_def(uint32_t col, const Form& f) {
     return t;
 }
 
+// the constraints that make a row ONE permutation out = poseidon2(in), at width T with RP internal rounds: ME the external matrix, rc_e /
+// rc_i / diag the round constants and the internal diagonal (canonical); L names the columns (p2chip's or p24chip's layout)
+template <uint32_t T, uint32_t RP, class L>
+void permutation_rounds(Builder& b, const uint32_t (&ME)[T][T], const uint32_t (&rc_e)[8][T], const uint32_t (&rc_i)[RP], const uint32_t (&diag)[T]) {
+    for (uint32_t i = 0; i < T; i++) {
+        Form f;
+        for (uint32_t j = 0; j < T; j++) f[L::IN + j] = ME[i][j];
+        b.add(ALL, linear_def(L::S0 + i, f));
+    }
+    auto external_round = [&](uint32_t r) {
+        const uint32_t c0 = L::ext_input(r);
+        for (uint32_t i = 0; i < T; i++) b.add(ALL, cube_def(L::x3e(r) + i, c0 + i, rc_e[r][i]));
+        for (uint32_t i = 0; i < T; i++) {
+            Terms t{{1u, {var(L::oute(r) + i)}}};
+            for (uint32_t j = 0; j < T; j++) {
+                const uint32_t x3 = var(L::x3e(r) + j), c = var(c0 + j);
+                t.push_back(Term{neg(ME[i][j]), {x3, x3, c}});
+                t.push_back(Term{neg(mulm(ME[i][j], rc_e[r][j])), {x3, x3}});
+            }
+            b.add(ALL, t);
+        }
+    };
+    for (uint32_t r = 0; r < 4; r++) external_round(r);
+    Form lin[T];
+    for (uint32_t i = 0; i < T; i++) lin[i][L::oute(3) + i] = 1u;
+    for (uint32_t r = 0; r < RP; r++) {
+        const uint32_t k = rc_i[r];
+        b.add(ALL, linear_def(L::s0p(r), lin[0]));
+        b.add(ALL, cube_def(L::x3p(r), L::s0p(r), k));
+        b.add(ALL, Terms{{1u, {var(L::sbp(r))}}, {P - 1, {var(L::x3p(r)), var(L::x3p(r)), var(L::s0p(r))}}, {neg(k), {var(L::x3p(r)), var(L::x3p(r))}}});
+        lin[0].clear();
+        lin[0][L::sbp(r)] = 1u;
+        Form total;
+        for (const Form& f : lin) for (const auto& e : f) total[e.first] = (uint32_t)(((uint64_t)total[e.first] + e.second) % P);
+        for (uint32_t i = 0; i < T; i++) {                       // M_I = J + diag(d): s_i' = d_i s_i + sum
+            Form nf;
+            for (const auto& e : total) {
+                const auto it = lin[i].find(e.first);
+                nf[e.first] = (uint32_t)(((uint64_t)mulm(diag[i], it == lin[i].end() ? 0u : it->second) + e.second) % P);
+            }
+            lin[i] = nf;
+        }
+    }
+    for (uint32_t i = 0; i < T; i++) b.add(ALL, linear_def(L::SP + i, lin[i]));
+    for (uint32_t r = 4; r < 8; r++) external_round(r);
+}
+struct Layout16 {
+    static constexpr uint32_t IN = p2chip::IN, S0 = p2chip::S0, SP = p2chip::SP;
+    static uint32_t x3e(uint32_t r) { return p2chip::x3e(r); }
+    static uint32_t oute(uint32_t r) { return p2chip::oute(r); }
+    static uint32_t s0p(uint32_t r) { return p2chip::s0p(r); }
+    static uint32_t x3p(uint32_t r) { return p2chip::x3p(r); }
+    static uint32_t sbp(uint32_t r) { return p2chip::sbp(r); }
+    static uint32_t ext_input(uint32_t r) { return p2chip::ext_input(r); }
+};
+
 // the constraints that make a row ONE permutation out = poseidon2(in): columns IN .. SP, shared by every variant of the chip
 void permutation_part(Builder& b) {
     // the matrices and constants of the tables in effect, canonical
@@ -82,47 +139,7 @@ void permutation_part(Builder& b) {
     for (int r = 0; r < 8; r++) for (int i = 0; i < 16; i++) rc_e[r][i] = from_monty(g_p2_tables.k16.ext_rc[r][i]);
     for (int r = 0; r < 13; r++) rc_i[r] = from_monty(g_p2_tables.k16.int_rc[r]);
     for (int i = 0; i < 16; i++) diag[i] = from_monty(g_p2_tables.k16.diag[i]);
-    for (uint32_t i = 0; i < 16; i++) {
-        Form f;
-        for (uint32_t j = 0; j < 16; j++) f[IN + j] = ME[i][j];
-        b.add(ALL, linear_def(S0 + i, f));
-    }
-    auto external_round = [&](uint32_t r) {
-        const uint32_t c0 = ext_input(r);
-        for (uint32_t i = 0; i < 16; i++) b.add(ALL, cube_def(x3e(r) + i, c0 + i, rc_e[r][i]));
-        for (uint32_t i = 0; i < 16; i++) {
-            Terms t{{1u, {var(oute(r) + i)}}};
-            for (uint32_t j = 0; j < 16; j++) {
-                const uint32_t x3 = var(x3e(r) + j), c = var(c0 + j);
-                t.push_back(Term{neg(ME[i][j]), {x3, x3, c}});
-                t.push_back(Term{neg(mulm(ME[i][j], rc_e[r][j])), {x3, x3}});
-            }
-            b.add(ALL, t);
-        }
-    };
-    for (uint32_t r = 0; r < 4; r++) external_round(r);
-    Form lin[16];
-    for (uint32_t i = 0; i < 16; i++) lin[i][oute(3) + i] = 1u;
-    for (uint32_t r = 0; r < 13; r++) {
-        const uint32_t k = rc_i[r];
-        b.add(ALL, linear_def(s0p(r), lin[0]));
-        b.add(ALL, cube_def(x3p(r), s0p(r), k));
-        b.add(ALL, Terms{{1u, {var(sbp(r))}}, {P - 1, {var(x3p(r)), var(x3p(r)), var(s0p(r))}}, {neg(k), {var(x3p(r)), var(x3p(r))}}});
-        lin[0].clear();
-        lin[0][sbp(r)] = 1u;
-        Form total;
-        for (const Form& f : lin) for (const auto& e : f) total[e.first] = (uint32_t)(((uint64_t)total[e.first] + e.second) % P);
-        for (uint32_t i = 0; i < 16; i++) {                      // M_I = J + diag(d): s_i' = d_i s_i + sum
-            Form nf;
-            for (const auto& e : total) {
-                const auto it = lin[i].find(e.first);
-                nf[e.first] = (uint32_t)(((uint64_t)mulm(diag[i], it == lin[i].end() ? 0u : it->second) + e.second) % P);
-            }
-            lin[i] = nf;
-        }
-    }
-    for (uint32_t i = 0; i < 16; i++) b.add(ALL, linear_def(SP + i, lin[i]));
-    for (uint32_t r = 4; r < 8; r++) external_round(r);
+    permutation_rounds<16, 13, Layout16>(b, ME, rc_e, rc_i, diag);
 }
 
 std::vector<uint32_t> build_program(bool fri_layers = false, uint32_t n_public = N_PUBLIC, int transcript = -1, int queries = -1) {
@@ -353,6 +370,178 @@ int zkhip_verify_merkle_paths(const uint8_t* proof, size_t len, const uint32_t r
     pv[8] = (uint32_t)n_paths;
     const auto prog = p2chip::program();
     return zkhip_verify_shard_air(prog->data(), prog->size(), proof, len, log_n, p2chip::WIDTH, pv, p2chip::N_PUBLIC, prm, reason);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The width-24 chip (p24chip.h): the same construction for RISC Zero-shape commitments -- the width-24 permutation of the tables in effect
+// (rate 16, overwrite-mode sponge from the zero state, digest = state[0..8]; parent = permute(l || r || 0^8)[0..8]).  540 columns, every
+// constraint of degree <= 3 with its selector:
+//   IN 24 | S0 24 | X3E[r], OUTE[r] 24 each for external rounds 0..3 | S0P[r], X3P[r], SBP[r] for the 21 internal rounds | one unused column
+//   | SP 24 | X3E[r], OUTE[r] for external rounds 4..7 | D 8 = IN[j] (1 - BIT) + IN[8 + j] BIT | BIT CH END CNT as in the width-16 chip |
+//   SPG SS: the row continues a leaf's sponge / starts one | G1 G2 G3: rate words 4..8, 8..12, 12..16 are absorbed (prefix-ordered; words
+//   0..4 always are) -- opened rows are multiples of 4 wide, so a leaf's last block absorbs 4, 8, 12 or 16 values | C1 C2 C3 = SPG (1 - Gk):
+//   the group's words carry over from the previous row's output (the product that keeps that transition constraint at degree 3).
+// The capacity IN[16..24] is zero on every row but a continuing sponge row (SPG: the previous row's output): compression rows absorb
+// l || r || 0^8.  On an SS row the rate words of a group that is not absorbed are zero.  Public values: root[8], count.  Like the width-16
+// program, this one follows zkhip_load_poseidon2_params (a width-24 file changes its coefficients).  tests/poseidon2_24_air.py writes the
+// same program and trace independently; the words must be equal.
+namespace zk {
+namespace p24chip {
+namespace {
+using p2chip::Builder;
+using p2chip::Term;
+using p2chip::Terms;
+using p2chip::var;
+using p2chip::pub;
+
+struct Layout24 {
+    static constexpr uint32_t IN = p24chip::IN, S0 = p24chip::S0, SP = p24chip::SP;
+    static uint32_t x3e(uint32_t r) { return p24chip::x3e(r); }
+    static uint32_t oute(uint32_t r) { return p24chip::oute(r); }
+    static uint32_t s0p(uint32_t r) { return p24chip::s0p(r); }
+    static uint32_t x3p(uint32_t r) { return p24chip::x3p(r); }
+    static uint32_t sbp(uint32_t r) { return p24chip::sbp(r); }
+    static uint32_t ext_input(uint32_t r) { return p24chip::ext_input(r); }
+};
+
+std::vector<uint32_t> build_program() {
+    using p2chip::ALL; using p2chip::FIRST; using p2chip::LAST; using p2chip::TRANSITION;
+    Builder b;
+    uint32_t ME[24][24], rc_e[8][24], rc_i[21], diag[24];
+    for (int j = 0; j < 24; j++) {
+        uint32_t e[24] = {0};
+        e[j] = MONTY_R1;
+        p24_external_linear(e);
+        for (int i = 0; i < 24; i++) ME[i][j] = from_monty(e[i]);
+    }
+    for (int r = 0; r < 8; r++) for (int i = 0; i < 24; i++) rc_e[r][i] = from_monty(g_p2_tables.k24.ext_rc[r][i]);
+    for (int r = 0; r < 21; r++) rc_i[r] = from_monty(g_p2_tables.k24.int_rc[r]);
+    for (int i = 0; i < 24; i++) diag[i] = from_monty(g_p2_tables.k24.diag[i]);
+    p2chip::permutation_rounds<24, 21, Layout24>(b, ME, rc_e, rc_i, diag);
+    const uint32_t o7 = oute(7);
+    for (uint32_t j = 0; j < 8; j++)
+        b.add(ALL, Terms{{1u, {var(D + j)}}, {P - 1, {var(IN + j)}}, {1u, {var(BIT), var(IN + j)}}, {P - 1, {var(BIT), var(IN + 8 + j)}}});
+    for (uint32_t f : {BIT, CH, END, SPG, SS, G(1), G(2), G(3)}) b.add(ALL, Terms{{1u, {var(f), var(f)}}, {P - 1, {var(f)}}});
+    for (uint32_t k = 2; k <= 3; k++) b.add(ALL, Terms{{1u, {var(G(k))}}, {P - 1, {var(G(k - 1)), var(G(k))}}});          // G_k (1 - G_{k-1}) = 0
+    for (uint32_t k = 1; k <= 3; k++) b.add(ALL, Terms{{1u, {var(C(k))}}, {P - 1, {var(SPG)}}, {1u, {var(SPG), var(G(k))}}});  // C_k = SPG (1 - G_k)
+    b.add(FIRST, Terms{{1u, {var(CH)}}});
+    b.add(FIRST, Terms{{1u, {var(SPG)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(IN + 16 + j)}}, {P - 1, {var(SPG), var(IN + 16 + j)}}});        // capacity zero unless SPG
+    for (uint32_t k = 1; k <= 3; k++)                                                                                           // SS: groups not absorbed are zero
+        for (uint32_t j = 4 * k; j < 4 * k + 4; j++) b.add(ALL, Terms{{1u, {var(SS), var(IN + j)}}, {P - 1, {var(SS), var(G(k)), var(IN + j)}}});
+    for (uint32_t j = 0; j < 8; j++)                                                                                            // SPG: the capacity follows
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true), var(IN + 16 + j, true)}}, {P - 1, {var(SPG, true), var(o7 + 16 + j)}}});
+    for (uint32_t k = 1; k <= 3; k++)                                                                                           // ... and so do carried groups
+        for (uint32_t j = 4 * k; j < 4 * k + 4; j++)
+            b.add(TRANSITION, Terms{{1u, {var(C(k), true), var(IN + j, true)}}, {P - 1, {var(C(k), true), var(o7 + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(CH, true), var(D + j, true)}}, {P - 1, {var(CH, true), var(o7 + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(END), var(o7 + j)}}, {P - 1, {var(END), pub(j)}}});
+    b.add(FIRST, Terms{{1u, {var(CNT)}}, {P - 1, {var(END)}}});
+    b.add(TRANSITION, Terms{{1u, {var(CNT, true)}}, {P - 1, {var(CNT)}}, {P - 1, {var(END, true)}}});
+    b.add(LAST, Terms{{1u, {var(CNT)}}, {P - 1, {pub(8)}}});
+    std::vector<uint32_t> p{AIR_MAGIC, 1u, WIDTH, b.count, N_PUBLIC, (uint32_t)(6 + b.body.size())};
+    p.insert(p.end(), b.body.begin(), b.body.end());
+    return p;
+}
+
+// the program of the width-24 tables in effect (rebuilt when zkhip_load_poseidon2_params / _reset_ changes them)
+std::shared_ptr<const std::vector<uint32_t>> program() {
+    static std::mutex mu;
+    static std::shared_ptr<const std::vector<uint32_t>> cached;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (!cached || cached_gen != gen) { cached = std::make_shared<const std::vector<uint32_t>>(build_program()); cached_gen = gen; }
+    return cached;
+}
+
+int paths_shape(size_t n_paths, int depth, uint32_t row_width, int* log_n) {
+    if (row_width % 4 != 0 || row_width > 1024) return fail(ZKHIP_ERR_INVALID, "merkle paths p24: the opened row width is 0 (leaf digests are given) or a multiple of 4 up to 1024");
+    const size_t per = ((size_t)row_width + 15) / 16 + (size_t)(depth > 0 ? depth : 0);
+    if (n_paths < 1 || depth < 1 || depth > 32 || n_paths > ((size_t)1 << MAX_LOG_ROWS) / per) return fail(ZKHIP_ERR_INVALID, "merkle paths p24: 1..2^22 rows of paths, depth 1..32");
+    int ln = 5;
+    while (((size_t)1 << ln) < n_paths * per) ln++;
+    *log_n = ln;
+    return ln <= MAX_LOG_ROWS ? ZKHIP_OK : fail(ZKHIP_ERR_INVALID, "merkle paths p24: more than 2^22 rows");
+}
+
+}  // namespace
+}  // namespace p24chip
+}  // namespace zk
+
+extern "C" {
+
+size_t zkhip_p24chip_air(uint32_t* program, size_t cap_words) {
+    const auto p = p24chip::program();
+    if (program && cap_words >= p->size()) std::memcpy(program, p->data(), p->size() * 4);
+    return p->size();
+}
+
+int zkhip_p24chip_gen_merkle_trace(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t row_width, const uint32_t* siblings, const uint32_t* indices, size_t n_paths,
+                                   int depth, int log_n, uint32_t* d_trace, size_t ld, uint32_t* roots) {
+    CHECK_CTX(ctx);
+    if (!leaves || !siblings || !indices || !d_trace || !roots || ld < p24chip::WIDTH || ld % 4 != 0 || (uintptr_t)d_trace % 16 != 0)
+        return fail(ZKHIP_ERR_INVALID, "p24chip_gen_merkle_trace: bad arguments (ld >= 540 and a multiple of 4, a 16-byte aligned trace)");
+    int need;
+    ZK_TRY(p24chip::paths_shape(n_paths, depth, row_width, &need));
+    if (log_n < need || log_n > MAX_LOG_ROWS) return fail(ZKHIP_ERR_INVALID, "p24chip_gen_merkle_trace: 2^log_n rows do not hold the paths");
+    const size_t nl = n_paths * (row_width ? row_width : 8), ns = n_paths * (size_t)depth * 8, nr = n_paths * 8;
+    for (size_t i = 0; i < nl; i++) if (leaves[i] >= P) return fail(ZKHIP_ERR_INVALID, "p24chip_gen_merkle_trace: leaves must be canonical");
+    for (size_t i = 0; i < ns; i++) if (siblings[i] >= P) return fail(ZKHIP_ERR_INVALID, "p24chip_gen_merkle_trace: siblings must be canonical");
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, (nl + ns + n_paths + nr) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    ZK_HIP(hipMemcpyAsync(d, leaves, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(d + nl, siblings, ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(d + nl + ns, indices, n_paths * 4, hipMemcpyHostToDevice, ctx->stream));
+    p24chip::MerkleTraceArgs a{};
+    a.leaves = d; a.row_width = row_width; a.siblings = d + nl; a.indices = d + nl + ns; a.n_paths = n_paths; a.rows = (uint64_t)1 << log_n; a.depth = (uint32_t)depth;
+    a.trace = d_trace; a.ld = ld; a.roots = d + nl + ns + n_paths;
+    ZK_HIP(launch_p24chip_merkle(a, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(roots, a.roots, nr * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    return ZKHIP_OK;
+}
+
+size_t zkhip_merkle_paths_p24_proof_size(size_t n_paths, int depth, uint32_t row_width, const zkhip_params* prm) {
+    int log_n;
+    if (p24chip::paths_shape(n_paths, depth, row_width, &log_n) != ZKHIP_OK) return 0;
+    const auto p = p24chip::program();
+    return zkhip_proof_size_air(p->data(), p->size(), log_n, p24chip::WIDTH, prm, p24chip::N_PUBLIC);
+}
+
+int zkhip_prove_merkle_paths_p24(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t row_width, const uint32_t* siblings, const uint32_t* indices, size_t n_paths,
+                                 int depth, const uint32_t root[8], const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    if (!root || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_merkle_paths_p24: null argument");
+    int log_n;
+    ZK_TRY(p24chip::paths_shape(n_paths, depth, row_width, &log_n));
+    void* trace;
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, ((size_t)p24chip::WIDTH << log_n) * 4, &trace));
+    std::vector<uint32_t> roots(n_paths * 8);
+    ZK_TRY(zkhip_p24chip_gen_merkle_trace(ctx, leaves, row_width, siblings, indices, n_paths, depth, log_n, (uint32_t*)trace, p24chip::WIDTH, roots.data()));
+    for (size_t p = 0; p < n_paths; p++)
+        if (std::memcmp(roots.data() + 8 * p, root, 32) != 0) return fail(ZKHIP_ERR_INVALID, "prove_merkle_paths_p24: path " + std::to_string(p) + " does not end in the root");
+    uint32_t pv[p24chip::N_PUBLIC];
+    std::memcpy(pv, root, 32);
+    pv[8] = (uint32_t)n_paths;
+    const auto prog = p24chip::program();
+    return zkhip_prove_shard_air(ctx, prog->data(), prog->size(), (const uint32_t*)trace, p24chip::WIDTH, log_n, p24chip::WIDTH, pv, p24chip::N_PUBLIC, prm, proof, cap, len);
+}
+
+int zkhip_verify_merkle_paths_p24(const uint8_t* proof, size_t len, const uint32_t root[8], size_t n_paths, const zkhip_params* prm, int* reason) {
+    if (!proof || !root || !prm || len < 16) return fail(ZKHIP_ERR_INVALID, "verify_merkle_paths_p24: null argument");
+    uint32_t head[4];
+    std::memcpy(head, proof, 16);
+    const int log_n = (int)head[2];                                    // the trace height is read from the proof and bound by its transcript
+    if (log_n < 5 || log_n > MAX_LOG_ROWS || n_paths >= P) { if (reason) *reason = 1; return fail(ZKHIP_ERR_VERIFY, "verify_merkle_paths_p24: not a proof of the width-24 Poseidon2 chip"); }
+    uint32_t pv[p24chip::N_PUBLIC];
+    std::memcpy(pv, root, 32);
+    pv[8] = (uint32_t)n_paths;
+    const auto prog = p24chip::program();
+    return zkhip_verify_shard_air(prog->data(), prog->size(), proof, len, log_n, p24chip::WIDTH, pv, p24chip::N_PUBLIC, prm, reason);
 }
 
 }  // extern "C"

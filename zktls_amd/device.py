@@ -414,6 +414,38 @@ class Context:
                                                 rt.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    def p24chip_gen_merkle_trace(self, leaves, siblings, indices, log_n=None, row_width=0):
+        """the width-24 Poseidon2 chip's trace for a set of Merkle paths of a RISC Zero-shape commitment (numpy arrays of canonical words:
+        leaves [n][8] digests -- or, with row_width > 0 (a multiple of 4), the opened rows [n][row_width], hashed in-circuit --, siblings
+        [n][depth][8], indices [n]) -> (device buffer [2^log_n][540], roots [n][8], log_n)"""
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32)
+        sb = np.ascontiguousarray(siblings, dtype=np.uint32)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        n, depth = lv.shape[0], sb.shape[1]
+        if log_n is None:
+            log_n = max(5, (n * (depth + (row_width + 15) // 16) - 1).bit_length())
+        out = self.alloc(540 << log_n)
+        roots = np.zeros((n, 8), dtype=np.uint32)
+        check(self.lib.zkhip_p24chip_gen_merkle_trace(self.handle, lv.ctypes.data_as(u32p), row_width, sb.ctypes.data_as(u32p), ix.ctypes.data_as(u32p), n, depth,
+                                                      log_n, C.c_void_p(out.ptr), 540, roots.ctypes.data_as(u32p)))
+        return out, roots, log_n
+
+    def prove_merkle_paths_p24(self, leaves, siblings, indices, root, params=None, row_width=0):
+        """-> proof bytes of "I know len(leaves) openings of this RISC Zero-shape commitment (row_width > 0: whole opened rows) that end in root"
+        (the width-24 Poseidon2 chip)"""
+        params = params or Params(1, 100, 16)
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32)
+        sb = np.ascontiguousarray(siblings, dtype=np.uint32)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        rt = np.ascontiguousarray(root, dtype=np.uint32)
+        n, depth = lv.shape[0], sb.shape[1]
+        size = self.lib.zkhip_merkle_paths_p24_proof_size(n, depth, row_width, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_merkle_paths_p24(self.handle, lv.ctypes.data_as(u32p), row_width, sb.ctypes.data_as(u32p), ix.ctypes.data_as(u32p), n, depth,
+                                                    rt.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def sha256_setup(self, params=None):
         """zkhip_sha256_setup: the SHA-256 machine's key (the range table's preprocessed values, committed once) -> MachineKey; .root is the vk"""
         params = params or Params(1, 100, 16)
@@ -1220,6 +1252,26 @@ def verify_merkle_paths(proof, root, n_paths, params=None):
     rt = np.ascontiguousarray(root, dtype=np.uint32)
     reason = C.c_int(0)
     rc = lib.zkhip_verify_merkle_paths(pr.ctypes.data_as(u8p), pr.size, rt.ctypes.data_as(u32p), n_paths, C.byref(params), C.byref(reason))
+    return rc, reason.value
+
+
+def p24chip_air():
+    """the width-24 Poseidon2 chip's constraint program for the parameter set in effect"""
+    lib = _lib.load()
+    n = lib.zkhip_p24chip_air(None, 0)
+    out = np.empty(n, dtype=np.uint32)
+    assert lib.zkhip_p24chip_air(out.ctypes.data_as(u32p), n) == n
+    return out
+
+
+def verify_merkle_paths_p24(proof, root, n_paths, params=None):
+    """host-only check of a zkhip_prove_merkle_paths_p24 proof -> (rc, reason)"""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    rt = np.ascontiguousarray(root, dtype=np.uint32)
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_merkle_paths_p24(pr.ctypes.data_as(u8p), pr.size, rt.ctypes.data_as(u32p), n_paths, C.byref(params), C.byref(reason))
     return rc, reason.value
 
 
