@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Contract benchmark: whole-shard STARK proofs on MI355X through libzkhip's C ABI.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks are the launcher's; started
    plainly, bench.py spawns its N rank processes itself BEFORE anything in the parent touches the GPU)
 
@@ -16,12 +16,15 @@ beyond that shards repeat and `distinct_shards_proven` says so).
 Up to --streams shards are in flight per GPU, each on its own context + HIP stream + host
 thread, so the latency-bound stretches of one proof hide under the kernels of the others.
 
-Prints ONE JSON line (rank 0): metric trace-cells/s (+ proofs/s), `roofline` for the NTT
-pass kernel (HIP events on the launch stream; the LDE launches of a proof -- first inverse pass, the fused
+Prints ONE JSON line (rank 0): metric trace-cells/s (+ proofs/s).  A plain run sets up, warms up, times the K steps,
+checks that every timed shard was proven once and that the last proof verifies, writes --dump-outputs and prints the
+line.  With --full it then measures everything else the line can carry, each section after the timed steps: `roofline`
+for the NTT pass kernel (HIP events on the launch stream; the LDE launches of a proof -- first inverse pass, the fused
 middle launch, second forward pass per coset -- on the proving context's OWN workspaces, i.e. the in-proof
 buffer placement), `valu_roofline` for the Poseidon2 leaf kernel
-(the largest share of a proof, integer-multiply bound) and `cpu_baseline` (the CPU oracle
-timed on the host cores, bounded sample, N = 1 only).
+(the largest share of a proof, integer-multiply bound), `cpu_baseline` (the CPU oracle
+timed on the host cores, bounded sample, N = 1 only), the one-process entry, single-shard latency, host verification
+time, `batch64`, `recursion16`, `multichip` and `execution22`; in a plain run those fields are null.
 """
 import argparse
 import gc
@@ -115,6 +118,10 @@ def main():
                     help="TEST MODE with --one-process on a box with fewer GPUs than --gpus: load the A/B build (libzkhip_ab.so) with "
                          "ZKHIP_LOGICAL_DEVICES=K, whose device ordinals 0..K-1 are logical devices on the physical ones (own pools, own workers, "
                          "traces checked to live where their shard is dealt); the line says so and is not a scaling result")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (roofline, valu_roofline, the one-process entry, "
+                         "single-shard latency, host verification time, batch64, recursion16, multichip, execution22, cpu_baseline); the --no-* "
+                         "switches below skip single sections of a --full run")
     ap.add_argument("--no-execution", action="store_true", help="skip the reference-sized execution (22 shards: core, then core + compress) through the host mirror of ZkProver::prove")
     ap.add_argument("--no-multichip", action="store_true", help="skip the multi-chip shard with LogUp pairs (SP1's shard structure, rows a7 mixed heights + a8) measured beside the headline")
     ap.add_argument("--no-fri-graph", action="store_true",
@@ -297,7 +304,9 @@ def main():
         with torch.cuda.stream(stream):
             # destinations of the stand-alone strided-pass scan of the roofline section (context only: the roofline itself is
             # measured on the proving context's own workspaces).  The strided pass runs in one of two modes depending on where
-            # source and destination lie; the scan reports the spread over 16 pairs.
+            # source and destination lie; the scan reports the spread over 16 pairs.  Allocated without --full too:
+            # the proving contexts reserve their workspaces at the first step, after these, so that the timed steps run on the same
+            # buffer placement with and without --full.
             roof_scratch, spacers = [], []
             for _k in range(4):          # 2, 6, 10 GiB apart: buffer classes come in runs of several GiB, neighbours share one
                 roof_scratch.append(torch.empty(n * width, dtype=torch.int32, device="cuda"))
@@ -313,7 +322,7 @@ def main():
         nbuf = 1
         chip_bufs = [(ctx.gen_trace(SEED, 100 * rank + j, ln, w), ln, w) for j, (ln, w) in enumerate(chip_list)]
         with torch.cuda.stream(stream):
-            traces = [torch.empty(n * width, dtype=torch.int32, device="cuda")]      # source of the roofline section only
+            traces = [torch.empty(n * width, dtype=torch.int32, device="cuda")]      # source of the roofline section only (allocated in every run: above)
             roof_scratch, spacers = [], []
             for _k in range(4):          # 2, 6, 10 GiB apart: buffer classes come in runs of several GiB, neighbours share one
                 roof_scratch.append(torch.empty(n * width, dtype=torch.int32, device="cuda"))
@@ -437,7 +446,7 @@ def main():
     # the library's own multi-GPU entry on the same shards (one process, device list [this GPU]): the path a ZkProver::prove binds
     # (INTEGRATION.md 2), measured beside the rank-per-GPU path whenever this rank is alone on the node
     one_process = None
-    if not one_proc and world == 1 and chip_list is None and host_traces is None and LQ == 0:
+    if args.full and not one_proc and world == 1 and chip_list is None and host_traces is None and LQ == 0:
         from zktls_amd.device import prove_shards_multi
         ids = [i % nbuf for i in range(K)]
         prove_shards_multi([bufs[i] for i in ids[:max(S, 1)]], log_n, width, [public + [my[i]] for i in ids[:max(S, 1)]], prm, devices=None if zk_lib.device_count() == 1 else [local_rank], in_flight=S)
@@ -452,7 +461,7 @@ def main():
 
     # single-shard latency (one shard in flight, nothing else on the GPU): NOT the metric -- `value` is throughput with S shards in flight
     latency_ms = None
-    if rank == 0 and chip_list is None and host_traces is None:
+    if args.full and rank == 0 and chip_list is None and host_traces is None:
         ctx.sync()
         step(0)
         tl = time.perf_counter()
@@ -461,18 +470,19 @@ def main():
         ctx.sync()
         latency_ms = (time.perf_counter() - tl) / 2 * 1e3
 
-    # the last proof of the timed region must verify (host verifier of the product); its second run is timed: the reference verifies
-    # every proof on the CPU inside `prove` (sp1.rs:120), outside the span it times
+    # the last proof of the timed region must verify (host verifier of the product); with --full its second run is timed: the reference
+    # verifies every proof on the CPU inside `prove` (sp1.rs:120), outside the span it times
     tv = time.perf_counter()
     if chip_list is None:
         rc, reason = verify_shard(last, log_n, width, last_public, prm)
-        tv = time.perf_counter()
-        rc, reason = verify_shard(last, log_n, width, last_public, prm)
+        if args.full:
+            tv = time.perf_counter()
+            rc, reason = verify_shard(last, log_n, width, last_public, prm)
     else:
         from zktls_amd.device import verify_chips
         rc, reason = verify_chips(last, [c[0] for c in chip_list], [c[1] for c in chip_list], last_public, prm)
     verified = rc == 0
-    host_verify_ms = (time.perf_counter() - tv) * 1e3
+    host_verify_ms = (time.perf_counter() - tv) * 1e3 if args.full else None
 
     # ---- roofline of the NTT pass kernel: one launch = 8 B/element (read 4 + write 4).
     # Measured on the IN-PROOF placement: the four launches of the trace LDE (inverse strided / inverse contiguous / forward
@@ -481,7 +491,7 @@ def main():
     # LDE (I1, I2, 2 x F1, 2 x F2).  Nothing is selected: the placement is whatever the proving context got.  A scan of the
     # stand-alone strided pass over 16 (source, destination) buffer pairs is reported beside it (min / median / max) for context.
     roof = None
-    if rank == 0 and log_n > 20:
+    if args.full and rank == 0 and log_n > 20:
         # 2^21 / 2^22 rows: the 2^20-row machinery on R = 2 / 4 row classes plus one streaming radix-R pass either way
         # (ntt_combine_kernel).  No single-launch hook at this size: the whole trace LDE is timed (HIP events, own output buffer)
         # and priced against the bytes it must move.  With the fused middle launch (width a multiple of 32):
@@ -505,7 +515,7 @@ def main():
                 "algorithmic_bytes_per_launch": bpc * n * width, "avg_launch_ms": round(lde_ms, 4),
                 "lde": {"ms": round(lde_ms, 4), "bytes_per_trace_cell": bpc, "GB/s": round(ach, 1)}}
         del big_out
-    if rank == 0 and log_n <= 20:
+    if args.full and rank == 0 and log_n <= 20:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
         def timed(fn, reps, warm=3):
@@ -624,7 +634,7 @@ def main():
     # measured integer-multiply roof (v_mul_lo / v_mad_u64_u32 issue at 4.2 clk per wave64 per SIMD at the
     # nominal 2.4 GHz -> 256 CUs x 4 SIMDs x 64 / 4.2 x 2.4e9 = 37.4 T int-mul/s; tools/microbench.hip)
     valu = None
-    if rank == 0 and args.shape == "sp1":
+    if args.full and rank == 0 and args.shape == "sp1":
         rows = 2 * n
         with torch.cuda.stream(stream):
             lde_t = torch.empty(rows * width, dtype=torch.int32, device="cuda")
@@ -654,7 +664,7 @@ def main():
     # ---- BASELINE configs[2]: sixty-four 13 KB transcripts in ONE call, each a keyed SHA-256 machine proof (padding, trace, range table,
     # proof; host bytes in, proofs out), in lock-step batches (csrc/batch.h) and, beside it, one context + stream per worker
     batch64 = None
-    if rank == 0 and not args.no_batch64 and chip_list is None:
+    if args.full and rank == 0 and not args.no_batch64 and chip_list is None:
         import hashlib
         from zktls_amd.device import lockstep_stats, prove_transcripts, set_lockstep, verify_sha256_machine
         base = open(os.path.join(ROOT, "tests", "golden", "reference", "guest_input0.cbor"), "rb").read()
@@ -743,7 +753,7 @@ def main():
     # ---- the compress-like step (sp1.rs:116: core -> compress verifies the shard proofs): the FRI check of sixteen shard proofs of the headline
     # shape proven in-circuit (Merkle paths, folds, challenges, proof of work, query indices) by ONE call of zkhip_prove_fri_indices_batch
     recursion16 = None
-    if rank == 0 and not args.no_recursion16 and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and 6 <= log_n <= 20:
+    if args.full and rank == 0 and not args.no_recursion16 and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and 6 <= log_n <= 20:
         from zktls_amd.device import prove_fri_indices_batch, set_lockstep, verify_fri_indices
         sps, spv = [], []
         for i in range(16):
@@ -864,7 +874,7 @@ def main():
     # ---- SP1's real shard structure beside the headline: six chips of different heights in ONE proof (mixed-height commitments, row a7)
     # with in-table LogUp pairs (permutation traces + their commitment, row a8), proven with the same number of shards in flight
     multichip = None
-    if rank == 0 and not args.no_multichip and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and log_n == 20 and not one_proc:
+    if args.full and rank == 0 and not args.no_multichip and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and log_n == 20 and not one_proc:
         from zktls_amd.device import verify_chips
         mc_spec = [(20, 96), (20, 32), (19, 64), (18, 128), (16, 256), (14, 40)]
         mc_pairs = [max(1, w_ // 32) for _, w_ in mc_spec]
@@ -973,7 +983,7 @@ def main():
     # sp1.rs:116-120), then core + COMPRESS (the shard proofs joined into one proof, checked on the host without them)
     execution = None
     mirror_so = os.path.join(ROOT, "zktls_amd", "libzktls_guest_prover.so")
-    if (rank == 0 and world == 1 and not args.no_execution and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and log_n <= 20 and width % 8 == 0
+    if (args.full and rank == 0 and world == 1 and not args.no_execution and chip_list is None and host_traces is None and args.shape == "sp1" and LQ == 0 and log_n <= 20 and width % 8 == 0
             and not one_proc and os.path.exists(mirror_so)):
         import ctypes as C_
 
@@ -1074,7 +1084,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample of the same workload
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         cores = os.cpu_count() or 1
@@ -1131,6 +1141,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u32",
             "data": "synthetic",
+            "full": bool(args.full),
             "streams_per_gpu": in_flight, "host_wait": "block" if wait_block else "poll", "host_cores_usable": cores_ok,
             "host_cores_busy_per_rank": round(host_cores_busy, 2),
             "fri_commit_phase_as_hip_graph": (not args.no_fri_graph), "one_process_mode": bool(one_proc), "logical_devices_test_mode": int(args.logical_devices),
@@ -1151,7 +1162,7 @@ def main():
                        "shards_per_step": world},
             "proofs_per_s": round(K * world / elapsed, 3),
             "proof_bytes": int(last.size),
-            "verified": bool(verified), "host_verify_ms": round(host_verify_ms, 2),
+            "verified": bool(verified), "host_verify_ms": (round(host_verify_ms, 2) if host_verify_ms is not None else None),
             "roofline": roof,
             "valu_roofline": valu,
             "transcripts_per_s": (batch64["transcripts_per_s"] if batch64 else None),

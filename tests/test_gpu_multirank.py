@@ -4,7 +4,9 @@ ranks before anything in it touches the GPU, and nothing here replaces a process
   * two ranks on one GPU (--share-gpu: gloo collectives, because RCCL refuses two ranks on one device): the shard dealing, the seed
     broadcast, the max-over-ranks timing and the digest gather run end to end, every shard is proven on exactly one rank;
   * one rank with --force-collective: the 'nccl' (= RCCL) process group is initialised on the GPU and a broadcast, a MAX
-    all-reduce and a barrier go through it, so RCCL is loaded and called on hardware in every driver run."""
+    all-reduce and a barrier go through it, so RCCL is loaded and called on hardware in every driver run.
+These runs pass --full, so the sections rank 0 measures after the timed steps also run beside other ranks and in one-process
+mode; test_a_plain_run_measures_the_headline_alone covers a run without it."""
 import json
 import os
 import subprocess
@@ -30,7 +32,7 @@ def run_bench(*flags, timeout=900):
 
 
 def test_two_ranks_share_one_gpu_and_prove_every_shard_once():
-    r = run_bench("--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64")
+    r = run_bench("--full", "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64")
     assert r["n_gpus"] == 2 and r["rccl_world_size"] == 2 and r["share_gpu_test_mode"] is True
     assert r["collective_backend"] == "gloo"
     assert r["shards_proven"] == 4 and r["distinct_shards_proven"] == 4 and r["shard_digests_gathered"] == 4
@@ -39,14 +41,14 @@ def test_two_ranks_share_one_gpu_and_prove_every_shard_once():
 
 
 def test_rccl_is_initialised_and_called_at_world_size_one():
-    r = run_bench("--gpus", "1", "--force-collective", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64")
+    r = run_bench("--full", "--gpus", "1", "--force-collective", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64")
     assert r["collective_backend"] == "nccl" and r["rccl_selfcheck_calls"] == 3
     assert r["rccl_world_size"] == 1 and r["shards_proven"] == 2 and r["verified"] is True
 
 
 def test_one_process_deals_the_shards_through_the_librarys_device_list():
     """bench.py --one-process: zkhip_prove_shards_multi(NULL, 0, ...) is the measuring path (the entry a ZkProver::prove binds on a multi-GPU node)"""
-    r = run_bench("--gpus", "1", "--one-process", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-batch64", "--no-recursion16",
+    r = run_bench("--full", "--gpus", "1", "--one-process", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-batch64", "--no-recursion16",
                   "--log-n", "18", "--width", "128")
     assert r["one_process_mode"] is True and r["n_gpus"] == 1 and r["logical_devices_test_mode"] == 0
     assert r["shards_proven"] == 3 and r["distinct_shards_proven"] == 3
@@ -56,7 +58,7 @@ def test_one_process_deals_the_shards_through_the_librarys_device_list():
 
 def test_one_process_over_two_logical_devices():
     """the same with a device list of TWO: the A/B build's logical devices (own pools, own workers, traces generated where their shard is dealt)"""
-    r = run_bench("--gpus", "2", "--one-process", "--logical-devices", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-batch64",
+    r = run_bench("--full", "--gpus", "2", "--one-process", "--logical-devices", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-batch64",
                   "--no-recursion16", "--log-n", "18", "--width", "128")
     assert r["one_process_mode"] is True and r["n_gpus"] == 2 and r["logical_devices_test_mode"] == 2
     assert r["shards_proven"] == 6 and r["distinct_shards_proven"] == 6
@@ -64,12 +66,22 @@ def test_one_process_over_two_logical_devices():
 
 
 def test_the_rank_per_gpu_line_carries_the_one_process_entry_too():
-    r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-batch64", "--no-recursion16", "--log-n", "18", "--width", "128")
+    r = run_bench("--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-batch64", "--no-recursion16", "--log-n", "18", "--width", "128")
     assert r["one_process"]["shards_proven"] == 2 and r["one_process"]["distinct_proofs"] == 2 and r["one_process"]["same_bytes_as_the_timed_step"] is True
     assert r["one_process_value"] > 0
     # ... and the plug point itself: one call of the host mirror of ZkProver::prove for 22 shards, core and core + compress
     e = r["execution22"]
     assert e["compressed_blob_verified_on_host"] is True and e["compressed_blob_bytes"] * 4 < e["core_blob_bytes"] and e["core_plus_compress_ms"] > e["core_ms"] * 0.5
+
+
+def test_a_plain_run_measures_the_headline_alone():
+    """without --full a run warms up, times its steps, checks their proofs and prints the line: every section measured beside the headline is null"""
+    r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "18", "--width", "128")
+    assert r["full"] is False and r["metric"] == "trace-cells/s" and r["value"] > 0 and r["ms_per_step"] > 0
+    assert r["shards_proven"] == 2 and r["distinct_shards_proven"] == 2 and r["verified"] is True
+    for k in ("roofline", "valu_roofline", "one_process", "single_shard_latency_ms", "host_verify_ms", "batch64", "recursion16", "multichip",
+              "execution22", "cpu_baseline"):
+        assert r[k] is None, k
 
 
 def test_multi_device_entries_on_two_logical_devices():
@@ -89,7 +101,7 @@ def test_dry_run_of_the_eight_gpu_configuration_on_logical_devices():
     """the 8-GPU configuration dry-run LOGICALLY on the one GPU -- a device list of eight (A/B build), four shards in flight per
     device = 32 prover threads under the container's CPU quota, so `--wait auto` must pick blocking waits; every shard proven exactly once.  No
     scaling number comes out of this; it removes first-contact failures from the day an 8-GPU node exists."""
-    r = run_bench("--gpus", "8", "--one-process", "--logical-devices", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-batch64",
+    r = run_bench("--full", "--gpus", "8", "--one-process", "--logical-devices", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-batch64",
                   "--no-recursion16", "--log-n", "18", "--width", "64", timeout=1500)
     assert r["one_process_mode"] is True and r["n_gpus"] == 8 and r["logical_devices_test_mode"] == 8
     assert r["shards_proven"] == 16 and r["distinct_shards_proven"] == 16
@@ -101,7 +113,7 @@ def test_dry_run_of_four_ranks_sharing_the_one_gpu():
     """the rank-per-GPU path at world size 4 (gloo collectives: RCCL refuses several ranks on one device): dealing, seed broadcast, max-over-ranks
     timing and the digest gather with four processes; blocking waits by default for N >= 4.  Four ranks and this process keep the number of
     processes with the GPU open at five; world size 8 runs on the CPU (tests/test_shards_gloo_cpu.py::test_eight_rank_shard_parallel)."""
-    r = run_bench("--gpus", "4", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64", timeout=1500)
+    r = run_bench("--full", "--gpus", "4", "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--log-n", "18", "--width", "64", timeout=1500)
     assert r["n_gpus"] == 4 and r["rccl_world_size"] == 4 and r["share_gpu_test_mode"] is True and r["collective_backend"] == "gloo"
     assert r["shards_proven"] == 8 and r["distinct_shards_proven"] == 8 and r["shard_digests_gathered"] == 8
     assert r["host_wait"] == "block" and r["verified"] is True and r["value"] > 0

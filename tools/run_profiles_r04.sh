@@ -16,11 +16,11 @@ run_kt() {   # name, command...
         echo "$name: attempt $attempt died" >> $P/log.txt
     done
 }
-run_kt kt python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-multichip
-run_kt kt1 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64 --no-recursion16
-run_kt r0 python3 bench.py --shape r0 --width 128 --steps 8 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64
-run_kt big21 python3 bench.py --log-n 21 --width 256 --steps 4 --warmup 1 --no-cpu-baseline --streams 1 --no-batch64
-run_kt big22 python3 bench.py --log-n 22 --width 128 --steps 4 --warmup 1 --no-cpu-baseline --streams 1 --no-batch64
+run_kt kt python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-multichip
+run_kt kt1 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64 --no-recursion16
+run_kt r0 python3 bench.py --full --shape r0 --width 128 --steps 8 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64
+run_kt big21 python3 bench.py --full --log-n 21 --width 256 --steps 4 --warmup 1 --no-cpu-baseline --streams 1 --no-batch64
+run_kt big22 python3 bench.py --full --log-n 22 --width 128 --steps 4 --warmup 1 --no-cpu-baseline --streams 1 --no-batch64
 run_kt join python3 tools/recursion_time.py
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/pmc_fetch -o run -- python3 tools/profile_fused.py > $P/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $P/pmc_write -o run -- python3 tools/profile_fused.py > $P/pmc_write.log 2>&1
@@ -30,7 +30,7 @@ for c in TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_TCC_RE
   rocprofv3 --pmc $c --output-format csv -d $P/pass_$c -o run -- python3 tools/profile_fused.py > $P/pass_$c.log 2>&1
 done
 python3 tools/pass_pmc_report.py $P > $P/pass_pmc.md 2>&1; cat $P/pass_pmc.md
-python3 bench.py > $P/bench_default.json 2> $P/bench_default.err
+python3 bench.py --full > $P/bench_default.json 2> $P/bench_default.err
 find $P -name "*.csv" | head -40
 # keep the transfer small: only the stats tables, counter tables and logs travel back
 find $P -name "*kernel_trace.csv" -delete

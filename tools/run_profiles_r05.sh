@@ -24,7 +24,7 @@ grep -v "^$" $P/multichip.log | tail -60 > $P/multichip_phases.txt
 # ... and the same four proofs WITHOUT the profiler (its interception of graph launches inflates the FRI commit phase: 5.2 against 2.2 ms)
 python3 tools/multichip_breakdown.py > $P/multichip_plain.log 2>&1; grep -E "chips prover|multichip shard" $P/multichip_plain.log | tail -24 > $P/multichip_phases_plain.txt
 # 2. the headline shard alone, one in flight: the clean per-proof table
-run_kt kt1 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64 --no-recursion16 --no-execution --no-multichip
+run_kt kt1 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --streams 1 --no-batch64 --no-recursion16 --no-execution --no-multichip
 # 2b. 64 transcript proofs -> ONE proof (air mode of the shard verifier machine): kernels, and the phases (A/B build, no profiler)
 run_kt compress64 python3 tools/compress64_trace.py
 python3 tools/join_breakdown.py --sha 64 > $P/compress64_phases.log 2>&1; tail -19 $P/compress64_phases.log > $P/compress64_phases.txt
@@ -35,7 +35,7 @@ python3 tools/tree_breakdown.py 4 > $P/tree_phases.log 2>&1; grep -E "machine ve
 python3 tools/join_overlap_probe.py 4 16 > $P/join_overlap.txt 2>&1
 if [ "$WHAT" = all ]; then
 # 3. the contract command (four in flight)
-run_kt kt python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-multichip --no-execution
+run_kt kt python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-multichip --no-execution
 fi
 # 4. counters for the streaming passes over the finished LDE (quotient_kernel<4>, rowdot_regs_kernel<4>) and the leaf hash beside them:
 # one --pmc pass per counter over six single-shard proofs
@@ -44,7 +44,7 @@ for c in FETCH_SIZE WRITE_SIZE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VME
   rocprofv3 --pmc $c --output-format csv -d $P/stream_$c -o run -- python3 tools/single_shard_trace.py > $P/stream_$c.log 2>&1 || echo "pmc $c died" >> $P/attempts.txt
 done
 python3 tools/stream_pmc_report.py $P > $P/stream_pmc.md 2>&1; cat $P/stream_pmc.md
-python3 bench.py > $P/bench_default.json 2> $P/bench_default.err
+python3 bench.py --full > $P/bench_default.json 2> $P/bench_default.err
 # keep the transfer small: only the stats tables, counter tables and logs travel back
 find $P -name "*kernel_trace.csv" -delete
 find $P -name "*counter_collection.csv" -size +8M -delete

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 P=gpurun_out/prof6
 mkdir -p $P
 WHAT=${1:-all}
-CONTRACT="python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-multichip --no-execution --no-batch64 --no-recursion16"
+CONTRACT="python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-multichip --no-execution --no-batch64 --no-recursion16"
 run_kt() {   # name, command...
     local name=$1; shift
     echo "$*" > $P/${name}_cmd.txt
@@ -27,7 +27,7 @@ python3 tools/hash_dispatch_report.py $P/hash4 $P/hash4_grbm "the contract comma
 fi
 if [ "$WHAT" = evidence ] || [ "$WHAT" = all ]; then
 # 2. the contract command (the driver's: default line) under the kernel trace
-run_kt contract python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-multichip --no-execution
+run_kt contract python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-multichip --no-execution
 # 3. ONE headline shard at a time, proofs only (tools/single_shard_trace.py: six proofs): the per-proof kernel table, and the HBM counters of the LDE passes
 run_kt single python3 tools/single_shard_trace.py
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -41,8 +41,8 @@ ZKHIP_REC_HOST=1 python3 tools/join_breakdown.py --sha 64 2>&1 | grep -E "shard 
 ZKHIP_REC_HOST=1 python3 tools/join_breakdown.py --keyed 64 2>&1 | grep -E "machine verifier\]|compress" | tail -6 > $P/keyed64_phases_hostwalk.txt
 ZKHIP_REC_HOST=1 python3 tools/tree_breakdown.py 4 2>&1 | grep -E "machine verifier\]|top over" | tail -6 > $P/tree_phases_hostwalk.txt
 # 5. the default line and the driver's command, no profiler
-python3 bench.py > $P/bench_default.json 2> $P/bench_default.err
-python3 bench.py --steps 20 --warmup 5 > $P/bench_driver_command.json 2> $P/bench_driver_command.err
+python3 bench.py --full > $P/bench_default.json 2> $P/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $P/bench_driver_command.json 2> $P/bench_driver_command.err
 python3 tools/summarize_profile_r06.py $P > $P/summary.log 2>&1; tail -30 $P/summary.log
 fi
 find $P -name "*kernel_trace.csv" -size +40M -delete
