@@ -1,0 +1,159 @@
+// tools/p2mx_bench.hip -- the width-16 Poseidon2 permutation with its full rounds' external layer on the int8 matrix cores
+// (p2_permute_mx_dev) against the all-VALU device form (p2_permute_dev), stand-alone, at the same states and the same wave count.
+//   ./tools/p2mx_bench [log_states] [chain]   log_states default 21 (states = lanes), chain = permutations per lane (default 32,
+//                                              the 256-wide leaf row of the headline shard)
+// Prints one JSON line: word-for-word mismatches of the two device forms (random states plus edge words, chains of 1 and 3, and the first
+// 256 states against the host's portable form), each kernel's resources, and min / median milliseconds of alternating timed launches.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/p2mx_bench tools/p2mx_bench.hip   (__graft_entry__.build() does)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../zktls_amd/csrc/poseidon2.cuh"
+
+namespace zk { P2Tables g_p2_tables = P2_BUILTIN; }
+using namespace zk;
+
+#define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("{\"error\": \"%s at line %d\"}\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
+
+__device__ __forceinline__ void load_state(const uint32_t* st, uint64_t i, uint32_t s[16]) {
+    const uint4* p = reinterpret_cast<const uint4*>(st + 16 * i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint4 v = p[k]; s[4 * k] = v.x; s[4 * k + 1] = v.y; s[4 * k + 2] = v.z; s[4 * k + 3] = v.w; }
+}
+__device__ __forceinline__ void store_state(uint32_t* st, uint64_t i, const uint32_t s[16]) {
+    uint4* p = reinterpret_cast<uint4*>(st + 16 * i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) p[k] = make_uint4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+}
+
+__global__ void __launch_bounds__(256) perm_vec_kernel(uint32_t* st, uint64_t n, int chain) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s[16];
+    load_state(st, i, s);
+    for (int c = 0; c < chain; c++) p2_permute_dev(s);
+    store_state(st, i, s);
+}
+// wave-cooperative: every lane runs the permutation; lanes past n work on state n - 1 and store nothing.  WPE = the register budget in
+// waves per SIMD (0: the compiler's own choice, 4 waves; 5 and 6 spill a few values outside the rounds' inner work)
+template <int WPE>
+__device__ __forceinline__ void perm_mx_body(uint32_t* st, uint64_t n, int chain) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t s[16];
+    load_state(st, i < n ? i : n - 1, s);
+    for (int c = 0; c < chain; c++) p2_permute_mx_dev(s);
+    if (i < n) store_state(st, i, s);
+}
+__global__ void __launch_bounds__(256) perm_mx_kernel(uint32_t* st, uint64_t n, int chain) { perm_mx_body<0>(st, n, chain); }
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) perm_mx5_kernel(uint32_t* st, uint64_t n, int chain) {
+    perm_mx_body<5>(st, n, chain);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) perm_mx6_kernel(uint32_t* st, uint64_t n, int chain) {
+    perm_mx_body<6>(st, n, chain);
+}
+
+static uint64_t splitmix(uint64_t& x) {
+    uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// random canonical words; the first states are edge words: all 0, all P - 1, all 1, all R mod P, 0 / P - 1 alternating both ways,
+// P - 1 in one position, and P / 2, P / 2 + 1 patterns
+static void fill_states(std::vector<uint32_t>& h, uint64_t n, uint64_t seed) {
+    for (uint64_t k = 0; k < 16 * n; k++) h[k] = (uint32_t)(splitmix(seed) % P);
+    const uint32_t edge[8] = {0u, P - 1, 1u, MONTY_R1, P / 2, P / 2 + 1, P - 2, 2u};
+    uint64_t e = 0;
+    for (int a = 0; a < 8 && e < n; a++, e++) for (int k = 0; k < 16; k++) h[16 * e + k] = edge[a];
+    for (int a = 0; a < 8 && e < n; a++, e++) for (int k = 0; k < 16; k++) h[16 * e + k] = ((k ^ a) & 1) ? edge[a] : edge[(a + 1) & 7];
+    for (int k = 0; k < 16 && e < n; k++, e++) for (int j = 0; j < 16; j++) h[16 * e + j] = j == k ? P - 1 : 0u;
+}
+
+static void launch(int form, uint32_t* d, uint64_t n, int chain) {
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (form == 3) perm_mx6_kernel<<<blocks, 256>>>(d, n, chain);
+    else if (form == 2) perm_mx5_kernel<<<blocks, 256>>>(d, n, chain);
+    else if (form == 1) perm_mx_kernel<<<blocks, 256>>>(d, n, chain);
+    else perm_vec_kernel<<<blocks, 256>>>(d, n, chain);
+    CK(hipGetLastError());
+}
+
+int main(int argc, char** argv) {
+    const int log_n = argc > 1 ? atoi(argv[1]) : 21;
+    const int chain = argc > 2 ? atoi(argv[2]) : 32;
+    if (log_n < 6 || log_n > 24 || chain < 1 || chain > 256) { printf("{\"error\": \"bad arguments\"}\n"); return 2; }
+    const uint64_t n = 1ull << log_n;
+    std::vector<uint32_t> h0(16 * n), ha(16 * n), hb(16 * n);
+    fill_states(h0, n, 0x5A4B544C53ull);
+    uint32_t *d0, *d1;
+    CK(hipMalloc(&d0, 16 * n * 4));
+    CK(hipMalloc(&d1, 16 * n * 4));
+
+    // correctness: both device forms, chains of 1 and 3, word for word; the first 256 states of chain 1 against the host form.
+    // A state count that is not a multiple of 64 exercises the partial last wave.
+    uint64_t mism = 0, host_mism = 0;
+    const uint64_t nchk = std::min<uint64_t>(n, 1u << 16) - 5;
+    for (int c : {1, 3})
+    for (int form : {1, 2, 3}) {
+        CK(hipMemcpy(d0, h0.data(), 16 * nchk * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d1, h0.data(), 16 * nchk * 4, hipMemcpyHostToDevice));
+        launch(0, d0, nchk, c);
+        launch(form, d1, nchk, c);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(ha.data(), d0, 16 * nchk * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hb.data(), d1, 16 * nchk * 4, hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < 16 * nchk; k++) mism += ha[k] != hb[k];
+        if (c == 1 && form == 1)
+            for (uint64_t i = 0; i < 256; i++) {
+                uint32_t s[16];
+                for (int k = 0; k < 16; k++) s[k] = h0[16 * i + k];
+                p2_permute_scalar(s);
+                for (int k = 0; k < 16; k++) host_mism += s[k] != hb[16 * i + k];
+            }
+    }
+
+    hipFuncAttributes fa, fb, fc, fd;
+    CK(hipFuncGetAttributes(&fd, reinterpret_cast<const void*>(perm_mx6_kernel)));
+    CK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(perm_vec_kernel)));
+    CK(hipFuncGetAttributes(&fb, reinterpret_cast<const void*>(perm_mx_kernel)));
+    CK(hipFuncGetAttributes(&fc, reinterpret_cast<const void*>(perm_mx5_kernel)));
+
+    // throughput: alternating launches on the same buffer contents, after one warm-up launch of each
+    CK(hipMemcpy(d0, h0.data(), 16 * n * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d1, h0.data(), 16 * n * 4, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    for (int form = 0; form < 4; form++) launch(form, form ? d1 : d0, n, chain);
+    CK(hipDeviceSynchronize());
+    const int reps = 7;
+    std::vector<float> t[4];
+    for (int r = 0; r < 4 * reps; r++) {
+        const int form = r % 4;
+        CK(hipEventRecord(e0));
+        launch(form, form ? d1 : d0, n, chain);
+        CK(hipEventRecord(e1));
+        CK(hipEventSynchronize(e1));
+        float ms = 0;
+        CK(hipEventElapsedTime(&ms, e0, e1));
+        t[form].push_back(ms);
+    }
+    for (auto& v : t) std::sort(v.begin(), v.end());
+    printf("{\"states\": %llu, \"chain\": %d, \"mismatches\": %llu, \"checked_words\": %llu, \"host_mismatches\": %llu, "
+           "\"vec_regs\": %d, \"mx_regs\": %d, \"mx5_regs\": %d, \"vec_scratch\": %d, \"mx_scratch\": %d, \"mx5_scratch\": %d, "
+           "\"vec_ms_min\": %.4f, \"vec_ms_med\": %.4f, \"mx_ms_min\": %.4f, \"mx_ms_med\": %.4f, \"mx5_ms_min\": %.4f, \"mx5_ms_med\": %.4f, "
+           "\"mx6_ms_min\": %.4f, \"mx6_ms_med\": %.4f, \"mx6_regs\": %d, \"mx6_scratch\": %d, "
+           "\"mx_over_vec_med\": %.4f, \"mx5_over_vec_med\": %.4f, \"mx6_over_vec_med\": %.4f}\n",
+           (unsigned long long)n, chain, (unsigned long long)mism, (unsigned long long)(4 * 16 * nchk), (unsigned long long)host_mism,
+           fa.numRegs, fb.numRegs, fc.numRegs, (int)fa.localSizeBytes, (int)fb.localSizeBytes, (int)fc.localSizeBytes,
+           t[0][0], t[0][reps / 2], t[1][0], t[1][reps / 2], t[2][0], t[2][reps / 2], t[3][0], t[3][reps / 2],
+           fd.numRegs, (int)fd.localSizeBytes, t[1][reps / 2] / t[0][reps / 2], t[2][reps / 2] / t[0][reps / 2], t[3][reps / 2] / t[0][reps / 2]);
+    CK(hipFree(d0));
+    CK(hipFree(d1));
+    return mism || host_mism ? 1 : 0;
+}

@@ -71,11 +71,14 @@ struct hash_rows_generic_kernel_bargs { LeafArgs a; uint32_t total_w; static has
 __global__ void __launch_bounds__(256) hash_rows_generic_kernel_batch(const hash_rows_generic_kernel_bargs* __restrict__ zk_arr) { const hash_rows_generic_kernel_bargs& zk_b = zk_arr[blockIdx.z]; hash_rows_generic_kernel_body(zk_b.a, zk_b.total_w); }
 
 
-// single matrix, width % 4 == 0, 16-byte aligned rows: 2 x dwordx4 per absorbed block
-__device__ __forceinline__ void hash_rows_vec_kernel_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) {
+// single matrix, width % 4 == 0, 16-byte aligned rows: 2 x dwordx4 per absorbed block.  The permutation is the matrix-core form
+// (p2_permute_mx_dev, wave-cooperative): a wave past the last row leaves as a whole, and in the last wave the lanes past it hash the last
+// row again and store nothing.  Its register budget is set to 5 waves per SIMD (the compiler's own choice is 4, and slower).
+template <bool MX>
+__device__ __forceinline__ void hash_rows_vec_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) {
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= height) return;
-    const uint4* rp = reinterpret_cast<const uint4*>(mat + row * ld);
+    if (MX ? row - __lane_id() >= height : row >= height) return;
+    const uint4* rp = reinterpret_cast<const uint4*>(mat + (row < height ? row : height - 1) * ld);
     uint32_t s[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) s[i] = 0u;
@@ -83,21 +86,26 @@ __device__ __forceinline__ void hash_rows_vec_kernel_body(const uint32_t* __rest
         uint4 v0 = rp[2 * q], v1 = rp[2 * q + 1];
         s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
         s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
-        p2_permute_dev(s);
+        if (MX) p2_permute_mx_dev(s); else p2_permute_dev(s);
     }
     if (width & 4u) {                       // a last half block: the other four rate words keep the state (overwrite mode)
         const uint4 v0 = rp[width / 4 - 1];
         s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
-        p2_permute_dev(s);
+        if (MX) p2_permute_mx_dev(s); else p2_permute_dev(s);
     }
+    if (row >= height) return;
     uint4* d = reinterpret_cast<uint4*>(digests + row * 8);
     d[0] = make_uint4(s[0], s[1], s[2], s[3]);
     d[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
-__global__ void __launch_bounds__(256) hash_rows_vec_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_kernel_body(mat, ld, width, height, digests); }
+__device__ __forceinline__ void hash_rows_vec_kernel_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_body<true>(mat, ld, width, height, digests); }
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) hash_rows_vec_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_kernel_body(mat, ld, width, height, digests); }
 struct hash_rows_vec_kernel_bargs { const uint32_t* mat; uint64_t ld; uint32_t width; uint64_t height; uint32_t* digests; static hash_rows_vec_kernel_bargs make(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* digests) { return hash_rows_vec_kernel_bargs{mat, ld, width, height, digests}; } };
-__global__ void __launch_bounds__(256) hash_rows_vec_kernel_batch(const hash_rows_vec_kernel_bargs* __restrict__ zk_arr) { const hash_rows_vec_kernel_bargs& zk_b = zk_arr[blockIdx.z]; hash_rows_vec_kernel_body(zk_b.mat, zk_b.ld, zk_b.width, zk_b.height, zk_b.digests); }
-
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) hash_rows_vec_kernel_batch(const hash_rows_vec_kernel_bargs* __restrict__ zk_arr) { const hash_rows_vec_kernel_bargs& zk_b = zk_arr[blockIdx.z]; hash_rows_vec_kernel_body(zk_b.mat, zk_b.ld, zk_b.width, zk_b.height, zk_b.digests); }
+#ifdef ZKHIP_AB_HOOKS
+// the all-VALU permutation in the same kernel, for A/B timing (ZKHIP_HASH_VEC_VALU set)
+__global__ void __launch_bounds__(256) hash_rows_vec_valu_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_body<false>(mat, ld, width, height, digests); }
+#endif
 
 // Several matrices of one height whose widths and pitches are multiples of 4 words (16-byte aligned rows): the sponge absorbs the
 // CONCATENATED row, so with quads as the unit a rate block is two consecutive quads of the virtual row, wherever the matrix boundaries
@@ -193,6 +201,13 @@ hipError_t launch_hash_rows(const LeafArgs& a, hipStream_t s) {
     const MatDesc& m0 = a.mats[0];
     bool vec = a.nmats == 1 && m0.width % 4 == 0 && m0.ld % 4 == 0 &&
                (reinterpret_cast<uintptr_t>(m0.ptr) & 15) == 0;
+#ifdef ZKHIP_AB_HOOKS
+    static const bool valu = getenv("ZKHIP_HASH_VEC_VALU") != nullptr;
+    if (vec && valu) {
+        hash_rows_vec_valu_kernel<<<grid, block, 0, s>>>(m0.ptr, m0.ld, m0.width, a.height, a.digests);
+        return hipGetLastError();
+    }
+#endif
     if (vec)
         ZK_LAUNCH(hash_rows_vec_kernel, hash_rows_vec_kernel_batch, hash_rows_vec_kernel_bargs, grid, block, 0, s, m0.ptr, m0.ld, m0.width, a.height, a.digests);
     else if (leaf_mats_vec(a))
