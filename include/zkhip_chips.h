@@ -162,6 +162,45 @@ typedef struct zkhip_fri_job {
 int zkhip_prove_fri_indices_batch(const int* devices, int n_devices, zkhip_fri_job* jobs, int n_jobs, int log_n, uint32_t width,
                                   const zkhip_params* inner, const zkhip_params* outer, int in_flight_per_device, int verify);
 
+/* ---- the FRI check of a FOLD-BY-16 proof in-circuit (the RISC Zero shape, log_fold = 4: zkhip_prove_segment and every prover given that shape): the FOLD16
+ * and FINAL chips (fri16_chip.hip), two of the pieces a lift -> join needs (prover.rs:90) beside the width-24 Poseidon2 chip above.  With
+ * R = (log_n - log_final) / 4 committed layers a query reads, per layer, a row of 16 adjacent extension entries, folds it four times by 2 with beta, beta^2,
+ * beta^4, beta^8, and after R layers compares with the final polynomial (2^log_final coefficients) at its last point.
+ * zkhip_fri16_view_shard runs the host verifier on a proof zkhip_verify_shard accepts with log_fold = 4 (versions 3 and 8, either hash width, with or without
+ * lookups and code groups) and hands out, in canonical words: betas [R][4], final_poly [2^F][4], per query the index, the reduced opening values [Q][4], the 15
+ * other entries of every layer row in proof order siblings [Q][R][15][4], and -- roots / paths may be NULL -- the layer roots [R][8] and per query the layers'
+ * authentication paths one after the other (8 (log_n + log_blowup - 4 (l + 1)) words for layer l; zkhip_fri16_view_path_words per query).  It fails like
+ * zkhip_verify_shard when the proof is rejected; zkhip_fri_view_shard keeps refusing these proofs.
+ * The machine (proof version 11, zkhip_prove_machine_keyed; any outer shape machines take) proves, for the public challenges beta_0 .. beta_{R-1} and the key:
+ * "every query listed in QUERIES, taken as entry index & 15 of row index >> 4 of layer 0, folds through rows listed in LAYERS -- each listed row read exactly
+ * as often as listed -- at the points its index fixes, to the value at its last point of the polynomial whose coefficients are listed in COEFFS."  Five tables,
+ * tallest first (equal heights by table number): 0 FOLD16 (main, one row per (query, layer)), 1 FINAL (Horner, one block of 2^F rows per query; its schedule is
+ * preprocessed), and the preprocessed 2 LAYERS (distinct (layer, row) with the 16 entries and the number of readers), 3 QUERIES ((index, reduced opening) with
+ * multiplicity), 4 COEFFS.  zkhip_fri16_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..4), its height and
+ * widths, and which table it is.  zkhip_fri16_key_host (no GPU) / zkhip_fri16_key: the preprocessed tables of a view and their commitment vk -- what a verifier
+ * recomputes from the inner proof.  zkhip_fri16_gen_traces: the two main traces alone on the device (d_fold [2^lr][ld_fold], d_final [2^lr][ld_final], 16-byte
+ * aligned, ld a multiple of 4).  zkhip_prove_fri16 is handed the view and refuses, before proving, one whose chains do not end in the final polynomial;
+ * zkhip_verify_fri16 is host only.  Shapes: 1 <= R <= 5, 0 <= log_final <= 8, log_final + log_blowup <= 11, 4 R + log_final + log_blowup <= 27, up to 1024
+ * queries; anything else is refused with a message.
+ * NOT in-circuit yet: the Merkle paths of the layer rows (LAYERS is the table a bus variant of the width-24 chip replaces: its leaf rows will receive the tuples
+ * (layer, 16 row + j, entry) FOLD16 sends), the transcript (challenges, query indices), the reduced openings; the shard verifier machines do not use these chips. */
+size_t zkhip_fri16_view_path_words(int log_n, const zkhip_params* prm);
+int zkhip_fri16_view_shard(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                           uint32_t* betas, uint32_t* final_poly, uint32_t* indices, uint32_t* values, uint32_t* siblings, uint32_t* roots, uint32_t* paths);
+size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                            uint32_t* pre_width, int* table);
+int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                         const uint32_t* siblings, const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                    const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+int zkhip_fri16_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                           const uint32_t* values, const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final);
+size_t zkhip_fri16_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm);
+int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly,
+                      const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
+                       int* reason);
+
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */
 int zkhip_air_synthetic(uint32_t width, size_t n_public, uint32_t* out, size_t cap, size_t* words);

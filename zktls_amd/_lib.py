@@ -48,6 +48,8 @@ EXPORTS = [
     "zkhip_prove_fri_indices_batch", "zkhip_fri_view_all",
     "zkhip_p2chip_air", "zkhip_p2chip_gen_merkle_trace", "zkhip_merkle_paths_proof_size", "zkhip_prove_merkle_paths", "zkhip_verify_merkle_paths",
     "zkhip_p24chip_air", "zkhip_p24chip_gen_merkle_trace", "zkhip_merkle_paths_p24_proof_size", "zkhip_prove_merkle_paths_p24", "zkhip_verify_merkle_paths_p24",
+    "zkhip_fri16_view_path_words", "zkhip_fri16_view_shard", "zkhip_fri16_describe", "zkhip_fri16_key_host", "zkhip_fri16_key", "zkhip_fri16_gen_traces", "zkhip_fri16_proof_size",
+    "zkhip_prove_fri16", "zkhip_verify_fri16",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -325,6 +327,20 @@ def load():
     L.zkhip_merkle_paths_p24_proof_size.argtypes = [C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Params)]
     L.zkhip_prove_merkle_paths_p24.argtypes = [C.c_void_p, u32p, C.c_uint32, u32p, u32p, C.c_size_t, C.c_int, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
     L.zkhip_verify_merkle_paths_p24.argtypes = [u8p, C.c_size_t, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int)]
+    L.zkhip_fri16_view_path_words.restype = C.c_size_t
+    L.zkhip_fri16_view_path_words.argtypes = [C.c_int, C.POINTER(Params)]
+    L.zkhip_fri16_view_shard.argtypes = [u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), u32p, u32p, u32p, u32p, u32p, u32p, u32p]
+    L.zkhip_fri16_describe.restype = C.c_size_t
+    L.zkhip_fri16_describe.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_int)]
+    fri16_view = [C.c_int, C.c_int, C.c_int, C.c_size_t, u32p, u32p, u32p, u32p, u32p]          # R, F, log_blowup, queries, betas, final_poly, indices, values, siblings
+    L.zkhip_fri16_key_host.argtypes = fri16_view + [C.POINTER(Params), u32p]
+    L.zkhip_fri16_key.argtypes = [C.c_void_p] + fri16_view + [C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_gen_traces.argtypes = [C.c_void_p] + fri16_view + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.zkhip_fri16_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_proof_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(Params)]
+    L.zkhip_prove_fri16.argtypes = [C.c_void_p, C.c_void_p] + fri16_view + [C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -1,0 +1,552 @@
+// fri16_chip.hip -- the FRI check of a FOLD-BY-16 proof (the RISC Zero shape: zkhip_prove_segment, log_fold = 4) inside a proof: the FOLD16 and FINAL chips.
+//
+// The RISC Zero side's lift -> join (prover.rs:90) needs, beside the width-24 Poseidon2 chip (poseidon2_chip.cpp), a chip that folds rows of 16 entries and
+// one that evaluates the final polynomial at every query's last point.  This file is those two as a keyed machine of its own, the way fri_chip.hip's first
+// generation was for the SP1 shape.  With H = log_n + log_blowup, R = (log_n - F) / 4 committed layers, lf = F + log_blowup: layer l is a matrix of 2^lh
+// rows, lh = H - 4 (l + 1), of 16 adjacent extension entries; a query (idx, val) reads row idx >> 4, puts val at position idx & 15, folds the row four times
+// by 2 with beta, beta^2, beta^4, beta^8 and goes on with (idx >> 4, folded); after R layers the value must be sum_j c_j xf^j, xf = w_{2^lf}^bitrev(idx, lf).
+// With row = idx >> 4 and x0 = w_{2^(lh+4)}^bitrev(row, lh): fold step s folds pair t at x0^(2^s) w_{2^(4-s)}^bitrev(t, 3-s); x0 = prod_i w_{2^(i+5)}^bit_i(row);
+// the next row's x0' = x0^16 w_16^(-bitrev(row & 15, 4)); after the last layer x0^16 = xf.
+//
+// Statement (public values: beta_0 .. beta_{R-1}; the key commits LAYERS, QUERIES, COEFFS):
+//     "every query listed in QUERIES, taken as entry index & 15 of row index >> 4 of layer 0, folds through rows listed in LAYERS -- each listed row read
+//      exactly as often as listed -- at the points its index fixes, to the value at its last point of the polynomial whose coefficients are listed in COEFFS"
+// Five tables (machine order: tallest first, equal heights by the numbers below):
+//   0 FOLD16   main, one row per (query, layer): the 16 entries, the 8 + 4 + 2 + 1 folds, beta and its squarings, x0, 1 / x0 and their squarings, the row
+//              index, the own position as sixteen one-hot flags, layer selectors, and the BACKWARD product B = T B' (T: the factor of the own position's
+//              nibble in the chain's FIRST x0; on the last row times TL, the factor of the lf bits left of ROW, held as up to three one-hot nibbles) with
+//              X = B on a chain's first row: the forward recurrence alone fixes x0 only up to a 16^R-th root of unity.  Columns: fri16_rows.cuh.
+//              Sends the 16 entries (LN, 16 ROW + j, E_j) to LAYERS, (IDX, OWN) on a chain's first row to QUERIES, (X16, FOLD) on its last row to FINAL.
+//   1 FINAL    one block of 2^F rows per query, Horner from the top coefficient down.  Preprocessed schedule J FIRST LAST ACT NL; main C ACC AX = ACC X, X.
+//              Receives (J, C) from COEFFS on every row and (X, ACC) from FOLD16 on a block's last row: the multiset of chain ends = that of block ends.
+//   2 LAYERS   preprocessed: per distinct (layer, row), ascending: LN, the 16 keys, the number of queries reading it, the 16 entries.  THE TABLE A
+//              WIDTH-24 POSEIDON2 CHIP ON THE SAME BUS REPLACES (its leaf rows then receive these tuples): until then the rows' Merkle paths are NOT proven.
+//   3 QUERIES  preprocessed: distinct (index, reduced opening) with multiplicity.       4 COEFFS  preprocessed: (j, c_j, queries).
+// NOT in this machine: the Merkle paths of the layer rows, the transcript (challenges, query indices), the reduced openings.  tests/fri16_air.py writes
+// the programs, tables and traces independently; the words must be equal.
+#include <algorithm>
+#include <array>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "air.h"
+#include "context.h"
+#include "batch.h"
+#include "fri16_rows.cuh"
+
+namespace zk {
+namespace fri16 {
+namespace {
+
+constexpr uint32_t BUS_L16 = 70, BUS_Q16 = 71, BUS_FIN16 = 72, BUS_COEF = 73;
+constexpr uint32_t FJ = 0, FFIRST = 1, FLAST = 2, FACT = 3, FNL = 4;                                  // FINAL's schedule; its main columns in the combined row:
+constexpr uint32_t CFC = FIN_PRE + FC, CFACC = FIN_PRE + FACC, CFAX = FIN_PRE + FAX, CFX = FIN_PRE + FX;
+constexpr uint32_t LAY_PRE = 84, LAY_LN = 0, LAY_KEY = 1, LAY_M = 17, LAY_E = 20, Q_PRE = 8, C_PRE = 8, TAB_MAIN = 4;
+enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_QUERIES = 3, T_COEFFS = 4 };
+
+struct Term { uint32_t coeff; std::vector<uint32_t> vars; };
+typedef std::vector<Term> Terms;
+inline uint32_t var(uint32_t col, bool next = false) { return next ? ((1u << 30) | col) : col; }
+inline uint32_t pub(uint32_t idx) { return (2u << 30) | idx; }
+inline uint32_t neg(uint64_t c) { c %= P; return c ? (uint32_t)(P - c) : 0u; }
+inline uint32_t mulm(uint64_t a, uint64_t b) { return (uint32_t)((a % P) * (b % P) % P); }
+enum : uint32_t { ALL = 0, FIRST = 1, LAST = 2, TRANSITION = 3 };
+struct Builder {
+    std::vector<uint32_t> body;
+    uint32_t count = 0;
+    void add(uint32_t selector, const Terms& terms) {
+        body.push_back(selector);
+        const size_t at = body.size();
+        body.push_back(0u);
+        uint32_t kept = 0;
+        for (const Term& t : terms) {
+            if (t.coeff % P == 0) continue;
+            body.push_back(t.coeff % P);
+            body.push_back((uint32_t)t.vars.size());
+            for (uint32_t v : t.vars) body.push_back(v);
+            kept++;
+        }
+        body[at] = kept;
+        count++;
+    }
+    std::vector<uint32_t> finish(uint32_t width, uint32_t n_public) const {
+        std::vector<uint32_t> p{AIR_MAGIC, 1u, width, count, n_public, (uint32_t)(6 + body.size())};
+        p.insert(p.end(), body.begin(), body.end());
+        return p;
+    }
+};
+inline uint32_t canon_nibble_factor(uint32_t first_bit, uint32_t nbits, uint32_t j) { return from_monty(nibble_factor(first_bit, nbits, j)); }
+
+struct Shape {
+    int R = 0, F = 0, b = 0, lf = 0, H = 0;
+    size_t Q = 0;
+    int log_rows[5];            // by table number
+    int order[5];               // machine position -> table number
+    uint32_t main_w[5], pre_w[5];
+};
+inline int lg(size_t n) { int l = 5; while (((size_t)1 << l) < n) l++; return l; }
+int shape_of(int R, int F, int b, size_t Q, Shape& s) {
+    if (R < 1 || R > MAX_R || F < 0 || F > MAX_F || b < 1 || b > 3 || F + b > MAX_LF || Q < 1 || Q > MAX_Q || 4 * R + F + b > TWO_ADICITY)
+        return fail(ZKHIP_ERR_INVALID, "fri16: 1..5 layers, log_final 0..8, log_blowup 1..3 (log_final + log_blowup <= 11), 1..1024 queries, and a domain of at most 2^27 points");
+    s.R = R; s.F = F; s.b = b; s.lf = F + b; s.H = 4 * R + s.lf; s.Q = Q;
+    const int lr[5] = {lg(Q * (size_t)R), lg(Q << F), lg(Q * (size_t)R), lg(Q), lg((size_t)1 << F)};
+    const uint32_t mw[5] = {fold16_width((uint32_t)s.lf), FIN_MAIN, TAB_MAIN, TAB_MAIN, TAB_MAIN}, pw[5] = {0u, FIN_PRE, LAY_PRE, Q_PRE, C_PRE};
+    for (int i = 0; i < 5; i++) { s.log_rows[i] = lr[i]; s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
+    std::stable_sort(s.order, s.order + 5, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    return ZKHIP_OK;
+}
+
+std::vector<uint32_t> build_fold16_program(int R, int lf) {
+    Builder b;
+    const uint32_t END = L + (uint32_t)R - 1u, W = fold16_width((uint32_t)lf), inv2 = (P + 1) / 2;
+    const W16Inv w16 = w16_inverse_powers();
+    auto ext_product = [&](uint32_t out, uint32_t x, uint32_t y) {      // out = x y in F_p[t] / (t^4 - 11)
+        for (uint32_t c = 0; c < 4; c++) {
+            Terms t{{1u, {var(out + c)}}};
+            for (uint32_t i = 0; i < 4; i++)
+                for (uint32_t j = 0; j < 4; j++)
+                    if ((i + j) % 4 == c) t.push_back(Term{neg(i + j >= 4 ? EXT_W : 1u), {var(x + i), var(y + j)}});
+            b.add(ALL, t);
+        }
+    };
+    {
+        Terms t{{1u, {var(ACTIVE)}}}, n{{1u, {var(LN)}}};
+        for (int l = 0; l < R; l++) { t.push_back(Term{P - 1, {var(L + l)}}); n.push_back(Term{neg((uint64_t)l), {var(L + l)}}); }
+        b.add(ALL, t);
+        b.add(ALL, n);
+    }
+    b.add(ALL, Terms{{1u, {var(ACTIVE), var(ACTIVE)}}, {P - 1, {var(ACTIVE)}}});
+    for (int l = 0; l < 8; l++) {
+        if (l < R) b.add(ALL, Terms{{1u, {var(L + l), var(L + l)}}, {P - 1, {var(L + l)}}});
+        else b.add(ALL, Terms{{1u, {var(L + l)}}});
+    }
+    for (uint32_t j = 0; j < 16; j++) b.add(ALL, Terms{{1u, {var(OF + j), var(OF + j)}}, {P - 1, {var(OF + j)}}});
+    {
+        Terms t{{1u, {var(ACTIVE)}}};
+        for (uint32_t j = 0; j < 16; j++) t.push_back(Term{P - 1, {var(OF + j)}});
+        b.add(ALL, t);
+    }
+    for (uint32_t c = 0; c < 4; c++) {      // BETA = the layer's public challenge
+        Terms t{{1u, {var(BETA + c)}}};
+        for (int l = 0; l < R; l++) t.push_back(Term{P - 1, {var(L + l), pub(4u * (uint32_t)l + c)}});
+        b.add(ALL, t);
+    }
+    ext_product(B2, BETA, BETA);
+    ext_product(B4, B2, B2);
+    ext_product(B8, B4, B4);
+    b.add(ALL, Terms{{1u, {var(G)}}, {P - 1, {var(ACTIVE)}}, {1u, {var(END)}}});
+    const uint32_t squares[7][2] = {{X2, X}, {X4, X2}, {X8, X4}, {X16, X8}, {XI2, XI}, {XI4, XI2}, {XI8, XI4}};
+    for (const auto& sq : squares) b.add(ALL, Terms{{1u, {var(sq[0])}}, {P - 1, {var(sq[1]), var(sq[1])}}});
+    b.add(ALL, Terms{{1u, {var(ACTIVE), var(X), var(XI)}}, {P - 1, {var(ACTIVE)}}});
+    b.add(ALL, Terms{{1u, {var(GX16)}}, {P - 1, {var(G), var(X16)}}});
+    b.add(ALL, Terms{{1u, {var(GT)}}, {P - 1, {var(G), var(T)}}});
+    {
+        Terms t{{1u, {var(IDX)}}, {P - 16, {var(ROW)}}};
+        for (uint32_t j = 0; j < 16; j++) t.push_back(Term{neg(j), {var(OF + j)}});
+        b.add(ALL, t);
+    }
+    for (uint32_t j = 0; j < 16; j++) b.add(ALL, Terms{{1u, {var(KJ + j)}}, {P - 16, {var(ROW)}}, {neg(j), {var(ACTIVE)}}});
+    for (uint32_t c = 0; c < 4; c++) {      // OWN = sum_j O_j E_j
+        Terms t{{1u, {var(OWN + c)}}};
+        for (uint32_t j = 0; j < 16; j++) t.push_back(Term{P - 1, {var(OF + j), var(E + 4 * j + c)}});
+        b.add(ALL, t);
+    }
+    const uint32_t step_in[4] = {E, F1, F2, F3}, step_out[4] = {F1, F2, F3, FOLD}, step_beta[4] = {BETA, B2, B4, B8}, step_xi[4] = {XI, XI2, XI4, XI8};
+    for (uint32_t s = 0; s < 4; s++)        // out = (e0 + e1)/2 + beta_s (e0 - e1) xi_s c / 2, c = 1 / w_{2^(4-s)}^bitrev(t, 3-s)
+        for (uint32_t t = 0; t < (8u >> s); t++) {
+            const uint32_t e0 = step_in[s] + 8 * t, e1 = e0 + 4, ci = from_monty(w16.v[step_exponent(s, t)]);
+            for (uint32_t c = 0; c < 4; c++) {
+                Terms ts{{1u, {var(step_out[s] + 4 * t + c)}}, {neg(inv2), {var(e0 + c)}}, {neg(inv2), {var(e1 + c)}}};
+                for (uint32_t a = 0; a < 4; a++)
+                    for (uint32_t d = 0; d < 4; d++) {
+                        if ((a + d) % 4 != c) continue;
+                        const uint32_t w = mulm(mulm(inv2, ci), a + d >= 4 ? EXT_W : 1u);
+                        ts.push_back(Term{neg(w), {var(step_beta[s] + a), var(e0 + d), var(step_xi[s])}});
+                        ts.push_back(Term{w, {var(step_beta[s] + a), var(e1 + d), var(step_xi[s])}});
+                    }
+                b.add(ALL, ts);
+            }
+        }
+    {   // T = L_0 + sum_{l >= 1} sum_j (factor of nibble l - 1 holding j) L_l O_j
+        Terms t{{1u, {var(T)}}, {P - 1, {var(L)}}};
+        for (int l = 1; l < R; l++)
+            for (uint32_t j = 0; j < 16; j++) t.push_back(Term{neg(canon_nibble_factor(4u * (uint32_t)(l - 1), 4u, j)), {var(L + l), var(OF + j)}});
+        b.add(ALL, t);
+    }
+    // the last row's nibbles: one-hot on a last row, zero elsewhere; their linear forms
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> forms;
+    uint32_t col = N;
+    for (uint32_t k = 0; k < 3 && nibble_bits((uint32_t)lf, k); k++) {
+        const uint32_t nb = nibble_bits((uint32_t)lf, k);
+        Terms sum{{1u, {var(END)}}};
+        std::vector<std::pair<uint32_t, uint32_t>> form;
+        for (uint32_t j = 0; j < (1u << nb); j++) b.add(ALL, Terms{{1u, {var(col + j), var(col + j)}}, {P - 1, {var(col + j)}}});
+        for (uint32_t j = 0; j < (1u << nb); j++) {
+            sum.push_back(Term{P - 1, {var(col + j)}});
+            form.push_back({canon_nibble_factor(4u * (uint32_t)(R - 1) + 4u * k, nb, j), col + j});
+        }
+        b.add(ALL, sum);
+        forms.push_back(form);
+        col += 1u << nb;
+    }
+    for (uint32_t c = col; c < W; c++) b.add(ALL, Terms{{1u, {var(c)}}});
+    {
+        Terms t{{1u, {var(END), var(ROW)}}};
+        uint32_t c0 = N;
+        for (uint32_t k = 0; k < forms.size(); k++) {
+            const uint32_t nb = nibble_bits((uint32_t)lf, k);
+            for (uint32_t j = 0; j < (1u << nb); j++) t.push_back(Term{neg((uint64_t)j << (4 * k)), {var(c0 + j)}});
+            c0 += 1u << nb;
+        }
+        b.add(ALL, t);
+    }
+    {
+        Terms u{{1u, {var(U)}}};
+        if (forms.size() == 1) for (const auto& f : forms[0]) u.push_back(Term{neg(f.first), {var(f.second)}});
+        else for (const auto& f0 : forms[0]) for (const auto& f1 : forms[1]) u.push_back(Term{neg(mulm(f0.first, f1.first)), {var(f0.second), var(f1.second)}});
+        b.add(ALL, u);
+        Terms tl{{1u, {var(TL)}}};
+        if (forms.size() == 3) for (const auto& f : forms[2]) tl.push_back(Term{neg(f.first), {var(U), var(f.second)}});
+        else tl.push_back(Term{P - 1, {var(U)}});
+        b.add(ALL, tl);
+    }
+    b.add(ALL, Terms{{1u, {var(END), var(B)}}, {P - 1, {var(END), var(T), var(TL)}}});
+    b.add(ALL, Terms{{1u, {var(L), var(X)}}, {P - 1, {var(L), var(B)}}});
+    // the chain
+    for (int l = 0; l + 1 < R; l++) b.add(TRANSITION, Terms{{1u, {var(L + l + 1, true)}}, {P - 1, {var(L + l)}}});
+    b.add(TRANSITION, Terms{{1u, {var(G), var(ROW)}}, {P - 1, {var(G), var(IDX, true)}}});
+    {
+        Terms t{{1u, {var(G), var(X, true)}}};
+        for (uint32_t j = 0; j < 16; j++) t.push_back(Term{neg(from_monty(w16.v[reverse_bits(j, 4)])), {var(GX16), var(OF + j, true)}});
+        b.add(TRANSITION, t);
+    }
+    b.add(TRANSITION, Terms{{1u, {var(G), var(B)}}, {P - 1, {var(GT), var(B, true)}}});
+    for (uint32_t c = 0; c < 4; c++) b.add(TRANSITION, Terms{{1u, {var(G), var(FOLD + c)}}, {P - 1, {var(G), var(OWN + c, true)}}});
+    b.add(FIRST, Terms{{1u, {var(ACTIVE)}}, {P - 1, {var(L)}}});
+    b.add(LAST, Terms{{1u, {var(G)}}});
+    return b.finish(W, 4u * (uint32_t)R);
+}
+std::vector<uint32_t> build_final_program(int R) {
+    Builder b;
+    for (uint32_t c = 0; c < 4; c++) b.add(ALL, Terms{{1u, {var(CFAX + c)}}, {P - 1, {var(CFACC + c), var(CFX)}}});
+    for (uint32_t c = 0; c < 4; c++) b.add(ALL, Terms{{1u, {var(FFIRST), var(CFACC + c)}}, {P - 1, {var(FFIRST), var(CFC + c)}}});
+    b.add(TRANSITION, Terms{{1u, {var(FNL), var(CFX, true)}}, {P - 1, {var(FNL), var(CFX)}}});
+    for (uint32_t c = 0; c < 4; c++)
+        b.add(TRANSITION, Terms{{1u, {var(FNL), var(CFACC + c, true)}}, {P - 1, {var(FNL), var(CFAX + c)}}, {P - 1, {var(FNL), var(CFC + c, true)}}});
+    return b.finish(FIN_PRE + FIN_MAIN, 4u * (uint32_t)R);
+}
+std::vector<uint32_t> build_table_program(int R, uint32_t pre_width) {          // the contents are fixed by the KEY: one harmless identity
+    return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + TAB_MAIN, 1u, 4u * (uint32_t)R, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + TAB_MAIN - 1u)};
+}
+std::vector<uint32_t> build_interactions(int R, int table) {
+    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
+    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
+        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
+        v.insert(v.end(), cols.begin(), cols.end());
+        v[1]++;
+    };
+    switch (table) {
+    case T_FOLD16:
+        for (uint32_t j = 0; j < 16; j++) add(0u, ACTIVE, BUS_L16, {LN, KJ + j, E + 4 * j, E + 4 * j + 1, E + 4 * j + 2, E + 4 * j + 3});
+        add(0u, L, BUS_Q16, {IDX, OWN, OWN + 1, OWN + 2, OWN + 3});
+        add(0u, L + (uint32_t)R - 1u, BUS_FIN16, {X16, FOLD, FOLD + 1, FOLD + 2, FOLD + 3});
+        break;
+    case T_FINAL:
+        add(1u, FACT, BUS_COEF, {FJ, CFC, CFC + 1, CFC + 2, CFC + 3});
+        add(1u, FLAST, BUS_FIN16, {CFX, CFACC, CFACC + 1, CFACC + 2, CFACC + 3});
+        break;
+    case T_LAYERS:
+        for (uint32_t j = 0; j < 16; j++) add(1u, LAY_M, BUS_L16, {LAY_LN, LAY_KEY + j, LAY_E + 4 * j, LAY_E + 4 * j + 1, LAY_E + 4 * j + 2, LAY_E + 4 * j + 3});
+        break;
+    case T_QUERIES: add(1u, 5u, BUS_Q16, {0u, 1u, 2u, 3u, 4u}); break;
+    default: add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u}); break;
+    }
+    v[2] = (uint32_t)v.size();
+    return v;
+}
+
+// programs and interaction tables of a shape, in MACHINE order, with the arrays the keyed-machine entries take
+struct Machine {
+    Shape s;
+    std::vector<uint32_t> prog[5], tab[5];
+    int32_t log_ns[5]; uint32_t widths[5], pre_widths[5];
+    const uint32_t* progs[5]; size_t prog_words[5]; const uint32_t* tabs[5]; size_t tab_words[5];
+};
+std::shared_ptr<const Machine> machine_of(const Shape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 4>, std::shared_ptr<const Machine>> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    const std::array<uint64_t, 4> key{(uint64_t)s.R, (uint64_t)s.F, (uint64_t)s.b, (uint64_t)s.Q};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<Machine>();
+    m->s = s;
+    for (int i = 0; i < 5; i++) {
+        const int t = s.order[i];
+        m->prog[i] = t == T_FOLD16 ? build_fold16_program(s.R, s.lf) : t == T_FINAL ? build_final_program(s.R) : build_table_program(s.R, s.pre_w[t]);
+        m->tab[i] = build_interactions(s.R, t);
+        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
+        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
+    }
+    if (cache.size() > 64) cache.clear();
+    cache.emplace(key, m);
+    return m;
+}
+
+inline Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
+bool canonical(const uint32_t* v, size_t n) { for (size_t i = 0; i < n; i++) if (v[i] >= P) return false; return true; }
+int check_view(const Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const char* who) {
+    if (!betas || !final_poly || !indices || !values || !siblings) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(betas, 4 * (size_t)s.R) || !canonical(final_poly, (size_t)4 << s.F) || !canonical(values, 4 * s.Q) || !canonical(siblings, 60 * s.Q * (size_t)s.R))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    return ZKHIP_OK;
+}
+// the fold of one row on the host (the kernels' arithmetic, portable forms)
+Ext fold_row_host(uint32_t row, int lh, const Ext& beta, const Ext* entries) {
+    const W16Inv w16 = w16_inverse_powers();
+    const uint32_t w = two_adic_generator(lh + 4), br = reverse_bits(row, lh), mask = (1u << (lh + 4)) - 1u;
+    uint32_t xi = fpow(w, (mask + 1u - br) & mask);
+    Ext cur[16], bs = beta;
+    for (int j = 0; j < 16; j++) cur[j] = entries[j];
+    for (uint32_t s = 0; s < 4; s++) {
+        for (uint32_t t = 0; t < (8u >> s); t++) {
+            const Ext even = ext_mul_base(ext_add(cur[2 * t], cur[2 * t + 1]), MONTY_INV2);
+            const Ext odd = ext_mul_base(ext_sub(cur[2 * t], cur[2 * t + 1]), fmul(fmul(xi, MONTY_INV2), w16.v[step_exponent(s, t)]));
+            cur[t] = ext_add(even, ext_mul(bs, odd));
+        }
+        bs = ext_mul(bs, bs);
+        xi = fmul(xi, xi);
+    }
+    return cur[0];
+}
+// The three key tables and FINAL's schedule from a view (host, canonical -> Montgomery), by table number.  Walks every chain: queries that meet must
+// agree about the row, and every chain must end in the final polynomial at its last point -- a view taken from an accepted proof always does.
+int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings,
+                 std::vector<uint32_t> pre[5]) {
+    const size_t R = (size_t)s.R, n = (size_t)1 << s.F;
+    std::map<std::pair<uint32_t, uint32_t>, std::pair<std::array<uint32_t, 64>, uint32_t>> layers;      // (layer, row) -> entries (Montgomery), count
+    std::map<std::array<uint32_t, 5>, uint32_t> queries;                                                 // (index, value) canonical -> count
+    for (size_t q = 0; q < s.Q; q++) {
+        std::array<uint32_t, 5> qk{indices[q], values[4 * q], values[4 * q + 1], values[4 * q + 2], values[4 * q + 3]};
+        queries[qk]++;
+        uint32_t idx = indices[q];
+        Ext val = ext_from_canon(values + 4 * q);
+        for (size_t l = 0; l < R; l++) {
+            const uint32_t row = idx >> 4, own = idx & 15u;
+            const int lh = s.H - 4 * ((int)l + 1);
+            Ext e[16];
+            const uint32_t* sib = siblings + 60 * (q * R + l);
+            for (uint32_t j = 0, k = 0; j < 16; j++) e[j] = j == own ? val : ext_from_canon(sib + 4 * k++);
+            std::array<uint32_t, 64> flat;
+            for (int j = 0; j < 16; j++) for (int c = 0; c < 4; c++) flat[4 * j + c] = e[j].c[c];
+            auto it = layers.find({(uint32_t)l, row});
+            if (it == layers.end()) layers.emplace(std::make_pair((uint32_t)l, row), std::make_pair(flat, 1u));
+            else {
+                if (it->second.first != flat) return fail(ZKHIP_ERR_INVALID, "fri16: two queries disagree about a layer row");
+                it->second.second++;
+            }
+            val = fold_row_host(row, lh, ext_from_canon(betas + 4 * l), e);
+            idx = row;
+        }
+        const uint32_t xf = fpow(two_adic_generator(s.lf), reverse_bits(idx, s.lf));
+        Ext v = ext_zero();
+        for (size_t i = n; i-- > 0;) v = ext_add(ext_mul_base(v, xf), ext_from_canon(final_poly + 4 * i));
+        if (!ext_eq(v, val)) return fail(ZKHIP_ERR_INVALID, "fri16: the chain of query " + std::to_string(q) + " does not end in the final polynomial");
+    }
+    for (int t = 1; t < 5; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
+    pre[0].clear();
+    for (size_t r = 0; r < s.Q * n; r++) {
+        uint32_t* w = pre[T_FINAL].data() + FIN_PRE * r;
+        const size_t i = r & (n - 1);
+        w[FJ] = to_monty((uint32_t)(n - 1 - i)); w[FFIRST] = i == 0 ? MONTY_R1 : 0u; w[FLAST] = i == n - 1 ? MONTY_R1 : 0u; w[FACT] = MONTY_R1; w[FNL] = i == n - 1 ? 0u : MONTY_R1;
+    }
+    size_t r = 0;
+    for (const auto& e : layers) {
+        uint32_t* w = pre[T_LAYERS].data() + LAY_PRE * r++;
+        w[LAY_LN] = to_monty(e.first.first);
+        for (uint32_t j = 0; j < 16; j++) w[LAY_KEY + j] = to_monty(16u * e.first.second + j);
+        w[LAY_M] = to_monty(e.second.second);
+        std::memcpy(w + LAY_E, e.second.first.data(), 256);
+    }
+    r = 0;
+    for (const auto& e : queries) {
+        uint32_t* w = pre[T_QUERIES].data() + Q_PRE * r++;
+        for (int i = 0; i < 5; i++) w[i] = to_monty(e.first[i]);
+        w[5] = to_monty(e.second);
+    }
+    for (size_t j = 0; j < n; j++) {
+        uint32_t* w = pre[T_COEFFS].data() + C_PRE * j;
+        w[0] = to_monty((uint32_t)j);
+        for (int i = 0; i < 4; i++) w[1 + i] = to_monty(final_poly[4 * j + i]);
+        w[5] = to_monty((uint32_t)s.Q);
+    }
+    return ZKHIP_OK;
+}
+
+struct fold_rows_bargs { FoldRowsArgs a; static fold_rows_bargs make(FoldRowsArgs a) { return fold_rows_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_fold_rows_kernel_batch(const fold_rows_bargs* __restrict__ zk_arr) { fri16_fold_rows_body(zk_arr[blockIdx.z].a); }
+struct final_rows_bargs { FinalRowsArgs a; static final_rows_bargs make(FinalRowsArgs a) { return final_rows_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_final_rows_kernel_batch(const final_rows_bargs* __restrict__ zk_arr) { fri16_final_rows_body(zk_arr[blockIdx.z].a); }
+
+}  // namespace
+}  // namespace fri16
+}  // namespace zk
+
+using namespace zk;
+
+#define CHECK_CTX(ctx)                                                  \
+    do {                                                                \
+        if (!(ctx)) return fail(ZKHIP_ERR_INVALID, "null context");     \
+        ZK_HIP(hipSetDevice((ctx)->device));                            \
+    } while (0)
+
+// both main traces from the view's arrays, uploaded once; every chain's end (FOLD16's last row) against its block's end (FINAL's last row)
+static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                                 const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
+    const size_t R = (size_t)s.R, Q = s.Q, nb = 4 * R, nf = (size_t)4 << s.F, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q, ns = 60 * Q * R, up_words = nb + nf + ni + nv + ns;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 16 * Q) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(up_words, 0u);
+        std::memcpy(up.data(), betas, nb * 4);
+        std::memcpy(up.data() + nb, final_poly, nf * 4);
+        std::memcpy(up.data() + nb + nf, indices, Q * 4);
+        std::memcpy(up.data() + nb + nf + ni, values, nv * 4);
+        std::memcpy(up.data() + nb + nf + ni + nv, siblings, ns * 4);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
+    }
+    fri16::ViewArgs v{d, d + nb, d + nb + nf, d + nb + nf + ni, d + nb + nf + ni + nv, (uint32_t)Q, (uint32_t)s.R, (uint32_t)s.F, (uint32_t)s.lf, (uint32_t)s.H};
+    uint32_t* d_ends = d + up_words;
+    fri16::FoldRowsArgs fa{v, s.main_w[0], (uint64_t)1 << s.log_rows[0], d_fold, ld_fold, d_ends};
+    const size_t pad = (size_t)fa.rows - Q * R, fold_lanes = Q * R + (pad < 4096 ? pad : 4096);        // the padding rows are shared among up to 4096 extra lanes
+    ZK_LAUNCH(fri16::fri16_fold_rows_kernel, fri16::fri16_fold_rows_kernel_batch, fri16::fold_rows_bargs, dim3((unsigned)((fold_lanes + 63) / 64)), dim3(64), 0, ctx->stream, fa);
+    ZK_HIP(hipGetLastError());
+    fri16::FinalRowsArgs na{v, (uint64_t)1 << s.log_rows[1], d_final, ld_final, d_ends + 8 * Q};
+    const size_t per = s.F > 6 ? (size_t)1 << (s.F - 6) : 1, final_lanes = (size_t)na.rows / per;
+    ZK_LAUNCH(fri16::fri16_final_rows_kernel, fri16::fri16_final_rows_kernel_batch, fri16::final_rows_bargs, dim3((unsigned)((final_lanes + 63) / 64)), dim3(64), 0, ctx->stream, na);
+    ZK_HIP(hipGetLastError());
+    std::vector<uint32_t> ends(16 * Q);
+    ZK_TRY(dev_d2h(ctx, ends.data(), d_ends, ends.size() * 4));
+    for (size_t q = 0; q < Q; q++)
+        if (std::memcmp(ends.data() + 8 * q, ends.data() + 8 * (Q + q), 20) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16: the chain of query " + std::to_string(q) + " does not end in the final polynomial");
+    return ZKHIP_OK;
+}
+
+extern "C" {
+
+size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                            uint32_t* pre_width, int* table) {
+    fri16::Shape s;
+    if (which < 0 || which > 4 || kind < 0 || kind > 1 || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::machine_of(s);
+    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+
+int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                         const uint32_t* siblings, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key_host: null argument");
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key_host"));
+    std::vector<uint32_t> pre[5];
+    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
+    const auto m = fri16::machine_of(s);
+    const uint32_t* h[5];
+    for (int i = 0; i < 5; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, 5, prm, vk);
+}
+
+int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                    const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key: null argument");
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key"));
+    std::vector<uint32_t> pre[5];
+    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
+    const auto m = fri16::machine_of(s);
+    const int slots[5] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G};
+    zkhip_chip chips[5]{};
+    for (int i = 0; i < 5; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[i], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips, 5, prm, key, vk);
+}
+
+int zkhip_fri16_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                           const uint32_t* values, const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_gen_traces"));
+    if (!d_fold || !d_final || ld_fold < s.main_w[0] || ld_final < fri16::FIN_MAIN || ld_fold % 4 || ld_final % 4 || ((uintptr_t)d_fold | (uintptr_t)d_final) % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_gen_traces: 16-byte aligned traces, leading dimensions multiples of 4 that hold the tables' widths");
+    return fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, ld_final);
+}
+
+size_t zkhip_fri16_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
+    fri16::Shape s;
+    if (!prm || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, 5, prm, 4 * (size_t)R);
+}
+
+int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly,
+                      const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
+    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16: null argument");
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "prove_fri16"));
+    const auto m = fri16::machine_of(s);
+    void *t_fold, *t_final, *t_zero;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
+    // the three key tables' main columns: unused, zero; one region each
+    size_t zoff[5] = {0}, zwords = 0;
+    for (int t = 2; t < 5; t++) { zoff[t] = zwords; zwords += (size_t)fri16::TAB_MAIN << s.log_rows[t]; }
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_zero));
+    ZK_TRY(dev_memset(ctx, t_zero, 0, zwords * 4));
+    // refused here, before anything is proven: a view whose chains do not end in the final polynomial
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
+    zkhip_chip chips[5]{};
+    for (int i = 0; i < 5; i++) {
+        const int t = s.order[i];
+        chips[i].d_trace = t == 0 ? (const uint32_t*)t_fold : t == 1 ? (const uint32_t*)t_final : (const uint32_t*)t_zero + zoff[t];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, 5, betas, 4 * (size_t)R, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
+                       int* reason) {
+    fri16::Shape s;
+    if (!proof || !betas || !vk || !prm || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, "verify_fri16: bad arguments");
+    }
+    const auto m = fri16::machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, 5, betas, 4 * (size_t)R, prm, reason);
+}
+
+}  // extern "C"

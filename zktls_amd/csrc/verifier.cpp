@@ -170,6 +170,10 @@ struct FriViewSink {
     // skip_paths: the Merkle paths are NOT hashed (every other check runs).  For a caller that recomputes every opening itself and
     // compares the roots -- the shard verifier machine, whose device kernel hashes exactly these paths for its trace (shard_verifier.inl)
     bool skip_paths = false;
+    // fold16: the view of a fold-by-16 proof (zkhip_fri16_view_shard) -- final_poly receives every final coefficient, siblings the 15 other entries of
+    // every layer row in proof order ([query][layer][15][4]), paths the layers' paths one after the other (8 lh words for layer l, lh = H - 4 (l + 1))
+    bool fold16 = false;
+    uint32_t* final_poly = nullptr;
 };
 
 static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
@@ -348,9 +352,10 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
     std::vector<size_t> indices(NQ_);
     for (int q = 0; q < NQ_; q++) indices[q] = ch.sample_bits(H);
     if (sink) {
-        if (K != 1 || sh.F != 0 || RL != sink->layers) return reject(1);
+        if ((sink->fold16 ? K != 4 : (K != 1 || sh.F != 0)) || RL != sink->layers) return reject(1);
         for (int l = 0; l < RL; l++) for (int i = 0; i < 4; i++) sink->betas[4 * l + i] = from_monty(betas[l].c[i]);
-        for (int i = 0; i < 4; i++) sink->final_value[i] = from_monty(final_poly[0].c[i]);
+        if (sink->fold16) { for (size_t c = 0; c < keep; c++) for (int i = 0; i < 4; i++) sink->final_poly[4 * c + i] = from_monty(final_poly[c].c[i]); }
+        else for (int i = 0; i < 4; i++) sink->final_value[i] = from_monty(final_poly[0].c[i]);
         for (int q = 0; q < NQ_; q++) sink->indices[q] = (uint32_t)indices[q];
         if (sink->roots) for (int l = 0; l < RL; l++) for (int i = 0; i < 8; i++) sink->roots[8 * l + i] = from_monty(commits[8 * l + i]);
     }
@@ -428,11 +433,16 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
                     else {
                         e[k] = ext_from_canon(pf + qpos[j]);
                         for (int i = 0; i < 4; i++) rb[4 * k + i] = pf[qpos[j] + i];
-                        if (sink) for (int i = 0; i < 4; i++) sink->siblings[4 * ((size_t)(q0 + j) * RL + l) + i] = pf[qpos[j] + i];
+                        if (sink) for (int i = 0; i < 4; i++) sink->siblings[4 * (((size_t)(q0 + j) * RL + l) * (arity - 1) + (k > own ? k - 1 : k)) + i] = pf[qpos[j] + i];
                         qpos[j] += 4;
                     }
                 }
                 rows[j] = rb; paths[j] = pf + qpos[j]; rowidx[j] = row;
+                if (sink && sink->paths && sink->fold16) {       // per query: 8 lh words per layer, lh = H - 4 (l + 1)
+                    size_t per_query = 0, before = 0;
+                    for (int m = 0; m < RL; m++) { if (m == l) before = per_query; per_query += 8 * (size_t)(H - K * (m + 1)); }
+                    std::memcpy(sink->paths + (size_t)(q0 + j) * per_query + before, pf + qpos[j], 32 * (size_t)lh);
+                } else
                 if (sink && sink->paths) {       // per query: the layers' paths one after the other, 8 (RL - l) words for layer l (fold by 2, H = RL + 1)
                     const size_t per_query = 4 * (size_t)RL * ((size_t)RL + 1), before = 8 * ((size_t)l * RL - (size_t)l * ((size_t)l - 1) / 2);
                     std::memcpy(sink->paths + (size_t)(q0 + j) * per_query + before, pf + qpos[j], 32 * (size_t)lh);
@@ -483,6 +493,28 @@ int zkhip_fri_view_shard(const uint8_t* proof, size_t len, int log_n, uint32_t w
     shape_of(log_n, prm, sh);
     if (sh.K != 1 || sh.F != 0) return fail(ZKHIP_ERR_INVALID, "fri_view_shard: fold-by-2 proofs with a constant final value only");
     FriViewSink sink{betas, final_value, indices, values, siblings, sh.R, nullptr, nullptr, nullptr};
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
+}
+// The view of a FOLD-BY-16 proof (fri16_chip.hip proves statements about these values): betas [R][4], every final coefficient, per query the index, the reduced
+// opening and the 15 other entries of every layer row in proof order; roots / paths optional (NULL: not wanted).  A new entry: zkhip_fri_view_shard keeps refusing these proofs.
+size_t zkhip_fri16_view_path_words(int log_n, const zkhip_params* prm) {
+    Shape sh;
+    if (!prm || log_n < 5 || log_n > MAX_LOG_ROWS || !shape_of(log_n, prm, sh) || sh.K != 4) return 0;
+    size_t w = 0;
+    for (int l = 0; l < sh.R; l++) w += 8 * (size_t)(log_n + sh.b - 4 * (l + 1));
+    return w;
+}
+int zkhip_fri16_view_shard(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                           uint32_t* betas, uint32_t* final_poly, uint32_t* indices, uint32_t* values, uint32_t* siblings, uint32_t* roots, uint32_t* paths) {
+    if (!prm || !betas || !final_poly || !indices || !values || !siblings) return fail(ZKHIP_ERR_INVALID, "fri16_view_shard: null argument");
+    Shape sh;
+    if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_shard: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    FriViewSink sink{betas, nullptr, indices, values, siblings, sh.R, roots, paths, nullptr};
+    sink.fold16 = true;
+    sink.final_poly = final_poly;
     int why = 0;
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }

@@ -658,6 +658,39 @@ class Context:
                                                cap8.ctypes.data_as(u32p), int(witness), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 FRI machine (FOLD16 + FINAL): key, traces, proof
+    def fri16_key(self, view, params=None):
+        """zkhip_fri16_key: the LAYERS / QUERIES / COEFFS tables and FINAL's schedule of a fold-16 view, committed on the device -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, arrs = _fri16_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_key(self.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_gen_traces(self, view, out=None):
+        """zkhip_fri16_gen_traces: the two main traces of a fold-16 view -> (FOLD16 buffer, its log rows, its width, FINAL buffer, its log rows);
+        out = (FOLD16 buffer, FINAL buffer) of an earlier call: filled again instead of new ones"""
+        shape, arrs = _fri16_arrays(view)
+        dims = {}
+        for which in range(5):
+            _, ln, mw, _, table = fri16_describe(*shape, which, 0)
+            dims[table] = (ln, mw)
+        (lf, wf), (ln, wn) = dims[0], dims[1]
+        fold, final = out if out is not None else (self.alloc(wf << lf), self.alloc(wn << ln))
+        check(self.lib.zkhip_fri16_gen_traces(self.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.c_void_p(fold.ptr), wf, C.c_void_p(final.ptr), wn))
+        return fold, lf, wf, final, ln
+
+    def prove_fri16(self, key, view, params=None):
+        """zkhip_prove_fri16: "every listed query folds by 16 through the listed rows to the listed final polynomial at its last point"; a view whose
+        chains do not end there is refused before anything is proven"""
+        params = params or Params(1, 100, 16)
+        shape, arrs = _fri16_arrays(view)
+        size = self.lib.zkhip_fri16_proof_size(*shape, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16(self.handle, key.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1320,6 +1353,71 @@ def fri_view_shard(proof, log_n, width, public_values=(), params=None):
                                    sibs.ctypes.data_as(u32p)))
     return {"betas": betas.reshape(R, 4).tolist(), "final": final.tolist(),
             "queries": [(int(idx[q]), vals[4 * q:4 * q + 4].tolist(), sibs[4 * q * R:4 * (q + 1) * R].reshape(R, 4).tolist()) for q in range(Q)]}
+
+
+def _fri16_arrays(view):
+    """a fold-16 view (fri16_view_shard's dict) -> ((R, F, log_blowup, queries), the flat canonical arrays the entries take)"""
+    R, Q = len(view["betas"]), len(view["queries"])
+    u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+    arrs = (u(view["betas"]), u(view["final_poly"]), u([q[0] for q in view["queries"]]), u([q[1] for q in view["queries"]]), u([q[2] for q in view["queries"]]))
+    assert arrs[1].size == 4 << view["F"] and arrs[4].size == 60 * Q * R
+    return (R, view["F"], view["b"], Q), arrs
+
+
+def fri16_view_shard(proof, log_n, width, public_values=(), params=None):
+    """zkhip_fri16_view_shard: what the FRI check of a fold-by-16 shard proof reads -> {"betas": [R][4], "final_poly": [2^F][4], "queries": [(index,
+    value[4], siblings [R][15][4])], "roots": [R][8], "paths": [query][layer] flat words, "F", "b", "H"} (canonical), or raises if the proof is
+    rejected.  Host only."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+    F, b, Q = params.log_final, params.log_blowup, params.num_queries
+    R, H = max((log_n - F) // 4, 0), log_n + b
+    pw = lib.zkhip_fri16_view_path_words(log_n, C.byref(params))
+    betas, fp, roots = np.zeros(4 * R, dtype=np.uint32), np.zeros(4 << F, dtype=np.uint32), np.zeros(8 * R, dtype=np.uint32)
+    idx, vals, sibs, paths = np.zeros(Q, dtype=np.uint32), np.zeros(4 * Q, dtype=np.uint32), np.zeros(60 * Q * R, dtype=np.uint32), np.zeros(max(pw * Q, 1), dtype=np.uint32)
+    check(lib.zkhip_fri16_view_shard(pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size, C.byref(params), betas.ctypes.data_as(u32p),
+                                     fp.ctypes.data_as(u32p), idx.ctypes.data_as(u32p), vals.ctypes.data_as(u32p), sibs.ctypes.data_as(u32p), roots.ctypes.data_as(u32p),
+                                     paths.ctypes.data_as(u32p)))
+    lhs = [H - 4 * (l + 1) for l in range(R)]
+    offs = np.concatenate([[0], np.cumsum([8 * lh for lh in lhs])]).astype(int)
+    return {"betas": betas.reshape(R, 4).tolist(), "final_poly": fp.reshape(-1, 4).tolist(), "roots": roots.reshape(R, 8).tolist(), "F": F, "b": b, "H": H,
+            "queries": [(int(idx[q]), vals[4 * q:4 * q + 4].tolist(), sibs[60 * q * R:60 * (q + 1) * R].reshape(R, 15, 4).tolist()) for q in range(Q)],
+            "paths": [[paths[q * pw + offs[l]:q * pw + offs[l + 1]].tolist() for l in range(R)] for q in range(Q)]}
+
+
+def fri16_describe(R, F, log_blowup, n_queries, which, kind):
+    """zkhip_fri16_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` of the fold-16 FRI machine
+    -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16, 1 FINAL, 2 LAYERS, 3 QUERIES, 4 COEFFS)"""
+    lib = _lib.load()
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    n = lib.zkhip_fri16_describe(R, F, log_blowup, n_queries, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    if n == 0:
+        raise _lib.ZkHipError(-1, "fri16_describe: " + lib.zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib.zkhip_fri16_describe(R, F, log_blowup, n_queries, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb)) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def fri16_key_host(view, params=None):
+    """zkhip_fri16_key_host: the fold-16 FRI machine's key of a view, without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, arrs = _fri16_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_key_host(*shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
+    """zkhip_verify_fri16: the challenges, the key, the shape -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    bt = np.ascontiguousarray(np.array(betas, dtype=np.uint32).reshape(-1))
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_fri16(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params), C.byref(reason))
+    return rc, reason.value
 
 
 def fri_view_transcript(proof, log_n, width, public_values=(), params=None):
