@@ -52,8 +52,9 @@ int zkhip_verify_merkle_paths(const uint8_t* proof, size_t len, const uint32_t r
  * a positive multiple of 4 (up to 1024) leaves[p][row_width] is the OPENED ROW and the path starts with ceil(row_width / 16) sponge rows;
  * siblings, indices and roots as above.  zkhip_prove_merkle_paths_p24 / zkhip_verify_merkle_paths_p24: as the width-16 entries (paths that
  * do not end in root are refused before anything is proven; the verifier needs no GPU and reads the trace height from the proof).  Any
- * proof shape is accepted, the SP1 default and the RISC Zero shape (log_blowup 2, log_fold 4, hash_width 24) among them.  Not yet: lookup
- * or bus variants of this chip, and its use inside the recursion machines. */
+ * proof shape is accepted, the SP1 default and the RISC Zero shape (log_blowup 2, log_fold 4, hash_width 24) among them.  One bus variant
+ * exists: the layer-paths table P24L of the fold-16 paths machine (zkhip_prove_fri16_paths below).  Not yet: its use inside the recursion
+ * machines. */
 #define ZKHIP_P24CHIP_WIDTH 540
 size_t zkhip_p24chip_air(uint32_t* program, size_t cap_words);
 int zkhip_p24chip_gen_merkle_trace(zkhip_ctx* ctx, const uint32_t* leaves, uint32_t row_width, const uint32_t* siblings, const uint32_t* indices, size_t n_paths,
@@ -182,8 +183,9 @@ int zkhip_prove_fri_indices_batch(const int* devices, int n_devices, zkhip_fri_j
  * aligned, ld a multiple of 4).  zkhip_prove_fri16 is handed the view and refuses, before proving, one whose chains do not end in the final polynomial;
  * zkhip_verify_fri16 is host only.  Shapes: 1 <= R <= 5, 0 <= log_final <= 8, log_final + log_blowup <= 11, 4 R + log_final + log_blowup <= 27, up to 1024
  * queries; anything else is refused with a message.
- * NOT in-circuit yet: the Merkle paths of the layer rows (LAYERS is the table a bus variant of the width-24 chip replaces: its leaf rows will receive the tuples
- * (layer, 16 row + j, entry) FOLD16 sends), the transcript (challenges, query indices), the reduced openings; the shard verifier machines do not use these chips. */
+ * NOT in-circuit in THIS machine: the Merkle paths of the layer rows (its verifier must be handed the LAYERS rows and trust them; the paths machine below,
+ * zkhip_prove_fri16_paths, puts a width-24 chip where LAYERS stands and proves them), the transcript (challenges, query indices), the reduced openings; the shard
+ * verifier machines do not use these chips. */
 size_t zkhip_fri16_view_path_words(int log_n, const zkhip_params* prm);
 int zkhip_fri16_view_shard(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
                            uint32_t* betas, uint32_t* final_poly, uint32_t* indices, uint32_t* values, uint32_t* siblings, uint32_t* roots, uint32_t* paths);
@@ -200,6 +202,45 @@ int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F
                       const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
 int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
                        int* reason);
+
+/* ---- the same check with the layer rows' MERKLE PATHS in-circuit: the fold-16 PATHS machine.  A layer-paths variant of the width-24 chip, P24L, stands where
+ * LAYERS stood and a preprocessed ROOTS table lists the layer commitments, so THE KEY HOLDS THE LAYER ROOTS AND NO LAYER VALUE.  Statement, for the public
+ * challenges beta_0 .. beta_{R-1} and the key (QUERIES, COEFFS, ROOTS, FINAL's schedule): "every query listed in QUERIES, taken as entry index & 15 of row
+ * index >> 4 of layer 0, opens the layer commitments listed in ROOTS row by row -- each of its R rows is the 64-word leaf at its row index of the width-24
+ * Merkle tree whose root ROOTS lists for that layer -- and folds through these rows, at the points its index fixes, to the value at its last point of the
+ * polynomial whose coefficients are listed in COEFFS."  Six tables, tallest first (equal heights by table number): 0 FOLD16 and 1 FINAL, 3 QUERIES and 4 COEFFS
+ * exactly as above (FOLD16 keeps sending (layer, 16 row + j, entry_j) on its bus); 2 P24L, main only, 552 columns: the width-24 chip's 540 and a tail LN KP M DEP |
+ * Z0..Z3 | K0..K3 -- one path per DISTINCT (layer, row), ascending: four sponge rows over the row's 64 words, each receiving four of FOLD16's tuples with
+ * multiplicity M = the queries reading the row, then lh_l = log_n + log_blowup - 4 (l + 1) compression rows, the last of which sends (layer, lh_l, digest) to
+ * ROOTS in two halves; its height, 2^ceil(lg(Q sum_l (4 + lh_l))), is a function of the shape alone; 5 ROOTS, preprocessed (layer, depth, root[8]), 2^5 rows,
+ * with the number of path ends per layer in a main column.  The leaf is EXACTLY four full sponge rows followed by a compression row: a sponge over one 16-word
+ * block equals the compression of its halves, so a leaf of floating length would let an inner node pass for a leaf.
+ * Inner proofs: fold-16 proofs whose commitments are width-24 trees (hash_width 24: zkhip_prove_segment, versions 3 and 8).  Entries that take a view also take
+ * inner_hash_width and refuse anything but 24 with a message (zkhip_prove_fri16 keeps taking width-16-hash proofs).  zkhip_fri16_paths_describe: as
+ * zkhip_fri16_describe, six positions.  zkhip_fri16_paths_key_host (no GPU) / zkhip_fri16_paths_key: the key from the shape, the final coefficients, the
+ * indices, the reduced openings and the layer roots [R][8] -- no sibling, no layer entry, no challenge.  zkhip_fri16_paths_gen_trace: P24L alone on the device
+ * (d_trace [2^log_rows][ld], ld >= 552 and a multiple of 4, 16-byte aligned) from the whole view (paths as zkhip_fri16_view_shard hands them out); ends
+ * [n_paths][8] receives where each path ends and *n_paths their number (cap_paths >= Q R always suffices).  zkhip_prove_fri16_paths refuses, before anything is
+ * proven and with a message that names query and layer: a path that does not end in its layer's root ("query q layer l does not open"), two queries that
+ * disagree about a shared row or its path, a chain that does not end in the final polynomial.  zkhip_verify_fri16_paths is host only: challenges, key, shape.
+ * STILL OUTSIDE after this machine: the transcript (challenges, query indices), the reduced openings, the trace / quotient openings; the shard verifier
+ * machines (shard_verifier.inl) do not use these chips. */
+#define ZKHIP_P24CHIP_LAYERS_WIDTH 552
+size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                                  uint32_t* pre_width, int* table);
+int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
+                          const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly,
+                                const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* paths, uint32_t* d_trace, size_t ld,
+                                uint32_t* ends, size_t cap_paths, size_t* n_paths);
+size_t zkhip_fri16_paths_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm);
+int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas,
+                            const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
+                            const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
+                             const zkhip_params* prm, int* reason);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */

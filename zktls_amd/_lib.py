@@ -50,6 +50,8 @@ EXPORTS = [
     "zkhip_p24chip_air", "zkhip_p24chip_gen_merkle_trace", "zkhip_merkle_paths_p24_proof_size", "zkhip_prove_merkle_paths_p24", "zkhip_verify_merkle_paths_p24",
     "zkhip_fri16_view_path_words", "zkhip_fri16_view_shard", "zkhip_fri16_describe", "zkhip_fri16_key_host", "zkhip_fri16_key", "zkhip_fri16_gen_traces", "zkhip_fri16_proof_size",
     "zkhip_prove_fri16", "zkhip_verify_fri16",
+    "zkhip_fri16_paths_describe", "zkhip_fri16_paths_key_host", "zkhip_fri16_paths_key", "zkhip_fri16_paths_gen_trace", "zkhip_fri16_paths_proof_size", "zkhip_prove_fri16_paths",
+    "zkhip_verify_fri16_paths",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -341,6 +343,17 @@ def load():
     L.zkhip_fri16_proof_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(Params)]
     L.zkhip_prove_fri16.argtypes = [C.c_void_p, C.c_void_p] + fri16_view + [C.POINTER(Params), u8p, C.c_size_t, szp]
     L.zkhip_verify_fri16.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
+    # the fold-16 PATHS machine: the same shape; the entries that take a view also take the inner proof's hash width
+    L.zkhip_fri16_paths_describe.restype = C.c_size_t
+    L.zkhip_fri16_paths_describe.argtypes = L.zkhip_fri16_describe.argtypes
+    fri16_shape = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int]                                 # R, F, log_blowup, queries, inner hash width
+    L.zkhip_fri16_paths_key_host.argtypes = fri16_shape + [u32p, u32p, u32p, u32p, C.POINTER(Params), u32p]       # final_poly, indices, values, roots
+    L.zkhip_fri16_paths_key.argtypes = [C.c_void_p] + fri16_shape + [u32p, u32p, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_paths_gen_trace.argtypes = [C.c_void_p] + fri16_shape + [u32p, u32p, u32p, u32p, u32p, u32p, C.c_void_p, C.c_size_t, u32p, C.c_size_t, szp]
+    L.zkhip_fri16_paths_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_paths_proof_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(Params)]
+    L.zkhip_prove_fri16_paths.argtypes = [C.c_void_p, C.c_void_p] + fri16_shape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16_paths.argtypes = L.zkhip_verify_fri16.argtypes
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -24,8 +24,11 @@
 //   3 QUERIES  preprocessed: distinct (index, reduced opening) with multiplicity.       4 COEFFS  preprocessed: (j, c_j, queries).
 // NOT in this machine: the Merkle paths of the layer rows, the transcript (challenges, query indices), the reduced openings.  tests/fri16_air.py writes
 // the programs, tables and traces independently; the words must be equal.
+// The PATHS machine (further down; zkhip_prove_fri16_paths) is this machine with P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands,
+// and a preprocessed ROOTS table: there the layer rows' Merkle paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py).
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -37,8 +40,12 @@
 #include "context.h"
 #include "batch.h"
 #include "fri16_rows.cuh"
+#include "kernels.h"
+#include "p24chip.h"
 
 namespace zk {
+extern std::atomic<uint64_t> g_p2_generation;      // params.cpp
+namespace p24chip { std::shared_ptr<const std::vector<uint32_t>> program_fri16_layers(uint32_t n_public); }      // poseidon2_chip.cpp
 namespace fri16 {
 namespace {
 
@@ -324,6 +331,28 @@ Ext fold_row_host(uint32_t row, int lh, const Ext& beta, const Ext* entries) {
     }
     return cur[0];
 }
+// FINAL's schedule, QUERIES and COEFFS (zeroed, at their heights): what both machines' keys share
+void fill_schedule_queries_coeffs(const Shape& s, const uint32_t* final_poly, const std::map<std::array<uint32_t, 5>, uint32_t>& queries, std::vector<uint32_t>& fin,
+                                  std::vector<uint32_t>& qs, std::vector<uint32_t>& cs) {
+    const size_t n = (size_t)1 << s.F;
+    for (size_t r = 0; r < s.Q * n; r++) {
+        uint32_t* w = fin.data() + FIN_PRE * r;
+        const size_t i = r & (n - 1);
+        w[FJ] = to_monty((uint32_t)(n - 1 - i)); w[FFIRST] = i == 0 ? MONTY_R1 : 0u; w[FLAST] = i == n - 1 ? MONTY_R1 : 0u; w[FACT] = MONTY_R1; w[FNL] = i == n - 1 ? 0u : MONTY_R1;
+    }
+    size_t r = 0;
+    for (const auto& e : queries) {
+        uint32_t* w = qs.data() + Q_PRE * r++;
+        for (int i = 0; i < 5; i++) w[i] = to_monty(e.first[i]);
+        w[5] = to_monty(e.second);
+    }
+    for (size_t j = 0; j < n; j++) {
+        uint32_t* w = cs.data() + C_PRE * j;
+        w[0] = to_monty((uint32_t)j);
+        for (int i = 0; i < 4; i++) w[1 + i] = to_monty(final_poly[4 * j + i]);
+        w[5] = to_monty((uint32_t)s.Q);
+    }
+}
 // The three key tables and FINAL's schedule from a view (host, canonical -> Montgomery), by table number.  Walks every chain: queries that meet must
 // agree about the row, and every chain must end in the final polynomial at its last point -- a view taken from an accepted proof always does.
 int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings,
@@ -360,11 +389,6 @@ int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_po
     }
     for (int t = 1; t < 5; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
     pre[0].clear();
-    for (size_t r = 0; r < s.Q * n; r++) {
-        uint32_t* w = pre[T_FINAL].data() + FIN_PRE * r;
-        const size_t i = r & (n - 1);
-        w[FJ] = to_monty((uint32_t)(n - 1 - i)); w[FFIRST] = i == 0 ? MONTY_R1 : 0u; w[FLAST] = i == n - 1 ? MONTY_R1 : 0u; w[FACT] = MONTY_R1; w[FNL] = i == n - 1 ? 0u : MONTY_R1;
-    }
     size_t r = 0;
     for (const auto& e : layers) {
         uint32_t* w = pre[T_LAYERS].data() + LAY_PRE * r++;
@@ -373,17 +397,137 @@ int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_po
         w[LAY_M] = to_monty(e.second.second);
         std::memcpy(w + LAY_E, e.second.first.data(), 256);
     }
-    r = 0;
-    for (const auto& e : queries) {
-        uint32_t* w = pre[T_QUERIES].data() + Q_PRE * r++;
-        for (int i = 0; i < 5; i++) w[i] = to_monty(e.first[i]);
-        w[5] = to_monty(e.second);
+    fill_schedule_queries_coeffs(s, final_poly, queries, pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
+    return ZKHIP_OK;
+}
+
+// ---------------------------------------------------------------- the PATHS machine: P24L where LAYERS stood, and the ROOTS table
+// Table numbers 0 FOLD16, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS.  FOLD16, FINAL, QUERIES and COEFFS are the machine's above, word for word; P24L is the
+// width-24 chip's layer-paths variant (p24chip.h, poseidon2_chip.cpp): its sponge rows receive on BUS_L16 what FOLD16 sends, its END rows send
+// (layer, depth, digest) in two halves to ROOTS (preprocessed layer, depth, root[8]; main: the number of path ends of the layer, the prover's).
+constexpr uint32_t BUS_RT0 = 74, BUS_RT1 = 75, ROOTS_PRE16 = 12, RT_LN = 0, RT_DEP = 1, RT_ROOT = 2;
+enum : int { T_P24L = 2, T_ROOTS = 5, N_PT = 6 };
+struct PShape {
+    Shape base;
+    int log_rows[N_PT], order[N_PT];
+    uint32_t main_w[N_PT], pre_w[N_PT];
+};
+int paths_shape_of(int R, int F, int b, size_t Q, PShape& s) {
+    ZK_TRY(shape_of(R, F, b, Q, s.base));
+    size_t per_query = 0;
+    for (int l = 0; l < R; l++) per_query += (size_t)p24chip::LEAF_ROWS + (size_t)(s.base.H - 4 * (l + 1));
+    const int lr[N_PT] = {s.base.log_rows[0], s.base.log_rows[1], lg(Q * per_query), s.base.log_rows[3], s.base.log_rows[4], lg((size_t)R)};
+    const uint32_t mw[N_PT] = {s.base.main_w[0], FIN_MAIN, p24chip::WIDTH_L, TAB_MAIN, TAB_MAIN, TAB_MAIN}, pw[N_PT] = {0u, FIN_PRE, 0u, Q_PRE, C_PRE, ROOTS_PRE16};
+    for (int i = 0; i < N_PT; i++) { s.log_rows[i] = lr[i]; s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
+    std::stable_sort(s.order, s.order + N_PT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    return ZKHIP_OK;
+}
+std::vector<uint32_t> build_paths_interactions(int R, int table) {
+    if (table != T_P24L && table != T_ROOTS) return build_interactions(R, table);          // FOLD16, FINAL, QUERIES, COEFFS: the numbers and the words of the machine above
+    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
+    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
+        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
+        v.insert(v.end(), cols.begin(), cols.end());
+        v[1]++;
+    };
+    if (table == T_P24L) {
+        using namespace p24chip;
+        const uint32_t o7 = oute(7);
+        for (uint32_t i = 0; i < 4; i++) add(1u, L_M, BUS_L16, {L_LN, L_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
+        add(0u, END, BUS_RT0, {L_LN, L_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
+        add(0u, END, BUS_RT1, {L_LN, L_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
+    } else {
+        add(1u, ROOTS_PRE16, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
+        add(1u, ROOTS_PRE16, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
     }
-    for (size_t j = 0; j < n; j++) {
-        uint32_t* w = pre[T_COEFFS].data() + C_PRE * j;
-        w[0] = to_monty((uint32_t)j);
-        for (int i = 0; i < 4; i++) w[1 + i] = to_monty(final_poly[4 * j + i]);
-        w[5] = to_monty((uint32_t)s.Q);
+    v[2] = (uint32_t)v.size();
+    return v;
+}
+struct PMachine {
+    PShape s;
+    std::vector<uint32_t> prog[N_PT], tab[N_PT];
+    int32_t log_ns[N_PT]; uint32_t widths[N_PT], pre_widths[N_PT];
+    const uint32_t* progs[N_PT]; size_t prog_words[N_PT]; const uint32_t* tabs[N_PT]; size_t tab_words[N_PT];
+};
+// (P24L's program follows the width-24 tables in effect: the cache is dropped when they change)
+std::shared_ptr<const PMachine> paths_machine_of(const PShape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 4>, std::shared_ptr<const PMachine>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
+    const std::array<uint64_t, 4> key{(uint64_t)s.base.R, (uint64_t)s.base.F, (uint64_t)s.base.b, (uint64_t)s.base.Q};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<PMachine>();
+    m->s = s;
+    const int R = s.base.R;
+    for (int i = 0; i < N_PT; i++) {
+        const int t = s.order[i];
+        m->prog[i] = t == T_FOLD16 ? build_fold16_program(R, s.base.lf) : t == T_FINAL ? build_final_program(R)
+                   : t == T_P24L ? *p24chip::program_fri16_layers(4u * (uint32_t)R) : build_table_program(R, s.pre_w[t]);
+        m->tab[i] = build_paths_interactions(R, t);
+        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
+        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
+    }
+    cache.emplace(key, m);
+    return m;
+}
+int check_hash_width(int inner_hash_width, const char* who) {
+    if (inner_hash_width == 24) return ZKHIP_OK;
+    return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the paths machine opens width-24 Poseidon2 commitments (inner hash_width 24); a fold-16 proof with the width-16 hash is taken by zkhip_prove_fri16 only");
+}
+// the key's tables by table number: FINAL's schedule, QUERIES, COEFFS, ROOTS -- from the shape, the final coefficients, the queries and the layer roots alone
+int build_paths_key_tables(const PShape& s, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[N_PT],
+                           const char* who) {
+    const Shape& b = s.base;
+    if (!final_poly || !indices || !values || !roots) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(final_poly, (size_t)4 << b.F) || !canonical(values, 4 * b.Q) || !canonical(roots, 8 * (size_t)b.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    std::map<std::array<uint32_t, 5>, uint32_t> queries;
+    for (size_t q = 0; q < b.Q; q++) {
+        if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+        queries[std::array<uint32_t, 5>{indices[q], values[4 * q], values[4 * q + 1], values[4 * q + 2], values[4 * q + 3]}]++;
+    }
+    for (int t = 0; t < N_PT; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
+    fill_schedule_queries_coeffs(b, final_poly, queries, pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
+    for (int l = 0; l < b.R; l++) {
+        uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (size_t)l;
+        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(b.H - 4 * (l + 1)));
+        for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty(roots[8 * l + j]);
+    }
+    return ZKHIP_OK;
+}
+// One path per distinct (layer, row), ascending: the kernel's descriptors, every path's readers (rows of the FOLD16 trace, query order) and what the refusals name.
+// Queries that share a row must bring the same authentication path.
+struct PathPlan {
+    std::vector<uint32_t> desc, readers, layer_of, first_query, counts;     // [n][8], [Q R], [n], [n], [R]
+    size_t n = 0, used_rows = 0, path_words = 0;
+};
+int plan_paths(const Shape& b, const uint32_t* indices, const uint32_t* paths, PathPlan& pl) {
+    const size_t R = (size_t)b.R;
+    std::vector<size_t> off(R + 1, 0);
+    for (size_t l = 0; l < R; l++) off[l + 1] = off[l] + 8 * (size_t)(b.H - 4 * ((int)l + 1));
+    pl.path_words = off[R];
+    if (!canonical(paths, b.Q * pl.path_words)) return fail(ZKHIP_ERR_INVALID, "fri16 paths: values must be canonical");
+    std::map<std::pair<uint32_t, uint32_t>, std::vector<uint32_t>> rows;
+    for (size_t q = 0; q < b.Q; q++)
+        for (size_t l = 0; l < R; l++) rows[{(uint32_t)l, indices[q] >> (4 * (l + 1))}].push_back((uint32_t)q);
+    pl.n = rows.size();
+    pl.counts.assign(R, 0u);
+    for (const auto& e : rows) {
+        const uint32_t l = e.first.first, depth = (uint32_t)(b.H - 4 * ((int)l + 1)), q0 = e.second[0];
+        const uint32_t* mine = paths + q0 * pl.path_words + off[l];
+        for (uint32_t q : e.second)
+            if (std::memcmp(mine, paths + q * pl.path_words + off[l], 32 * (size_t)depth) != 0)
+                return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(q) + " layer " + std::to_string(l) + " disagrees with query " + std::to_string(q0) +
+                                                   " about the path of a shared row");
+        const uint32_t d[8] = {l, e.first.second, depth, (uint32_t)e.second.size(), (uint32_t)pl.used_rows, (uint32_t)pl.readers.size(), (uint32_t)(q0 * pl.path_words + off[l]), 0u};
+        pl.desc.insert(pl.desc.end(), d, d + 8);
+        for (uint32_t q : e.second) pl.readers.push_back((uint32_t)(q * R + l));
+        pl.layer_of.push_back(l); pl.first_query.push_back(q0);
+        pl.counts[l]++;
+        pl.used_rows += p24chip::LEAF_ROWS + depth;
     }
     return ZKHIP_OK;
 }
@@ -439,7 +583,181 @@ static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const ui
     return ZKHIP_OK;
 }
 
+// P24L from the view's paths and the FOLD16 trace already on the device (its E columns are the leaves); ends [n][8]: where every path ends.  Refused here: two
+// queries that disagree about a shared row or its path.
+static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::PShape& s, const uint32_t* indices, const uint32_t* paths, const uint32_t* d_fold, size_t ld_fold,
+                                     uint32_t* d_trace, size_t ld, fri16::PathPlan& pl, std::vector<uint32_t>& ends) {
+    const fri16::Shape& b = s.base;
+    ZK_TRY(fri16::plan_paths(b, indices, paths, pl));
+    const size_t rows = (size_t)1 << s.log_rows[fri16::T_P24L];
+    if (pl.used_rows > rows) return fail(ZKHIP_ERR_INVALID, "fri16 paths: the paths do not fit the table");
+    const size_t nd = 8 * pl.n, nr = (pl.readers.size() + 3) & ~(size_t)3, ns = b.Q * pl.path_words, up_words = nd + nr + ns;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_REC_I, (up_words + 9 * pl.n) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(up_words, 0u);
+        std::memcpy(up.data(), pl.desc.data(), nd * 4);
+        std::memcpy(up.data() + nd, pl.readers.data(), pl.readers.size() * 4);
+        std::memcpy(up.data() + nd + nr, paths, ns * 4);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
+    }
+    p24chip::LayerPathsArgs a{};
+    a.desc = d; a.readers = d + nd; a.fold = d_fold; a.fold_ld = ld_fold; a.siblings = d + nd + nr; a.n_paths = pl.n; a.rows = rows; a.used_rows = pl.used_rows;
+    a.trace = d_trace; a.ld = ld; a.ends = d + up_words; a.differs = d + up_words + 8 * pl.n;
+    ZK_HIP(launch_p24chip_layer_paths(a, ctx->stream));
+    ends.resize(9 * pl.n);
+    ZK_TRY(dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4));
+    for (size_t p = 0; p < pl.n; p++)
+        if (const uint32_t k = ends[8 * pl.n + p])
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.readers[pl.desc[8 * p + 5] + k - 1] / (uint32_t)b.R) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " disagrees with query " + std::to_string(pl.first_query[p]) + " about a shared row");
+    ends.resize(8 * pl.n);
+    return ZKHIP_OK;
+}
+static int fri16_paths_check_view(const fri16::Shape& s, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                                  const uint32_t* siblings, const uint32_t* paths, const char* who) {
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, who));
+    if (!paths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    return fri16::check_view(s, betas, final_poly, indices, values, siblings, who);
+}
+
 extern "C" {
+
+size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                                  uint32_t* pre_width, int* table) {
+    fri16::PShape s;
+    if (which < 0 || which >= fri16::N_PT || kind < 0 || kind > 1 || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::paths_machine_of(s);
+    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+
+int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::PShape s;
+    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::N_PT];
+    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key_host"));
+    const auto m = fri16::paths_machine_of(s);
+    const uint32_t* h[fri16::N_PT];
+    for (int i = 0; i < fri16::N_PT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_PT, prm, vk);
+}
+
+int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
+                          const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::PShape s;
+    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key: null argument");
+    std::vector<uint32_t> pre[fri16::N_PT];
+    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key"));
+    const auto m = fri16::paths_machine_of(s);
+    const int slots[fri16::N_PT] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
+    zkhip_chip chips[fri16::N_PT]{};
+    for (int i = 0; i < fri16::N_PT; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[i], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips, fri16::N_PT, prm, key, vk);
+}
+
+int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly,
+                                const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* paths, uint32_t* d_trace, size_t ld,
+                                uint32_t* ends, size_t cap_paths, size_t* n_paths) {
+    CHECK_CTX(ctx);
+    fri16::PShape s;
+    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
+    ZK_TRY(fri16_paths_check_view(s.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "fri16_paths_gen_trace"));
+    if (!d_trace || !ends || !n_paths || ld < p24chip::WIDTH_L || ld % 4 || (uintptr_t)d_trace % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: a 16-byte aligned trace, a leading dimension that is a multiple of 4 and holds 552 columns, ends and n_paths");
+    void *t_fold, *t_final;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
+    ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
+    fri16::PathPlan pl;
+    std::vector<uint32_t> e;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, indices, paths, (const uint32_t*)t_fold, s.main_w[0], d_trace, ld, pl, e));
+    *n_paths = pl.n;
+    if (cap_paths < pl.n) return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: more paths than `ends` holds");
+    std::memcpy(ends, e.data(), e.size() * 4);
+    return ZKHIP_OK;
+}
+
+size_t zkhip_fri16_paths_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
+    fri16::PShape s;
+    if (!prm || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::paths_machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, prm, 4 * (size_t)R);
+}
+
+int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas,
+                            const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
+                            const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    fri16::PShape s;
+    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
+    if (!key || !prm || !proof || !len || !roots) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: null argument");
+    ZK_TRY(fri16_paths_check_view(s.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_paths"));
+    if (!fri16::canonical(roots, 8 * (size_t)R)) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: values must be canonical");
+    const auto m = fri16::paths_machine_of(s);
+    void *t_fold, *t_final, *t_p24, *t_tabs;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
+    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
+    // the three tables' main columns: QUERIES and COEFFS unused, zero; ROOTS the number of path ends per layer
+    size_t zoff[fri16::N_PT] = {0}, zwords = 0;
+    for (int t : {(int)fri16::T_QUERIES, (int)fri16::T_COEFFS, (int)fri16::T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)fri16::TAB_MAIN << s.log_rows[t]; }
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
+    // refused here, before anything is proven: chains that do not end in the final polynomial, queries that disagree, paths that do not end in their layer's root
+    ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
+    fri16::PathPlan pl;
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, indices, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    for (size_t p = 0; p < pl.n; p++)
+        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " does not open: its path does not end in the layer's root");
+    {
+        std::vector<uint32_t> tabs(zwords, 0u);
+        for (int l = 0; l < R; l++) tabs[zoff[fri16::T_ROOTS] + (size_t)fri16::TAB_MAIN * l] = to_monty(pl.counts[l]);
+        ZK_TRY(dev_h2d(ctx, t_tabs, tabs.data(), zwords * 4));
+    }
+    zkhip_chip chips[fri16::N_PT]{};
+    for (int i = 0; i < fri16::N_PT; i++) {
+        const int t = s.order[i];
+        chips[i].d_trace = t == fri16::T_FOLD16 ? (const uint32_t*)t_fold : t == fri16::T_FINAL ? (const uint32_t*)t_final : t == fri16::T_P24L ? (const uint32_t*)t_p24
+                                                                                                                           : (const uint32_t*)t_tabs + zoff[t];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, betas, 4 * (size_t)R, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
+                             const zkhip_params* prm, int* reason) {
+    fri16::PShape s;
+    if (!proof || !betas || !vk || !prm || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_paths: bad arguments");
+    }
+    const auto m = fri16::paths_machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, betas, 4 * (size_t)R, prm,
+                                      reason);
+}
 
 size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
                             uint32_t* pre_width, int* table) {

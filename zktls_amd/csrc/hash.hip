@@ -1370,4 +1370,120 @@ hipError_t launch_p24chip_merkle(const p24chip::MerkleTraceArgs& a, hipStream_t 
     return hipGetLastError();
 }
 
+// the LAYER-PATHS variant (p24chip.h, LayerPathsArgs): the P24L table of the fold-16 paths machine, all layers in ONE launch.  A WAVE per path: lane i < 24 holds
+// state word i.  A path is 14 - 27 dependent permutations, so a lane per path (the form above) is bound by one lane's arithmetic; here the S-boxes of an
+// external round run side by side, the 4 x 4 blocks and the column sums of the external layer and the internal layer's sum go over cross-lane moves (no LDS),
+// and the internal rounds' S-box is computed from lane 0's word.  Every 24-column section is stored by 24 adjacent lanes (96 contiguous bytes), the 64 columns of
+// the internal rounds by the whole wave.  The leaf's 64 words are read from the first reader's row of the FOLD16 trace -- already Montgomery, where
+// fri16_fold_rows_kernel put the query's own value or the previous layer's fold among the 15 siblings -- and compared, a word per lane, with the other readers'.
+// A wave past the paths computes the padding row once and stores it 16 times.  (Timed against the lane-per-path form: DESIGN.md section 3c.)
+__device__ __forceinline__ uint32_t p24l_coop_ext_linear(uint32_t x, int lane) {
+    const int base = lane & ~3, k = lane & 3;
+    uint32_t b0 = (uint32_t)__shfl((int)x, base), b1 = (uint32_t)__shfl((int)x, base + 1), b2 = (uint32_t)__shfl((int)x, base + 2), b3 = (uint32_t)__shfl((int)x, base + 3);
+    p2_m4_hl_dev(b0, b1, b2, b3);
+    const uint32_t y = k == 0 ? b0 : k == 1 ? b1 : k == 2 ? b2 : b3;
+    uint32_t t = 0u;
+#pragma unroll
+    for (int j = 0; j < 6; j++) t = dadd(t, (uint32_t)__shfl((int)y, k + 4 * j));
+    return dadd(y, t);
+}
+// one row: `in` = this lane's input word (lanes < 24), `ft` = this lane's word of the 24 columns BIT .. K3; the row goes to t, t + ld, ... (nrep times)
+__device__ __forceinline__ uint32_t p24l_coop_row(uint32_t* t, uint64_t ld, uint32_t nrep, uint32_t in, uint32_t ft, uint32_t bit) {
+    using namespace p24chip;
+    const int lane = (int)threadIdx.x, li = lane < 24 ? lane : 0;
+    const bool act = lane < 24;
+    auto put = [&](uint32_t col, uint32_t v, int n) {
+        if (lane < n) for (uint32_t r = 0; r < nrep; r++) t[(uint64_t)r * ld + col + lane] = v;
+    };
+    uint32_t s = act ? in : 0u;
+    put(IN, s, 24);
+    s = p24l_coop_ext_linear(s, lane);
+    put(S0, s, 24);
+    auto external_round = [&](uint32_t r) {
+        const uint32_t y = fadd(s, P24K.ext_rc[r][li]), x3 = fmul(fmul(y, y), y);
+        put(x3e(r), x3, 24);
+        s = p24l_coop_ext_linear(fmul(fmul(x3, x3), y), lane);
+        put(oute(r), s, 24);
+    };
+#pragma unroll 1
+    for (uint32_t r = 0; r < 4; r++) external_round(r);
+    uint32_t w = 0u;                                            // column s0p(0) + lane of the internal rounds' section
+    const uint32_t dg = P24K.diag[li];
+#pragma unroll 1
+    for (int r = 0; r < 21; r++) {
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s), y = fadd(s0, P24K.int_rc[r]), x3 = fmul(fmul(y, y), y), s7 = fmul(fmul(x3, x3), y);
+        w = lane == 3 * r ? s0 : lane == 3 * r + 1 ? x3 : lane == 3 * r + 2 ? s7 : w;
+        if (lane == 0) s = s7;
+        uint32_t sum = act ? s : 0u;
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) sum = dadd(sum, (uint32_t)__shfl_xor((int)sum, d));
+        s = fadd(fmul(s, dg), sum);
+    }
+    for (uint32_t r = 0; r < nrep; r++) t[(uint64_t)r * ld + s0p(0) + lane] = w;
+    put(SP, s, 24);
+#pragma unroll 1
+    for (uint32_t r = 4; r < 8; r++) external_round(r);
+    const uint32_t hi = (uint32_t)__shfl((int)in, (lane + 8) & 63);
+    put(D, bit ? hi : in, 8);
+    put(BIT, ft, 24);
+    return s;
+}
+static_assert(p24chip::WIDTH_L == p24chip::BIT + 24 && p24chip::s0p(0) + 64 == p24chip::SP, "p24l_coop_row: the flag and tail columns are 24 words, the internal rounds' section 64");
+__device__ __forceinline__ void p24chip_layer_paths_kernel_body(const p24chip::LayerPathsArgs& a) {
+    using namespace p24chip;
+    const uint64_t p = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const uint32_t one = MONTY_R1;
+    auto pick = [&](const uint32_t (&v)[24]) {
+        uint32_t x = 0u;
+#pragma unroll
+        for (int j = 0; j < 24; j++) x = lane == j ? v[j] : x;
+        return x;
+    };
+    if (p < a.n_paths) {
+        const uint4 d0 = reinterpret_cast<const uint4*>(a.desc)[2 * p], d1 = reinterpret_cast<const uint4*>(a.desc)[2 * p + 1];
+        const uint32_t layer = d0.x, row = d0.y, depth = d0.z, mult = d0.w, first = d1.x, rd = d1.y, sib_off = d1.z;
+        const uint32_t* leaf = a.fold + (uint64_t)a.readers[rd] * a.fold_ld;
+        const uint32_t mine = leaf[lane];
+        uint32_t differs = 0u;
+        for (uint32_t r = 1; r < mult; r++) {
+            const uint32_t theirs = (a.fold + (uint64_t)a.readers[rd + r] * a.fold_ld)[lane];
+            if (__ballot(mine != theirs) != 0ull && !differs) differs = r + 1u;
+        }
+        if (lane == 0) a.differs[p] = differs;
+        uint32_t* t = a.trace + (uint64_t)first * a.ld;
+        const uint32_t ln = to_monty(layer), kp2 = to_monty(2u * row), m = to_monty(mult), cnt = to_monty((uint32_t)p);
+        uint32_t out = 0u;
+        for (uint32_t k = 0; k < LEAF_ROWS; k++, t += a.ld) {
+            const uint32_t key = 16u * row + 4u * k;
+            const uint32_t ft[24] = {0u, 0u, 0u, cnt, k ? one : 0u, k ? 0u : one, one, one, one, 0u, 0u, 0u, ln, kp2, m, 0u,
+                                     k == 0 ? one : 0u, k == 1 ? one : 0u, k == 2 ? one : 0u, k == 3 ? one : 0u, to_monty(key), to_monty(key + 1u), to_monty(key + 2u), to_monty(key + 3u)};
+            out = p24l_coop_row(t, a.ld, 1u, lane < 16 ? leaf[16u * k + (uint32_t)(lane & 15)] : out, pick(ft), 0u);
+        }
+        const uint32_t* sib = a.siblings + sib_off;
+        for (uint32_t lvl = 0; lvl < depth; lvl++, t += a.ld) {
+            const uint32_t bit = (row >> lvl) & 1u, end = lvl + 1 == depth ? 1u : 0u;
+            const uint32_t sv = to_monty(sib[8u * lvl + (uint32_t)(lane & 7)]), lo = (uint32_t)__shfl((int)out, lane & 7);
+            const uint32_t in = lane < 8 ? (bit ? sv : lo) : lane < 16 ? (bit ? lo : sv) : 0u;
+            const uint32_t ft[24] = {bit ? one : 0u, one, end ? one : 0u, to_monty((uint32_t)p + end), 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, ln, to_monty(row >> lvl), 0u, to_monty(lvl + 1u),
+                                     0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            out = p24l_coop_row(t, a.ld, 1u, in, pick(ft), bit);
+        }
+        if (lane < 8) a.ends[8 * p + lane] = from_monty(out);
+        return;
+    }
+    const uint64_t r0 = a.used_rows + (p - a.n_paths) * 16u;
+    if (r0 >= a.rows) return;
+    const uint32_t n = a.rows - r0 < 16u ? (uint32_t)(a.rows - r0) : 16u;
+    p24l_coop_row(a.trace + r0 * a.ld, a.ld, n, 0u, lane == 3 ? to_monty((uint32_t)a.n_paths) : 0u, 0u);
+}
+__global__ void __launch_bounds__(64) p24chip_layer_paths_kernel(p24chip::LayerPathsArgs a) { p24chip_layer_paths_kernel_body(a); }
+struct p24chip_layer_paths_kernel_bargs { p24chip::LayerPathsArgs a; static p24chip_layer_paths_kernel_bargs make(p24chip::LayerPathsArgs a) { return p24chip_layer_paths_kernel_bargs{a}; } };
+__global__ void __launch_bounds__(64) p24chip_layer_paths_kernel_batch(const p24chip_layer_paths_kernel_bargs* __restrict__ zk_arr) { const p24chip_layer_paths_kernel_bargs& zk_b = zk_arr[blockIdx.z]; p24chip_layer_paths_kernel_body(zk_b.a); }
+hipError_t launch_p24chip_layer_paths(const p24chip::LayerPathsArgs& a, hipStream_t s) {
+    const uint64_t waves = a.n_paths + (a.rows - a.used_rows + 15) / 16;
+    ZK_LAUNCH(p24chip_layer_paths_kernel, p24chip_layer_paths_kernel_batch, p24chip_layer_paths_kernel_bargs, dim3((unsigned)waves), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace zk

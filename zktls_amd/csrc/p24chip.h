@@ -38,5 +38,24 @@ struct MerkleTraceArgs {
     uint32_t* roots;             // [n_paths][8], canonical
 };
 
+// The LAYER-PATHS variant (the fold-16 paths machine, fri16_chip.hip: P24L stands where the LAYERS table stood).  The 540 columns above keep their
+// positions; a tail section follows: LN layer | KP index walk | M receive multiplicity | DEP compression rows so far | Z0..Z3 one-hot number of a
+// leaf's sponge row | K0..K3 the bus keys of the four entries a sponge row absorbs.  A path = four sponge rows over the 64 words of a layer row
+// (KP = 2 row, BIT = 0, DEP = 0, K_i = 16 row + 4 k + i on sponge row k, M = readers on all four), then `depth` compression rows (KP = row >> level,
+// DEP = level + 1, M = K = Z = 0).  Padding rows: the permutation of the zero state, every flag and the tail zero.
+constexpr uint32_t L_LN = 540, L_KP = 541, L_M = 542, L_DEP = 543, L_Z = 544, L_K = 548, WIDTH_L = 552, LEAF_ROWS = 4, LEAF_WORDS = 64;
+static_assert(L_LN == WIDTH && L_Z % 4 == 0 && L_K % 4 == 0 && WIDTH_L % 4 == 0, "p24chip layer-paths tail: 16-byte sections");
+struct LayerPathsArgs {
+    const uint32_t* desc;        // [n_paths][8]: layer, row index, depth, readers, first trace row, offset into `readers`, word offset into `siblings`, 0
+    const uint32_t* readers;     // per path its readers' rows of the FOLD16 trace; the first one's E columns are the leaf
+    const uint32_t* fold;        // the FOLD16 trace (Montgomery; fri16_rows.cuh: E = columns 0..64), leading dimension fold_ld
+    uint64_t fold_ld;
+    const uint32_t* siblings;    // canonical digests, `depth` of them per path from its offset
+    uint64_t n_paths, rows, used_rows;
+    uint32_t* trace; uint64_t ld;   // [rows][ld], Montgomery; 16-byte aligned, ld % 4 == 0
+    uint32_t* ends;              // [n_paths][8] canonical: where each path ends
+    uint32_t* differs;           // [n_paths]: 0, or 1 + the number (within the path's readers) of the first reader whose 64 words are not the first reader's
+};
+
 }  // namespace p24chip
 }  // namespace zk

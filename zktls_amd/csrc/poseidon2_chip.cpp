@@ -395,6 +395,7 @@ using p2chip::Term;
 using p2chip::Terms;
 using p2chip::var;
 using p2chip::pub;
+using p2chip::neg;
 
 struct Layout24 {
     static constexpr uint32_t IN = p24chip::IN, S0 = p24chip::S0, SP = p24chip::SP;
@@ -406,7 +407,9 @@ struct Layout24 {
     static uint32_t ext_input(uint32_t r) { return p24chip::ext_input(r); }
 };
 
-std::vector<uint32_t> build_program() {
+// layers: the layer-paths variant P24L of the fold-16 paths machine (p24chip.h: the tail columns; fri16_chip.hip: the machine) -- no public root and
+// count, n_public public values of the machine's, and the constraints of leaf shape, path shape, index, depth and bus keys at the end
+std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_PUBLIC) {
     using p2chip::ALL; using p2chip::FIRST; using p2chip::LAST; using p2chip::TRANSITION;
     Builder b;
     uint32_t ME[24][24], rc_e[8][24], rc_i[21], diag[24];
@@ -437,11 +440,41 @@ std::vector<uint32_t> build_program() {
         for (uint32_t j = 4 * k; j < 4 * k + 4; j++)
             b.add(TRANSITION, Terms{{1u, {var(C(k), true), var(IN + j, true)}}, {P - 1, {var(C(k), true), var(o7 + j)}}});
     for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(CH, true), var(D + j, true)}}, {P - 1, {var(CH, true), var(o7 + j)}}});
-    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(END), var(o7 + j)}}, {P - 1, {var(END), pub(j)}}});
+    if (!layers) for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(END), var(o7 + j)}}, {P - 1, {var(END), pub(j)}}});
     b.add(FIRST, Terms{{1u, {var(CNT)}}, {P - 1, {var(END)}}});
     b.add(TRANSITION, Terms{{1u, {var(CNT, true)}}, {P - 1, {var(CNT)}}, {P - 1, {var(END, true)}}});
-    b.add(LAST, Terms{{1u, {var(CNT)}}, {P - 1, {pub(8)}}});
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, WIDTH, b.count, N_PUBLIC, (uint32_t)(6 + b.body.size())};
+    if (!layers) b.add(LAST, Terms{{1u, {var(CNT)}}, {P - 1, {pub(8)}}});
+    if (layers) {
+        const uint32_t Z0 = L_Z, Z1 = L_Z + 1, Z2 = L_Z + 2, Z3 = L_Z + 3;
+        // leaf shape: Z_k one-hot number of a sponge row, Z0 = SS, SPG = Z1 + Z2 + Z3, stepping 0 1 2 3; every block is full
+        for (uint32_t k = 0; k < 4; k++) b.add(ALL, Terms{{1u, {var(L_Z + k), var(L_Z + k)}}, {P - 1, {var(L_Z + k)}}});
+        b.add(ALL, Terms{{1u, {var(Z0)}}, {P - 1, {var(SS)}}});
+        b.add(ALL, Terms{{1u, {var(SPG)}}, {P - 1, {var(Z1)}}, {P - 1, {var(Z2)}}, {P - 1, {var(Z3)}}});
+        b.add(ALL, Terms{{1u, {var(SS), var(SPG)}}});
+        for (uint32_t k = 1; k <= 3; k++) b.add(ALL, Terms{{1u, {var(G(k))}}, {P - 1, {var(SS)}}, {P - 1, {var(SPG)}}});
+        for (uint32_t k = 0; k < 3; k++) b.add(TRANSITION, Terms{{1u, {var(L_Z + k + 1, true)}}, {P - 1, {var(L_Z + k)}}});
+        // path shape: the row after a leaf's fourth row, and after a compression row that does not end the path, continues it -- and no other row does
+        b.add(TRANSITION, Terms{{1u, {var(CH, true)}}, {P - 1, {var(Z3)}}, {P - 1, {var(CH)}}, {1u, {var(END)}}});
+        b.add(LAST, Terms{{1u, {var(Z0)}}, {1u, {var(Z1)}}, {1u, {var(Z2)}}, {1u, {var(Z3)}}, {1u, {var(CH)}}, {P - 1, {var(END)}}});
+        b.add(ALL, Terms{{1u, {var(END)}}, {P - 1, {var(END), var(CH)}}});                                       // a path ends on a compression row
+        b.add(ALL, Terms{{1u, {var(SS), var(CH)}}, {1u, {var(SPG), var(CH)}}});
+        b.add(ALL, Terms{{1u, {var(SS), var(BIT)}}, {1u, {var(SPG), var(BIT)}}});
+        b.add(TRANSITION, Terms{{1u, {var(CH, true), var(L_LN, true)}}, {P - 1, {var(CH, true), var(L_LN)}},      // one layer per path
+                                {1u, {var(SPG, true), var(L_LN, true)}}, {P - 1, {var(SPG, true), var(L_LN)}}});
+        // index: the sponge rows hold 2 row (BIT = 0), so ONE recurrence covers the step into the first compression row as well
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true), var(L_KP, true)}}, {P - 1, {var(SPG, true), var(L_KP)}}});
+        b.add(TRANSITION, Terms{{1u, {var(CH, true), var(L_KP)}}, {P - 2, {var(CH, true), var(L_KP, true)}}, {P - 1, {var(CH, true), var(BIT)}}});   // KP = 2 KP' + BIT
+        b.add(ALL, Terms{{1u, {var(END), var(L_KP)}}, {P - 1, {var(END), var(BIT)}}});                           // exactly depth bits
+        // depth: zero on sponge rows, then one more per compression row
+        b.add(ALL, Terms{{1u, {var(SS), var(L_DEP)}}, {1u, {var(SPG), var(L_DEP)}}});
+        b.add(TRANSITION, Terms{{1u, {var(CH, true), var(L_DEP, true)}}, {P - 1, {var(CH, true), var(L_DEP)}}, {P - 1, {var(CH, true)}}});
+        // tuples are received on sponge rows only; their keys K_i = 16 row + 4 k + i = 8 KP + 4 k + i there, zero elsewhere
+        b.add(ALL, Terms{{1u, {var(L_M)}}, {P - 1, {var(L_M), var(SS)}}, {P - 1, {var(L_M), var(SPG)}}});
+        for (uint32_t i = 0; i < 4; i++)
+            b.add(ALL, Terms{{1u, {var(L_K + i)}}, {P - 8, {var(SS), var(L_KP)}}, {P - 8, {var(SPG), var(L_KP)}}, {neg(i), {var(Z0)}}, {neg(4 + i), {var(Z1)}},
+                             {neg(8 + i), {var(Z2)}}, {neg(12 + i), {var(Z3)}}});
+    }
+    std::vector<uint32_t> p{AIR_MAGIC, 1u, layers ? WIDTH_L : WIDTH, b.count, n_public, (uint32_t)(6 + b.body.size())};
     p.insert(p.end(), b.body.begin(), b.body.end());
     return p;
 }
@@ -456,6 +489,21 @@ std::shared_ptr<const std::vector<uint32_t>> program() {
     if (!cached || cached_gen != gen) { cached = std::make_shared<const std::vector<uint32_t>>(build_program()); cached_gen = gen; }
     return cached;
 }
+
+}  // namespace
+// the layer-paths variant for a machine with n_public public values (fri16_chip.hip); follows the width-24 tables in effect like program()
+std::shared_ptr<const std::vector<uint32_t>> program_fri16_layers(uint32_t n_public) {
+    static std::mutex mu;
+    static std::map<uint32_t, std::shared_ptr<const std::vector<uint32_t>>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen) { cache.clear(); cached_gen = gen; }
+    auto it = cache.find(n_public);
+    if (it == cache.end()) it = cache.emplace(n_public, std::make_shared<const std::vector<uint32_t>>(build_program(true, n_public))).first;
+    return it->second;
+}
+namespace {
 
 int paths_shape(size_t n_paths, int depth, uint32_t row_width, int* log_n) {
     if (row_width % 4 != 0 || row_width > 1024) return fail(ZKHIP_ERR_INVALID, "merkle paths p24: the opened row width is 0 (leaf digests are given) or a multiple of 4 up to 1024");

@@ -691,6 +691,41 @@ class Context:
         check(self.lib.zkhip_prove_fri16(self.handle, key.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 PATHS machine (the layer rows' Merkle paths in-circuit: P24L + ROOTS where LAYERS stood)
+    def fri16_paths_key(self, view, params=None):
+        """zkhip_fri16_paths_key: QUERIES, COEFFS, ROOTS and FINAL's schedule of a fold-16 view, committed on the device -- from the final coefficients,
+        the indices, the reduced openings and the layer roots alone -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_paths_key(self.handle, *shape, hw, *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[2], arrs[3], roots)], C.byref(params), C.byref(handle),
+                                             root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_paths_gen_trace(self, view, out=None):
+        """zkhip_fri16_paths_gen_trace: the P24L table of a fold-16 view -> (buffer, its log rows, path ends [n][8]); out: a buffer of an earlier call"""
+        shape, hw, arrs, _, paths = _fri16_paths_arrays(view)
+        ln = [d[1] for d in (fri16_paths_describe(*shape, which, 0) for which in range(6)) if d[4] == 2][0]
+        buf = out if out is not None else self.alloc(552 << ln)
+        cap = shape[0] * shape[3]
+        ends, n = np.zeros(8 * cap, dtype=np.uint32), C.c_size_t(0)
+        check(self.lib.zkhip_fri16_paths_gen_trace(self.handle, *shape, hw, *[a.ctypes.data_as(u32p) for a in arrs], paths.ctypes.data_as(u32p), C.c_void_p(buf.ptr), 552,
+                                                   ends.ctypes.data_as(u32p), cap, C.byref(n)))
+        return buf, ln, ends[:8 * n.value].reshape(-1, 8)
+
+    def prove_fri16_paths(self, key, view, params=None):
+        """zkhip_prove_fri16_paths: "every listed query opens the listed layer commitments row by row and folds by 16 through these rows to the listed final
+        polynomial at its last point"; refused before anything is proven: a path that does not end in its layer's root, queries that disagree about a
+        shared row or its path, a chain that does not end in the final polynomial"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
+        size = self.lib.zkhip_fri16_paths_proof_size(*shape, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_paths(self.handle, key.handle, *shape, hw, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+                                               paths.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1382,6 +1417,7 @@ def fri16_view_shard(proof, log_n, width, public_values=(), params=None):
     lhs = [H - 4 * (l + 1) for l in range(R)]
     offs = np.concatenate([[0], np.cumsum([8 * lh for lh in lhs])]).astype(int)
     return {"betas": betas.reshape(R, 4).tolist(), "final_poly": fp.reshape(-1, 4).tolist(), "roots": roots.reshape(R, 8).tolist(), "F": F, "b": b, "H": H,
+            "hash_width": 24 if params.hash_width == 24 else 16,
             "queries": [(int(idx[q]), vals[4 * q:4 * q + 4].tolist(), sibs[60 * q * R:60 * (q + 1) * R].reshape(R, 15, 4).tolist()) for q in range(Q)],
             "paths": [[paths[q * pw + offs[l]:q * pw + offs[l + 1]].tolist() for l in range(R)] for q in range(Q)]}
 
@@ -1417,6 +1453,52 @@ def verify_fri16(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
     k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
     reason = C.c_int(0)
     rc = lib.zkhip_verify_fri16(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params), C.byref(reason))
+    return rc, reason.value
+
+
+def _fri16_paths_arrays(view):
+    """a fold-16 view with roots and paths -> ((R, F, log_blowup, queries), inner hash width, the arrays of _fri16_arrays, roots [R][8], paths flat).  A view
+    that does not say which hash its commitments use ("hash_width") is taken as width-24."""
+    shape, arrs = _fri16_arrays(view)
+    u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+    roots, paths = u(view["roots"]), u([c for pq in view["paths"] for pl in pq for c in pl])
+    H = view["H"]
+    assert roots.size == 8 * shape[0] and paths.size == shape[3] * sum(8 * (H - 4 * (l + 1)) for l in range(shape[0]))
+    return shape, int(view.get("hash_width", 24)), arrs, roots, paths
+
+
+def fri16_paths_describe(R, F, log_blowup, n_queries, which, kind):
+    """zkhip_fri16_paths_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..5) of the fold-16 paths
+    machine -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS)"""
+    lib = _lib.load()
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    n = lib.zkhip_fri16_paths_describe(R, F, log_blowup, n_queries, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    if n == 0:
+        raise _lib.ZkHipError(-1, "fri16_paths_describe: " + lib.zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib.zkhip_fri16_paths_describe(R, F, log_blowup, n_queries, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb)) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def fri16_paths_key_host(view, params=None):
+    """zkhip_fri16_paths_key_host: the fold-16 paths machine's key of a view, without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_paths_key_host(*shape, hw, *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[2], arrs[3], roots)], C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_paths(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
+    """zkhip_verify_fri16_paths: the challenges, the key, the shape -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    bt = np.ascontiguousarray(np.array(betas, dtype=np.uint32).reshape(-1))
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_fri16_paths(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params),
+                                      C.byref(reason))
     return rc, reason.value
 
 
