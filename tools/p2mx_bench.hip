@@ -4,6 +4,9 @@
 //                                              the 256-wide leaf row of the headline shard)
 // Prints one JSON line: word-for-word mismatches of the two device forms (random states plus edge words, chains of 1 and 3, and the first
 // 256 states against the host's portable form), each kernel's resources, and min / median milliseconds of alternating timed launches.
+// The width-16 partial rounds run paired (elements 1..15 updated once per two rounds, p2_internal_pair_dev) or one at a time by a flag of
+// the constant tables: the correctness pass also runs every form with the flag cleared ("pair_mismatches": against the paired all-VALU
+// words), and the throughput pass times both settings of both permutations ("*_pr_ms_*": one round at a time).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/p2mx_bench tools/p2mx_bench.hip   (__graft_entry__.build() does)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -117,6 +120,27 @@ int main(int argc, char** argv) {
             }
     }
 
+    // the partial rounds one at a time (the flag cleared in this program's constant tables) against the paired words, every form
+    uint64_t pair_mism = 0;
+    P2Tables per_round = P2_BUILTIN;
+    per_round.pk16.pair = 0;
+    for (int c : {1, 3})
+    for (int form : {0, 1, 2, 3}) {
+        CK(hipMemcpy(d0, h0.data(), 16 * nchk * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d1, h0.data(), 16 * nchk * 4, hipMemcpyHostToDevice));
+        CK(p2_upload_tables(g_p2_tables, 0));
+        launch(0, d0, nchk, c);
+        CK(hipDeviceSynchronize());
+        CK(p2_upload_tables(per_round, 0));
+        launch(form, d1, nchk, c);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(ha.data(), d0, 16 * nchk * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hb.data(), d1, 16 * nchk * 4, hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < 16 * nchk; k++) pair_mism += ha[k] != hb[k];
+    }
+    CK(p2_upload_tables(g_p2_tables, 0));
+    CK(hipDeviceSynchronize());
+
     hipFuncAttributes fa, fb, fc, fd;
     CK(hipFuncGetAttributes(&fd, reinterpret_cast<const void*>(perm_mx6_kernel)));
     CK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(perm_vec_kernel)));
@@ -144,16 +168,38 @@ int main(int argc, char** argv) {
         t[form].push_back(ms);
     }
     for (auto& v : t) std::sort(v.begin(), v.end());
+    // paired against one round at a time: the all-VALU form and the 5-wave matrix-core form (the leaf kernel's), settings alternating
+    std::vector<float> tp[4];                                                     // vec paired, vec per-round, mx5 paired, mx5 per-round
+    for (int r = 0; r < 4 * reps; r++) {
+        const int k = r % 4, form = k < 2 ? 0 : 2;
+        CK(p2_upload_tables(k & 1 ? per_round : g_p2_tables, 0));
+        CK(hipDeviceSynchronize());
+        CK(hipEventRecord(e0));
+        launch(form, form ? d1 : d0, n, chain);
+        CK(hipEventRecord(e1));
+        CK(hipEventSynchronize(e1));
+        float ms = 0;
+        CK(hipEventElapsedTime(&ms, e0, e1));
+        tp[k].push_back(ms);
+    }
+    CK(p2_upload_tables(g_p2_tables, 0));
+    CK(hipDeviceSynchronize());
+    for (auto& v : tp) std::sort(v.begin(), v.end());
     printf("{\"states\": %llu, \"chain\": %d, \"mismatches\": %llu, \"checked_words\": %llu, \"host_mismatches\": %llu, "
            "\"vec_regs\": %d, \"mx_regs\": %d, \"mx5_regs\": %d, \"vec_scratch\": %d, \"mx_scratch\": %d, \"mx5_scratch\": %d, "
            "\"vec_ms_min\": %.4f, \"vec_ms_med\": %.4f, \"mx_ms_min\": %.4f, \"mx_ms_med\": %.4f, \"mx5_ms_min\": %.4f, \"mx5_ms_med\": %.4f, "
            "\"mx6_ms_min\": %.4f, \"mx6_ms_med\": %.4f, \"mx6_regs\": %d, \"mx6_scratch\": %d, "
-           "\"mx_over_vec_med\": %.4f, \"mx5_over_vec_med\": %.4f, \"mx6_over_vec_med\": %.4f}\n",
+           "\"mx_over_vec_med\": %.4f, \"mx5_over_vec_med\": %.4f, \"mx6_over_vec_med\": %.4f, "
+           "\"pair_mismatches\": %llu, \"vec_pair_ms_min\": %.4f, \"vec_pair_ms_med\": %.4f, \"vec_pr_ms_min\": %.4f, \"vec_pr_ms_med\": %.4f, "
+           "\"mx5_pair_ms_min\": %.4f, \"mx5_pair_ms_med\": %.4f, \"mx5_pr_ms_min\": %.4f, \"mx5_pr_ms_med\": %.4f, "
+           "\"vec_pair_over_pr_med\": %.4f, \"mx5_pair_over_pr_med\": %.4f}\n",
            (unsigned long long)n, chain, (unsigned long long)mism, (unsigned long long)(4 * 16 * nchk), (unsigned long long)host_mism,
            fa.numRegs, fb.numRegs, fc.numRegs, (int)fa.localSizeBytes, (int)fb.localSizeBytes, (int)fc.localSizeBytes,
            t[0][0], t[0][reps / 2], t[1][0], t[1][reps / 2], t[2][0], t[2][reps / 2], t[3][0], t[3][reps / 2],
-           fd.numRegs, (int)fd.localSizeBytes, t[1][reps / 2] / t[0][reps / 2], t[2][reps / 2] / t[0][reps / 2], t[3][reps / 2] / t[0][reps / 2]);
+           fd.numRegs, (int)fd.localSizeBytes, t[1][reps / 2] / t[0][reps / 2], t[2][reps / 2] / t[0][reps / 2], t[3][reps / 2] / t[0][reps / 2],
+           (unsigned long long)pair_mism, tp[0][0], tp[0][reps / 2], tp[1][0], tp[1][reps / 2], tp[2][0], tp[2][reps / 2], tp[3][0], tp[3][reps / 2],
+           tp[0][reps / 2] / tp[1][reps / 2], tp[2][reps / 2] / tp[3][reps / 2]);
     CK(hipFree(d0));
     CK(hipFree(d1));
-    return mism || host_mism ? 1 : 0;
+    return mism || host_mism || pair_mism ? 1 : 0;
 }

@@ -801,8 +801,16 @@ int zkhip_ctx_create(int device, void* stream, zkhip_ctx** out) {
         if ((e = launch_fused_table(ctx->w1024f_fwd, ctx->w1024_fwd, 1, 0, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "fused_table"); break; }
         if ((e = launch_fused_table(ctx->w1024f_inv, ctx->w1024_inv, 1, 0, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "fused_table"); break; }
         // the Poseidon2 tables in effect (built-in or zkhip_load_poseidon2_params) go to this device's constant memory
-        if ((e = hash_upload_p2_tables(g_p2_tables, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "upload Poseidon2 tables"); break; }
-        if ((e = stark_upload_p2_tables(g_p2_tables, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "upload Poseidon2 tables"); break; }
+#ifdef ZKHIP_AB_HOOKS
+        // A/B timing only: ZKHIP_P2_PER_ROUND runs the width-16 partial rounds one at a time where the diagonal would take the paired form
+        static P2Tables p2t;
+        p2t = g_p2_tables;
+        if (getenv("ZKHIP_P2_PER_ROUND")) p2t.pk16.pair = 0;
+#else
+        const P2Tables& p2t = g_p2_tables;
+#endif
+        if ((e = hash_upload_p2_tables(p2t, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "upload Poseidon2 tables"); break; }
+        if ((e = stark_upload_p2_tables(p2t, ctx->stream)) != hipSuccess) { rc = hip_fail(e, "upload Poseidon2 tables"); break; }
         if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) { rc = hip_fail(e, "sync"); break; }
     } while (0);
     if (rc != ZKHIP_OK) { zkhip_ctx_destroy(ctx); return rc; }
