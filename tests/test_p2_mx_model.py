@@ -5,6 +5,7 @@ way.  The layer is linear, so the model works on canonical words: the Montgomery
 import numpy as np
 
 import pyref
+from p2_device_model import dsmred, mx_layer  # noqa: F401
 
 P = pyref.P
 MX_BIAS = 0x80808080 - P
@@ -33,41 +34,6 @@ ME_INV = _inv_mod_matrix(pyref.ME)
 
 def _pre(v):
     return [sum(ME_INV[i][j] * v[j] for j in range(16)) % P for i in range(16)]
-
-
-def dsmred(t):
-    """babybear.cuh dsmred: t / 2^32 mod P for a signed 64-bit t, with the device's exact integer steps"""
-    assert -2**63 <= t < 2**63
-    m = (t & 0xFFFFFFFF) * MU & 0xFFFFFFFF
-    m = m - 2**32 if m >= 2**31 else m
-    y = t - m * P
-    assert y % 2**32 == 0
-    return y >> 32
-
-
-def mx_layer(u, stats=None):
-    """u: 16 ints in [0, 2P) (the S-box's lazy outputs, or canonical input + M_E^-1 rc_0).  Returns w = M_E (u - P) mod P as signed words."""
-    u = np.asarray(u, dtype=np.int64)
-    assert ((u >= 0) & (u < 2 * P)).all()
-    y = u + MX_BIAS                                                       # step 1: what dmred_lazy returns with the biased fold constant
-    assert ((y >= 0) & (y < 2**32)).all()
-    b = (y[:, None] >> (8 * np.arange(4))) & 255                        # bytes of y; xor 0x80 and read as int8
-    d = (b ^ 0x80).astype(np.int8).astype(np.int64)
-    assert (d @ (256 ** np.arange(4)) == u - P).all()
-    assert d.min() >= -128 and d.max() <= 127 and np.abs(d[:, 3]).max() <= 120
-    Y = ME @ d                                                            # step 2: [element i][plane k], exact in i32
-    assert np.abs(Y).max() <= 35 * 128 < 2**13
-    L = Y[:, 0] + (Y[:, 1] << 8) + (Y[:, 2] << 16)                       # step 3
-    assert np.abs(L).max() < 2**28.2
-    T = [(int(L[i]) << 32) + int(Y[i, 3]) * C24 for i in range(16)]
-    assert max(abs(t) for t in T) < 2**60.2
-    w = [dsmred(t) for t in T]
-    assert max(abs(x) for x in w) < 2**28.2 + P / 2 < P
-    assert all((w[i] - sum(int(ME[i, j]) * int(u[j]) for j in range(16))) % P == 0 for i in range(16))
-    if stats is not None:
-        stats["Y"] = max(stats.get("Y", 0), int(np.abs(Y).max()))
-        stats["w"] = max(stats.get("w", 0), max(abs(x) for x in w))
-    return w
 
 
 def _lazy(v, rng):

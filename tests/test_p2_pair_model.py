@@ -12,144 +12,8 @@ import numpy as np
 
 import pyref
 
-P = pyref.P
-R = 2**32 % P
-MU = pow(P, -1, 2**32)
-H = (P - 1) // 2                        # the largest magnitude of a centred constant
-SH_ONE, SH_PAIR = 27, 24                # row-sum scales: the one-round form's, a pair's first round's
-I32 = 2**31 - 1
-
-
-def cen(x):
-    x %= P
-    return x - P if x > P // 2 else x
-
-
-def dsmred(t):
-    """babybear.cuh dsmred: t / 2^32 mod P for a signed 64-bit t, the device's exact integer steps"""
-    assert -2**63 <= t < 2**63
-    m = (t & 0xFFFFFFFF) * MU & 0xFFFFFFFF
-    m = m - 2**32 if m >= 2**31 else m
-    y = t - m * P
-    assert -2**63 <= y < 2**63 and y % 2**32 == 0
-    r = y >> 32
-    assert -2**31 <= r < 2**31
-    return r
-
-
-def mad(a, k, c):
-    """v_mad_i64_i32: a, k int32, c and the result int64"""
-    assert -2**31 <= a < 2**31 and -2**31 <= k < 2**31
-    d = a * k + c
-    assert -2**63 <= d < 2**63
-    return d
-
-
-def sbox(t):
-    x2 = dsmred(mad(t, t, 0))
-    x4 = dsmred(mad(x2, x2, 0))
-    x6 = dsmred(mad(x4, x2, 0))
-    return dsmred(mad(x6, t, 0))
-
-
-def pair_budget_ok(sum_d, sh_pair=SH_PAIR):
-    """The interval pass: magnitudes only, every centred constant taken at its largest (P - 1) / 2, so the answer depends on the diagonal
-    through sum_{i>=1} d_i alone.  red(x) bounds |dsmred(X)| for |X| <= x; sh_pair is the row-sum scale of a pair's first round."""
-    def red(x):
-        if x > 2**63 - 1 - 2**31 * P:
-            raise OverflowError
-        r = x // 2**32 + P // 2 + 1
-        if r > I32:
-            raise OverflowError
-        return r
-
-    def sbox_b(t):
-        x2 = red(t * t)
-        x4 = red(x2 * x2)
-        x6 = red(x4 * x2)
-        return red(x6 * t)
-
-    try:
-        b0 = bv = P - 1
-        u = sbox_b(b0)                                                  # the leading round, one-round form
-        s = red((u + 15 * bv) << SH_ONE)
-        b0, bv = red(u * H + s * H + H), red(bv * H + s * H)
-        if max(b0, bv) > P - 1:
-            return False
-        for _ in range(6):
-            u = sbox_b(b0)
-            st = red((u + 15 * bv) << sh_pair)
-            v0 = red(u * H + st * H + H)
-            u2 = sbox_b(v0)
-            s1 = red(sum_d * bv + st * 15 * 2**(32 - sh_pair) + u2)
-            t2 = s1 * H
-            b0, bv = red(u2 * H + t2 + H), red(bv * H + st * H + t2)
-            if max(b0, bv, v0) > P - 1:
-                return False
-        return True
-    except OverflowError:
-        return False
-
-
-class Consts:
-    def __init__(self, diag, rc_i):
-        self.d = [x % P for x in diag]
-        self.D = [cen(x * R) for x in self.d]
-        self.rc_fold = [cen(rc_i[r + 1] * R * R) for r in range(12)] + [0]
-        self.K27 = cen(2**(64 - SH_ONE))
-        self.K24 = cen(2**(64 - SH_PAIR))
-        self.K1 = cen(R * R)
-        self.C15 = cen(15 * 2**(32 - SH_PAIR))
-        self.D2 = [cen(x * x * R) for x in self.d]
-        self.E = [cen(x * 2**(64 - SH_PAIR)) for x in self.d]
-        self.pair = all(1 <= x <= 2**15 for x in self.d[1:]) and pair_budget_ok(sum(self.d[1:]))
-
-
-def round_one(v, r, k):
-    u = sbox(v[0])
-    T = 0
-    for x in [u] + v[1:]:
-        T = mad(x, 1 << SH_ONE, T)
-    s = dsmred(T)
-    T2 = mad(s, k.K27, 0)
-    return [dsmred(mad(u, k.D[0], T2 + k.rc_fold[r]))] + [dsmred(mad(v[i], k.D[i], T2)) for i in range(1, 16)]
-
-
-def round_pair(v, r, k, track=None):
-    A = 0
-    for i in range(1, 16):
-        A = mad(v[i], k.d[i], A)                                       # the exact multipliers d_i 2^s, s = 0
-    u = sbox(v[0])
-    T = 0
-    for x in [u] + v[1:]:
-        T = mad(x, 1 << SH_PAIR, T)
-    st = dsmred(T)
-    v0 = dsmred(mad(u, k.D[0], mad(st, k.K24, 0) + k.rc_fold[r]))
-    A = mad(st, k.C15, A)
-    u2 = sbox(v0)
-    A = mad(u2, 1, A)
-    s1 = dsmred(A)
-    T2 = mad(s1, k.K1, 0)
-    out = [dsmred(mad(u2, k.D[0], T2 + k.rc_fold[r + 1]))] + [dsmred(mad(v[i], k.D2[i], mad(st, k.E[i], T2))) for i in range(1, 16)]
-    if track is not None:
-        track["st"] = max(track.get("st", 0), abs(st))
-        track["s1"] = max(track.get("s1", 0), abs(s1))
-        track["v"] = max(track.get("v", 0), max(abs(x) for x in out), abs(v0))
-    return out
-
-
-def internal_rounds(v, k, track=None):
-    """v: signed Montgomery-form words in (-P, P), int_rc[0] already in v[0]; returns canonical Montgomery-form words"""
-    assert all(abs(x) < P for x in v)
-    v = round_one(v, 0, k)
-    if k.pair:
-        for r in range(1, 13, 2):
-            v = round_pair(v, r, k, track)
-    else:
-        for r in range(1, 13):
-            v = round_one(v, r, k)
-    assert all(abs(x) < P for x in v)
-    return [x % P for x in v]
+from p2_device_model import (H, I32, MU, P, R, SH_ONE, SH_PAIR, Consts, cen, dsmred, internal_rounds, mad, pair_budget_ok, round_one,  # noqa: F401
+                             round_pair, sbox)
 
 
 def reference(state, diag, rc_i):

@@ -7,16 +7,25 @@
 // The width-16 partial rounds run paired (elements 1..15 updated once per two rounds, p2_internal_pair_dev) or one at a time by a flag of
 // the constant tables: the correctness pass also runs every form with the flag cleared ("pair_mismatches": against the paired all-VALU
 // words), and the throughput pass times both settings of both permutations ("*_pr_ms_*": one round at a time).
+//   ./tools/p2mx_bench states [--w24] <in.bin> <out.bin>
+//       no timing: reads N states of 16 canonical u32 words (24 with --w24), permutes them with every device form and writes the raw device
+//       words (Montgomery form) of each form, N states per block, in the order the JSON line names: p2_permute_dev, p2_permute_mx_dev at the
+//       compiler's register budget, at 5 and at 6 waves, each with the paired partial rounds and with the flag cleared, then coop_permute
+//       (poseidon2_coop.cuh, 16 lanes per state); with --w24 one block from p24_permute_dev.  tests/test_gpu_p2_steer.py feeds it states
+//       steered to edge words inside the rounds.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/p2mx_bench tools/p2mx_bench.hip   (__graft_entry__.build() does)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <string.h>
+
 #include <algorithm>
 #include <vector>
 
 #include "../zktls_amd/csrc/poseidon2.cuh"
+#include "../zktls_amd/csrc/poseidon2_coop.cuh"
 
 namespace zk { P2Tables g_p2_tables = P2_BUILTIN; }
 using namespace zk;
@@ -60,6 +69,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) p
     perm_mx_body<6>(st, n, chain);
 }
 
+// one state over the 16 lanes of a DPP row, as the cooperative leaf and tree kernels of hash.hip run it; whole rows leave together
+__global__ void __launch_bounds__(256) perm_coop_kernel(uint32_t* st, uint64_t n) {
+    const uint64_t node = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const int lane16 = threadIdx.x & 15;
+    if (node >= n) return;
+    const CoopConsts k = coop_load_consts(lane16);
+    st[16 * node + lane16] = coop_permute(st[16 * node + lane16], lane16, k);
+}
+__global__ void __launch_bounds__(256) perm24_kernel(uint32_t* st, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s[24];
+#pragma unroll
+    for (int k = 0; k < 24; k++) s[k] = st[24 * i + k];
+    p24_permute_dev(s);
+#pragma unroll
+    for (int k = 0; k < 24; k++) st[24 * i + k] = s[k];
+}
+
 static uint64_t splitmix(uint64_t& x) {
     uint64_t z = (x += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -86,7 +114,71 @@ static void launch(int form, uint32_t* d, uint64_t n, int chain) {
     CK(hipGetLastError());
 }
 
+// the "states" mode: every device form on the states of a file
+static int run_states(int argc, char** argv) {
+    bool w24 = false;
+    const char* path[2] = {nullptr, nullptr};
+    int np = 0;
+    for (int a = 2; a < argc; a++) {
+        if (!strcmp(argv[a], "--w24")) w24 = true;
+        else if (np < 2) path[np++] = argv[a];
+        else np = 3;
+    }
+    if (np != 2) { printf("{\"error\": \"usage: states [--w24] <in.bin> <out.bin>\"}\n"); return 2; }
+    const size_t W = w24 ? 24 : 16;
+    FILE* f = fopen(path[0], "rb");
+    if (!f) { printf("{\"error\": \"cannot open the input file\"}\n"); return 2; }
+    fseek(f, 0, SEEK_END);
+    const long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (bytes <= 0 || bytes % (long)(4 * W) || (size_t)bytes / (4 * W) > (1u << 20)) { fclose(f); printf("{\"error\": \"bad input size\"}\n"); return 2; }
+    const uint64_t n = (uint64_t)bytes / (4 * W);
+    std::vector<uint32_t> h(W * n), out(W * n);
+    const size_t got = fread(h.data(), 4, W * n, f);
+    fclose(f);
+    if (got != W * n) { printf("{\"error\": \"short read\"}\n"); return 2; }
+    for (auto& x : h) {
+        if (x >= P) { printf("{\"error\": \"input word not canonical\"}\n"); return 2; }
+        x = to_monty(x);
+    }
+    FILE* o = fopen(path[1], "wb");
+    if (!o) { printf("{\"error\": \"cannot open the output file\"}\n"); return 2; }
+    uint32_t* d;
+    CK(hipMalloc(&d, W * n * 4));
+    const auto run = [&](int form) {                                             // 0..3 as launch(); 4 coop_permute; 5 width 24
+        CK(hipMemcpy(d, h.data(), W * n * 4, hipMemcpyHostToDevice));
+        if (form == 5) perm24_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d, n);
+        else if (form == 4) perm_coop_kernel<<<(unsigned)((16 * n + 255) / 256), 256>>>(d, n);
+        else launch(form, d, n, 1);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(out.data(), d, W * n * 4, hipMemcpyDeviceToHost));
+        if (fwrite(out.data(), 4, W * n, o) != W * n) { printf("{\"error\": \"short write\"}\n"); exit(1); }
+    };
+    if (w24) {
+        run(5);
+        printf("{\"states\": %llu, \"width\": 24, \"blocks\": [\"p24\"]}\n", (unsigned long long)n);
+    } else {
+        P2Tables per_round = P2_BUILTIN;
+        per_round.pk16.pair = 0;
+        for (int pair : {1, 0}) {
+            CK(p2_upload_tables(pair ? g_p2_tables : per_round, 0));
+            CK(hipDeviceSynchronize());
+            for (int form = 0; form < 4; form++) run(form);
+        }
+        CK(p2_upload_tables(g_p2_tables, 0));
+        CK(hipDeviceSynchronize());
+        run(4);
+        printf("{\"states\": %llu, \"width\": 16, \"blocks\": [\"vec_pair\", \"mx_pair\", \"mx5_pair\", \"mx6_pair\", "
+               "\"vec_one\", \"mx_one\", \"mx5_one\", \"mx6_one\", \"coop\"]}\n", (unsigned long long)n);
+    }
+    fclose(o);
+    CK(hipFree(d));
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "states")) return run_states(argc, argv);
     const int log_n = argc > 1 ? atoi(argv[1]) : 21;
     const int chain = argc > 2 ? atoi(argv[2]) : 32;
     if (log_n < 6 || log_n > 24 || chain < 1 || chain > 256) { printf("{\"error\": \"bad arguments\"}\n"); return 2; }
