@@ -27,11 +27,11 @@
  *       the reference's batch and large-transcript configurations (BASELINE.json configs[2], configs[3]) with a real statement per proof:
  *       many transcripts, or the shards of one long message, dealt over the GPUs of the node by one call.
  *   zkhip_p2chip_air, zkhip_prove_merkle_paths / zkhip_verify_merkle_paths
- *   (DEPRECATED generations of the recursion step -- kept for their tests; new callers: zkhip_prove_shard_verifier, or zkhip_prove_fri_indices_batch as the cheap FRI-only mode)
- *   zkhip_fri_view_shard, zkhip_fri_chip_air, zkhip_fri_queries_key, zkhip_prove_fri_queries / zkhip_verify_fri_queries,
- *   zkhip_fri_view_shard_paths, zkhip_fri_layers_key, zkhip_prove_fri_layers / zkhip_verify_fri_layers,
- *   zkhip_fri_view_transcript, zkhip_fri_transcript_key, zkhip_prove_fri_transcript / zkhip_verify_fri_transcript,
- *   zkhip_fri_indices_key, zkhip_prove_fri_indices / zkhip_verify_fri_indices
+ *   (the FRI-only mode of the recursion step, include/zkhip_chips.h -- new callers: zkhip_prove_shard_verifier, or zkhip_prove_fri_indices_batch as the cheap mode)
+ *   zkhip_fri_view_shard, zkhip_fri_view_shard_paths, zkhip_fri_view_transcript, zkhip_fri_view_all (what the FRI check of a shard proof reads),
+ *   zkhip_fri_chip_air, zkhip_fri_layers_chip_air, zkhip_fri_transcript_chip_air, zkhip_fri_indices_program (the chips' programs),
+ *   zkhip_fri_indices_key, zkhip_prove_fri_indices / zkhip_verify_fri_indices, zkhip_prove_fri_indices_batch
+ *   (round 6 removed the three earlier generations: zkhip_prove_fri_queries / _layers / _transcript with their keys, sizes, trace generators and verifiers)
  *       a first recursion step: the FRI folds of a shard proof checked inside a (keyed machine) proof -- what `compress` behind
  *       SP1ProofMode::Groth16 (sp1.rs:116) spends its rows on besides Poseidon2.
  *       a second real chip -- the Poseidon2 permutation with Merkle-path / leaf-hash chaining, what the recursion stages behind

@@ -73,12 +73,9 @@ int zkhip_verify_merkle_paths_p24(const uint8_t* proof, size_t len, const uint32
  * The FRI-fold chip (fri_chip.hip; 32 + layers columns rounded up to a multiple of 4, one row per (query, layer), degree 3) folds these
  * chains; its rows send the layer pairs on two lookup buses to a PREPROCESSED table that lists every distinct pair of the view with the
  * number of queries reading it -- fixed multiplicities, so every listed pair is folded exactly as often as the inner proof reads it.
- * zkhip_fri_queries_key commits that table (zkhip_machine_setup): vk is what a verifier recomputes from the inner proof; final_value is
- * what the chains end in.  zkhip_prove_fri_queries generates the chip's trace on the device and proves the two-chip keyed machine
- * (proof version 11; public values: the challenges, then the final value); zkhip_verify_fri_queries checks it on the host.
- * NOT in-circuit yet: the Merkle paths of the pairs (the Poseidon2 chip above proves such paths, it is not on this bus yet), the reduced
- * openings, the transcript.  zkhip_fri_chip_air writes the chip's constraint program (its size in words), zkhip_fri_chip_gen_trace the
- * trace alone (finals: [n_queries][4], the value each chain ends in). */
+ * That two-chip machine was the first generation (zkhip_prove_fri_queries; removed in round 6 with its key, size, trace generator and
+ * verifier): the chip lives on as the fold chip of the machines below and of the shard verifier.  zkhip_fri_chip_air writes its
+ * constraint program (its size in words), zkhip_fri_chip_width its width. */
 int zkhip_fri_view_shard(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public,
                          const zkhip_params* prm, uint32_t* betas, uint32_t final_value[4], uint32_t* indices, uint32_t* values, uint32_t* siblings);
 uint32_t zkhip_fri_chip_width(int layers);
@@ -89,7 +86,7 @@ size_t zkhip_fri_chip_air(int layers, uint32_t* program, size_t cap_words);
  * chip's FRI-layers variant (zkhip_p2chip_air_fri_layers: one path per (query, layer) -- a leaf row hashing the pair, then the compression
  * rows up to the layer's root; leaf rows receive the pairs from the bus, END rows send (layer, root) to the ROOTS table), the fold chip
  * in its wired form (zkhip_fri_layers_chip_air: sends the pairs, and (index, reduced opening) on a query's first row), and two
- * PREPROCESSED tables: QUERIES (index, reduced opening) and ROOTS (layer, root).  The key (zkhip_fri_layers_key) therefore holds no FRI
+ * PREPROCESSED tables: QUERIES (index, reduced opening) and ROOTS (layer, root).  The key of that machine (the second generation, removed in round 6 with its entries) therefore held no FRI
  * layer value any more: a verifier needs the layer roots of the inner proof and the reduced openings it computes itself.  Statement: "for
  * the layer commitments and the (index, reduced opening) pairs in the key, every query's chain opens the commitments layer by layer and
  * folds, under the public challenges, to the public final value."  Still outside: the trace / quotient openings, the reduced openings,
@@ -223,8 +220,8 @@ int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_b
  * [n_paths][8] receives where each path ends and *n_paths their number (cap_paths >= Q R always suffices).  zkhip_prove_fri16_paths refuses, before anything is
  * proven and with a message that names query and layer: a path that does not end in its layer's root ("query q layer l does not open"), two queries that
  * disagree about a shared row or its path, a chain that does not end in the final polynomial.  zkhip_verify_fri16_paths is host only: challenges, key, shape.
- * STILL OUTSIDE after this machine: the transcript (challenges, query indices), the reduced openings, the trace / quotient openings; the shard verifier
- * machines (shard_verifier.inl) do not use these chips. */
+ * STILL OUTSIDE after this machine: the transcript (challenges, query indices: the indices machine below takes them in), the reduced openings, the trace /
+ * quotient openings; the shard verifier machines (shard_verifier.inl) do not use these chips. */
 #define ZKHIP_P24CHIP_LAYERS_WIDTH 552
 size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
                                   uint32_t* pre_width, int* table);
@@ -241,6 +238,51 @@ int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R,
                             const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
 int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
                              const zkhip_params* prm, int* reason);
+
+/* ---- the same check with the FIAT-SHAMIR TRANSCRIPT in-circuit from the commit phase on: the fold-16 INDICES machine.  Public values: the 8 capacity words of
+ * the duplex challenger as the commit phase finds it.  The key commits the layer roots, the final coefficients and (query number, reduced opening): IT HOLDS NO
+ * INDEX AND NO CHALLENGE.  Statement: "a sponge chain starts from this capacity; it absorbs root_0 .. root_{R-1} and draws beta_l after each; it then absorbs the
+ * listed final coefficients and a proof-of-work witness; the first word it hands out has its low inner_pow_bits bits zero; the low H = 4 R + F + log_blowup bits of
+ * the following words are the indices of queries 0 .. Q - 1; every query, at the index drawn for it, opens the listed layer commitments row by row and folds under
+ * the drawn challenges to the value of the listed polynomial at its last point."  The duplex rules (proof_common.h Challenger): pending inputs are zero when the
+ * commit phase starts; a root is one full rate block and beta_l = (out[7], out[6], out[5], out[4]); for F >= 1 the 4 2^F coefficient words are 2^(F-1) full blocks
+ * and the witness then overwrites rate word 0 only (words 1..7 keep the previous output); for F = 0 one block takes the coefficient in words 0..3 and the witness
+ * in word 4; words are handed out from out[7] down, a permutation with no input follows whenever the eight are used up, and the proof-of-work word is always drawn.
+ * Eight tables, tallest first (equal heights by table number): 0 FOLD16B = FOLD16 without the constraints that tie BETA to public values and with one receive of
+ * (LN, BETA[4]) on every active row; 1 FINAL and 2 P24L as in the paths machine; 3 QUERIES, one row per query number: preprocessed (q, value[4], 1), main the index,
+ * received as (q, index) from SAMPLES and handed as (index, value) to the chain's first row; 4 COEFFS with one more send (j, c_j), multiplicity 1, to the transcript
+ * table; 5 ROOTS: preprocessed (layer, depth, root[8], 1), main (path ends, beta[4], fold rows of the layer) -- root and beta received from the layer's transcript
+ * row, beta sent on to FOLD16B, and fold rows (1 - listed) = 0 so that a padding row (layer number 0, nothing received) sends no challenge; 6 P2T, the width-16 Poseidon2 chip as a transcript-only table: main the 352 permutation columns, preprocessed the chain's schedule
+ * (chained, kept rate words [8], root row and its layer, the two coefficient receives and their keys, hands-out flag and the sponge row's number); 7 SAMPLES, the
+ * chip of zkhip_prove_fri_indices with H index bits.  Shapes: the paths machine's, and inner_pow_bits <= 30.
+ * zkhip_fri16_view_transcript (host only; fails like zkhip_fri16_view_shard): the layer roots [R][8], the challenges [R][4], and transcript[0..8) = the capacity,
+ * transcript[8] = pending inputs (0), transcript[9] = the witness.  zkhip_fri16_indices_describe: as zkhip_fri16_paths_describe, eight positions.
+ * zkhip_fri16_indices_key_host (no GPU) / _key: the key from the shape, inner_pow_bits, the final coefficients, the reduced openings BY QUERY NUMBER and the layer
+ * roots.  zkhip_fri16_indices_gen_traces: the P2T and SAMPLES main traces on the device (dense: [2^lr][352] and [2^lr][288], 16-byte aligned) from the capacity,
+ * the roots, the final coefficients and the witness alone; betas [R][4] and indices [Q] receive what the chain draws.  zkhip_fri16_samples_gen_trace: the SAMPLES
+ * main trace (2^max(5, ceil lg ceil((1 + Q) / 8)) rows) from given canonical words [ceil((1 + Q) / 8)][8].  zkhip_prove_fri16_indices takes the paths machine's
+ * view, the capacity and the witness, and refuses before anything is proven, each with a message: challenges the chain does not draw from these roots and this
+ * capacity, a witness that fails the proof of work, indices that are not the drawn ones, everything zkhip_prove_fri16_paths refuses, width-16-hash inner proofs.
+ * zkhip_verify_fri16_indices is host only: shape, inner_pow_bits, capacity, key.
+ * STILL OUTSIDE after this machine: the reduced openings, the trace / quotient openings, the transcript before the commit phase; the shard verifier machines
+ * (shard_verifier.inl) do not use these chips. */
+int zkhip_fri16_view_transcript(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                                uint32_t* roots, uint32_t* betas, uint32_t transcript[10]);
+size_t zkhip_fri16_indices_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows,
+                                    uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_indices_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly, const uint32_t* values,
+                                 const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_indices_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly,
+                            const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_indices_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const zkhip_params* prm);
+int zkhip_fri16_indices_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8], const uint32_t* roots,
+                                   const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2t, uint32_t* d_samples, uint32_t* betas, uint32_t* indices);
+int zkhip_fri16_samples_gen_trace(zkhip_ctx* ctx, int index_bits, size_t n_queries, const uint32_t* words, uint32_t* d_samples);
+int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                              const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
+                              const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
+                               const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */

@@ -26,6 +26,9 @@
 // the programs, tables and traces independently; the words must be equal.
 // The PATHS machine (further down; zkhip_prove_fri16_paths) is this machine with P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands,
 // and a preprocessed ROOTS table: there the layer rows' Merkle paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py).
+// The INDICES machine (last; zkhip_prove_fri16_indices) is the paths machine with the Fiat-Shamir transcript inside: a transcript-only width-16 Poseidon2 table (P2T)
+// walks the duplex challenger from the commit phase on, the SAMPLES chip of fri_chip.hip takes the bits of the words it hands out; the challenges reach FOLD16 over a
+// bus and the key holds neither a challenge nor an index (tests/fri16_transcript_air.py).
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -42,10 +45,18 @@
 #include "fri16_rows.cuh"
 #include "kernels.h"
 #include "p24chip.h"
+#include "p2chip.h"
 
 namespace zk {
 extern std::atomic<uint64_t> g_p2_generation;      // params.cpp
 namespace p24chip { std::shared_ptr<const std::vector<uint32_t>> program_fri16_layers(uint32_t n_public); }      // poseidon2_chip.cpp
+namespace p2chip { std::vector<uint32_t> permutation_body(uint32_t col_offset, uint32_t* count); }                // poseidon2_chip.cpp: the permutation's constraints behind preprocessed columns
+namespace frichip {                                                                                               // fri_chip.hip: the SAMPLES chip
+std::shared_ptr<const std::vector<uint32_t>> samples_chip_program(int index_bits, int pow_bits, uint32_t n_public);
+const std::vector<uint32_t>& samples_chip_interactions();
+size_t samples_chip_rows(size_t nq);
+void samples_chip_pre(size_t nq, int log_rows, int first_row, std::vector<uint32_t>& t);
+}
 namespace fri16 {
 namespace {
 
@@ -107,7 +118,7 @@ int shape_of(int R, int F, int b, size_t Q, Shape& s) {
     return ZKHIP_OK;
 }
 
-std::vector<uint32_t> build_fold16_program(int R, int lf) {
+std::vector<uint32_t> build_fold16_program(int R, int lf, bool beta_bus = false, uint32_t n_public = 0) {      // beta_bus: FOLD16B, BETA is received, not public
     Builder b;
     const uint32_t END = L + (uint32_t)R - 1u, W = fold16_width((uint32_t)lf), inv2 = (P + 1) / 2;
     const W16Inv w16 = w16_inverse_powers();
@@ -137,7 +148,7 @@ std::vector<uint32_t> build_fold16_program(int R, int lf) {
         for (uint32_t j = 0; j < 16; j++) t.push_back(Term{P - 1, {var(OF + j)}});
         b.add(ALL, t);
     }
-    for (uint32_t c = 0; c < 4; c++) {      // BETA = the layer's public challenge
+    for (uint32_t c = 0; c < 4 && !beta_bus; c++) {      // BETA = the layer's public challenge
         Terms t{{1u, {var(BETA + c)}}};
         for (int l = 0; l < R; l++) t.push_back(Term{P - 1, {var(L + l), pub(4u * (uint32_t)l + c)}});
         b.add(ALL, t);
@@ -235,19 +246,19 @@ std::vector<uint32_t> build_fold16_program(int R, int lf) {
     for (uint32_t c = 0; c < 4; c++) b.add(TRANSITION, Terms{{1u, {var(G), var(FOLD + c)}}, {P - 1, {var(G), var(OWN + c, true)}}});
     b.add(FIRST, Terms{{1u, {var(ACTIVE)}}, {P - 1, {var(L)}}});
     b.add(LAST, Terms{{1u, {var(G)}}});
-    return b.finish(W, 4u * (uint32_t)R);
+    return b.finish(W, beta_bus ? n_public : 4u * (uint32_t)R);
 }
-std::vector<uint32_t> build_final_program(int R) {
+std::vector<uint32_t> build_final_program(uint32_t n_public) {
     Builder b;
     for (uint32_t c = 0; c < 4; c++) b.add(ALL, Terms{{1u, {var(CFAX + c)}}, {P - 1, {var(CFACC + c), var(CFX)}}});
     for (uint32_t c = 0; c < 4; c++) b.add(ALL, Terms{{1u, {var(FFIRST), var(CFACC + c)}}, {P - 1, {var(FFIRST), var(CFC + c)}}});
     b.add(TRANSITION, Terms{{1u, {var(FNL), var(CFX, true)}}, {P - 1, {var(FNL), var(CFX)}}});
     for (uint32_t c = 0; c < 4; c++)
         b.add(TRANSITION, Terms{{1u, {var(FNL), var(CFACC + c, true)}}, {P - 1, {var(FNL), var(CFAX + c)}}, {P - 1, {var(FNL), var(CFC + c, true)}}});
-    return b.finish(FIN_PRE + FIN_MAIN, 4u * (uint32_t)R);
+    return b.finish(FIN_PRE + FIN_MAIN, n_public);
 }
-std::vector<uint32_t> build_table_program(int R, uint32_t pre_width) {          // the contents are fixed by the KEY: one harmless identity
-    return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + TAB_MAIN, 1u, 4u * (uint32_t)R, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + TAB_MAIN - 1u)};
+std::vector<uint32_t> build_table_program(uint32_t n_public, uint32_t pre_width, uint32_t main_width = TAB_MAIN) {          // the contents are fixed by the KEY: one harmless identity
+    return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + main_width, 1u, n_public, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + main_width - 1u)};
 }
 std::vector<uint32_t> build_interactions(int R, int table) {
     std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
@@ -294,7 +305,7 @@ std::shared_ptr<const Machine> machine_of(const Shape& s) {
     m->s = s;
     for (int i = 0; i < 5; i++) {
         const int t = s.order[i];
-        m->prog[i] = t == T_FOLD16 ? build_fold16_program(s.R, s.lf) : t == T_FINAL ? build_final_program(s.R) : build_table_program(s.R, s.pre_w[t]);
+        m->prog[i] = t == T_FOLD16 ? build_fold16_program(s.R, s.lf) : t == T_FINAL ? build_final_program(4u * (uint32_t)s.R) : build_table_program(4u * (uint32_t)s.R, s.pre_w[t]);
         m->tab[i] = build_interactions(s.R, t);
         m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
         m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
@@ -465,8 +476,8 @@ std::shared_ptr<const PMachine> paths_machine_of(const PShape& s) {
     const int R = s.base.R;
     for (int i = 0; i < N_PT; i++) {
         const int t = s.order[i];
-        m->prog[i] = t == T_FOLD16 ? build_fold16_program(R, s.base.lf) : t == T_FINAL ? build_final_program(R)
-                   : t == T_P24L ? *p24chip::program_fri16_layers(4u * (uint32_t)R) : build_table_program(R, s.pre_w[t]);
+        m->prog[i] = t == T_FOLD16 ? build_fold16_program(R, s.base.lf) : t == T_FINAL ? build_final_program(4u * (uint32_t)R)
+                   : t == T_P24L ? *p24chip::program_fri16_layers(4u * (uint32_t)R) : build_table_program(4u * (uint32_t)R, s.pre_w[t]);
         m->tab[i] = build_paths_interactions(R, t);
         m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
         m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
@@ -532,6 +543,206 @@ int plan_paths(const Shape& b, const uint32_t* indices, const uint32_t* paths, P
     return ZKHIP_OK;
 }
 
+// ---------------------------------------------------------------- the INDICES machine: the paths machine with the transcript inside
+// Table numbers 0 FOLD16B, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES.  Public values: the 8 capacity words of the duplex challenger as the commit
+// phase finds it (pending inputs zero: the step before is a sample).  The sponge chain (P2T, one width-16 permutation per row, rows 0 .. NT - 1):
+//   R root rows        row l absorbs root_l as one full rate block; beta_l = (out[7], out[6], out[5], out[4])
+//   C coefficient rows (F >= 1: C = 2^(F-1), row R + i absorbs c_2i, c_2i+1; F = 0: none)
+//   the witness row    F >= 1: rate word 0 <- the witness, words 1..7 keep the previous output; F = 0: words 0..3 <- c_0, word 4 <- the witness, 5..7 kept
+//   S - 1 permute rows (S = ceil((1 + Q) / 8)) the whole previous output
+// The witness row and the permute rows hand their eight rate words out from out[7] down: the proof-of-work word, then one word per query.
+// FOLD16B is FOLD16 without the constraints BETA = public and with a receive of (LN, BETA) on every active row; FINAL and P24L are the paths machine's word for word
+// (but the public-value count in the header); QUERIES: preprocessed (q, value[4], 1), main the index, received from SAMPLES by query number and handed to the chain's
+// first row; COEFFS: one more send (j, c_j), multiplicity 1 (column 6), to P2T; ROOTS: preprocessed (layer, depth, root[8], 1), main (path ends, beta[4], fold rows):
+// root and beta received from the layer's root row, beta sent on to the fold rows -- by listed rows only (build_roots_program); SAMPLES: fri_chip.hip's chip with H index bits, first row number R + C.
+constexpr uint32_t BUS_TR0 = 76, BUS_TR1 = 77, BUS_TB = 78, BUS_BF16 = 79, BUS_CT = 80, N_PUBLIC_I = 8, ROOTS_MAIN_I = 8;
+constexpr uint32_t PT_PRE = 20, PT_SPG = 0, PT_K = 1, PT_ROOT = 9, PT_LN = 10, PT_C0 = 11, PT_KEY0 = 12, PT_C1 = 13, PT_KEY1 = 14, PT_SMP = 15, PT_ROW = 16;
+enum : int { T_P2T = 6, T_SAMPLES = 7, N_IT = 8 };
+struct IShape {
+    PShape p;
+    int pow_bits = 0;
+    size_t C = 0, S = 0, NT = 0;        // coefficient rows, rows that hand words out, rows of the chain
+    int log_rows[N_IT], order[N_IT];
+    uint32_t main_w[N_IT], pre_w[N_IT];
+};
+int indices_shape_of(int R, int F, int b, size_t Q, int pow_bits, IShape& s) {
+    ZK_TRY(paths_shape_of(R, F, b, Q, s.p));
+    if (pow_bits < 0 || pow_bits > 30) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
+    s.pow_bits = pow_bits;
+    s.C = F >= 1 ? (size_t)1 << (F - 1) : 0; s.S = frichip::samples_chip_rows(Q); s.NT = (size_t)R + s.C + s.S;
+    const uint32_t mw[N_IT] = {s.p.main_w[0], FIN_MAIN, p24chip::WIDTH_L, TAB_MAIN, TAB_MAIN, ROOTS_MAIN_I, p2chip::T_WIDTH, frichip::S_MAIN};
+    const uint32_t pw[N_IT] = {0u, FIN_PRE, 0u, Q_PRE, C_PRE, ROOTS_PRE16, PT_PRE, frichip::S_PRE};
+    for (int i = 0; i < N_IT; i++) { s.log_rows[i] = i < N_PT ? s.p.log_rows[i] : i == T_P2T ? lg(s.NT) : lg(s.S); s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
+    std::stable_sort(s.order, s.order + N_IT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    return ZKHIP_OK;
+}
+// P2T's program: the permutation; D and BIT pinned (no path in this table); the chain behind the preprocessed schedule
+std::vector<uint32_t> build_p2t_program() {
+    using namespace p2chip;
+    const uint32_t M0 = PT_PRE, OUT = M0 + oute(7);
+    Builder b;
+    b.body = permutation_body(M0, &b.count);
+    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(M0 + D + j)}}, {P - 1, {var(M0 + IN + j)}}});
+    b.add(ALL, Terms{{1u, {var(M0 + BIT)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(FIRST, Terms{{1u, {var(M0 + IN + 8 + j)}}, {P - 1, {pub(j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_SPG, true), var(M0 + IN + 8 + j, true)}}, {P - 1, {var(PT_SPG, true), var(OUT + 8 + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_K + j, true), var(M0 + IN + j, true)}}, {P - 1, {var(PT_K + j, true), var(OUT + j)}}});
+    return b.finish(PT_PRE + T_WIDTH, N_PUBLIC_I);
+}
+// ROOTS' program: the harmless identity of a key table, and FOLDROWS (1 - LISTED) = 0 -- the multiplicity of the send (layer, beta) to FOLD16B is a MAIN column, and a
+// padding row's preprocessed cells are zero (layer 0, nothing received from the transcript): without this a padding row could hand layer 0 a challenge of the prover's choice
+std::vector<uint32_t> build_roots_program() {
+    Builder b;
+    b.add(FIRST, Terms{{1u, {var(ROOTS_PRE16 + ROOTS_MAIN_I - 1u)}}});
+    b.add(ALL, Terms{{1u, {var(ROOTS_PRE16 + 5u)}}, {P - 1, {var(ROOTS_PRE16 + 5u), var(10u)}}});
+    return b.finish(ROOTS_PRE16 + ROOTS_MAIN_I, N_PUBLIC_I);
+}
+std::vector<uint32_t> build_indices_interactions(int R, int table) {
+    if (table == T_FINAL || table == T_P24L) return build_paths_interactions(R, table);
+    if (table == T_SAMPLES) return frichip::samples_chip_interactions();
+    std::vector<uint32_t> v = table == T_FOLD16 ? build_interactions(R, T_FOLD16) : std::vector<uint32_t>{LOOKUP_MAGIC, 0u, 0u};
+    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
+        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
+        v.insert(v.end(), cols.begin(), cols.end());
+        v[1]++;
+    };
+    const uint32_t RM = ROOTS_PRE16, in = PT_PRE + p2chip::IN, o = PT_PRE + p2chip::oute(7);
+    switch (table) {
+    case T_FOLD16: add(1u, ACTIVE, BUS_BF16, {LN, BETA, BETA + 1, BETA + 2, BETA + 3}); break;
+    case T_QUERIES:
+        add(1u, 5u, BUS_Q16, {Q_PRE, 1u, 2u, 3u, 4u});
+        add(1u, 5u, frichip::BUS_I, {0u, Q_PRE});
+        break;
+    case T_COEFFS:
+        add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u});
+        add(0u, 6u, BUS_CT, {0u, 1u, 2u, 3u, 4u});
+        break;
+    case T_ROOTS:
+        add(1u, RM, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
+        add(1u, RM, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+        add(1u, 10u, BUS_TR0, {RT_LN, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
+        add(1u, 10u, BUS_TR1, {RT_LN, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+        add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
+        add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
+        break;
+    default:        // P2T
+        add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
+        add(1u, PT_C1, BUS_CT, {PT_KEY1, in + 4, in + 5, in + 6, in + 7});
+        add(0u, PT_ROOT, BUS_TR0, {PT_LN, in, in + 1, in + 2, in + 3});
+        add(0u, PT_ROOT, BUS_TR1, {PT_LN, in + 4, in + 5, in + 6, in + 7});
+        add(0u, PT_ROOT, BUS_TB, {PT_LN, o + 7, o + 6, o + 5, o + 4});
+        add(0u, PT_SMP, frichip::BUS_S0, {PT_ROW, o + 7, o + 6, o + 5, o + 4});
+        add(0u, PT_SMP, frichip::BUS_S1, {PT_ROW, o + 3, o + 2, o + 1, o});
+        break;
+    }
+    v[2] = (uint32_t)v.size();
+    return v;
+}
+struct IMachine {
+    IShape s;
+    std::vector<uint32_t> prog[N_IT], tab[N_IT];
+    int32_t log_ns[N_IT]; uint32_t widths[N_IT], pre_widths[N_IT];
+    const uint32_t* progs[N_IT]; size_t prog_words[N_IT]; const uint32_t* tabs[N_IT]; size_t tab_words[N_IT];
+};
+// (P24L's and P2T's programs follow the Poseidon2 tables in effect: the cache is dropped when they change)
+std::shared_ptr<const IMachine> indices_machine_of(const IShape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 5>, std::shared_ptr<const IMachine>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
+    const Shape& b = s.p.base;
+    const std::array<uint64_t, 5> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.pow_bits};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<IMachine>();
+    m->s = s;
+    for (int i = 0; i < N_IT; i++) {
+        const int t = s.order[i];
+        switch (t) {
+        case T_FOLD16: m->prog[i] = build_fold16_program(b.R, b.lf, true, N_PUBLIC_I); break;
+        case T_FINAL: m->prog[i] = build_final_program(N_PUBLIC_I); break;
+        case T_P24L: m->prog[i] = *p24chip::program_fri16_layers(N_PUBLIC_I); break;
+        case T_P2T: m->prog[i] = build_p2t_program(); break;
+        case T_SAMPLES: m->prog[i] = *frichip::samples_chip_program(b.H, s.pow_bits, N_PUBLIC_I); break;
+        case T_ROOTS: m->prog[i] = build_roots_program(); break;
+        default: m->prog[i] = build_table_program(N_PUBLIC_I, s.pre_w[t], s.main_w[t]); break;
+        }
+        m->tab[i] = build_indices_interactions(b.R, t);
+        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
+        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
+    }
+    cache.emplace(key, m);
+    return m;
+}
+// the key's tables by table number: FINAL's schedule, QUERIES by query number, COEFFS, ROOTS, and the schedules of P2T and SAMPLES -- no index and no challenge
+int build_indices_key_tables(const IShape& s, const uint32_t* final_poly, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[N_IT], const char* who) {
+    const Shape& b = s.p.base;
+    if (!final_poly || !values || !roots) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(final_poly, (size_t)4 << b.F) || !canonical(values, 4 * b.Q) || !canonical(roots, 8 * (size_t)b.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (int t = 0; t < N_IT; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
+    fill_schedule_queries_coeffs(b, final_poly, std::map<std::array<uint32_t, 5>, uint32_t>(), pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
+    for (size_t q = 0; q < b.Q; q++) {
+        uint32_t* w = pre[T_QUERIES].data() + Q_PRE * q;
+        w[0] = to_monty((uint32_t)q);
+        for (int i = 0; i < 4; i++) w[1 + i] = to_monty(values[4 * q + i]);
+        w[5] = MONTY_R1;
+    }
+    for (size_t j = 0; j < ((size_t)1 << b.F); j++) pre[T_COEFFS][C_PRE * j + 6] = MONTY_R1;
+    for (int l = 0; l < b.R; l++) {
+        uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (size_t)l;
+        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(b.H - 4 * (l + 1)));
+        for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty(roots[8 * l + j]);
+        w[10] = MONTY_R1;
+    }
+    const size_t R = (size_t)b.R;
+    for (size_t r = 0; r < s.NT; r++) {
+        uint32_t* w = pre[T_P2T].data() + PT_PRE * r;
+        if (r) w[PT_SPG] = MONTY_R1;
+        uint32_t kept_from = 8;                                  // rate words kept_from .. 7 keep the previous output
+        if (r < R) { w[PT_ROOT] = MONTY_R1; w[PT_LN] = to_monty((uint32_t)r); }
+        else if (r < R + s.C) {
+            const uint32_t i = (uint32_t)(r - R);
+            w[PT_C0] = w[PT_C1] = MONTY_R1; w[PT_KEY0] = to_monty(2u * i); w[PT_KEY1] = to_monty(2u * i + 1u);
+        } else if (r == R + s.C) {
+            if (b.F == 0) { w[PT_C0] = MONTY_R1; kept_from = 5; } else kept_from = 1;
+        } else kept_from = 0;
+        for (uint32_t j = kept_from; j < 8; j++) w[PT_K + j] = MONTY_R1;
+        if (r >= R + s.C) { w[PT_SMP] = MONTY_R1; w[PT_ROW] = to_monty((uint32_t)r); }
+    }
+    frichip::samples_chip_pre(b.Q, s.log_rows[T_SAMPLES], (int)(R + s.C), pre[T_SAMPLES]);
+    return ZKHIP_OK;
+}
+// the chain walked on the host (NT permutations): every row's input state, the challenges and the words it hands out -- canonical
+struct Chain { std::vector<uint32_t> inputs, words, betas, drawn; };
+void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, Chain& c) {
+    const Shape& b = s.p.base;
+    const size_t R = (size_t)b.R;
+    c.inputs.assign(16 * s.NT, 0u); c.words.assign(8 * s.S, 0u); c.betas.assign(4 * R, 0u); c.drawn.assign(b.Q, 0u);
+    uint32_t st[16];
+    size_t r = 0;
+    auto step = [&]() { for (int j = 0; j < 16; j++) c.inputs[16 * r + j] = from_monty(st[j]); r++; p2_permute(st); };
+    for (int j = 0; j < 8; j++) st[8 + j] = to_monty(capacity[j]);
+    for (size_t l = 0; l < R; l++) {
+        for (int j = 0; j < 8; j++) st[j] = to_monty(roots[8 * l + j]);
+        step();
+        for (int j = 0; j < 4; j++) c.betas[4 * l + j] = from_monty(st[7 - j]);
+    }
+    for (size_t i = 0; i < s.C; i++) {
+        for (int j = 0; j < 8; j++) st[j] = to_monty(final_poly[8 * i + j]);
+        step();
+    }
+    if (b.F == 0) { for (int j = 0; j < 4; j++) st[j] = to_monty(final_poly[j]); st[4] = to_monty(witness); }
+    else st[0] = to_monty(witness);
+    for (size_t i = 0; i < s.S; i++) {
+        step();
+        for (int j = 0; j < 8; j++) c.words[8 * i + j] = from_monty(st[7 - j]);
+    }
+    const uint32_t mask = (1u << b.H) - 1u;
+    for (size_t q = 0; q < b.Q; q++) c.drawn[q] = c.words[q + 1] & mask;
+}
+
 struct fold_rows_bargs { FoldRowsArgs a; static fold_rows_bargs make(FoldRowsArgs a) { return fold_rows_bargs{a}; } };
 __global__ void __launch_bounds__(64) fri16_fold_rows_kernel_batch(const fold_rows_bargs* __restrict__ zk_arr) { fri16_fold_rows_body(zk_arr[blockIdx.z].a); }
 struct final_rows_bargs { FinalRowsArgs a; static final_rows_bargs make(FinalRowsArgs a) { return final_rows_bargs{a}; } };
@@ -583,12 +794,11 @@ static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const ui
     return ZKHIP_OK;
 }
 
-// P24L from the view's paths and the FOLD16 trace already on the device (its E columns are the leaves); ends [n][8]: where every path ends.  Refused here: two
-// queries that disagree about a shared row or its path.
-static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::PShape& s, const uint32_t* indices, const uint32_t* paths, const uint32_t* d_fold, size_t ld_fold,
-                                     uint32_t* d_trace, size_t ld, fri16::PathPlan& pl, std::vector<uint32_t>& ends) {
+// P24L from the caller's plan of the view's paths (fri16::plan_paths, which refuses queries that disagree about the path of a shared row) and the FOLD16 trace already on
+// the device (its E columns are the leaves); ends [n][8]: where every path ends.  Refused here: two queries that disagree about a shared row.
+static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::PShape& s, const uint32_t* paths, const uint32_t* d_fold, size_t ld_fold, uint32_t* d_trace, size_t ld,
+                                     const fri16::PathPlan& pl, std::vector<uint32_t>& ends) {
     const fri16::Shape& b = s.base;
-    ZK_TRY(fri16::plan_paths(b, indices, paths, pl));
     const size_t rows = (size_t)1 << s.log_rows[fri16::T_P24L];
     if (pl.used_rows > rows) return fail(ZKHIP_ERR_INVALID, "fri16 paths: the paths do not fit the table");
     const size_t nd = 8 * pl.n, nr = (pl.readers.size() + 3) & ~(size_t)3, ns = b.Q * pl.path_words, up_words = nd + nr + ns;
@@ -691,7 +901,8 @@ int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, si
     ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
     fri16::PathPlan pl;
     std::vector<uint32_t> e;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, indices, paths, (const uint32_t*)t_fold, s.main_w[0], d_trace, ld, pl, e));
+    ZK_TRY(fri16::plan_paths(s.base, indices, paths, pl));
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, (const uint32_t*)t_fold, s.main_w[0], d_trace, ld, pl, e));
     *n_paths = pl.n;
     if (cap_paths < pl.n) return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: more paths than `ends` holds");
     std::memcpy(ends, e.data(), e.size() * 4);
@@ -727,7 +938,8 @@ int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R,
     ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
     fri16::PathPlan pl;
     std::vector<uint32_t> ends;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, indices, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    ZK_TRY(fri16::plan_paths(s.base, indices, paths, pl));
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
     for (size_t p = 0; p < pl.n; p++)
         if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
             return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
@@ -757,6 +969,207 @@ int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int
     const auto m = fri16::paths_machine_of(s);
     return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, betas, 4 * (size_t)R, prm,
                                       reason);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the indices machine's entries
+// P2T, SAMPLES and (non-null) the main columns of QUERIES and ROOTS in one launch from one staging block; status: what the kernel found different from the view
+static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::IShape& s, const fri16::Chain& c, const uint32_t* view_betas, const uint32_t* view_indices, const uint32_t* counts,
+                                 uint32_t* d_p2t, uint32_t* d_samples, uint32_t* d_qmain, uint32_t* d_rmain, uint32_t* status) {
+    const fri16::Shape& b = s.p.base;
+    const size_t R = (size_t)b.R, Q = b.Q, ni = (Q + 3) & ~(size_t)3, nr = (R + 3) & ~(size_t)3;
+    const size_t o_words = 16 * s.NT, o_betas = o_words + 8 * s.S, o_vbetas = o_betas + 4 * R, o_vidx = o_vbetas + 4 * R, o_counts = o_vidx + ni, o_status = o_counts + nr, up_words = o_status + 4;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_REC_E, up_words * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(up_words, 0u);
+        std::memcpy(up.data(), c.inputs.data(), c.inputs.size() * 4);
+        std::memcpy(up.data() + o_words, c.words.data(), c.words.size() * 4);
+        std::memcpy(up.data() + o_betas, c.betas.data(), 16 * R);
+        if (view_betas) std::memcpy(up.data() + o_vbetas, view_betas, 16 * R);
+        if (view_indices) std::memcpy(up.data() + o_vidx, view_indices, 4 * Q);
+        if (counts) std::memcpy(up.data() + o_counts, counts, 4 * R);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
+    }
+    p2chip::Fri16TranscriptArgs a{};
+    a.chain_inputs = d; a.words = d + o_words; a.drawn_betas = d + o_betas; a.view_betas = view_betas ? d + o_vbetas : nullptr; a.view_indices = view_indices ? d + o_vidx : nullptr;
+    a.counts = counts ? d + o_counts : nullptr;
+    a.n_chain = (uint32_t)s.NT; a.n_sample_rows = (uint32_t)s.S; a.R = (uint32_t)R; a.Q = (uint32_t)Q; a.index_bits = (uint32_t)b.H;
+    a.p2t_rows = d_p2t ? (uint64_t)1 << s.log_rows[fri16::T_P2T] : 0; a.samples_rows = (uint64_t)1 << s.log_rows[fri16::T_SAMPLES];
+    a.queries_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERIES]; a.roots_rows = (uint64_t)1 << s.log_rows[fri16::T_ROOTS];
+    a.p2t = d_p2t; a.samples = d_samples; a.queries_main = d_qmain; a.roots_main = d_rmain; a.status = d + o_status;
+    ZK_HIP(launch_fri16_transcript(a, ctx->stream));
+    return dev_d2h(ctx, status, a.status, 4);
+}
+static int fri16_indices_check_inputs(const fri16::IShape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, const char* who) {
+    const fri16::Shape& b = s.p.base;
+    if (!capacity || !roots || !final_poly) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(capacity, 8) || !fri16::canonical(roots, 8 * (size_t)b.R) || !fri16::canonical(final_poly, (size_t)4 << b.F) || witness >= P)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    return ZKHIP_OK;
+}
+
+extern "C" {
+
+size_t zkhip_fri16_indices_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows,
+                                    uint32_t* main_width, uint32_t* pre_width, int* table) {
+    fri16::IShape s;
+    if (which < 0 || which >= fri16::N_IT || kind < 0 || kind > 1 || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::indices_machine_of(s);
+    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+
+int zkhip_fri16_indices_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly, const uint32_t* values,
+                                 const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::IShape s;
+    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::N_IT];
+    ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key_host"));
+    const auto m = fri16::indices_machine_of(s);
+    const uint32_t* h[fri16::N_IT];
+    for (int i = 0; i < fri16::N_IT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_IT, prm, vk);
+}
+
+int zkhip_fri16_indices_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly,
+                            const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::IShape s;
+    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key: null argument");
+    std::vector<uint32_t> pre[fri16::N_IT];
+    ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key"));
+    const auto m = fri16::indices_machine_of(s);
+    const int slots[fri16::N_IT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};         // by table number: the six tables with preprocessed columns
+    zkhip_chip chips[fri16::N_IT]{};
+    for (int i = 0; i < fri16::N_IT; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips, fri16::N_IT, prm, key, vk);
+}
+
+size_t zkhip_fri16_indices_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const zkhip_params* prm) {
+    fri16::IShape s;
+    if (!prm || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::indices_machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, prm, fri16::N_PUBLIC_I);
+}
+
+int zkhip_fri16_indices_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8], const uint32_t* roots,
+                                   const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2t, uint32_t* d_samples, uint32_t* betas, uint32_t* indices) {
+    CHECK_CTX(ctx);
+    fri16::IShape s;
+    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, "fri16_indices_gen_traces"));
+    if (!d_p2t || !d_samples || !betas || !indices || ((uintptr_t)d_p2t | (uintptr_t)d_samples) % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_indices_gen_traces: 16-byte aligned dense traces (352 and 288 columns), betas and indices");
+    fri16::Chain c;
+    fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
+    uint32_t status = 0;
+    ZK_TRY(fri16_transcript_impl(ctx, s, c, nullptr, nullptr, nullptr, d_p2t, d_samples, nullptr, nullptr, &status));
+    std::memcpy(betas, c.betas.data(), c.betas.size() * 4);
+    std::memcpy(indices, c.drawn.data(), c.drawn.size() * 4);
+    return ZKHIP_OK;
+}
+
+int zkhip_fri16_samples_gen_trace(zkhip_ctx* ctx, int index_bits, size_t n_queries, const uint32_t* words, uint32_t* d_samples) {
+    CHECK_CTX(ctx);
+    if (index_bits < 1 || index_bits > TWO_ADICITY || n_queries < 1 || n_queries > fri16::MAX_Q || !words || !d_samples || (uintptr_t)d_samples % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_samples_gen_trace: 1..27 index bits, 1..1024 queries, the words and a 16-byte aligned dense trace of 288 columns");
+    const size_t S = frichip::samples_chip_rows(n_queries);
+    if (!fri16::canonical(words, 8 * S)) return fail(ZKHIP_ERR_INVALID, "fri16_samples_gen_trace: values must be canonical");
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_REC_E, (8 * S + 4) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(8 * S + 4, 0u);
+        std::memcpy(up.data(), words, 32 * S);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up.size() * 4));
+    }
+    p2chip::Fri16TranscriptArgs a{};
+    a.words = d; a.n_sample_rows = (uint32_t)S; a.Q = (uint32_t)n_queries; a.index_bits = (uint32_t)index_bits; a.samples_rows = (uint64_t)1 << fri16::lg(S);
+    a.samples = d_samples; a.status = d + 8 * S;
+    ZK_HIP(launch_fri16_transcript(a, ctx->stream));
+    return dev_sync(ctx);
+}
+
+int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                              const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
+                              const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    fri16::IShape s;
+    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: null argument");
+    ZK_TRY(fri16_paths_check_view(s.p.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_indices"));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, "prove_fri16_indices"));
+    const auto m = fri16::indices_machine_of(s);
+    const fri16::PShape& ps = s.p;
+    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
+    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
+    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
+    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
+    // the three tables' main columns: QUERIES the indices, COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer
+    size_t zoff[fri16::N_IT] = {0}, zwords = 0;
+    for (int t : {(int)fri16::T_QUERIES, (int)fri16::T_COEFFS, (int)fri16::T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)s.main_w[t] << s.log_rows[t]; }
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
+    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[fri16::T_COEFFS], 0, ((size_t)s.main_w[fri16::T_COEFFS] << s.log_rows[fri16::T_COEFFS]) * 4));
+    // refused here, before anything is proven: challenges and indices the chain does not draw, a witness that fails the proof of work; then all the paths machine refuses
+    fri16::Chain c;
+    fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
+    fri16::PathPlan pl;
+    ZK_TRY(fri16::plan_paths(ps.base, indices, paths, pl));
+    uint32_t status = 0;
+    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[fri16::T_QUERIES],
+                                 (uint32_t*)t_tabs + zoff[fri16::T_ROOTS], &status));
+    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the challenges are not the ones the transcript draws from these roots and this capacity");
+    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the witness does not satisfy the proof of work");
+    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the query indices are not the ones the transcript draws");
+    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    for (size_t p = 0; p < pl.n; p++)
+        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " does not open: its path does not end in the layer's root");
+    zkhip_chip chips[fri16::N_IT]{};
+    for (int i = 0; i < fri16::N_IT; i++) {
+        const int t = s.order[i];
+        chips[i].d_trace = t == fri16::T_FOLD16 ? (const uint32_t*)t_fold : t == fri16::T_FINAL ? (const uint32_t*)t_final : t == fri16::T_P24L ? (const uint32_t*)t_p24
+                         : t == fri16::T_P2T ? (const uint32_t*)t_p2t : t == fri16::T_SAMPLES ? (const uint32_t*)t_smp : (const uint32_t*)t_tabs + zoff[t];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, capacity, fri16::N_PUBLIC_I, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
+                               const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    fri16::IShape s;
+    if (!proof || !capacity || !vk || !prm || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_indices: bad arguments");
+    }
+    const auto m = fri16::indices_machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, capacity,
+                                      fri16::N_PUBLIC_I, prm, reason);
 }
 
 size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,

@@ -56,12 +56,7 @@ constexpr uint32_t K2 = 32, IDX = 33, L_WIRED = 34;
 constexpr uint32_t XS = 34, PT = 35, LNX = 36, L_REC = 37, BUS_FIN = 60;
 constexpr uint32_t BUS_E0 = 40, BUS_E1 = 41, BUS_R0 = 42, BUS_R1 = 43, BUS_Q = 44;
 constexpr uint32_t BUS_B = 45, BUS_BF = 46;                  // transcript machine: (layer, beta) from the Poseidon2 chip's transcript rows to the ROOTS table, and from there to the fold rows
-constexpr uint32_t BUS_S0 = 47, BUS_S1 = 48, BUS_I = 49;     // query-phase machine: a sponge row's sampled words (two halves) to the SAMPLES chip, (query, index) from there to QUERIES
-// SAMPLES chip, one row per query-phase sponge row.  Preprocessed: C (the sponge row's number), ROW, ACT[8] (word j is a query index), POW (row 0: word 0
-// is the proof-of-work sample), KQ[8] (the query's number).  Main: W[8] the words, IDX[8] their low layers + 1 bits, H1 H2 HH [8] (canonical-form
-// helpers), 8 x 31 bits.
-constexpr uint32_t S_PRE = 20, S_C = 0, S_ROW = 1, S_ACT = 2, S_POW = 10, S_KQ = 11;
-constexpr uint32_t S_W = 0, S_IDX = 8, S_H1 = 16, S_H2 = 24, S_HH = 32, S_BITS = 40, S_MAIN = 288;
+// (query-phase machine: BUS_S0, BUS_S1, BUS_I and the SAMPLES chip's columns S_* are in p2chip.h -- the fold-16 indices machine, fri16_chip.hip, uses the same chip)
 constexpr uint32_t ROOTS_MAIN_T = 8;                         // ... whose MAIN row is then (paths + 1, beta[4], queries, 0, 0); preprocessed (layer, root[8], 1, 0, 0)
 constexpr uint32_t N_PUBLIC_T = 12;                          // ... and whose public values are the final value and the challenger's capacity
 constexpr uint32_t QUERIES_PRE = 8, ROOTS_PRE = 12;          // QUERIES: (index, value[4], 1, 0, 0); ROOTS: (layer, root[8], 0, 0, 0) + main (count, 0, 0, 0)
@@ -679,6 +674,12 @@ void wired_machine(int layers, size_t nq, WiredMachine& m, bool transcript = fal
     for (int c = 0; c < m.n; c++) { m.progs[c] = m.p[c]->data(); m.prog_words[c] = m.p[c]->size(); m.tabs[c] = tabs[c]->data(); m.tab_words[c] = tabs[c]->size(); }
 }
 }  // namespace
+// the SAMPLES chip for the fold-16 indices machine (fri16_chip.hip): the same program, interactions and preprocessed rows, with `index_bits` index bits per word and
+// `first_row` the number of the first sponge row that hands words out
+std::shared_ptr<const std::vector<uint32_t>> samples_chip_program(int index_bits, int pow_bits, uint32_t n_public) { return samples_program(index_bits - 1, pow_bits, n_public); }
+const std::vector<uint32_t>& samples_chip_interactions() { return samples_interactions(); }
+size_t samples_chip_rows(size_t nq) { return sample_rows(nq); }
+void samples_chip_pre(size_t nq, int log_rows, int first_row, std::vector<uint32_t>& t) { samples_pre(0, nq, log_rows, t, first_row); }
 }  // namespace frichip
 }  // namespace zk
 

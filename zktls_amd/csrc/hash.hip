@@ -773,7 +773,7 @@ __device__ __forceinline__ void p2r_coop_put16(uint32_t* stage, const uint64_t* 
 // one row per lane, the shard-verifier machines' flags (bit; KP in column R_KP as a Montgomery word; every other flag zero): what p2chip_fill_row(t, in, bit, 0 ...)
 // followed by t[R_KP] = kp writes, word for word
 __device__ void p2chip_fill_row_coop(uint32_t* stage, uint64_t* rowoff, uint32_t* trace, uint64_t my_off, bool vec, const uint32_t in[16], uint32_t bit, uint32_t kp_monty,
-                                     uint32_t out16[16]) {
+                                     uint32_t out16[16], bool spare = true) {      // spare false: a 352-column row (P2T), columns 352 .. 359 do not exist
     using namespace p2chip;
     static_assert(R_WIDTH == 360 && SP == 327 && D == 343 && BIT == 351 && R_KP == 352 && s0p(0) == 288 && oute(7) == 272, "the cooperative writer knows the row's layout");
     __syncthreads();                                             // (the previous row's stores read rowoff)
@@ -816,7 +816,7 @@ __device__ void p2chip_fill_row_coop(uint32_t* stage, uint64_t* rowoff, uint32_t
     p2r_coop_put16(stage, rowoff, trace, 304, tail + 16, vec);
     p2r_coop_put16(stage, rowoff, trace, 320, tail + 32, vec);
     p2r_coop_put16(stage, rowoff, trace, 336, tail + 48, vec);
-    p2r_coop_put16(stage, rowoff, trace, 352, tail + 64, vec, 8);
+    if (spare) p2r_coop_put16(stage, rowoff, trace, 352, tail + 64, vec, 8);
     for (int j = 0; j < 16; j++) out16[j] = s[j];
 }
 
@@ -1439,6 +1439,87 @@ __global__ void __launch_bounds__(64) p24chip_layer_paths_kernel_batch(const p24
 hipError_t launch_p24chip_layer_paths(const p24chip::LayerPathsArgs& a, hipStream_t s) {
     const uint64_t waves = a.n_paths + (a.rows - a.used_rows + 15) / 16;
     ZK_LAUNCH(p24chip_layer_paths_kernel, p24chip_layer_paths_kernel_batch, p24chip_layer_paths_kernel_bargs, dim3((unsigned)waves), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the fold-16 indices machine's transcript side (p2chip.h, Fri16TranscriptArgs)
+// One launch, four tables.  The first blocks fill P2T, a lane per row and a wave per 64 rows through the cooperative writer above (the chain's states come from
+// the host's walk, so the rows are independent; the rows behind the chain are the permutation of the zero state).  The lanes of the remaining blocks take one group
+// of four columns each: 72 groups per SAMPLES row (words, indices, the three canonical-form helpers, 8 x 31 bits), one per QUERIES row, two per ROOTS row --
+// every store is 16 bytes.  The lanes that hold a drawn index or a drawn challenge compare it with the view's and mark the status word.
+__device__ __forceinline__ uint32_t samples_cell(const uint32_t* __restrict__ w8, uint32_t c, uint32_t mask) {       // w8: the row's eight words, null on a padding row
+    using namespace frichip;
+    if (!w8) return 0u;
+    if (c < S_BITS) {
+        const uint32_t w = w8[c & 7u];
+        if (c < S_IDX) return to_monty(w);
+        if (c < S_H1) return to_monty(w & mask);
+        const uint32_t h1 = (w >> 30) & (w >> 29) & 1u, h2 = (w >> 28) & (w >> 27) & 1u;
+        return (c < S_H2 ? h1 : c < S_HH ? h2 : h1 & h2) ? MONTY_R1 : 0u;
+    }
+    const uint32_t k = c - S_BITS;
+    return (w8[k / 31u] >> (k % 31u)) & 1u ? MONTY_R1 : 0u;
+}
+__device__ __forceinline__ void fri16_transcript_kernel_body(const p2chip::Fri16TranscriptArgs& a) {
+    using namespace p2chip;
+    using namespace frichip;
+    static_assert(S_MAIN % 4 == 0 && S_IDX == 8 && S_H1 == 16, "a group of four columns lies in one section up to BITS");
+    const uint32_t p2_blocks = (uint32_t)((a.p2t_rows + 63) / 64);
+    if (blockIdx.x < p2_blocks) {
+        __shared__ uint32_t stage[64 * 17];
+        __shared__ uint64_t rowoff[64];
+        const uint64_t r = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+        uint32_t in[16], out[16];
+        for (int j = 0; j < 16; j++) in[j] = r < a.n_chain ? to_monty(a.chain_inputs[16 * r + j]) : 0u;
+        p2chip_fill_row_coop(stage, rowoff, a.p2t, r < a.p2t_rows ? r * T_WIDTH : ~0ull, true, in, 0u, 0u, out, false);
+        return;
+    }
+    const uint32_t mask = (1u << a.index_bits) - 1u;
+    uint64_t g = (uint64_t)(blockIdx.x - p2_blocks) * 64 + threadIdx.x;
+    const uint64_t sample_groups = a.samples_rows * (S_MAIN / 4);
+    if (g < sample_groups) {
+        const uint64_t row = g / (S_MAIN / 4);
+        const uint32_t c0 = 4u * (uint32_t)(g % (S_MAIN / 4));
+        const uint32_t* w = row < a.n_sample_rows ? a.words + 8 * row : nullptr;
+        *reinterpret_cast<uint4*>(a.samples + row * S_MAIN + c0) = make_uint4(samples_cell(w, c0, mask), samples_cell(w, c0 + 1, mask), samples_cell(w, c0 + 2, mask), samples_cell(w, c0 + 3, mask));
+        if (a.view_indices && w && c0 >= S_IDX && c0 < S_H1)
+            for (uint32_t j = c0 - S_IDX; j < c0 - S_IDX + 4u; j++) {
+                const uint64_t slot = 8 * row + j;               // slot 0: the proof-of-work word; slot q + 1: query q
+                if (slot >= 1 && slot <= a.Q && (w[j] & mask) != a.view_indices[slot - 1]) atomicOr(a.status, 2u);
+            }
+        return;
+    }
+    g -= sample_groups;
+    if (a.queries_main) {
+        if (g < a.queries_rows) {
+            *reinterpret_cast<uint4*>(a.queries_main + 4 * g) = make_uint4(g < a.Q ? to_monty(a.words[g + 1] & mask) : 0u, 0u, 0u, 0u);
+            return;
+        }
+        g -= a.queries_rows;
+    }
+    if (a.roots_main && g < 2 * a.roots_rows) {
+        const uint64_t l = g >> 1;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (l < a.R) {
+            const uint32_t* b = a.drawn_betas + 4 * l;
+            if (g & 1) v = make_uint4(to_monty(b[3]), to_monty(a.Q), 0u, 0u);
+            else {
+                v = make_uint4(a.counts ? to_monty(a.counts[l]) : 0u, to_monty(b[0]), to_monty(b[1]), to_monty(b[2]));
+                if (a.view_betas)
+                    for (int i = 0; i < 4; i++) if (b[i] != a.view_betas[4 * l + i]) atomicOr(a.status, 1u);
+            }
+        }
+        *reinterpret_cast<uint4*>(a.roots_main + 4 * g) = v;
+    }
+}
+__global__ void __launch_bounds__(64) fri16_transcript_kernel(p2chip::Fri16TranscriptArgs a) { fri16_transcript_kernel_body(a); }
+struct fri16_transcript_kernel_bargs { p2chip::Fri16TranscriptArgs a; static fri16_transcript_kernel_bargs make(p2chip::Fri16TranscriptArgs a) { return fri16_transcript_kernel_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_transcript_kernel_batch(const fri16_transcript_kernel_bargs* __restrict__ zk_arr) { const fri16_transcript_kernel_bargs& zk_b = zk_arr[blockIdx.z]; fri16_transcript_kernel_body(zk_b.a); }
+hipError_t launch_fri16_transcript(const p2chip::Fri16TranscriptArgs& a, hipStream_t s) {
+    const uint64_t lanes = a.samples_rows * (frichip::S_MAIN / 4) + (a.queries_main ? a.queries_rows : 0) + (a.roots_main ? 2 * a.roots_rows : 0);
+    const uint64_t blocks = (a.p2t_rows + 63) / 64 + (lanes + 63) / 64;
+    if (blocks == 0) return hipSuccess;
+    ZK_LAUNCH(fri16_transcript_kernel, fri16_transcript_kernel_batch, fri16_transcript_kernel_bargs, dim3((unsigned)blocks), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -180,12 +180,13 @@ struct P2Tables;
 hipError_t hash_upload_p2_tables(const P2Tables& t, hipStream_t s);
 hipError_t stark_upload_p2_tables(const P2Tables& t, hipStream_t s);
 // trace of the Poseidon2 permutation chip for a set of Merkle paths (p2chip.h)
-namespace p2chip { struct MerkleTraceArgs; struct LayerPathsArgs; struct P2RArgs; struct MrecChainArgs; }
+namespace p2chip { struct MerkleTraceArgs; struct LayerPathsArgs; struct P2RArgs; struct MrecChainArgs; struct Fri16TranscriptArgs; }
 hipError_t launch_p2chip_merkle(const p2chip::MerkleTraceArgs& a, hipStream_t s);
 // ... and of the width-24 chip (p24chip.h)
 namespace p24chip { struct MerkleTraceArgs; struct LayerPathsArgs; }
 hipError_t launch_p24chip_merkle(const p24chip::MerkleTraceArgs& a, hipStream_t s);
 hipError_t launch_p24chip_layer_paths(const p24chip::LayerPathsArgs& a, hipStream_t s);   // the fold-16 paths machine's P24L table: one launch, all layers
+hipError_t launch_fri16_transcript(const p2chip::Fri16TranscriptArgs& a, hipStream_t s);    // the fold-16 indices machine: P2T, SAMPLES and the main columns of QUERIES and ROOTS, one launch
 hipError_t launch_p2chip_layer_paths(const p2chip::LayerPathsArgs& a, hipStream_t s);     // the FRI-layers variant: paths of different depths
 hipError_t launch_mrec_chains(const p2chip::MrecChainArgs& a, hipStream_t s);                // machine mode: the queries' Poseidon2 chains walked on the device
 hipError_t launch_p2r_rows(const p2chip::P2RArgs& a, hipStream_t s);                        // the shard verifier's chip: chains of sponge + path rows, transcript rows

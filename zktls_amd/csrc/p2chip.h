@@ -118,5 +118,34 @@ struct MerkleTraceArgs {
     uint32_t* roots;             // [n_paths][8], canonical
 };
 
+// The transcript-only table of the fold-16 indices machine (fri16_chip.hip: P2T): the 352 permutation columns IN .. BIT and nothing else in the main trace;
+// every flag and key of the chain's schedule is a preprocessed column.  Its rows, the SAMPLES chip's rows below and the main columns of that machine's QUERIES
+// and ROOTS tables are filled by ONE launch from one staging block (hash.hip, launch_fri16_transcript).
+constexpr uint32_t T_WIDTH = 352;
+static_assert(BIT + 1 == T_WIDTH && T_WIDTH % 4 == 0, "P2T: the permutation columns end with BIT");
+struct Fri16TranscriptArgs {
+    const uint32_t* chain_inputs;    // [n_chain][16] canonical: the input state of every sponge row, walked on the host
+    const uint32_t* words;           // [n_sample_rows][8] canonical: the words the chain hands out, out[7] first
+    const uint32_t* drawn_betas;     // [R][4] canonical: what the root rows hand out
+    const uint32_t* view_betas;      // [R][4] to compare with, or null
+    const uint32_t* view_indices;    // [Q] to compare with, or null
+    const uint32_t* counts;          // [R] path ends per layer (ROOTS), or null with roots_main
+    uint32_t n_chain, n_sample_rows, R, Q, index_bits;
+    uint64_t p2t_rows, samples_rows, queries_rows, roots_rows;     // table heights
+    uint32_t* p2t;                   // [p2t_rows][T_WIDTH] Montgomery, 16-byte aligned
+    uint32_t* samples;               // [samples_rows][S_MAIN]
+    uint32_t* queries_main;          // [queries_rows][4]: (index, 0, 0, 0), or null
+    uint32_t* roots_main;            // [roots_rows][8]: (path ends, beta[4], fold rows, 0, 0), or null
+    uint32_t* status;                // one word, zero on entry: bit 0 a drawn beta differs from the view's, bit 1 a drawn index does
+};
+
 }  // namespace p2chip
+
+// SAMPLES chip (fri_chip.hip), one row per query-phase sponge row.  Preprocessed: C (the sponge row's number), ROW, ACT[8] (word j is a query index), POW (row 0: word 0
+// is the proof-of-work word), KQ[8] (the query's number).  Main: W[8] the words, IDX[8] their low index bits, H1 H2 HH [8] the canonical-form helpers, BITS[8][31].
+namespace frichip {
+constexpr uint32_t S_PRE = 20, S_C = 0, S_ROW = 1, S_ACT = 2, S_POW = 10, S_KQ = 11;
+constexpr uint32_t S_W = 0, S_IDX = 8, S_H1 = 16, S_H2 = 24, S_HH = 32, S_BITS = 40, S_MAIN = 288;
+constexpr uint32_t BUS_S0 = 47, BUS_S1 = 48, BUS_I = 49;     // a sponge row's sampled words (two halves) to the SAMPLES chip, (query, index) from there to QUERIES
+}  // namespace frichip
 }  // namespace zk

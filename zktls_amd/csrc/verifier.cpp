@@ -549,6 +549,22 @@ int zkhip_fri_view_transcript(const uint8_t* proof, size_t len, int log_n, uint3
     int why = 0;
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }
+// ... and of a FOLD-BY-16 proof (the indices machine of fri16_chip.hip starts from this capacity): the chain then goes on through the 2^F final coefficients
+int zkhip_fri16_view_transcript(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                                uint32_t* roots, uint32_t* betas, uint32_t transcript[10]) {
+    if (!prm || !roots || !betas || !transcript) return fail(ZKHIP_ERR_INVALID, "fri16_view_transcript: null argument");
+    Shape sh;
+    if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_transcript: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    const size_t Q = (size_t)prm->num_queries;
+    std::vector<uint32_t> final_poly((size_t)4 << sh.F), indices(Q), values(4 * Q), siblings(60 * Q * (size_t)sh.R);
+    FriViewSink sink{betas, nullptr, indices.data(), values.data(), siblings.data(), sh.R, roots, nullptr, transcript};
+    sink.fold16 = true;
+    sink.final_poly = final_poly.data();
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
+}
 
 // the same view WITHOUT hashing the Merkle paths (library-internal: the caller recomputes every opening and compares the roots)
 extern "C++" {

@@ -726,6 +726,59 @@ class Context:
                                                paths.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    def fri16_indices_key(self, view, params=None):
+        """zkhip_fri16_indices_key: the key of the fold-16 indices machine, committed on the device -- from the shape, the inner proof's grinding bits, the
+        final coefficients, the reduced openings by query number and the layer roots: no index, no challenge -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_indices_key(self.handle, *shape, hw, int(view["pow_bits"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[3], roots)], C.byref(params),
+                                               C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_indices_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, capacity, roots, final_poly, witness):
+        """zkhip_fri16_indices_gen_traces: the P2T and SAMPLES main traces from the capacity, the layer roots, the final coefficients and the witness alone
+        -> (P2T [2^lr][352], SAMPLES [2^lr][288] (canonical words, downloaded), betas [R][4], the Q drawn indices)"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        lns = {d[4]: d[1] for d in (fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, 0) for which in range(8))}
+        p2t, smp = self.alloc(352 << lns[6]), self.alloc(288 << lns[7])
+        cp, rt, fp = u(capacity), u(roots), u(final_poly)
+        assert cp.size == 8 and rt.size == 8 * R and fp.size == 4 << F
+        betas, idx = np.zeros(4 * R, dtype=np.uint32), np.zeros(n_queries, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_indices_gen_traces(self.handle, R, F, log_blowup, n_queries, pow_bits, cp.ctypes.data_as(u32p), rt.ctypes.data_as(u32p), fp.ctypes.data_as(u32p),
+                                                      int(witness), C.c_void_p(p2t.ptr), C.c_void_p(smp.ptr), betas.ctypes.data_as(u32p), idx.ctypes.data_as(u32p)))
+        return p2t.download().reshape(-1, 352), smp.download().reshape(-1, 288), betas.reshape(R, 4), idx
+
+    def fri16_samples_gen_trace(self, index_bits, n_queries, words):
+        """zkhip_fri16_samples_gen_trace: the SAMPLES main trace from given canonical words [ceil((1 + Q) / 8)][8] -> [2^lr][288] (canonical words, downloaded)"""
+        w = np.ascontiguousarray(np.array(words, dtype=np.uint32).reshape(-1))
+        rows = (1 + n_queries + 7) // 8
+        assert w.size == 8 * rows
+        lr = 5
+        while (1 << lr) < rows:
+            lr += 1
+        buf = self.alloc(288 << lr)
+        check(self.lib.zkhip_fri16_samples_gen_trace(self.handle, index_bits, n_queries, w.ctypes.data_as(u32p), C.c_void_p(buf.ptr)))
+        return buf.download().reshape(-1, 288)
+
+    def prove_fri16_indices(self, key, view, params=None):
+        """zkhip_prove_fri16_indices: "a sponge chain from this capacity over the listed roots, final coefficients and a witness draws the challenges, a
+        proof-of-work word with its low bits zero and the query indices; every query, at the index drawn for it, opens the listed layer commitments and
+        folds under the drawn challenges to the listed final polynomial".  view: a paths view with "capacity" [8], "witness" and "pow_bits".  Refused before
+        anything is proven: challenges or indices the chain does not draw, a witness that fails the proof of work, and all prove_fri16_paths refuses"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
+        pb = int(view["pow_bits"])
+        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
+        assert cap.size == 8
+        size = self.lib.zkhip_fri16_indices_proof_size(*shape, pb, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_indices(self.handle, key.handle, *shape, hw, pb, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+                                                 paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]), C.byref(params), buf.ctypes.data_as(u8p), size,
+                                                 C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1499,6 +1552,59 @@ def verify_fri16_paths(proof, betas, R, F, log_blowup, n_queries, vk, params=Non
     reason = C.c_int(0)
     rc = lib.zkhip_verify_fri16_paths(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params),
                                       C.byref(reason))
+    return rc, reason.value
+
+
+def fri16_view_transcript(proof, log_n, width, public_values=(), params=None):
+    """zkhip_fri16_view_transcript: the Fiat-Shamir side of a fold-by-16 proof's FRI view -> {"roots": [R][8], "betas": [R][4], "capacity": [8] (the duplex
+    challenger's capacity as the commit phase finds it), "pending": inputs pending there (0), "witness": the proof-of-work witness, "pow_bits"}, or raises
+    if the proof is rejected.  Host only."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+    R = max((log_n - params.log_final) // 4, 0)
+    roots, betas, tr = np.zeros(8 * max(R, 1), dtype=np.uint32), np.zeros(4 * max(R, 1), dtype=np.uint32), np.zeros(10, dtype=np.uint32)
+    check(lib.zkhip_fri16_view_transcript(pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size, C.byref(params), roots.ctypes.data_as(u32p),
+                                          betas.ctypes.data_as(u32p), tr.ctypes.data_as(u32p)))
+    return {"roots": roots[:8 * R].reshape(R, 8).tolist(), "betas": betas[:4 * R].reshape(R, 4).tolist(), "capacity": tr[:8].tolist(), "pending": int(tr[8]),
+            "witness": int(tr[9]), "pow_bits": int(params.pow_bits)}
+
+
+def fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind):
+    """zkhip_fri16_indices_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..7) of the fold-16 indices
+    machine -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16B, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES)"""
+    lib = _lib.load()
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    n = lib.zkhip_fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    if n == 0:
+        raise _lib.ZkHipError(-1, "fri16_indices_describe: " + lib.zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib.zkhip_fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
+                                            C.byref(tb)) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def fri16_indices_key_host(view, params=None):
+    """zkhip_fri16_indices_key_host: the fold-16 indices machine's key of a view (with "pow_bits"), without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_indices_key_host(*shape, hw, int(view["pow_bits"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[3], roots)], C.byref(params),
+                                                   vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_indices(proof, capacity, R, F, log_blowup, n_queries, pow_bits, vk, params=None):
+    """zkhip_verify_fri16_indices: the shape, the inner proof's grinding bits, the capacity, the key -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    cp = np.ascontiguousarray(np.array(capacity, dtype=np.uint32).reshape(-1))
+    assert cp.size == 8
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_fri16_indices(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, cp.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
+                                        C.byref(params), C.byref(reason))
     return rc, reason.value
 
 
