@@ -194,3 +194,111 @@ def sp1_shaped_machine(spec, seed=1, shard=0, pre=(), n_public=3, key_shard=9999
     pres = [np.ascontiguousarray(gen(c, key_shard)[:, :pw[c]]) if pw.get(c) else None for c in range(len(spec))]
     mains = [np.ascontiguousarray(t[:, pw.get(c, 0):]) for c, t in enumerate(traces)]
     return mains, pres, progs, tabs, [(11 * (i + 1)) % P for i in range(n_public - 1)] + [shard]
+
+
+# ---- machines at the limits of the lookup kernels' staging (tests/test_gpu_lookup_edges.py, tests/test_lookup_edges_cpu.py)
+HALF = (P + 1) // 2
+EDGE_MULTS = (0, 1, P - 1, HALF)
+BOUNDARY_CASES = ("used56", "used57", "col511", "col512", "reuse", "one", "odd63", "max64", "edge",
+                  "keyed4", "keyed20", "keyed_col512", "keyed_used57")
+
+
+def _boundary_subject(case):
+    """the chip under test -> (combined width, preprocessed width, [(sign, multiplicity column or None, bus, [value columns])])"""
+    S, R = O.SEND, O.RECEIVE
+    sends56 = [(S, None, 100 + i, list(range(8 * i, 8 * i + 8))) for i in range(7)]           # 56 distinct columns, constant multiplicity
+    if case == "used56":                                    # staged with pitch 57: the largest LDS launch
+        return 64, 0, sends56
+    if case == "used57":                                    # one more column read (a multiplicity): unstaged
+        return 64, 0, sends56[:6] + [(S, 56, 106, list(range(48, 56)))]
+    if case in ("col511", "col512"):                        # column 511: chunk 31, bit 31 of chunk_mask, staged; column 512: unstaged
+        e = int(case[3:])
+        return 1024, 0, [(S, None, 100, [e - 3, e - 2, e - 1, e]), (R, 2, 101, [0, 1])]
+    if case == "reuse":                                     # column 5: a value of three interactions, the multiplicity of a fourth
+        return 64, 0, [(S, None, 100, [5]), (R, None, 101, [4, 5]), (S, 10, 102, [5, 6, 7]), (S, 5, 103, [8, 9])]
+    if case == "one":                                       # a single interaction: the last (only) column's phi in its single-term form
+        return 64, 0, [(S, None, 100, list(range(8, 16)))]
+    if case in ("odd63", "max64"):                          # tuple lengths 1 and 8; 63: 32 columns, the last single; 64: the table's maximum
+        ni = int(case[3:])
+        its = [(S, 50, 100, list(range(40, 48)))]
+        its += [(R if i % 3 == 0 else S, 51 if i % 5 == 0 else None, 100 + i, [i % 40]) for i in range(1, ni)]
+        return 64, 0, its
+    if case == "edge":                                      # buses 0 and P - 1, multiplicity columns on sends and receives
+        return 64, 0, [(S, 8, 0, list(range(0, 8))), (S, 9, P - 1, [10]), (R, 11, 0, [12]), (R, 13, P - 1, list(range(14, 22)))]
+    if case in ("keyed4", "keyed20", "keyed_col512", "keyed_used57"):
+        pw = 4 if case == "keyed4" else 20
+        its = [(S, None, 100, [pw - 2, pw - 1, pw, pw + 1]),               # a tuple with values on both sides of pre_w
+               (R, 0, 101, [pw + 4, pw + 5, pw + 6]),                      # multiplicity preprocessed, tuple in main
+               (S, pw + 8, 102, [1, 2])]                                   # multiplicity in main, tuple preprocessed
+        if case == "keyed_col512":
+            return 1024, pw, its + [(S, None, 103, [509, 510, 511, 512])]
+        if case == "keyed_used57":                                         # 11 columns above, 46 more: 57
+            free = [c for c in range(63) if c not in {pw - 2, pw - 1, pw, pw + 1, 0, pw + 4, pw + 5, pw + 6, pw + 8, 1, 2}][:46]
+            return 64, pw, its + [(S, None, 104 + i, free[8 * i:8 * i + 8]) for i in range(6)]
+        return 64, pw, its
+    raise ValueError(case)
+
+
+def boundary_machine(case, log_sender, log_receiver, seed):
+    """A SUBJECT table (2^log_sender rows) whose interaction table places its columns explicitly (_boundary_subject) and a BALANCER table
+    (2^log_receiver rows) that holds, per bus, every distinct tuple the subject puts on it with the opposite net multiplicity -- balanced
+    by construction, in plain integers mod P.  The columns the subject's interactions read repeat a few template rows of EDGE_WORDS (through
+    edge_canonical; multiplicity columns hold 0, 1, P - 1, (P + 1) / 2), so the balancer has room for every tuple; its other columns are
+    uniform.  The balancer's spare rows carry, per bus: a tuple nobody sends with multiplicity 0, one tuple three times with
+    (P + 1) / 2, (P + 1) / 2, P - 1 and one twice with 1, P - 1 (both cancel mod P).  In the col511 / col512 cases the balancer's first
+    tuple ends at that column too.  Each table's program: its last column is a bit.
+    -> (main traces, preprocessed traces (None: an unkeyed machine), programs, tables, public values), tallest first"""
+    from field_edges import EDGE_WORDS, edge_canonical
+    rng = np.random.default_rng(seed)
+    W, pw, its = _boundary_subject(case)
+    na, nb = 1 << log_sender, 1 << log_receiver
+    groups = {}                                                                  # (bus, tuple length) -> the subject's interactions
+    for it in its:
+        groups.setdefault((it[2], len(it[3])), []).append(it)
+    spare = 6
+    T = max(1, min(na, (nb - spare) // max(len(g) for g in groups.values())))
+    tmpl = edge_canonical(rng.choice(EDGE_WORDS, (T, W))).astype(np.int64)
+    for it in its:
+        if it[1] is not None:
+            tmpl[:, it[1]] = np.resize(rng.permutation(EDGE_MULTS), T)
+    pick = np.concatenate([np.arange(T), rng.integers(0, T, na - T)])
+    rng.shuffle(pick)
+    a = rng.integers(0, P, (na, W)).astype(np.int64)
+    read = sorted({c for it in its for c in it[3]} | {it[1] for it in its if it[1] is not None})
+    a[:, read] = tmpl[pick][:, read]
+    a[:, -1] = rng.integers(0, 2, na)
+    assert W - 1 not in read
+    # the balancer: per bus [multiplicity | values] from column 0 up; the first bus ends at column 511 / 512 where that is the case's point
+    end = int(case[-3:]) if case.endswith(("col511", "col512")) else None
+    wb = 1024 if end else max(64, 4 * ((sum(len(g[0][3]) + 1 for g in groups.values()) + 1 + 3) // 4))
+    bt = rng.integers(0, P, (nb, wb)).astype(np.int64)
+    bt[:, -1] = rng.integers(0, 2, nb)
+    b_its, col = [], 0
+    for gi, ((bus, nv), g) in enumerate(groups.items()):
+        at = end - nv if (end and gi == 0) else col
+        if not (end and gi == 0):
+            col += nv + 1
+        net = {}
+        for sign, mult, _, cols in g:
+            ms = np.ones(na, dtype=np.int64) if mult is None else a[:, mult]
+            for r in range(na):
+                k = tuple(int(x) for x in a[r, cols])
+                net[k] = (net.get(k, 0) + (-int(ms[r]) if sign else int(ms[r]))) % P
+        assert len(net) + spare <= nb, (case, bus, len(net), nb)
+        sign_b = O.RECEIVE if gi % 2 == 0 else O.SEND                             # a receive takes the net, a send gives its negative
+        rows = rng.permutation(nb)
+        bt[:, at] = 0                                                            # (the rows left over: junk tuples with multiplicity 0)
+        for r, (k, v) in zip(rows, net.items()):
+            bt[r, at + 1:at + 1 + nv], bt[r, at] = k, (v if sign_b == O.RECEIVE else (P - v) % P)
+        f = rows[len(net):len(net) + spare]                                      # f[0]: multiplicity 0 on a tuple nobody sends
+        for r, src, m in zip(f[1:], (f[1], f[1], f[1], f[4], f[4]), (HALF, HALF, P - 1, 1, P - 1)):
+            bt[r, at + 1:at + 1 + nv], bt[r, at] = bt[src, at + 1:at + 1 + nv], m
+        b_its.append((sign_b, at, bus, list(range(at + 1, at + 1 + nv))))
+    assert col <= wb - 1 and (end is None or col <= end - 8)
+    progs = [O.air_program(w, 2, [(O.SEL_ALL, [(1, [V(w - 1), V(w - 1)]), (P - 1, [V(w - 1)])])]) for w in (W, wb)]
+    chips = [(log_sender, a.astype(np.uint32), pw, progs[0], O.interaction_table(its)),
+             (log_receiver, bt.astype(np.uint32), 0, progs[1], O.interaction_table(b_its))]
+    chips.sort(key=lambda c: -c[0])
+    mains = [np.ascontiguousarray(c[1][:, c[2]:]) for c in chips]
+    pres = [np.ascontiguousarray(c[1][:, :c[2]]) if c[2] else None for c in chips] if pw else None
+    return mains, pres, [c[3] for c in chips], [c[4] for c in chips], [int(rng.integers(0, P)), int(rng.integers(0, P))]

@@ -139,11 +139,12 @@ class Context:
         check(self.lib.zkhip_gen_trace_logup(self.handle, seed, shard, log_n, width, pairs, C.c_void_p(out.ptr), width))
         return out
 
-    def perm_trace(self, trace, log_n, width, pairs, gamma, beta, out=None):
+    def perm_trace(self, trace, log_n, width, pairs, gamma, beta, out=None, ld=None):
+        """ld: the trace's row pitch in words when it exceeds its width"""
         out = out or self.alloc((4 * (pairs + 1)) << log_n)
         g = to_monty(np.asarray(gamma, dtype=np.uint32))
         b = to_monty(np.asarray(beta, dtype=np.uint32))
-        check(self.lib.zkhip_perm_trace(self.handle, C.c_void_p(trace.ptr), width, log_n, width, pairs,
+        check(self.lib.zkhip_perm_trace(self.handle, C.c_void_p(trace.ptr), ld or width, log_n, width, pairs,
                                         g.ctypes.data_as(u32p), b.ctypes.data_as(u32p), C.c_void_p(out.ptr)))
         return out
 
