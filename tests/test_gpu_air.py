@@ -3,6 +3,7 @@ whole proofs against programs (zkhip_prove_shard_air), byte for byte against the
 import numpy as np
 import pytest
 
+import air_forms
 import airs
 import pyverify
 from zktls_amd._lib import Params, ZkHipError
@@ -106,12 +107,10 @@ def test_bad_programs_fail_loudly(ctx):
         ctx.prove_shard_air(prog, trace, 6, 4, [1, 2, 3], Params(1, 6, 4, 1))  # lookups belong to the built-in AIR
 
 
-def test_many_public_values_take_the_row_per_lane_interpreter(ctx, oracle):
-    """more than 64 public values do not fit the per-point LDS slots of the term-parallel kernel (stark.hip): the row-per-lane
-    interpreter proves those programs -- same bytes as the oracle either way"""
+def _many_public_values(ctx, oracle, width):
     O = oracle
     V = O.air_var
-    width, n_pub, log_n = 8, 80, 9
+    n_pub, log_n = 80, 9
     cons = [(O.SEL_FIRST, [(1, [V(0)]), (P - 1, [V(79, public=True)])]),
             (O.SEL_TRANSITION, [(1, [V(0, True)]), (P - 1, [V(0)]), (P - 1, [V(3, public=True)])])]
     for j in range(1, width):
@@ -129,18 +128,35 @@ def test_many_public_values_take_the_row_per_lane_interpreter(ctx, oracle):
     proof = ctx.prove_shard_air(prog, ctx.from_numpy(t), log_n, width, pub, Params(*shape))
     assert proof.tobytes() == O.prove_shard_air(prog, t, pub, O.default_params(*shape)).tobytes()
     assert verify_shard_air(prog, proof, log_n, width, pub, Params(*shape)) == (0, 0)
+    return prog
 
 
-@pytest.mark.parametrize("n_monomials,lanes", [(300, 64), (3000, 128), (9000, 256)])
-def test_term_kernel_with_64_128_and_256_lanes_per_group(ctx, oracle, n_monomials, lanes):
-    """the term-parallel kernel takes one, two or four wavefronts per group of 8 points by the program's record count (one record per
-    distinct monomial).  Programs with that many distinct monomials on any trace: constraint k = m_k - m_k over a monomial m_k of its own
-    (the two terms merge into one record whose coefficient happens to be zero) next to a real counter constraint; quotient values
-    against the oracle, which evaluates the program term by term"""
+def test_many_public_values_take_the_row_per_lane_interpreter(ctx, oracle):
+    """80 public values on 8 columns.  The program takes the row-per-lane interpreter because it is SMALL (at most 512 records over at
+    most 16 columns: stark.hip launch_quotient_air), not because of its public values: since round 5 the host folds a term's
+    public-value factors into its record's coefficient (air.h air_term_coeff) and no kernel stages a public value when records exist.
+    Same bytes as the oracle."""
+    prog = _many_public_values(ctx, oracle, 8)
+    assert air_forms.form(8, air_forms.monomial_count(prog), 9) == "interpreter"
+
+
+def test_many_public_values_on_a_term_parallel_form(ctx, oracle):
+    """the same program over 20 columns: no longer small, it takes the chained term kernel, whose records carry the public values in
+    their coefficients -- same bytes as the oracle"""
+    prog = _many_public_values(ctx, oracle, 20)
+    assert air_forms.form(20, air_forms.monomial_count(prog), 9) == "chain<64,4>"
+
+
+def _zero_weight_records(ctx, oracle, n_monomials, log_n):
+    """Programs with that many distinct monomials on any trace: constraint k = m_k - m_k over a monomial m_k of its own (the two terms
+    merge into one record whose coefficient is zero) next to a real counter constraint.  ZERO-WEIGHT RECORDS TEST PLUMBING ONLY -- the
+    choice of the kernel, its launch, the records' addresses: a kernel that evaluated those monomials wrongly would still pass
+    (test_gpu_air_forms.py gives every monomial a weight).  Quotient values against the oracle, which evaluates the program term by
+    term, and a whole proof through that path."""
     import itertools
     O = oracle
     V = O.air_var
-    width, log_n = 48, 7
+    width = 48
     cons = [(O.SEL_FIRST, [(1, [V(0)]), (P - 1, [V(0, public=True)])]),
             (O.SEL_TRANSITION, [(1, [V(0, True)]), (P - 1, [V(0)]), (P - 1, [])])]
     for i, j, k in itertools.islice(itertools.combinations(range(width), 3), n_monomials):
@@ -159,3 +175,22 @@ def test_term_kernel_with_64_128_and_256_lanes_per_group(ctx, oracle, n_monomial
     prm = Params(1, 6, 4)
     proof = ctx.prove_shard_air(prog, ctx.from_numpy(t), log_n, width, [11], prm)
     assert proof.tobytes() == O.prove_shard_air(prog, t, [11], O.default_params(1, 6, 4)).tobytes()
+    return air_forms.form(width, air_forms.monomial_count(prog), log_n)
+
+
+@pytest.mark.parametrize("n_monomials,lanes", [(300, 64), (3000, 128), (9000, 256)])
+def test_term_kernel_with_64_128_and_256_lanes_per_group(ctx, oracle, n_monomials, lanes):
+    """the term-parallel kernel takes one, two or four wavefronts per group of 8 points by the program's record count (one record per
+    distinct monomial).  At 2^5 rows (below the wide form's 64) 3 000 and 9 000 records run quotient_air_terms_kernel<128> and <256>;
+    up to 512 records over more than 16 columns run one wavefront per group in the CHAINED form (quotient_air_chain_kernel<64,4>: the
+    unchained <64> is left to 2^3 rows, which no entry takes).  Zero-weight records: see _zero_weight_records."""
+    form = _zero_weight_records(ctx, oracle, n_monomials, 5)
+    assert form == {64: "chain<64,4>", 128: "terms<128>", 256: "terms<256>"}[lanes]
+
+
+@pytest.mark.parametrize("n_monomials", [300, 3000, 9000])
+def test_zero_weight_records_on_the_chained_and_wide_forms(ctx, oracle, n_monomials):
+    """the same programs at 2^7 rows (the shapes test_term_kernel_with_64_128_and_256_lanes_per_group had until the wide form took
+    them): 300 records run the chained form, 3 000 and 9 000 quotient_air_wide_kernel<16>"""
+    form = _zero_weight_records(ctx, oracle, n_monomials, 7)
+    assert form == ("chain<64,4>" if n_monomials == 300 else "wide<16>")

@@ -37,7 +37,8 @@ ntt_small.hip, ntt_fused.hip, hash.hip, stark.hip, hal.hip):
   hash_cols24, compress24_level / _top     merkle_commit_p24_colmajor 24 x 2^12 and 7 x 2^5
   hash_rows24 (row-major w24 leaves)       commit(..., hw=24) 2^10 x 16, blowup 2
   quotient_kernel                          quotient_values 2^10 x 16 and 2^12 x 256, edge alphas
-  quotient_air_* kernels                   quotient_values_air, synthetic programs 2^8 x 8 and 2^12 x 64
+  quotient_air_* kernels                   test_gpu_air_forms.py (every live form, with its own kernel / shape table); here the synthetic
+                                           program at 2^8 x 8 (the interpreter) and 2^12 x 64 (quotient_air_chain_kernel<64,4>)
   inv_denominators, open_partial*, final   open_at 2^10 x 20 and 2^12 x 64, two edge points
   fri_fold_kernel                          fri_fold 2^1, 2^10, 2^17, edge betas
   fri_fold_k (arities 2 .. 16)             fri_fold_k 2^12 x arities 2, 4, 8, 16 and 2^16 x 16
