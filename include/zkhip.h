@@ -276,6 +276,27 @@ int zkhip_fri_fold(zkhip_ctx* ctx, const uint32_t* d_in, int log_h,
 int zkhip_fri_fold_k(zkhip_ctx* ctx, const uint32_t* d_in, int log_h, int log_arity,
                      const uint32_t beta[4] /* host, Montgomery */, uint32_t* d_out);
 
+/* zkhip_fri_fold_k with the challenge read from DEVICE memory (d_beta: 4 Montgomery words), as the prover's commit phase folds: launch j squares
+ * the challenge j times itself.  d_add (device, may be NULL): 2^(log_h - log_arity) extension elements added to the result (a shorter chip's
+ * reduced openings joining the vector).  Device pointers are 16-byte aligned. */
+int zkhip_fri_fold_k_dev(zkhip_ctx* ctx, const uint32_t* d_in, int log_h, int log_arity, const uint32_t* d_beta,
+                         const uint32_t* d_add, uint32_t* d_out);
+/* the FRI input of one chip on caller-supplied data (all device words Montgomery, rows = 2^log_rows, row p of a matrix at p * pitch):
+ *   out[p] (+)= off_loc d1 (A_T - y_loc) + off_next d2 (A_T - y_next) + [off_pl d1 (A_P - y_pl) + off_pn d2 (A_P - y_pn)] + off_q d1 (A_Q - y_q),
+ *   A_M = sum_j weights[j] M[p][j], d1 = dinv[p], d2 = dinv[rows + p].
+ * d_weights: [n_weights][4] extension weights (the prover passes powers of the FRI alpha), n_weights >= every width; d_dinv: [2][rows][4];
+ * scalars (host): y_loc, y_next, y_pl, y_pn, y_q, off_next, off_pl, off_pn, off_q, off_loc, four words each; p_width 0: no permutation block
+ * (d_plde may be NULL); q_width 0, 8 or 16; accumulate 0 writes d_out[rows][4] without reading it, 1 adds to it.  forms[0], forms[1] (host) receive
+ * the row-sum kernel taken for the trace and the permutation block: 0 the generic one, 1..4 the register form with that many column quads per
+ * lane, -1 not run.  Widths and pitches are multiples of 4, pitch >= width, device pointers 16-byte aligned; anything else is ZKHIP_ERR_INVALID. */
+int zkhip_reduced_opening(zkhip_ctx* ctx, const uint32_t* d_tlde, size_t t_ld, uint32_t width, const uint32_t* d_plde, size_t p_ld,
+                          uint32_t p_width, const uint32_t* d_qlde, size_t q_ld, uint32_t q_width, int log_rows, const uint32_t* d_weights,
+                          size_t n_weights, const uint32_t* d_dinv, const uint32_t scalars[40], int accumulate, uint32_t* d_out, int forms[2]);
+/* one launch of the proof-of-work search: *result (host, in/out) = min(*result, smallest canonical w in [base, base + count) whose sponge output
+ * has `bits` low zero bits), 0xFFFFFFFF meaning none yet.  state: the 16 Montgomery words of the sponge with the pending inputs written to
+ * words [0, slot); the candidate goes to word `slot` (0..7).  Candidates >= p are never hits.  bits in [0, 31], count > 0. */
+int zkhip_grind(zkhip_ctx* ctx, const uint32_t state[16], int slot, int bits, uint32_t base, uint32_t count, uint32_t* result);
+
 /* ---- whole shard ---- */
 size_t zkhip_proof_size(int log_n, uint32_t width, const zkhip_params* prm, size_t n_public);
 /* d_trace: 2^log_n x width AIR trace (Montgomery).  public_values: host, canonical.

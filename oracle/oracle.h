@@ -154,6 +154,12 @@ void orc_fri_fold(const uint32_t* in, int log_h, const uint32_t beta[4], uint32_
 /* fold of arity 2^log_arity (<= 64), definition by interpolation; out has 2^(log_h-log_arity) entries */
 void orc_fri_fold_k(const uint32_t* in, int log_h, int log_arity, const uint32_t beta[4], uint32_t* out);
 
+/* FRI input (alpha-batched reduced openings) of one chip on caller-supplied matrices, weights [n][4], denominators dinv [2][2^log_rows][4]
+ * and ten extension scalars (y_loc, y_next, y_pl, y_pn, y_q, off_next, off_pl, off_pn, off_q, off_loc): step 4 of orc_prove_shard, which calls it. */
+void orc_reduced_opening(const uint32_t* tlde, size_t t_ld, size_t width, const uint32_t* plde, size_t p_ld, size_t p_width,
+                         const uint32_t* qlde, size_t q_ld, size_t q_width, int log_rows, const uint32_t* weights, const uint32_t* dinv,
+                         const uint32_t scalars[40], int accumulate, uint32_t* out);
+
 /* full shard proof; returns bytes written (0 on error); proof layout: DESIGN.md. */
 size_t orc_proof_size(int log_n, size_t width, const orc_params_t* prm, size_t n_public);
 size_t orc_prove_shard(const uint32_t* trace, int log_n, size_t width,

@@ -493,6 +493,35 @@ void orc__copy_path(uint32_t* pf, size_t* pos, const uint32_t* tree, size_t leav
     for (int k = 0; k < levels; k++) { memcpy(pf + *pos, lvl + 8 * (idx ^ 1), 32); *pos += 8; lvl += 8 * cnt; cnt >>= 1; idx >>= 1; }
 }
 
+/* The FRI input of one chip on caller-supplied data (rows = 2^log_rows, row p of a matrix at p * pitch):
+ *   out[p] (+)= off_loc d1 (A_T - y_loc) + off_next d2 (A_T - y_next) + [off_pl d1 (A_P - y_pl) + off_pn d2 (A_P - y_pn)] + off_q d1 (A_Q - y_q),
+ *   A_M = sum_j weights[j] M[p][j], d1 = dinv[p], d2 = dinv[rows + p];
+ * scalars: y_loc, y_next, y_pl, y_pn, y_q, off_next, off_pl, off_pn, off_q, off_loc.  p_width 0: no permutation terms; q_width 0: A_Q = 0. */
+void orc_reduced_opening(const uint32_t* tlde, size_t t_ld, size_t width, const uint32_t* plde, size_t p_ld, size_t p_width,
+                         const uint32_t* qlde, size_t q_ld, size_t q_width, int log_rows, const uint32_t* weights, const uint32_t* dinv,
+                         const uint32_t scalars[40], int accumulate, uint32_t* out) {
+    const size_t rows = (size_t)1 << log_rows;
+    const bb4_t* w = (const bb4_t*)weights;
+    const bb4_t y_loc = ld4(scalars), y_nxt = ld4(scalars + 4), y_pl = ld4(scalars + 8), y_pn = ld4(scalars + 12), y_q = ld4(scalars + 16);
+    const bb4_t off_next = ld4(scalars + 20), off_pl = ld4(scalars + 24), off_pn = ld4(scalars + 28), off_q = ld4(scalars + 32), off_loc = ld4(scalars + 36);
+#pragma omp parallel for schedule(static)
+    for (size_t p = 0; p < rows; p++) {
+        bb4_t d1 = ld4(dinv + 4 * p), d2 = ld4(dinv + 4 * (rows + p));
+        bb4_t at = row_dot(w, tlde + p * t_ld, width);
+        bb4_t aq = q_width ? row_dot(w, qlde + p * q_ld, q_width) : bb4_zero();
+        bb4_t r = bb4_mul(off_loc, bb4_mul(bb4_sub(at, y_loc), d1));
+        r = bb4_add(r, bb4_mul(off_next, bb4_mul(bb4_sub(at, y_nxt), d2)));
+        if (p_width) {
+            bb4_t ap = row_dot(w, plde + p * p_ld, p_width);
+            r = bb4_add(r, bb4_mul(off_pl, bb4_mul(bb4_sub(ap, y_pl), d1)));
+            r = bb4_add(r, bb4_mul(off_pn, bb4_mul(bb4_sub(ap, y_pn), d2)));
+        }
+        r = bb4_add(r, bb4_mul(off_q, bb4_mul(bb4_sub(aq, y_q), d1)));
+        if (accumulate) r = bb4_add(r, ld4(out + 4 * p));
+        st4(out + 4 * p, r);
+    }
+}
+
 size_t orc_prove_shard(const uint32_t* trace, int log_n, size_t width,
                        const uint32_t* public_values, size_t n_public,
                        const orc_params_t* prm, uint8_t* proof_bytes, size_t cap) {
@@ -639,24 +668,18 @@ size_t orc_prove_shard(const uint32_t* trace, int log_n, size_t width,
           off_q = bb4_pow(fa, 2 * width + 2 * wp);
     bb4_t* cur = (bb4_t*)malloc(m * sizeof(bb4_t));
     {
+        bb4_t* dinv = (bb4_t*)malloc(2 * m * sizeof(bb4_t));           /* [2][m]: 1/(x - zeta), 1/(x - zeta_next) */
         bb_t wm = bb_two_adic_generator(H);
 #pragma omp parallel for schedule(static)
         for (size_t p = 0; p < m; p++) {
             bb_t x = bb_mul(BB_GEN, bb_pow(wm, bb_reverse_bits((uint32_t)p, H)));
-            bb4_t d1 = bb4_inv(bb4_neg(bb4_sub_base(zeta, x)));        /* 1/(x - zeta) */
-            bb4_t d2 = bb4_inv(bb4_neg(bb4_sub_base(zeta_next, x)));
-            bb4_t at = row_dot(fapow, tlde + p * width, width);
-            bb4_t aq = row_dot(fapow, qlde + p * QW, QW);
-            bb4_t r = bb4_mul(bb4_sub(at, y_loc), d1);
-            r = bb4_add(r, bb4_mul(off_next, bb4_mul(bb4_sub(at, y_nxt), d2)));
-            if (Q) {
-                bb4_t ap = row_dot(fapow, plde + p * wp, wp);
-                r = bb4_add(r, bb4_mul(off_pl, bb4_mul(bb4_sub(ap, y_pl), d1)));
-                r = bb4_add(r, bb4_mul(off_pn, bb4_mul(bb4_sub(ap, y_pn), d2)));
-            }
-            r = bb4_add(r, bb4_mul(off_q, bb4_mul(bb4_sub(aq, y_q), d1)));
-            cur[p] = r;
+            dinv[p] = bb4_inv(bb4_neg(bb4_sub_base(zeta, x)));
+            dinv[m + p] = bb4_inv(bb4_neg(bb4_sub_base(zeta_next, x)));
         }
+        const bb4_t sc[10] = {y_loc, y_nxt, y_pl, y_pn, y_q, off_next, off_pl, off_pn, off_q, bb4_one()};
+        orc_reduced_opening(tlde, width, width, Q ? plde : NULL, wp, wp, qlde, QW, QW, H, (const uint32_t*)fapow, (const uint32_t*)dinv,
+                            (const uint32_t*)sc, 0, (uint32_t*)cur);
+        free(dinv);
     }
     free(fapow);
 

@@ -265,6 +265,28 @@ def fri_fold_k(vals, log_arity, beta):
     return out
 
 
+def _mat_view(a):
+    """(pointer, pitch in words, width) of a 2-D uint32 array or of a column slice of one (rows `pitch` words apart)"""
+    assert a.dtype == np.uint32 and a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0
+    return C.cast(a.ctypes.data, u32p), a.strides[0] // 4, a.shape[1]
+
+
+def reduced_opening(tlde, plde, qlde, weights, dinv, scalars, accumulate=0, out=None):
+    """orc_reduced_opening: the FRI input of one chip.  tlde / plde / qlde: [rows][w] arrays or column-slice views (plde, qlde None: absent);
+    weights [n][4]; dinv [2][rows][4]; scalars [10][4] (y_loc, y_next, y_pl, y_pn, y_q, off_next, off_pl, off_pn, off_q, off_loc);
+    out: the [rows][4] vector added to when accumulate is set.  Returns the result, the argument arrays unchanged."""
+    rows = tlde.shape[0]
+    tp, t_ld, w = _mat_view(tlde)
+    pp, p_ld, pw = _mat_view(plde) if plde is not None else (None, 0, 0)
+    qp, q_ld, qw = _mat_view(qlde) if qlde is not None else (None, 0, 0)
+    wt, dv, sc = _u32(weights), _u32(dinv), _u32(scalars)
+    assert wt.size >= 4 * max(w, pw, qw) and dv.size == 8 * rows and sc.size == 40
+    res = np.zeros((rows, 4), dtype=np.uint32) if out is None else _u32(out).reshape(rows, 4).copy()
+    lib().orc_reduced_opening(tp, C.c_size_t(t_ld), C.c_size_t(w), pp, C.c_size_t(p_ld), C.c_size_t(pw), qp, C.c_size_t(q_ld), C.c_size_t(qw),
+                              C.c_int(rows.bit_length() - 1), _p(wt), _p(dv), _p(sc), C.c_int(int(accumulate)), _p(res))
+    return res
+
+
 def default_params(log_blowup=1, num_queries=100, pow_bits=16, logup_pairs=0, log_fold=0, log_final=0, hash_width=0, code_width=0):
     return Params(log_blowup, num_queries, pow_bits, logup_pairs, log_fold, log_final, hash_width, code_width)
 

@@ -42,6 +42,13 @@ ntt_small.hip, ntt_fused.hip, hash.hip, stark.hip, hal.hip):
   inv_denominators, open_partial*, final   open_at 2^10 x 20 and 2^12 x 64, two edge points
   fri_fold_kernel                          fri_fold 2^1, 2^10, 2^17, edge betas
   fri_fold_k (arities 2 .. 16)             fri_fold_k 2^12 x arities 2, 4, 8, 16 and 2^16 x 16
+  rowdot_regs_kernel<1..4>, rowdot_kernel  test_gpu_reduced_edges.py (reduced_opening; its own table of which case takes which form, checked
+                                           against the form the library reports)
+  reduced_combine_kernel                   test_gpu_reduced_edges.py: every reduced_opening case (p_width 0 / 8 / 260, q_width 0 / 8 / 16,
+                                           accumulate 0 / 1, dense and [pre | main] rows)
+  fri_fold_dev_kernel, ext_add_kernel      test_gpu_reduced_edges.py: fri_fold_k_dev 2^1, 2^4, 2^9, 2^12 x arities 2 .. 16, edge betas in
+                                           device memory, with and without the added vector
+  grind_kernel                             test_gpu_reduced_edges.py: grind, slots 0 .. 7, bits 0 .. 10, windows around the witness and up to P
   hal_add / hal_sum_ext                    eltwise_add, eltwise_sum_ext
   hal_zk_shift(_scalar)                    zk_shift with shift P - 1 and edge shifts
   hal_mix_* (plan, sorted, register)       mix_poly_coeffs on the shapes of test_gpu_hal.py that pick each form

@@ -21,7 +21,8 @@ EXPORTS = [
     "zkhip_memcpy_d2h", "zkhip_to_monty", "zkhip_from_monty", "zkhip_fill_uniform", "zkhip_gen_trace",
     "zkhip_gen_trace_logup", "zkhip_gen_trace_logup_cross", "zkhip_perm_trace",
     "zkhip_dft", "zkhip_coset_lde", "zkhip_ntt_pass", "zkhip_poseidon2_permute", "zkhip_hash_rows",
-    "zkhip_merkle_commit", "zkhip_merkle_commit_mixed", "zkhip_merkle_commit_p24_colmajor", "zkhip_batch_interpolate_colmajor", "zkhip_batch_expand_colmajor", "zkhip_quotient_values", "zkhip_open_at", "zkhip_fri_fold", "zkhip_fri_fold_k",
+    "zkhip_merkle_commit", "zkhip_merkle_commit_mixed", "zkhip_merkle_commit_p24_colmajor", "zkhip_batch_interpolate_colmajor", "zkhip_batch_expand_colmajor", "zkhip_quotient_values", "zkhip_open_at", "zkhip_fri_fold", "zkhip_fri_fold_k", "zkhip_fri_fold_k_dev",
+    "zkhip_reduced_opening", "zkhip_grind",
     "zkhip_commit", "zkhip_proof_size", "zkhip_prove_shard", "zkhip_prove_shard_host", "zkhip_prove_shards", "zkhip_prove_shards_multi", "zkhip_shard_device", "zkhip_release_cached_contexts", "zkhip_prove_segment", "zkhip_verify_shard", "zkhip_last_prove_debug",
     "zkhip_chips_proof_size", "zkhip_prove_chips", "zkhip_verify_chips", "zkhip_request_digest",
     "zkhip_eltwise_add", "zkhip_eltwise_copy", "zkhip_eltwise_zeroize", "zkhip_eltwise_sum_ext", "zkhip_zk_shift", "zkhip_mix_poly_coeffs",
@@ -157,6 +158,10 @@ def load():
     L.zkhip_open_at.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, u32p, C.c_int, u32p]
     L.zkhip_fri_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, u32p, C.c_void_p]
     L.zkhip_fri_fold_k.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, u32p, C.c_void_p]
+    L.zkhip_fri_fold_k_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zkhip_reduced_opening.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                        C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, u32p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    L.zkhip_grind.argtypes = [C.c_void_p, u32p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, u32p]
     L.zkhip_proof_size.restype = C.c_size_t
     L.zkhip_proof_size.argtypes = [C.c_int, C.c_uint32, C.POINTER(Params), C.c_size_t]
     L.zkhip_prove_shard.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t,

@@ -325,6 +325,8 @@ struct ReducedArgs {
 };
 // scratch_at: [2][rows] ext workspace for the per-row alpha-dots of the trace / permutation matrices
 hipError_t launch_reduced_opening(const ReducedArgs& a, uint32_t* scratch_at, hipStream_t s);
+// the row-dot kernel launch_reduced_opening takes for a matrix of this shape: 1..4 = rowdot_regs_kernel<NK>, 0 = rowdot_kernel
+int rowdot_form(uint32_t width, uint64_t rows);
 
 struct PermArgs {
     const uint32_t* trace; uint64_t ld;     // main trace (natural rows), Montgomery

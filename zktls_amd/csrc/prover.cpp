@@ -527,6 +527,81 @@ int zkhip_fri_fold_k(zkhip_ctx* ctx, const uint32_t* d_in, int log_h, int log_ar
     return ZKHIP_OK;
 }
 
+// zkhip_fri_fold_k with the challenge in device memory: the launches of one layer of fri_commit_phase (fri_fold_dev_kernel with j squarings, then
+// ext_add_kernel where a shorter chip's vector joins)
+int zkhip_fri_fold_k_dev(zkhip_ctx* ctx, const uint32_t* d_in, int log_h, int log_arity, const uint32_t* d_beta, const uint32_t* d_add, uint32_t* d_out) {
+    CHECK_CTX(ctx);
+    if (!d_in || !d_out || !d_beta || log_arity < 1 || log_arity > 6 || log_h < log_arity || log_h > MAX_LOG_ROWS + 3)
+        return fail(ZKHIP_ERR_INVALID, "fri_fold_k_dev: bad arguments");
+    if (((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_beta) | reinterpret_cast<uintptr_t>(d_add)) & 15u) != 0)
+        return fail(ZKHIP_ERR_INVALID, "fri_fold_k_dev: pointers must be 16-byte aligned");
+    ZK_TRY(ensure_fold_table(ctx, log_h));
+    void* tmp;
+    ZK_TRY(ctx_reserve(ctx, S_PARTIAL, ((size_t)1 << log_h) * 16, &tmp));
+    uint32_t* ping = (uint32_t*)tmp;
+    uint32_t* pong = ping + ((size_t)2 << log_h);          // second half of the scratch
+    const uint32_t* src = d_in;
+    for (int j = 0; j < log_arity; j++) {
+        uint32_t* dst = (j == log_arity - 1) ? d_out : ((j & 1) ? pong : ping);
+        ZK_HIP(launch_fri_fold_dev(src, dst, ctx->dom_itw, (uint64_t)1 << (log_h - j - 1), d_beta, j, ctx->stream));
+        src = dst;
+    }
+    if (d_add) ZK_HIP(launch_ext_add(d_out, d_add, (uint64_t)1 << (log_h - log_arity), ctx->stream));
+    return ZKHIP_OK;
+}
+
+// exactly launch_reduced_opening on the caller's matrices, weights, denominators and scalars
+int zkhip_reduced_opening(zkhip_ctx* ctx, const uint32_t* d_tlde, size_t t_ld, uint32_t width, const uint32_t* d_plde, size_t p_ld, uint32_t p_width,
+                          const uint32_t* d_qlde, size_t q_ld, uint32_t q_width, int log_rows, const uint32_t* d_weights, size_t n_weights,
+                          const uint32_t* d_dinv, const uint32_t scalars[40], int accumulate, uint32_t* d_out, int forms[2]) {
+    CHECK_CTX(ctx);
+    if (!d_tlde || !d_weights || !d_dinv || !scalars || !d_out || !forms || (p_width && !d_plde) || (q_width && !d_qlde))
+        return fail(ZKHIP_ERR_INVALID, "reduced_opening: null pointer");
+    if (log_rows < 1 || log_rows > MAX_LOG_ROWS + 3) return fail(ZKHIP_ERR_INVALID, "reduced_opening: log_rows in [1, 25]");
+    if (width == 0 || width % 4 || t_ld % 4 || t_ld < width || p_width % 4 || (p_width && (p_ld % 4 || p_ld < p_width)) ||
+        (q_width != 0 && q_width != 8 && q_width != 16) || (q_width && (q_ld % 4 || q_ld < q_width)))
+        return fail(ZKHIP_ERR_INVALID, "reduced_opening: widths and pitches are multiples of 4, pitch >= width, q_width 0, 8 or 16");
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_tlde) | reinterpret_cast<uintptr_t>(d_weights) | reinterpret_cast<uintptr_t>(d_dinv) |
+                           reinterpret_cast<uintptr_t>(d_out) | (p_width ? reinterpret_cast<uintptr_t>(d_plde) : 0) | (q_width ? reinterpret_cast<uintptr_t>(d_qlde) : 0);
+    if (ptrs & 15u) return fail(ZKHIP_ERR_INVALID, "reduced_opening: device pointers must be 16-byte aligned");
+    size_t need = width > q_width ? width : q_width;
+    if (p_width > need) need = p_width;
+    if (n_weights < need) return fail(ZKHIP_ERR_INVALID, "reduced_opening: the weight table is shorter than the widest matrix");
+    ReducedArgs ra{};
+    ra.tlde = d_tlde; ra.t_ld = t_ld; ra.width = width;
+    ra.qlde = q_width ? d_qlde : nullptr; ra.q_ld = q_ld; ra.q_width = q_width;
+    ra.plde = p_width ? d_plde : nullptr; ra.p_ld = p_ld; ra.p_width = p_width;
+    ra.rows = (uint64_t)1 << log_rows;
+    ra.alpha_pow = d_weights; ra.dinv = d_dinv;
+    Ext* const sc[10] = {&ra.y_loc, &ra.y_next, &ra.y_pl, &ra.y_pn, &ra.y_q, &ra.off_next, &ra.off_pl, &ra.off_pn, &ra.off_q, &ra.off_loc};
+    for (int k = 0; k < 10; k++) memcpy(sc[k]->c, scalars + 4 * k, 16);
+    ra.accumulate = accumulate ? 1 : 0; ra.out = d_out;
+    void* v_at;
+    ZK_TRY(ctx_reserve(ctx, S_PARTIAL, 2 * ra.rows * 16, &v_at));
+    forms[0] = rowdot_form(width, ra.rows);
+    forms[1] = p_width ? rowdot_form(p_width, ra.rows) : -1;
+    ZK_HIP(launch_reduced_opening(ra, (uint32_t*)v_at, ctx->stream));
+    return ZKHIP_OK;
+}
+
+// one launch_grind over [base, base + count) on the caller's sponge state
+int zkhip_grind(zkhip_ctx* ctx, const uint32_t state[16], int slot, int bits, uint32_t base, uint32_t count, uint32_t* result) {
+    CHECK_CTX(ctx);
+    if (!state || !result || slot < 0 || slot > 7 || bits < 0 || bits > 31 || count == 0)
+        return fail(ZKHIP_ERR_INVALID, "grind: slot in [0, 7], bits in [0, 31], count > 0");
+    if ((uint64_t)base + (((uint64_t)count + 255) & ~(uint64_t)255) > ((uint64_t)1 << 32))
+        return fail(ZKHIP_ERR_INVALID, "grind: the window (rounded up to 256 candidates) passes 2^32");
+    GrindArgs ga{};
+    for (int i = 0; i < 16; i++) ga.state[i] = state[i];
+    ga.slot = slot;
+    ga.mask = (1u << bits) - 1u;
+    void* v_res;
+    ZK_TRY(ctx_reserve(ctx, S_GATHER_OUT, 4, &v_res));
+    ZK_TRY(h2d(ctx, v_res, result, 4));
+    ZK_HIP(launch_grind(ga, base, count, (uint32_t*)v_res, ctx->stream));
+    return d2h(ctx, result, v_res, 4);
+}
+
 // 8 canonical words binding (input, program): overwrite-mode Poseidon2 sponge over 3-byte limbs, both fields length-prefixed,
 // domain-separated by "ZKT".  Host only (no device needed): the glue on either side of the FFI derives the same public values.
 int zkhip_request_digest(const uint8_t* input, size_t input_len, const uint8_t* program, size_t program_len, uint32_t out[8]) {

@@ -1176,14 +1176,22 @@ struct reduced_combine_kernel_bargs { ReducedArgs a; const uint32_t* at_in; cons
 __global__ void __launch_bounds__(256) reduced_combine_kernel_batch(const reduced_combine_kernel_bargs* __restrict__ zk_arr) { const reduced_combine_kernel_bargs& zk_b = zk_arr[blockIdx.z]; reduced_combine_kernel_body(zk_b.a, zk_b.at_in, zk_b.ap_in); }
 
 static int lanes_for(uint32_t width) { int g = (int)(width / 4), l = 1; while (l < g && l < 16) l <<= 1; return l; }
-static hipError_t launch_rowdot(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* alpha_pow, uint32_t* out_at, hipStream_t s) {
+// which kernel a row-dot of this shape takes: 1..4 = rowdot_regs_kernel<NK>, 0 = rowdot_kernel.  launch_rowdot switches on this value, so what
+// zkhip_reduced_opening reports (prover.cpp) is what was launched.
+int rowdot_form(uint32_t width, uint64_t rows) {
     const int L = lanes_for(width);
     const uint32_t nq = width / 4;
     const int nk = (int)((nq + L - 1) / L);
     const uint64_t rows_per_wg = (uint64_t)(256 / L) * ROWDOT_TRIPS;
-    if (nk <= 4 && rows % (256 / L) == 0 && rows >= rows_per_wg) {
+    return (nk >= 1 && nk <= 4 && rows % (256 / L) == 0 && rows >= rows_per_wg) ? nk : 0;
+}
+static hipError_t launch_rowdot(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* alpha_pow, uint32_t* out_at, hipStream_t s) {
+    const int L = lanes_for(width);
+    const int form = rowdot_form(width, rows);
+    if (form) {
+        const uint64_t rows_per_wg = (uint64_t)(256 / L) * ROWDOT_TRIPS;
         const dim3 grid((unsigned)((rows + rows_per_wg - 1) / rows_per_wg)), block(256);
-        switch (nk) {
+        switch (form) {
             case 1: ZK_LAUNCH(rowdot_regs_kernel<1>, rowdot_regs_kernel_batch<1>, rowdot_regs_kernel_bargs, grid, block, 0, s, mat, ld, width, rows, L, alpha_pow, out_at); break;
             case 2: ZK_LAUNCH(rowdot_regs_kernel<2>, rowdot_regs_kernel_batch<2>, rowdot_regs_kernel_bargs, grid, block, 0, s, mat, ld, width, rows, L, alpha_pow, out_at); break;
             case 3: ZK_LAUNCH(rowdot_regs_kernel<3>, rowdot_regs_kernel_batch<3>, rowdot_regs_kernel_bargs, grid, block, 0, s, mat, ld, width, rows, L, alpha_pow, out_at); break;

@@ -317,6 +317,33 @@ class Context:
         check(self.lib.zkhip_fri_fold_k(self.handle, C.c_void_p(src.ptr), log_h, log_arity, b.ctypes.data_as(u32p), C.c_void_p(out.ptr)))
         return out
 
+    def fri_fold_k_dev(self, src, log_h, log_arity, beta, add=None, out=None):
+        """fri_fold_k with the challenge in device memory (beta: a buffer of 4 words), as the prover's commit phase folds; add: a device vector added to the result"""
+        out = out or self.alloc(4 << (log_h - log_arity))
+        check(self.lib.zkhip_fri_fold_k_dev(self.handle, C.c_void_p(src.ptr), log_h, log_arity, C.c_void_p(beta.ptr),
+                                            C.c_void_p(add.ptr) if add is not None else None, C.c_void_p(out.ptr)))
+        return out
+
+    def reduced_opening(self, tlde, t_ld, width, log_rows, weights, n_weights, dinv, scalars, out, plde=None, p_ld=0, p_width=0,
+                        qlde=None, q_ld=0, q_width=0, accumulate=0):
+        """the FRI input of one chip on the caller's device data (zkhip_reduced_opening); scalars: [10][4] canonical, in the header's order; matrices, weights,
+        dinv and out are buffers or views (or raw addresses); returns the row-sum forms taken for (trace, permutation) block"""
+        def addr(b):
+            return None if b is None else C.c_void_p(getattr(b, "ptr", b))
+        sc = to_monty(np.ascontiguousarray(scalars, dtype=np.uint32).reshape(40))
+        forms = (C.c_int * 2)(-2, -2)
+        check(self.lib.zkhip_reduced_opening(self.handle, addr(tlde), t_ld, width, addr(plde), p_ld, p_width, addr(qlde), q_ld, q_width, log_rows,
+                                             addr(weights), n_weights, addr(dinv), sc.ctypes.data_as(u32p), int(accumulate), addr(out), forms))
+        return forms[0], forms[1]
+
+    def grind(self, state, slot, bits, base, count, result=0xFFFFFFFF):
+        """one launch of the proof-of-work search over [base, base + count); state: 16 canonical words of the sponge with the pending inputs in [0, slot);
+        returns min(result, the smallest hit), 0xFFFFFFFF for none"""
+        st = to_monty(np.ascontiguousarray(state, dtype=np.uint32).reshape(16))
+        res = C.c_uint32(result)
+        check(self.lib.zkhip_grind(self.handle, st.ctypes.data_as(u32p), int(slot), int(bits), int(base), int(count), C.byref(res)))
+        return res.value
+
     def commit(self, trace, log_n, width, log_blowup=1, hash_width=16):
         """coset LDE + Merkle tree + root in one call; returns (lde, tree, root[8] canonical)"""
         h = log_n + log_blowup
@@ -1348,6 +1375,11 @@ def recursion_witnesses_on_host(enable):
 def set_lockstep(max_batch, lanes=0):
     """zkhip_set_lockstep: members per lock-step batch of small transcripts (0 / 1 = off), batches in flight per device (0 = keep)"""
     _lib.load().zkhip_set_lockstep(int(max_batch), int(lanes))
+
+
+def set_fri_graph(on):
+    """zkhip_set_fri_graph: 1 (the default) replays the FRI commit phase as one captured graph per proof, 0 enqueues its launches one by one (a debugging switch)"""
+    _lib.load().zkhip_set_fri_graph(1 if on else 0)
 
 
 def lockstep_stats():
