@@ -284,6 +284,55 @@ int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int 
 int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
                                const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
+/* ---- the same check with the REDUCED OPENINGS computed in-circuit: the fold-16 OPENINGS machine (ROWSUM16 and QUERY16 chips).  40 public values: the 8 capacity
+ * words of the indices machine, then fa, zeta, zeta g_N, YL, YN, YQ, OFFN = fa^W, OFFQ = fa^(2W), four words each (W = the inner proof's trace width; YL / YN / YQ =
+ * the fa-weighted sums of the values opened at zeta, at zeta g_N, and of the quotient chunks).  The key commits the layer roots, the final coefficients and, by
+ * query number, the opened trace row (W words) and quotient row (8 words): IT HOLDS NO REDUCED OPENING, no index and no challenge.  Statement: everything the
+ * indices machine states, and "the value at which query q enters layer 0 is (AT_q - YL) / (x - zeta) + OFFN (AT_q - YN) / (x - zeta g) + OFFQ (AQ_q - YQ) / (x - zeta),
+ * AT_q = sum_j fa^j t_{q,j} and AQ_q = sum_j fa^j u_{q,j} over the rows listed for query number q, x = g w_{2^H}^bitrev_H(index_q) at the index DRAWN for q".
+ * THE EIGHT CONSTANTS ARE PUBLIC IN THIS STEP (as beta was public in zkhip_prove_fri16 before the transcript came in): nothing in this machine ties them to the
+ * inner proof's transcript or opened values; bringing them in over buses is a later step.
+ * Ten tables, tallest first (equal heights by table number): 0 FOLD16C = FOLD16B plus the column XQ = X sum_j O_j w_16^bitrev(j, 4) (one constraint on every row; three
+ * unused cells keep the width a multiple of four), whose send on a chain's first row is (IDX, XQ, OWN[4]); 1 FINAL, 2 P24L, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES: the
+ * indices machine's word for word but the public-value count in the header; 3 QUERY16 where QUERIES stood, one row per query number: preprocessed (q, active), main
+ * IDX XQ RO AT AQ I1 I2 P1 P2 P2O P3 P3O and the seven constants, each tied to its public value on every row; receives (q, IDX) from SAMPLES, (IDX, XQ, RO) from
+ * FOLD16C's first rows, (q, AT) and (q, AQ) from ROWSUM16; 8 ROWSUM16, one row per 8 words of an opened row (per query the trace blocks from the last to the first,
+ * then the quotient block): main V[8] ACCIN[4] T[8][4] FA[4], preprocessed (tag = 2 q + tree, active, not-first, last-of-trace, last-of-quotient, q, K0 = 2 block,
+ * K1 = K0 + 1); sends (tag, K0, V0..V3) and (tag, K1, V4..V7) to ROWS, (q, T_0) to QUERY16 on a trace's block 0 and on the quotient block; 9 ROWS, preprocessed
+ * (tag, K, w0..w3, 1): one row per 4-word group of every opened row, in the tuple form in which P24L's sponge rows receive theirs -- the table a width-24 chip
+ * variant on the same bus replaces.  Heights: ROWSUM16 lg(Q (W / 8 + 1)), ROWS lg(Q (W + 8) / 4), QUERY16 lg(Q), at least 2^5.  Shapes: the indices machine's, W a
+ * multiple of 8 in 8 .. 1024, inner proofs without lookup pairs and with a quotient row of 8 words.
+ * zkhip_fri16_view_openings (host only; fails like zkhip_fri16_view_shard; refuses proofs with lookup pairs; takes version-8 group-order proofs): per query the
+ * trace row [Q][W] and the quotient row [Q][8] as the proof holds them, and the 32 constant words.  zkhip_fri16_openings_describe / _key_host (no GPU) / _key /
+ * _proof_size: as the _indices_ entries, with the trace width behind inner_pow_bits; the key takes the rows where the indices machine's took the reduced openings.
+ * zkhip_fri16_openings_gen_traces: the ROWSUM16 and QUERY16 main traces on the device (dense: [2^lr][48] and [2^lr][72], 16-byte aligned) from raw rows, constants
+ * and indices alone, one launch; openings [Q][4] receives the reduced openings (canonical).  zkhip_prove_fri16_openings takes the indices machine's view, the rows
+ * and the constants, and refuses before anything is proven, each with a message that names the query: everything zkhip_prove_fri16_indices refuses, a reduced
+ * opening computed from the rows (on the device) that differs from the view's `values`, a query point with x = zeta or x = zeta g, and constants that do not
+ * match each other (zeta g_N, fa^W, fa^(2W)).  zkhip_verify_fri16_openings is host only: shape, W, inner_pow_bits, the 40 public values, the key.
+ * STILL OUTSIDE after this machine: the Merkle paths of the trace and quotient rows, the transcript before the commit phase (so the eight constants), lookups, the
+ * AIR identity at zeta; the shard verifier machines (shard_verifier.inl) do not use these chips. */
+int zkhip_fri16_view_openings(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                              uint32_t* trace_rows, uint32_t* quotient_rows, uint32_t constants[32]);
+size_t zkhip_fri16_openings_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
+                                     size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_openings_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
+                                  const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_openings_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             const uint32_t* final_poly, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm,
+                             zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_openings_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm);
+int zkhip_fri16_openings_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
+                                    const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* indices, uint32_t* d_rowsum, uint32_t* d_query,
+                                    uint32_t* openings);
+int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness,
+                               const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const zkhip_params* prm, uint8_t* proof, size_t cap,
+                               size_t* len);
+int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason);
+
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */
 int zkhip_air_synthetic(uint32_t width, size_t n_public, uint32_t* out, size_t cap, size_t* words);

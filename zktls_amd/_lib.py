@@ -55,6 +55,8 @@ EXPORTS = [
     "zkhip_verify_fri16_paths",
     "zkhip_fri16_view_transcript", "zkhip_fri16_indices_describe", "zkhip_fri16_indices_key_host", "zkhip_fri16_indices_key", "zkhip_fri16_indices_proof_size",
     "zkhip_fri16_indices_gen_traces", "zkhip_fri16_samples_gen_trace", "zkhip_prove_fri16_indices", "zkhip_verify_fri16_indices",
+    "zkhip_fri16_view_openings", "zkhip_fri16_openings_describe", "zkhip_fri16_openings_key_host", "zkhip_fri16_openings_key", "zkhip_fri16_openings_proof_size",
+    "zkhip_fri16_openings_gen_traces", "zkhip_prove_fri16_openings", "zkhip_verify_fri16_openings",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -376,6 +378,20 @@ def load():
     L.zkhip_prove_fri16_indices.argtypes = [C.c_void_p, C.c_void_p] + fri16_ishape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, C.POINTER(Params), u8p,
                                                                                       C.c_size_t, szp]
     L.zkhip_verify_fri16_indices.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
+    # the fold-16 openings machine: the reduced openings in-circuit (the shape also names the inner proof's trace width)
+    L.zkhip_fri16_view_openings.argtypes = [u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), u32p, u32p, u32p]
+    L.zkhip_fri16_openings_describe.restype = C.c_size_t
+    L.zkhip_fri16_openings_describe.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_int, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    fri16_oshape = fri16_ishape + [C.c_uint32]                                                     # ..., inner pow bits, trace width
+    L.zkhip_fri16_openings_key_host.argtypes = fri16_oshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), u32p]    # final_poly, trace rows, quotient rows, roots
+    L.zkhip_fri16_openings_key.argtypes = [C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_openings_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_openings_proof_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(Params)]
+    L.zkhip_fri16_openings_gen_traces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, u32p, u32p, u32p, u32p, C.c_void_p, C.c_void_p, u32p]
+    L.zkhip_prove_fri16_openings.argtypes = [C.c_void_p, C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
+                                                                                        C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16_openings.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

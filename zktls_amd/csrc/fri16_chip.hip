@@ -29,6 +29,9 @@
 // The INDICES machine (last; zkhip_prove_fri16_indices) is the paths machine with the Fiat-Shamir transcript inside: a transcript-only width-16 Poseidon2 table (P2T)
 // walks the duplex challenger from the commit phase on, the SAMPLES chip of fri_chip.hip takes the bits of the words it hands out; the challenges reach FOLD16 over a
 // bus and the key holds neither a challenge nor an index (tests/fri16_transcript_air.py).
+// The OPENINGS machine (zkhip_prove_fri16_openings) is the indices machine with the reduced openings computed in-circuit: ROWSUM16 sums the opened trace row and quotient
+// row in fa, QUERY16 puts the three quotients together at the point FOLD16C hands it; the key holds the opened rows and no reduced opening; the eight constants of the
+// formula are PUBLIC VALUES in this step -- the step that brings them in over buses is a later one (tests/fri16_openings_air.py).
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -743,10 +746,256 @@ void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots
     for (size_t q = 0; q < b.Q; q++) c.drawn[q] = c.words[q + 1] & mask;
 }
 
+// ---------------------------------------------------------------- the OPENINGS machine: the indices machine with the reduced openings computed in-circuit
+// Table numbers 0 FOLD16C, 1 FINAL, 2 P24L, 3 QUERY16, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES, 8 ROWSUM16, 9 ROWS.  40 public values: the capacity, then fa, zeta, zeta g_N,
+// YL, YN, YQ, OFFN = fa^W, OFFQ = fa^(2W) -- PUBLIC in this step, as beta was public in the first machine before the transcript came in; the step that brings them in
+// over buses is a later one.  The key commits the layer roots, the final coefficients and by query number the opened trace row and quotient row: no reduced opening.
+//   FOLD16C  FOLD16B plus the column XQ = X sum_j O_j w_16^bitrev(j, 4) (the query's point without the coset shift; degree 2, zero on a padding row) behind the last
+//            column, three unused cells beside it; the send on a chain's first row is (IDX, XQ, OWN[4]) on the same bus
+//   QUERY16  where QUERIES stood, one row per query number.  Preprocessed (q, ACT); main the columns of the shard verifier's QUERY chip (IDX XQ RO AT AQ I1 I2 P1 P2 P2O
+//            P3 P3O and the seven constants), every constant tied to its public value on every row, the eight product constraints with x = g XQ.  Receives (q, IDX)
+//            from SAMPLES, (IDX, XQ, RO) from FOLD16C's first rows, (q, AT) and (q, AQ) from ROWSUM16
+//   ROWSUM16 one row per 8 words of an opened row, per query the trace blocks from the last to the first, then the quotient block: V[8] ACCIN[4] T[8][4] FA[4], FA tied
+//            to the public values; preprocessed TAG = 2 q + tree, ACT, NOTFIRST, LAST0, LAST1, QN, K0 = 2 block, K1 = K0 + 1.  Sends (TAG, K0, V0..V3) and
+//            (TAG, K1, V4..V7) to ROWS, (QN, T_0) to QUERY16 on a trace's block 0 (LAST0) and on the quotient block (LAST1)
+//   ROWS     preprocessed (TAG, K, w0..w3, 1): one row per 4-word group of every opened row, the tuple form in which P24L's sponge rows receive theirs -- THE TABLE A
+//            WIDTH-24 CHIP VARIANT ON THE SAME BUS REPLACES: until then the Merkle paths of the trace and quotient rows are NOT proven
+// STILL OUTSIDE: those paths, the transcript before the commit phase (so the eight constants), lookups, the AIR identity.  tests/fri16_openings_air.py writes it again.
+constexpr uint32_t BUS_ROW16 = 81, BUS_AT16 = 82, BUS_AQ16 = 83, N_PUBLIC_O = 40, Q16_PRE = 8, QP_QN = 0, QP_ACT = 1, RS16_PRE = 8, ROWS_PRE16 = 8, QROW16 = 8;
+constexpr uint32_t RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST0 = 3, RP_LAST1 = 4, RP_QN = 5, RP_K0 = 6, RP_K1 = 7;
+constexpr uint32_t PUB_FA = 8, PUB_ZETA = 12;       // public values: FA, then ZETA ZNX YL YN YQ OFFN OFFQ in QUERY16's column order
+enum : int { T_QUERY16 = 3, T_ROWSUM16 = 8, T_ROWS = 9, N_OT = 10 };
+struct OShape {
+    IShape i;
+    uint32_t W = 0;
+    int log_rows[N_OT], order[N_OT];
+    uint32_t main_w[N_OT], pre_w[N_OT];
+};
+int openings_shape_of(int R, int F, int b, size_t Q, int pow_bits, uint32_t W, OShape& s) {
+    ZK_TRY(indices_shape_of(R, F, b, Q, pow_bits, s.i));
+    if (W < 8 || W > MAX_OPEN_W || W % 8)
+        return fail(ZKHIP_ERR_INVALID, "fri16 openings: a trace width of 8 .. 1024 in multiples of 8 (inner proofs without lookup pairs and with a quotient row of 8 words)");
+    s.W = W;
+    const uint32_t mw[N_OT] = {s.i.main_w[0] + 4u, FIN_MAIN, p24chip::WIDTH_L, Q16_MAIN, TAB_MAIN, ROOTS_MAIN_I, p2chip::T_WIDTH, frichip::S_MAIN, RS_MAIN16, TAB_MAIN};
+    const uint32_t pw[N_OT] = {0u, FIN_PRE, 0u, Q16_PRE, C_PRE, ROOTS_PRE16, PT_PRE, frichip::S_PRE, RS16_PRE, ROWS_PRE16};
+    for (int t = 0; t < N_OT; t++) {
+        // (ROWSUM16 and ROWS: at least 2^6 rows -- a keyed machine takes at most 8 tables of one height, and the other eight can all have 2^5 rows; from 2^6 rows
+        // on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting)
+        s.log_rows[t] = t < N_IT ? s.i.log_rows[t] : std::max(6, t == T_ROWSUM16 ? lg(Q * (size_t)(W / 8 + 1)) : lg(Q * (size_t)(W + QROW16) / 4));
+        s.main_w[t] = mw[t]; s.pre_w[t] = pw[t]; s.order[t] = t;
+    }
+    std::stable_sort(s.order, s.order + N_OT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    return ZKHIP_OK;
+}
+// polynomials over columns, as in shard_verifier.inl: a list of (coefficient, variables), an extension expression = four of them; the order in which terms are
+// produced IS the program (tests/recursion_air.py's helpers produce them in the same order)
+typedef std::array<Terms, 4> EE;
+inline Terms pv(uint32_t col, bool nxt = false) { return Terms{Term{1u, {var(col, nxt)}}}; }
+inline Terms pc(uint64_t c) { c %= P; return c ? Terms{Term{(uint32_t)c, {}}} : Terms{}; }
+inline Terms padd(const Terms& a, const Terms& b) { Terms o = a; o.insert(o.end(), b.begin(), b.end()); return o; }
+inline Terms pscale(const Terms& a, uint64_t k) { Terms o; for (const Term& t : a) { const uint32_t c = mulm(t.coeff, k); if (c) o.push_back(Term{c, t.vars}); } return o; }
+inline Terms pneg(const Terms& a) { return pscale(a, P - 1); }
+inline Terms pmul(const Terms& a, const Terms& b) {
+    Terms o;
+    for (const Term& x : a) for (const Term& y : b) { const uint32_t c = mulm(x.coeff, y.coeff); if (!c) continue; Term t{c, x.vars}; t.vars.insert(t.vars.end(), y.vars.begin(), y.vars.end()); o.push_back(t); }
+    return o;
+}
+inline EE ev(uint32_t col, bool nxt = false) { return EE{pv(col, nxt), pv(col + 1, nxt), pv(col + 2, nxt), pv(col + 3, nxt)}; }
+inline EE epub(uint32_t idx) { return EE{Terms{Term{1u, {pub(idx)}}}, Terms{Term{1u, {pub(idx + 1)}}}, Terms{Term{1u, {pub(idx + 2)}}}, Terms{Term{1u, {pub(idx + 3)}}}}; }
+inline EE eone() { return EE{pc(1), Terms{}, Terms{}, Terms{}}; }
+inline EE eb(const Terms& p) { return EE{p, Terms{}, Terms{}, Terms{}}; }
+inline EE eadd(const EE& a, const EE& b) { return EE{padd(a[0], b[0]), padd(a[1], b[1]), padd(a[2], b[2]), padd(a[3], b[3])}; }
+inline EE esub(const EE& a, const EE& b) { return EE{padd(a[0], pneg(b[0])), padd(a[1], pneg(b[1])), padd(a[2], pneg(b[2])), padd(a[3], pneg(b[3]))}; }
+inline EE emul(const EE& a, const EE& b) {
+    EE o;
+    for (int j = 0; j < 4; j++)
+        for (int i = 0; i < 4; i++)
+            for (int k = 0; k < 4; k++) {
+                if ((i + k) % 4 != j) continue;
+                Terms t = pmul(a[i], b[k]);
+                if (i + k >= 4) t = pscale(t, EXT_W);
+                o[j].insert(o[j].end(), t.begin(), t.end());
+            }
+    return o;
+}
+inline EE egate(const Terms& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
+inline void add_ext(Builder& b, uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) b.add(sel, e[i]); }
+inline std::vector<uint32_t> with_public(std::vector<uint32_t> prog, uint32_t n_public) { prog[4] = n_public; return prog; }
+
+std::vector<uint32_t> build_fold16c_program(int R, int lf) {
+    const std::vector<uint32_t> p = build_fold16_program(R, lf, true, N_PUBLIC_O);
+    const uint32_t XQ = fold16_width((uint32_t)lf);
+    Builder b;
+    b.body.assign(p.begin() + 6, p.end());
+    b.count = p[3];
+    Terms t{{1u, {var(XQ)}}};
+    for (uint32_t j = 0; j < 16; j++) t.push_back(Term{neg(from_monty(fpow(two_adic_generator(4), reverse_bits(j, 4)))), {var(X), var(OF + j)}});
+    b.add(ALL, t);
+    return b.finish(XQ + 4u, N_PUBLIC_O);
+}
+// QUERY16's columns in the combined row: the shard verifier's QUERY chip's
+constexpr uint32_t QC_IDX = Q16_PRE + QM_IDX, QC_XQ = Q16_PRE + QM_XQ, QC_RO = Q16_PRE + QM_RO, QC_AT = QC_RO + 4, QC_AQ = QC_RO + 8, QC_I1 = QC_RO + 12, QC_I2 = QC_RO + 16,
+                   QC_P1 = QC_RO + 20, QC_P2 = QC_RO + 24, QC_P2O = QC_RO + 28, QC_P3 = QC_RO + 32, QC_P3O = QC_RO + 36, QC_ZETA = Q16_PRE + QM_ZETA, QC_ZNX = QC_ZETA + 4,
+                   QC_YL = QC_ZETA + 8, QC_YN = QC_ZETA + 12, QC_YQ = QC_ZETA + 16, QC_OFFN = QC_ZETA + 20, QC_OFFQ = QC_ZETA + 24;
+std::vector<uint32_t> build_query16_program() {
+    Builder b;
+    for (uint32_t i = 0; i < 7; i++) add_ext(b, ALL, esub(ev(QC_ZETA + 4 * i), epub(PUB_ZETA + 4 * i)));
+    const EE x = eb(pscale(pv(QC_XQ), GEN));
+    const Terms act = pv(QP_ACT);
+    add_ext(b, ALL, egate(act, esub(emul(esub(x, ev(QC_ZETA)), ev(QC_I1)), eone())));
+    add_ext(b, ALL, egate(act, esub(emul(esub(x, ev(QC_ZNX)), ev(QC_I2)), eone())));
+    add_ext(b, ALL, esub(ev(QC_P1), emul(esub(ev(QC_AT), ev(QC_YL)), ev(QC_I1))));
+    add_ext(b, ALL, esub(ev(QC_P2), emul(esub(ev(QC_AT), ev(QC_YN)), ev(QC_I2))));
+    add_ext(b, ALL, esub(ev(QC_P2O), emul(ev(QC_OFFN), ev(QC_P2))));
+    add_ext(b, ALL, esub(ev(QC_P3), emul(esub(ev(QC_AQ), ev(QC_YQ)), ev(QC_I1))));
+    add_ext(b, ALL, esub(ev(QC_P3O), emul(ev(QC_OFFQ), ev(QC_P3))));
+    add_ext(b, ALL, esub(ev(QC_RO), eadd(eadd(ev(QC_P1), ev(QC_P2O)), ev(QC_P3O))));
+    return b.finish(Q16_PRE + Q16_MAIN, N_PUBLIC_O);
+}
+std::vector<uint32_t> build_rowsum16_program() {
+    const uint32_t M0 = RS16_PRE;
+    Builder b;
+    const EE fa = ev(M0 + RS_FA);
+    add_ext(b, ALL, esub(fa, epub(PUB_FA)));
+    EE prev = ev(M0 + RS_ACCIN);
+    for (int s = 7; s >= 0; s--) {
+        const EE cur = ev(M0 + RS_T + 4u * (uint32_t)s);
+        add_ext(b, ALL, esub(cur, eadd(emul(prev, fa), eb(pv(M0 + RS_V + (uint32_t)s)))));
+        prev = cur;
+    }
+    add_ext(b, TRANSITION, egate(pv(RP_NOTFIRST, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
+    add_ext(b, ALL, egate(padd(pv(RP_ACT), pneg(pv(RP_NOTFIRST))), ev(M0 + RS_ACCIN)));
+    return b.finish(RS16_PRE + RS_MAIN16, N_PUBLIC_O);
+}
+std::vector<uint32_t> build_openings_interactions(int R, int lf, int table) {
+    if (table == T_FINAL || table == T_P24L) return build_paths_interactions(R, table);
+    if (table != T_FOLD16 && table != T_QUERY16 && table < N_IT) return build_indices_interactions(R, table);
+    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
+    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
+        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
+        v.insert(v.end(), cols.begin(), cols.end());
+        v[1]++;
+    };
+    const uint32_t XQ = fold16_width((uint32_t)lf), rv = RS16_PRE + RS_V, rt = RS16_PRE + RS_T;
+    switch (table) {
+    case T_FOLD16:
+        for (uint32_t j = 0; j < 16; j++) add(0u, ACTIVE, BUS_L16, {LN, KJ + j, E + 4 * j, E + 4 * j + 1, E + 4 * j + 2, E + 4 * j + 3});
+        add(0u, L, BUS_Q16, {IDX, XQ, OWN, OWN + 1, OWN + 2, OWN + 3});
+        add(0u, L + (uint32_t)R - 1u, BUS_FIN16, {X16, FOLD, FOLD + 1, FOLD + 2, FOLD + 3});
+        add(1u, ACTIVE, BUS_BF16, {LN, BETA, BETA + 1, BETA + 2, BETA + 3});
+        break;
+    case T_QUERY16:
+        add(1u, QP_ACT, frichip::BUS_I, {QP_QN, QC_IDX});
+        add(1u, QP_ACT, BUS_Q16, {QC_IDX, QC_XQ, QC_RO, QC_RO + 1, QC_RO + 2, QC_RO + 3});
+        add(1u, QP_ACT, BUS_AT16, {QP_QN, QC_AT, QC_AT + 1, QC_AT + 2, QC_AT + 3});
+        add(1u, QP_ACT, BUS_AQ16, {QP_QN, QC_AQ, QC_AQ + 1, QC_AQ + 2, QC_AQ + 3});
+        break;
+    case T_ROWSUM16:
+        add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
+        add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K1, rv + 4, rv + 5, rv + 6, rv + 7});
+        add(0u, RP_LAST0, BUS_AT16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
+        add(0u, RP_LAST1, BUS_AQ16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
+        break;
+    default: add(1u, 6u, BUS_ROW16, {0u, 1u, 2u, 3u, 4u, 5u}); break;          // ROWS
+    }
+    v[2] = (uint32_t)v.size();
+    return v;
+}
+struct OMachine {
+    OShape s;
+    std::vector<uint32_t> prog[N_OT], tab[N_OT];
+    int32_t log_ns[N_OT]; uint32_t widths[N_OT], pre_widths[N_OT];
+    const uint32_t* progs[N_OT]; size_t prog_words[N_OT]; const uint32_t* tabs[N_OT]; size_t tab_words[N_OT];
+};
+std::shared_ptr<const OMachine> openings_machine_of(const OShape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 6>, std::shared_ptr<const OMachine>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
+    const Shape& b = s.i.p.base;
+    const std::array<uint64_t, 6> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.i.pow_bits, (uint64_t)s.W};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<OMachine>();
+    m->s = s;
+    for (int i = 0; i < N_OT; i++) {
+        const int t = s.order[i];
+        switch (t) {
+        case T_FOLD16: m->prog[i] = build_fold16c_program(b.R, b.lf); break;
+        case T_FINAL: m->prog[i] = build_final_program(N_PUBLIC_O); break;
+        case T_P24L: m->prog[i] = *p24chip::program_fri16_layers(N_PUBLIC_O); break;
+        case T_QUERY16: m->prog[i] = build_query16_program(); break;
+        case T_P2T: m->prog[i] = with_public(build_p2t_program(), N_PUBLIC_O); break;
+        case T_SAMPLES: m->prog[i] = *frichip::samples_chip_program(b.H, s.i.pow_bits, N_PUBLIC_O); break;
+        case T_ROOTS: m->prog[i] = with_public(build_roots_program(), N_PUBLIC_O); break;
+        case T_ROWSUM16: m->prog[i] = build_rowsum16_program(); break;
+        default: m->prog[i] = build_table_program(N_PUBLIC_O, s.pre_w[t], s.main_w[t]); break;         // COEFFS, ROWS
+        }
+        m->tab[i] = build_openings_interactions(b.R, b.lf, t);
+        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
+        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
+    }
+    cache.emplace(key, m);
+    return m;
+}
+// the key's tables by table number: the indices machine's (QUERY16's schedule where its QUERIES stood), ROWSUM16's schedule and ROWS -- the rows go in, no reduced opening
+int build_openings_key_tables(const OShape& s, const uint32_t* final_poly, const uint32_t* trows, const uint32_t* qrows, const uint32_t* roots, std::vector<uint32_t> pre[N_OT],
+                              const char* who) {
+    const Shape& b = s.i.p.base;
+    const size_t Q = b.Q, W = s.W, WB = W / 8;
+    if (!trows || !qrows) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(trows, Q * W) || !canonical(qrows, Q * QROW16)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    const std::vector<uint32_t> no_values(4 * Q, 0u);
+    ZK_TRY(build_indices_key_tables(s.i, final_poly, no_values.data(), roots, pre, who));
+    pre[T_QUERY16].assign((size_t)Q16_PRE << s.log_rows[T_QUERY16], 0u);
+    for (size_t q = 0; q < Q; q++) { pre[T_QUERY16][Q16_PRE * q + QP_QN] = to_monty((uint32_t)q); pre[T_QUERY16][Q16_PRE * q + QP_ACT] = MONTY_R1; }
+    pre[T_ROWSUM16].assign((size_t)RS16_PRE << s.log_rows[T_ROWSUM16], 0u);
+    pre[T_ROWS].assign((size_t)ROWS_PRE16 << s.log_rows[T_ROWS], 0u);
+    size_t r = 0, g = 0;
+    for (size_t q = 0; q < Q; q++) {
+        for (size_t pos = 0; pos <= WB; pos++) {
+            const bool quot = pos == WB;
+            const size_t blk = quot ? 0 : WB - 1 - pos;
+            uint32_t* w = pre[T_ROWSUM16].data() + RS16_PRE * r++;
+            w[RP_TAG] = to_monty((uint32_t)(2 * q + (quot ? 1 : 0))); w[RP_ACT] = MONTY_R1; w[RP_NOTFIRST] = pos == 0 || quot ? 0u : MONTY_R1;
+            w[RP_LAST0] = !quot && blk == 0 ? MONTY_R1 : 0u; w[RP_LAST1] = quot ? MONTY_R1 : 0u; w[RP_QN] = to_monty((uint32_t)q);
+            w[RP_K0] = to_monty((uint32_t)(2 * blk)); w[RP_K1] = to_monty((uint32_t)(2 * blk + 1));
+        }
+        for (int tree = 0; tree < 2; tree++) {
+            const uint32_t* row = tree ? qrows + QROW16 * q : trows + W * q;
+            for (size_t k = 0; k < (tree ? QROW16 : W) / 4; k++) {
+                uint32_t* w = pre[T_ROWS].data() + ROWS_PRE16 * g++;
+                w[0] = to_monty((uint32_t)(2 * q + tree)); w[1] = to_monty((uint32_t)k);
+                for (int i = 0; i < 4; i++) w[2 + i] = to_monty(row[4 * k + i]);
+                w[6] = MONTY_R1;
+            }
+        }
+    }
+    return ZKHIP_OK;
+}
+// the constants among themselves: zeta g_N, fa^W, fa^(2W)
+int check_openings_constants(const OShape& s, const uint32_t* consts, const char* who) {
+    if (!consts) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(consts, 32)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    const Shape& b = s.i.p.base;
+    const Ext fa = ext_from_canon(consts), zeta = ext_from_canon(consts + 4);
+    if (!ext_eq(ext_from_canon(consts + 8), ext_mul_base(zeta, two_adic_generator(b.H - b.b))) || !ext_eq(ext_from_canon(consts + 24), ext_pow(fa, s.W)) ||
+        !ext_eq(ext_from_canon(consts + 28), ext_pow(fa, 2 * (uint64_t)s.W)))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constants do not match each other (zeta g_N, OFFN = fa^W, OFFQ = fa^(2W))");
+    return ZKHIP_OK;
+}
+
 struct fold_rows_bargs { FoldRowsArgs a; static fold_rows_bargs make(FoldRowsArgs a) { return fold_rows_bargs{a}; } };
 __global__ void __launch_bounds__(64) fri16_fold_rows_kernel_batch(const fold_rows_bargs* __restrict__ zk_arr) { fri16_fold_rows_body(zk_arr[blockIdx.z].a); }
 struct final_rows_bargs { FinalRowsArgs a; static final_rows_bargs make(FinalRowsArgs a) { return final_rows_bargs{a}; } };
 __global__ void __launch_bounds__(64) fri16_final_rows_kernel_batch(const final_rows_bargs* __restrict__ zk_arr) { fri16_final_rows_body(zk_arr[blockIdx.z].a); }
+struct openings_rows_bargs { OpeningsRowsArgs a; static openings_rows_bargs make(OpeningsRowsArgs a) { return openings_rows_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_openings_rows_kernel_batch(const openings_rows_bargs* __restrict__ zk_arr) { fri16_openings_rows_body<false>(zk_arr[blockIdx.z].a); }
+__global__ void __launch_bounds__(64) fri16_openings_rows_tall_kernel_batch(const openings_rows_bargs* __restrict__ zk_arr) { fri16_openings_rows_body<true>(zk_arr[blockIdx.z].a); }
+struct xq_cols_bargs { XqColsArgs a; static xq_cols_bargs make(XqColsArgs a) { return xq_cols_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_xq_cols_kernel_batch(const xq_cols_bargs* __restrict__ zk_arr) { fri16_xq_cols_body(zk_arr[blockIdx.z].a); }
 
 }  // namespace
 }  // namespace fri16
@@ -762,7 +1011,7 @@ using namespace zk;
 
 // both main traces from the view's arrays, uploaded once; every chain's end (FOLD16's last row) against its block's end (FINAL's last row)
 static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                                 const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
+                                 const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final, const uint32_t* d_values = nullptr) {
     const size_t R = (size_t)s.R, Q = s.Q, nb = 4 * R, nf = (size_t)4 << s.F, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q, ns = 60 * Q * R, up_words = nb + nf + ni + nv + ns;
     void* stage;
     ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 16 * Q) * 4, &stage));
@@ -776,7 +1025,8 @@ static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const ui
         std::memcpy(up.data() + nb + nf + ni + nv, siblings, ns * 4);
         ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
     }
-    fri16::ViewArgs v{d, d + nb, d + nb + nf, d + nb + nf + ni, d + nb + nf + ni + nv, (uint32_t)Q, (uint32_t)s.R, (uint32_t)s.F, (uint32_t)s.lf, (uint32_t)s.H};
+    // (d_values: the chains start from values already on the device -- the openings machine's, computed there from the opened rows)
+    fri16::ViewArgs v{d, d + nb, d + nb + nf, d_values ? d_values : d + nb + nf + ni, d + nb + nf + ni + nv, (uint32_t)Q, (uint32_t)s.R, (uint32_t)s.F, (uint32_t)s.lf, (uint32_t)s.H};
     uint32_t* d_ends = d + up_words;
     fri16::FoldRowsArgs fa{v, s.main_w[0], (uint64_t)1 << s.log_rows[0], d_fold, ld_fold, d_ends};
     const size_t pad = (size_t)fa.rows - Q * R, fold_lanes = Q * R + (pad < 4096 ? pad : 4096);        // the padding rows are shared among up to 4096 extra lanes
@@ -1278,6 +1528,229 @@ int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_b
     }
     const auto m = fri16::machine_of(s);
     return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, 5, betas, 4 * (size_t)R, prm, reason);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the openings machine's entries
+// ROWSUM16 and QUERY16 in one launch from one staging block (rows, constants, indices, the view's values); the reduced openings stay on the device (*d_openings,
+// canonical, where the fold kernel reads its chains' first values); status[0] / status[1]: the least query whose opening differs from view_values / whose point has no
+// inverse (0xFFFFFFFF: none)
+static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices,
+                                    const uint32_t* view_values, uint32_t* d_rowsum, uint32_t* d_query, uint32_t** d_openings, uint32_t status[2], const uint32_t** d_indices = nullptr) {
+    const fri16::Shape& b = s.i.p.base;
+    const size_t Q = b.Q, W = s.W, nt = Q * W, nq = Q * fri16::QROW16, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q;
+    const size_t o_q = nt, o_c = o_q + nq, o_i = o_c + 32, o_v = o_i + ni, o_open = o_v + nv, o_status = o_open + nv, words = o_status + 4;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_REC_J, words * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(words, 0u);
+        std::memcpy(up.data(), trows, nt * 4);
+        std::memcpy(up.data() + o_q, qrows, nq * 4);
+        std::memcpy(up.data() + o_c, consts, 32 * 4);
+        std::memcpy(up.data() + o_i, indices, Q * 4);
+        if (view_values) std::memcpy(up.data() + o_v, view_values, nv * 4);
+        for (int i = 0; i < 4; i++) up[o_status + i] = 0xFFFFFFFFu;
+        ZK_TRY(dev_h2d(ctx, d, up.data(), words * 4));
+    }
+    fri16::OpeningsRowsArgs a{};
+    a.trows = d; a.qrows = d + o_q; a.consts = d + o_c; a.indices = d + o_i; a.view_values = view_values ? d + o_v : nullptr;
+    a.Q = (uint32_t)Q; a.W = (uint32_t)W; a.H = (uint32_t)b.H;
+    a.rowsum_rows = (uint64_t)1 << s.log_rows[fri16::T_ROWSUM16]; a.query_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERY16];
+    a.rowsum = d_rowsum; a.query = d_query; a.openings = d + o_open; a.status = d + o_status;
+    const size_t per = W / 8 + 1;
+    if (per <= 64) {
+        const size_t qpw = 64 / per;
+        ZK_LAUNCH(fri16::fri16_openings_rows_kernel, fri16::fri16_openings_rows_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)((Q + qpw - 1) / qpw)), dim3(64), 0, ctx->stream, a);
+    } else
+        ZK_LAUNCH(fri16::fri16_openings_rows_tall_kernel, fri16::fri16_openings_rows_tall_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)Q), dim3(64), 0, ctx->stream, a);
+    ZK_HIP(hipGetLastError());
+    uint32_t st[4];
+    ZK_TRY(dev_d2h(ctx, st, a.status, 16));
+    status[0] = st[0]; status[1] = st[1];
+    *d_openings = a.openings;
+    if (d_indices) *d_indices = a.indices;
+    return ZKHIP_OK;
+}
+static int fri16_openings_check_rows(const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices, const char* who) {
+    const fri16::Shape& b = s.i.p.base;
+    if (!trows || !qrows || !consts || !indices) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(trows, b.Q * (size_t)s.W) || !fri16::canonical(qrows, b.Q * fri16::QROW16) || !fri16::canonical(consts, 32))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (size_t q = 0; q < b.Q; q++) if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    return ZKHIP_OK;
+}
+static int fri16_openings_no_inverse(const char* who, uint32_t q) {
+    return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the point of query " + std::to_string(q) + " is zeta or zeta g: its reduced opening has no inverse");
+}
+
+extern "C" {
+
+size_t zkhip_fri16_openings_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
+                                     size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
+    fri16::OShape s;
+    if (which < 0 || which >= fri16::N_OT || kind < 0 || kind > 1 || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::openings_machine_of(s);
+    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+
+int zkhip_fri16_openings_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
+                                  const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::OShape s;
+    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::N_OT];
+    ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key_host"));
+    const auto m = fri16::openings_machine_of(s);
+    const uint32_t* h[fri16::N_OT];
+    for (int i = 0; i < fri16::N_OT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_OT, prm, vk);
+}
+
+int zkhip_fri16_openings_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             const uint32_t* final_poly, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm,
+                             zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::OShape s;
+    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key: null argument");
+    std::vector<uint32_t> pre[fri16::N_OT];
+    ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key"));
+    const auto m = fri16::openings_machine_of(s);
+    const int slots[fri16::N_OT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B};      // by table number: the eight tables with preprocessed columns
+    zkhip_chip chips[fri16::N_OT]{};
+    for (int i = 0; i < fri16::N_OT; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips, fri16::N_OT, prm, key, vk);
+}
+
+size_t zkhip_fri16_openings_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
+    fri16::OShape s;
+    if (!prm || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::openings_machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, prm, fri16::N_PUBLIC_O);
+}
+
+int zkhip_fri16_openings_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
+                                    const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* indices, uint32_t* d_rowsum, uint32_t* d_query,
+                                    uint32_t* openings) {
+    CHECK_CTX(ctx);
+    fri16::OShape s;
+    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, "fri16_openings_gen_traces"));
+    if (!d_rowsum || !d_query || !openings || ((uintptr_t)d_rowsum | (uintptr_t)d_query) % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_openings_gen_traces: 16-byte aligned dense traces (48 and 72 columns) and the openings");
+    uint32_t status[2], *d_open = nullptr;
+    ZK_TRY(fri16_openings_rows_impl(ctx, s, trace_rows, quotient_rows, constants, indices, nullptr, d_rowsum, d_query, &d_open, status));
+    if (status[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse("fri16_openings_gen_traces", status[1]);
+    return dev_d2h(ctx, openings, d_open, 16 * n_queries);
+}
+
+int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness,
+                               const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const zkhip_params* prm, uint8_t* proof, size_t cap,
+                               size_t* len) {
+    CHECK_CTX(ctx);
+    fri16::OShape s;
+    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: null argument");
+    const fri16::IShape& is = s.i;
+    const fri16::PShape& ps = is.p;
+    ZK_TRY(fri16_paths_check_view(ps.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_openings"));
+    ZK_TRY(fri16_indices_check_inputs(is, capacity, roots, final_poly, witness, "prove_fri16_openings"));
+    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, "prove_fri16_openings"));
+    ZK_TRY(fri16::check_openings_constants(s, constants, "prove_fri16_openings"));
+    const auto m = fri16::openings_machine_of(s);
+    using namespace fri16;
+    const size_t ld_fold = s.main_w[T_FOLD16];
+    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp, *t_rs, *t_q;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, (ld_fold << s.log_rows[T_FOLD16]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[T_FINAL] << s.log_rows[T_FINAL]) * 4, &t_final));
+    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[T_P24L]) * 4, &t_p24));
+    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[T_P2T]) * 4, &t_p2t));
+    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[T_SAMPLES]) * 4, &t_smp));
+    ZK_TRY(ctx_reserve(ctx, S_REC_F, ((size_t)RS_MAIN16 << s.log_rows[T_ROWSUM16]) * 4, &t_rs));
+    ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
+    // the small tables' main columns: COEFFS and ROWS unused (zero), ROOTS path ends, challenge and fold rows per layer; a scratch QUERIES block the transcript kernel
+    // fills with the indices (this machine's QUERY16 holds them in its own row)
+    size_t zoff[N_OT] = {0}, zwords = 0;
+    for (int t : {(int)T_QUERIES, (int)T_COEFFS, (int)T_ROOTS, (int)T_ROWS}) { zoff[t] = zwords; zwords += (size_t)(t == T_QUERIES ? TAB_MAIN : s.main_w[t]) << s.log_rows[t]; }
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
+    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_COEFFS], 0, ((size_t)s.main_w[T_COEFFS] << s.log_rows[T_COEFFS]) * 4));
+    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_ROWS], 0, ((size_t)s.main_w[T_ROWS] << s.log_rows[T_ROWS]) * 4));
+    // refused here, before anything is proven: all zkhip_prove_fri16_indices refuses; then openings the rows do not give, points without an inverse
+    Chain c;
+    walk_chain(is, capacity, roots, final_poly, witness, c);
+    PathPlan pl;
+    ZK_TRY(plan_paths(ps.base, indices, paths, pl));
+    uint32_t status = 0;
+    ZK_TRY(fri16_transcript_impl(ctx, is, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[T_QUERIES],
+                                 (uint32_t*)t_tabs + zoff[T_ROOTS], &status));
+    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the challenges are not the ones the transcript draws from these roots and this capacity");
+    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the witness does not satisfy the proof of work");
+    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the query indices are not the ones the transcript draws");
+    uint32_t ost[2], *d_open = nullptr;
+    const uint32_t* d_idx = nullptr;
+    ZK_TRY(fri16_openings_rows_impl(ctx, s, trace_rows, quotient_rows, constants, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx));
+    if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse("prove_fri16_openings", ost[1]);
+    if (ost[0] != 0xFFFFFFFFu)
+        return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
+    // the fold chains start from the openings the device computed; XQ beside the fold kernel's columns
+    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, ld_fold, (uint32_t*)t_final, s.main_w[T_FINAL], d_open));
+    {
+        XqColsArgs xa{};
+        xa.indices = d_idx; xa.Q = (uint32_t)ps.base.Q; xa.R = (uint32_t)R; xa.H = (uint32_t)ps.base.H;
+        xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = (uint32_t*)t_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
+        ZK_LAUNCH(fri16_xq_cols_kernel, fri16_xq_cols_kernel_batch, xq_cols_bargs, dim3((unsigned)((xa.rows + 63) / 64)), dim3(64), 0, ctx->stream, xa);
+        ZK_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    for (size_t p = 0; p < pl.n; p++)
+        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " does not open: its path does not end in the layer's root");
+    zkhip_chip chips[N_OT]{};
+    for (int i = 0; i < N_OT; i++) {
+        const int t = s.order[i];
+        chips[i].d_trace = t == T_FOLD16 ? (const uint32_t*)t_fold : t == T_FINAL ? (const uint32_t*)t_final : t == T_P24L ? (const uint32_t*)t_p24
+                         : t == T_P2T ? (const uint32_t*)t_p2t : t == T_SAMPLES ? (const uint32_t*)t_smp : t == T_ROWSUM16 ? (const uint32_t*)t_rs
+                         : t == T_QUERY16 ? (const uint32_t*)t_q : (const uint32_t*)t_tabs + zoff[t];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    uint32_t pub[N_PUBLIC_O];
+    std::memcpy(pub, capacity, 32);
+    std::memcpy(pub + 8, constants, 128);
+    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, N_OT, pub, N_PUBLIC_O, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    fri16::OShape s;
+    if (!proof || !public_values || !vk || !prm || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_openings: bad arguments");
+    }
+    const auto m = fri16::openings_machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, public_values,
+                                      fri16::N_PUBLIC_O, prm, reason);
 }
 
 }  // extern "C"

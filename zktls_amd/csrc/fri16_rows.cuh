@@ -58,6 +58,24 @@ struct FinalRowsArgs {
     uint32_t* trace; uint64_t ld;
     uint32_t* ends;                     // [Q][8] Montgomery: (x, acc[4], 0, 0, 0) of every block's last row
 };
+// the openings machine: ROWSUM16 (V[8] ACCIN[4] T[8][4] FA[4]) and QUERY16 (IDX XQ, then RO AT AQ I1 I2 P1 P2 P2O P3 P3O ZETA ZNX YL YN YQ OFFN OFFQ, four words
+// each, two unused), both dense
+constexpr uint32_t RS_V = 0, RS_ACCIN = 8, RS_T = 12, RS_FA = 44, RS_MAIN16 = 48;
+constexpr uint32_t QM_IDX = 0, QM_XQ = 1, QM_RO = 2, QM_ZETA = 42, Q16_MAIN = 72;
+constexpr uint32_t MAX_OPEN_W = 1024;
+struct OpeningsRowsArgs {
+    const uint32_t *trows, *qrows, *consts, *indices;   // canonical words on the device, each array 16-byte aligned: [Q][W], [Q][8], fa zeta zeta g YL YN YQ OFFN OFFQ [8][4], [Q]
+    const uint32_t* view_values;                        // [Q][4] canonical, or null: what every reduced opening is compared with
+    uint32_t Q, W, H;
+    uint64_t rowsum_rows, query_rows;                   // the tables' heights
+    uint32_t *rowsum, *query;                           // Montgomery, dense, 16-byte aligned
+    uint32_t* openings;                                 // [Q][4] CANONICAL: the reduced openings, where the fold kernel reads its chains' first values
+    uint32_t* status;                                   // [4], 0xFFFFFFFF before the launch: the least query whose opening differs from the view's; the least whose point has no inverse
+};
+struct XqColsArgs {
+    const uint32_t* indices; uint32_t Q, R, H;
+    uint64_t rows; uint32_t* trace; uint64_t ld; uint32_t col;
+};
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ Ext ld_ext(const uint32_t* p) {
@@ -233,6 +251,133 @@ __device__ __forceinline__ void fri16_final_rows_body(const FinalRowsArgs& a) {
     if (active && first + per == n) { st4(a.ends + 8u * blk, x, acc.c[0], acc.c[1], acc.c[2]); st4(a.ends + 8u * blk + 4, acc.c[3], 0u, 0u, 0u); }
 }
 __global__ void __launch_bounds__(64) fri16_final_rows_kernel(FinalRowsArgs a) { fri16_final_rows_body(a); }
+
+// ---- the openings machine's rows
+__device__ __forceinline__ uint32_t canon_dev(uint32_t m) { return dmul(m, 1u); }          // Montgomery -> canonical
+__device__ __forceinline__ Ext ext_sub_from_base(uint32_t x, const Ext& z) { return Ext{{dsub(x, z.c[0]), dsub(0u, z.c[1]), dsub(0u, z.c[2]), dsub(0u, z.c[3])}}; }
+__device__ __forceinline__ bool ext_is_zero(const Ext& e) { return (e.c[0] | e.c[1] | e.c[2] | e.c[3]) == 0u; }
+// one QUERY16 row from the query's two sums: x = g XQ, I1 = 1 / (x - zeta), I2 = 1 / (x - zeta g), RO = (AT - YL) I1 + OFFN (AT - YN) I2 + OFFQ (AQ - YQ) I1
+__device__ __forceinline__ void query16_row(const OpeningsRowsArgs& a, uint32_t q, const Ext& at, const Ext& aq) {
+    Ext k[7];                                                          // ZETA ZNX YL YN YQ OFFN OFFQ
+#pragma unroll
+    for (int i = 0; i < 7; i++) k[i] = ld_ext(a.consts + 4 + 4 * i);
+    const uint32_t index = a.indices[q], xq = fpow_dev(root_dev(a.H), brev_dev(index, a.H)), x = dmul(xq, MONTY_GEN);
+    const Ext d1 = ext_sub_from_base(x, k[0]), d2 = ext_sub_from_base(x, k[1]);
+    const Ext i1 = ext_inv_dev(d1), i2 = ext_inv_dev(d2);
+    const Ext p1 = ext_mul_dev(ext_sub_dev(at, k[2]), i1), p2 = ext_mul_dev(ext_sub_dev(at, k[3]), i2), p2o = ext_mul_dev(k[5], p2);
+    const Ext p3 = ext_mul_dev(ext_sub_dev(aq, k[4]), i1), p3o = ext_mul_dev(k[6], p3), ro = ext_add_dev(ext_add_dev(p1, p2o), p3o);
+    uint32_t w[Q16_MAIN];
+    w[QM_IDX] = dmul(index, MONTY_R2); w[QM_XQ] = xq; w[Q16_MAIN - 2] = 0u; w[Q16_MAIN - 1] = 0u;
+    auto put = [&](uint32_t col, const Ext& e) { w[col] = e.c[0]; w[col + 1] = e.c[1]; w[col + 2] = e.c[2]; w[col + 3] = e.c[3]; };
+    put(QM_RO, ro); put(QM_RO + 4, at); put(QM_RO + 8, aq); put(QM_RO + 12, i1); put(QM_RO + 16, i2);
+    put(QM_RO + 20, p1); put(QM_RO + 24, p2); put(QM_RO + 28, p2o); put(QM_RO + 32, p3); put(QM_RO + 36, p3o);
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) w[QM_ZETA + 4 * i + c] = k[i].c[c];
+    uint32_t* t = a.query + (uint64_t)q * Q16_MAIN;
+#pragma unroll
+    for (uint32_t c = 0; c < Q16_MAIN; c += 4) st4(t + c, w[c], w[c + 1], w[c + 2], w[c + 3]);
+    const uint32_t r0 = canon_dev(ro.c[0]), r1 = canon_dev(ro.c[1]), r2 = canon_dev(ro.c[2]), r3 = canon_dev(ro.c[3]);
+    st4(a.openings + 4u * q, r0, r1, r2, r3);
+    if (a.view_values) {
+        const uint4 want = *reinterpret_cast<const uint4*>(a.view_values + 4u * q);
+        if (want.x != r0 || want.y != r1 || want.z != r2 || want.w != r3) atomicMin(a.status, q);
+    }
+    if (ext_is_zero(d1) || ext_is_zero(d2)) atomicMin(a.status + 1, q);
+}
+// the padding rows of both tables, shared among `lanes` lanes: the constants in the constant columns, zero elsewhere
+__device__ __forceinline__ void openings_padding_rows(const OpeningsRowsArgs& a, uint64_t g, uint64_t lanes) {
+    const uint4 fa = make_uint4(dmul(a.consts[0], MONTY_R2), dmul(a.consts[1], MONTY_R2), dmul(a.consts[2], MONTY_R2), dmul(a.consts[3], MONTY_R2));
+    for (uint64_t r = (uint64_t)a.Q * ((a.W >> 3) + 1u) + g; r < a.rowsum_rows; r += lanes) {
+        uint32_t* t = a.rowsum + r * RS_MAIN16;
+#pragma unroll
+        for (uint32_t c = 0; c < RS_FA; c += 4) st4(t + c, 0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4*>(t + RS_FA) = fa;
+    }
+    for (uint64_t r = (uint64_t)a.Q + g; r < a.query_rows; r += lanes) {
+        uint32_t* t = a.query + r * Q16_MAIN;
+        uint32_t w[Q16_MAIN];
+#pragma unroll
+        for (uint32_t c = 0; c < Q16_MAIN; c++) w[c] = c >= QM_ZETA && c < QM_ZETA + 28u ? dmul(a.consts[4u + c - QM_ZETA], MONTY_R2) : 0u;
+#pragma unroll
+        for (uint32_t c = 0; c < Q16_MAIN; c += 4) st4(t + c, w[c], w[c + 1], w[c + 2], w[c + 3]);
+    }
+}
+
+// ROWSUM16 and QUERY16 (the openings machine), one launch.  ROWSUM16 has one row per 8 words of an opened row, per query the trace blocks from the last to the
+// first and then the quotient block; a query's trace blocks are one Horner chain in fa (T_s = T_{s+1} fa + V_s down the eight words, ACCIN = the block before's
+// T_0), its quotient block a chain of one row.  A lane per ROW: Horner over its own eight words from zero, a segmented cross-lane scan of the blocks' partial sums
+// (fri16_final_rows_body's scan with an extension multiplier, fa^8, squared per step; a lane takes from lane - d only while its position in its segment is >= d),
+// then each lane redoes its eight steps from the ACCIN that reaches it and writes its row with twelve 16-byte stores.  A segment never straddles a wave without a
+// carry: while W / 8 + 1 <= 64 whole queries are packed into a wave (64 / (W / 8 + 1) of them), a taller query has a wave of its own and takes rounds of 64 blocks
+// from the top, the running value carried from round to round.  The quotient lane has the trace's sum in the lane before it (or in the carry) and its own in
+// hand: it computes the query's QUERY16 row -- the point, the two inversions, the five products -- writes the reduced opening where the fold kernel reads its
+// chains' first values and compares it with the view's.  Then all lanes share the padding rows of both tables.
+template <bool TALL>
+__device__ __forceinline__ void fri16_openings_rows_body(const OpeningsRowsArgs& a) {
+    const uint32_t lane = threadIdx.x, WB = a.W >> 3, per = WB + 1u, Q = a.Q;
+    const uint32_t qpw = TALL ? 1u : 64u / per, sub = TALL ? 0u : lane / per, q = blockIdx.x * qpw + sub;
+    const uint32_t rounds = TALL ? (per + 63u) >> 6 : 1u, reach = TALL ? 64u : per;
+    const Ext fa = ld_ext(a.consts), fa2 = ext_mul_dev(fa, fa), fa4 = ext_mul_dev(fa2, fa2), fa8 = ext_mul_dev(fa4, fa4);
+    Ext carry = ext_zero();
+#pragma unroll 1
+    for (uint32_t rd = 0; rd < rounds; rd++) {
+        const uint32_t pos = TALL ? rd * 64u + lane : lane - sub * per;
+        const bool act = q < Q && sub < qpw && pos < per, quot = pos == WB;
+        const uint32_t seg = quot ? 0u : (TALL ? lane : pos);          // position in the segment (TALL: counted from this round's first lane, which starts from the carry)
+        uint32_t v[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) v[s] = 0u;
+        if (act) {
+            const uint32_t* src = quot ? a.qrows + 8u * (size_t)q : a.trows + (size_t)q * a.W + 8u * (WB - 1u - pos);
+            const uint4 lo = *reinterpret_cast<const uint4*>(src), hi = *reinterpret_cast<const uint4*>(src + 4);
+            v[0] = dmul(lo.x, MONTY_R2); v[1] = dmul(lo.y, MONTY_R2); v[2] = dmul(lo.z, MONTY_R2); v[3] = dmul(lo.w, MONTY_R2);
+            v[4] = dmul(hi.x, MONTY_R2); v[5] = dmul(hi.y, MONTY_R2); v[6] = dmul(hi.z, MONTY_R2); v[7] = dmul(hi.w, MONTY_R2);
+        }
+        Ext p = seg == 0u && !quot ? carry : ext_zero();
+#pragma unroll
+        for (int s = 7; s >= 0; s--) { p = ext_mul_dev(p, fa); p.c[0] = dadd(p.c[0], v[s]); }
+        Ext m = fa8;
+#pragma unroll 1
+        for (uint32_t d = 1; d < reach; d <<= 1) {
+            const Ext o = shfl_up_ext(p, d, 64);
+            if (seg >= d) p = ext_add_dev(ext_mul_dev(o, m), p);
+            m = ext_mul_dev(m, m);
+        }
+        Ext prev = shfl_up_ext(p, 1u, 64);                             // T_0 of the row before
+        if (TALL && lane == 0u) prev = carry;
+        const Ext accin = quot ? ext_zero() : (seg == 0u ? carry : prev);
+        if (TALL) carry = Ext{{(uint32_t)__shfl((int)p.c[0], 63, 64), (uint32_t)__shfl((int)p.c[1], 63, 64), (uint32_t)__shfl((int)p.c[2], 63, 64), (uint32_t)__shfl((int)p.c[3], 63, 64)}};
+        if (!act) continue;
+        uint32_t* t = a.rowsum + ((uint64_t)q * per + pos) * RS_MAIN16;
+        st4(t + RS_V, v[0], v[1], v[2], v[3]); st4(t + RS_V + 4, v[4], v[5], v[6], v[7]);
+        st_ext(t + RS_ACCIN, accin);
+        Ext acc = accin;
+#pragma unroll
+        for (int s = 7; s >= 0; s--) { acc = ext_mul_dev(acc, fa); acc.c[0] = dadd(acc.c[0], v[s]); st_ext(t + RS_T + 4 * s, acc); }
+        st_ext(t + RS_FA, fa);
+        if (quot) query16_row(a, q, prev, acc);
+    }
+    openings_padding_rows(a, blockIdx.x * 64u + lane, gridDim.x * 64u);
+}
+// (the plain form -- a lane per query walking its blocks -- that this one was checked against and timed beside: tools/fri16_openings_forms.hip)
+__global__ void __launch_bounds__(64) fri16_openings_rows_kernel(OpeningsRowsArgs a) { fri16_openings_rows_body<false>(a); }
+__global__ void __launch_bounds__(64) fri16_openings_rows_tall_kernel(OpeningsRowsArgs a) { fri16_openings_rows_body<true>(a); }
+
+// FOLD16C's column XQ = X sum_j O_j w_16^bitrev(j, 4) = w_{2^(H - 4 l)}^bitrev(index >> 4 l, H - 4 l) on the row of (query, layer l), and the three unused cells
+// beside it; zero on the padding rows.  The fold kernel above writes the columns in front of it.
+__device__ __forceinline__ void fri16_xq_cols_body(const XqColsArgs& a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.rows) return;
+    uint32_t xq = 0u;
+    if (r < (uint64_t)a.Q * a.R) {
+        const uint32_t q = (uint32_t)(r / a.R), l = (uint32_t)(r % a.R), bits = a.H - 4u * l;
+        xq = fpow_dev(root_dev(bits), brev_dev(a.indices[q] >> (4u * l), bits));
+    }
+    st4(a.trace + r * a.ld + a.col, xq, 0u, 0u, 0u);
+}
+__global__ void __launch_bounds__(64) fri16_xq_cols_kernel(XqColsArgs a) { fri16_xq_cols_body(a); }
 #endif
 
 }  // namespace fri16

@@ -174,6 +174,9 @@ struct FriViewSink {
     // every layer row in proof order ([query][layer][15][4]), paths the layers' paths one after the other (8 lh words for layer l, lh = H - 4 (l + 1))
     bool fold16 = false;
     uint32_t* final_poly = nullptr;
+    // openings (zkhip_fri16_view_openings): per query the opened trace row (width words) and quotient row as the proof holds them, and the eight constants
+    // of the reduced opening -- fa, zeta, zeta g_N, y_loc, y_nxt, y_q, fa^width, fa^(2 width), four words each
+    uint32_t *trace_rows = nullptr, *quotient_rows = nullptr, *constants = nullptr;
 };
 
 static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
@@ -329,6 +332,10 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
               off_pn = ext_pow(fa, 2 * (uint64_t)width + wp), off_q = ext_pow(fa, 2 * (uint64_t)width + 2 * wp);
     std::vector<uint32_t> commits((size_t)RL * 8 + 8);
     std::vector<Ext> betas(RL + 1);
+    if (sink && sink->constants) {
+        const Ext cs[8] = {fa, zeta, zeta_next, y_loc, y_nxt, y_q, off_next, off_q};
+        for (int k = 0; k < 8; k++) for (int i = 0; i < 4; i++) sink->constants[4 * k + i] = from_monty(cs[k].c[i]);
+    }
     if (sink && sink->transcript) {               // the challenger as the commit phase finds it: capacity half of the state, pending inputs
         for (int i = 0; i < 8; i++) sink->transcript[i] = from_monty(ch.state[8 + i]);
         sink->transcript[8] = (uint32_t)ch.n_in;
@@ -384,6 +391,10 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
             qrow[j] = pf + pos; pos += QW;
             qpath[j] = pf + pos; pos += 8 * (size_t)H;
             qpos[j] = pos;
+            if (sink && sink->trace_rows) {
+                std::memcpy(sink->trace_rows + (size_t)(q0 + j) * width, trow[j], 4 * (size_t)width);
+                std::memcpy(sink->quotient_rows + (size_t)(q0 + j) * QW, qrow[j], 4 * QW);
+            }
         }
         auto batch = [&](const uint32_t* const* rows, size_t row_off, const uint32_t* const* paths, const size_t* idx) {
             PathBatch b;
@@ -562,6 +573,26 @@ int zkhip_fri16_view_transcript(const uint8_t* proof, size_t len, int log_n, uin
     FriViewSink sink{betas, nullptr, indices.data(), values.data(), siblings.data(), sh.R, roots, nullptr, transcript};
     sink.fold16 = true;
     sink.final_poly = final_poly.data();
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
+}
+// ... and what the reduced openings of a FOLD-BY-16 proof are made of (the openings machine of fri16_chip.hip): per query the opened trace row [Q][width] and
+// quotient row [Q][8] as the proof holds them, and the eight constants [8][4] (fa, zeta, zeta g_N, y_loc, y_nxt, y_q, fa^width, fa^(2 width)).  Proofs with lookup
+// pairs are refused (their reduced opening has two more terms); version-8 proofs (group order) are taken: the row is the same.
+int zkhip_fri16_view_openings(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                              uint32_t* trace_rows, uint32_t* quotient_rows, uint32_t constants[32]) {
+    if (!prm || !trace_rows || !quotient_rows || !constants) return fail(ZKHIP_ERR_INVALID, "fri16_view_openings: null argument");
+    Shape sh;
+    if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_openings: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    if (prm->logup_pairs) return fail(ZKHIP_ERR_INVALID, "fri16_view_openings: proofs with lookup pairs are not taken (logup_pairs = 0 only)");
+    const size_t Q = (size_t)prm->num_queries;
+    std::vector<uint32_t> betas(4 * (size_t)sh.R), final_poly((size_t)4 << sh.F), indices(Q), values(4 * Q), siblings(60 * Q * (size_t)sh.R);
+    FriViewSink sink{betas.data(), nullptr, indices.data(), values.data(), siblings.data(), sh.R, nullptr, nullptr, nullptr};
+    sink.fold16 = true;
+    sink.final_poly = final_poly.data();
+    sink.trace_rows = trace_rows; sink.quotient_rows = quotient_rows; sink.constants = constants;
     int why = 0;
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }

@@ -807,6 +807,50 @@ class Context:
                                                  C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 OPENINGS machine (the reduced openings in-circuit: ROWSUM16 and QUERY16)
+    def fri16_openings_key(self, view, params=None):
+        """zkhip_fri16_openings_key: the key of the fold-16 openings machine, committed on the device -- from the shape, the inner proof's grinding bits and trace
+        width, the final coefficients, the opened trace and quotient rows by query number and the layer roots: no reduced opening, no index, no challenge -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+        W, trows, qrows, _ = _fri16_openings_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_openings_key(self.handle, *shape, hw, int(view["pow_bits"]), W, *[a.ctypes.data_as(u32p) for a in (arrs[1], trows, qrows, roots)],
+                                                C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_openings_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, trows, qrows, consts, indices):
+        """zkhip_fri16_openings_gen_traces: the ROWSUM16 and QUERY16 main traces from raw rows [Q][W] and [Q][8], the constants [8][4] and the indices alone
+        -> (ROWSUM16 [2^lr][48], QUERY16 [2^lr][72] (canonical words, downloaded), the reduced openings [Q][4])"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        lns = {d[4]: d[1] for d in (fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, 0) for which in range(10))}
+        rs, qm = self.alloc(48 << lns[8]), self.alloc(72 << lns[3])
+        tr, qr, cs, ix = u(trows), u(qrows), u(consts), u(indices)
+        assert tr.size == n_queries * W and qr.size == 8 * n_queries and cs.size == 32 and ix.size == n_queries
+        ros = np.zeros(4 * n_queries, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_openings_gen_traces(self.handle, R, F, log_blowup, n_queries, pow_bits, W, tr.ctypes.data_as(u32p), qr.ctypes.data_as(u32p),
+                                                       cs.ctypes.data_as(u32p), ix.ctypes.data_as(u32p), C.c_void_p(rs.ptr), C.c_void_p(qm.ptr), ros.ctypes.data_as(u32p)))
+        return rs.download().reshape(-1, 48), qm.download().reshape(-1, 72), ros.reshape(-1, 4)
+
+    def prove_fri16_openings(self, key, view, params=None):
+        """zkhip_prove_fri16_openings: everything prove_fri16_indices states, and "the value at which query q enters layer 0 is the reduced opening of the trace
+        row and the quotient row listed for q, under the public constants, at the index drawn for q".  view: an indices view with "W", "trows" [Q][W], "qrows"
+        [Q][8] and "consts" {FA, ZETA, ZNX, YL, YN, YQ, OFFN, OFFQ: [4]}.  Refused before anything is proven, each naming the query: all prove_fri16_indices
+        refuses, a reduced opening the rows do not give, a point equal to zeta or zeta g, constants that do not match each other"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
+        W, trows, qrows, consts = _fri16_openings_arrays(view)
+        pb = int(view["pow_bits"])
+        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
+        assert cap.size == 8
+        size = self.lib.zkhip_fri16_openings_proof_size(*shape, pb, W, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_openings(self.handle, key.handle, *shape, hw, pb, W, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+                                                  paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]), trows.ctypes.data_as(u32p),
+                                                  qrows.ctypes.data_as(u32p), consts.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1638,6 +1682,72 @@ def verify_fri16_indices(proof, capacity, R, F, log_blowup, n_queries, pow_bits,
     reason = C.c_int(0)
     rc = lib.zkhip_verify_fri16_indices(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, cp.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
                                         C.byref(params), C.byref(reason))
+    return rc, reason.value
+
+
+FRI16_OPENING_CONSTANTS = ("FA", "ZETA", "ZNX", "YL", "YN", "YQ", "OFFN", "OFFQ")          # the order of the openings machine's public values behind the capacity
+
+
+def _fri16_openings_arrays(view):
+    """an openings view -> (trace width, trace rows [Q][W] flat, quotient rows [Q][8] flat, the constants [8][4] flat)"""
+    u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+    W, Q = int(view["W"]), len(view["queries"])
+    trows, qrows, consts = u(view["trows"]), u(view["qrows"]), u([view["consts"][n] for n in FRI16_OPENING_CONSTANTS])
+    assert trows.size == Q * W and qrows.size == 8 * Q and consts.size == 32
+    return W, trows, qrows, consts
+
+
+def fri16_view_openings(proof, log_n, width, public_values=(), params=None):
+    """zkhip_fri16_view_openings: what the reduced openings of a fold-by-16 proof are made of -> {"W", "trows": [Q][W], "qrows": [Q][8], "consts": {name: [4]}},
+    or raises if the proof is rejected or has lookup pairs.  Host only."""
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+    Q = int(params.num_queries)
+    trows, qrows, consts = np.zeros(Q * width, dtype=np.uint32), np.zeros(Q * 8, dtype=np.uint32), np.zeros(32, dtype=np.uint32)
+    check(lib.zkhip_fri16_view_openings(pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size, C.byref(params), trows.ctypes.data_as(u32p),
+                                        qrows.ctypes.data_as(u32p), consts.ctypes.data_as(u32p)))
+    return {"W": int(width), "trows": trows.reshape(Q, width).tolist(), "qrows": qrows.reshape(Q, 8).tolist(),
+            "consts": {n: consts[4 * i:4 * i + 4].tolist() for i, n in enumerate(FRI16_OPENING_CONSTANTS)}}
+
+
+def fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind):
+    """zkhip_fri16_openings_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..9) of the fold-16 openings machine
+    -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16C, 1 FINAL, 2 P24L, 3 QUERY16, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES, 8 ROWSUM16, 9 ROWS)"""
+    lib = _lib.load()
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    n = lib.zkhip_fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    if n == 0:
+        raise _lib.ZkHipError(-1, "fri16_openings_describe: " + lib.zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib.zkhip_fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
+                                             C.byref(tb)) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def fri16_openings_key_host(view, params=None):
+    """zkhip_fri16_openings_key_host: the fold-16 openings machine's key of a view (with "pow_bits", "W", "trows", "qrows"), without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+    W, trows, qrows, _ = _fri16_openings_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_openings_key_host(*shape, hw, int(view["pow_bits"]), W, *[a.ctypes.data_as(u32p) for a in (arrs[1], trows, qrows, roots)], C.byref(params),
+                                                    vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_openings(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
+    """zkhip_verify_fri16_openings: the shape, the inner proof's grinding bits and trace width, the 40 public values (capacity, then the eight constants), the key
+    -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32).reshape(-1))
+    assert pv.size == 40
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_fri16_openings(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, W, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
+                                         C.byref(params), C.byref(reason))
     return rc, reason.value
 
 
