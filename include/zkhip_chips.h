@@ -299,8 +299,8 @@ int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, i
  * FOLD16C's first rows, (q, AT) and (q, AQ) from ROWSUM16; 8 ROWSUM16, one row per 8 words of an opened row (per query the trace blocks from the last to the first,
  * then the quotient block): main V[8] ACCIN[4] T[8][4] FA[4], preprocessed (tag = 2 q + tree, active, not-first, last-of-trace, last-of-quotient, q, K0 = 2 block,
  * K1 = K0 + 1); sends (tag, K0, V0..V3) and (tag, K1, V4..V7) to ROWS, (q, T_0) to QUERY16 on a trace's block 0 and on the quotient block; 9 ROWS, preprocessed
- * (tag, K, w0..w3, 1): one row per 4-word group of every opened row, in the tuple form in which P24L's sponge rows receive theirs -- the table a width-24 chip
- * variant on the same bus replaces.  Heights: ROWSUM16 lg(Q (W / 8 + 1)), ROWS lg(Q (W + 8) / 4), QUERY16 lg(Q), at least 2^5.  Shapes: the indices machine's, W a
+ * (tag, K, w0..w3, 1): one row per 4-word group of every opened row, in the tuple form in which P24L's sponge rows receive theirs -- the table the width-24 chip
+ * variant P24R on the same bus replaces in the row-paths machine below.  Heights: ROWSUM16 lg(Q (W / 8 + 1)), ROWS lg(Q (W + 8) / 4), QUERY16 lg(Q), at least 2^5.  Shapes: the indices machine's, W a
  * multiple of 8 in 8 .. 1024, inner proofs without lookup pairs and with a quotient row of 8 words.
  * zkhip_fri16_view_openings (host only; fails like zkhip_fri16_view_shard; refuses proofs with lookup pairs; takes version-8 group-order proofs): per query the
  * trace row [Q][W] and the quotient row [Q][8] as the proof holds them, and the 32 constant words.  zkhip_fri16_openings_describe / _key_host (no GPU) / _key /
@@ -331,6 +331,55 @@ int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const zkhip_params* prm, uint8_t* proof, size_t cap,
                                size_t* len);
 int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason);
+
+/* ---- The fold-by-16 ROW-PATHS machine (fri16_chip.hip): the openings machine with the Merkle paths of the opened rows proven.  Everything the openings machine
+ * states, and: "the W words from which AT_q is summed are the leaf at the index drawn for query q of the width-24 Merkle tree of depth H = 4 R + F + log_blowup
+ * whose root the key lists as the trace root; the 8 words from which AQ_q is summed are the leaf at that index of the tree whose root it lists as the quotient
+ * root".  The 40 public values stay (the eight constants remain public in this step).  The key commits the layer roots, the final coefficients, the trace root
+ * and the quotient root: NO opened word, no index, no value.  Ten tables, the openings machine's numbering with P24R at 9 (tests/fri16_rowpaths_air.py writes all
+ * of it again): 0 FOLD16C, 1 FINAL, 2 P24L, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES, 8 ROWSUM16: the openings machine's programs and interaction tables word for word;
+ * ROOTS' key table gains the rows (R, H, trace root, not listed) and (R + 1, H, quotient root, not listed): nothing reaches them from the transcript, the existing
+ * constraint FOLDROWS (1 - LISTED) = 0 keeps them from handing FOLD16C a challenge, their path-end count is the prover's main column; 3 QUERY16: the program
+ * unchanged, preprocessed (q, active, 2 q, 2 q + 1, R, R + 1), two more sends (2 q, R, IDX) and (2 q + 1, R + 1, IDX) on a bus of their own -- which tree a tag
+ * belongs to and at which index it is opened; 9 P24R, a second layer-paths-style variant of the width-24 Poseidon2 chip, main only, 552 columns: the chip's 540
+ * in place, then TAG LNR KP DEP | IX BL LSP M0 | K0..K3.  One path per (query, tree), 2 Q paths, none shared: ceil(W / 16) sponge rows (the last one partial when
+ * W mod 16 = 8; one row of two groups for a quotient row), then H compression rows.  A sponge row receives (TAG, K_i = 4 BL + i, IN[4 i .. 4 i + 4]) with the
+ * multiplicities M0 = SS + SPG, G1, G2, G3 on ROWSUM16's bus (an absorbed group is always received, one not absorbed never); the SS row receives (TAG, LNR, IX) from
+ * QUERY16; the END row sends (LNR, DEP, digest) in two halves to ROOTS, whose tuple pins the depth to H.  The leaf's LENGTH is pinned by the bus, not by a one-hot
+ * as in P24L: ROWSUM16's sends are preprocessed, every group (tag, k) is sent exactly once, and with BL = 0 on SS and BL' = BL + 1 it can be received in block k / 4
+ * of a chain that starts at SS only (on the table's first row the chip's FIRST-row constraints CH = 0 and SPG = 0 stand in for the missing predecessor).  Heights: P24R lg(Q (ceil(W / 16) + 1 + 2 H)), at least 2^6 as ROWS had; a keyed machine takes at most 8 tables of one
+ * height, and a shape at which nine would meet is refused with a message (none of the shapes the openings machine takes is).
+ * zkhip_fri16_view_row_paths (host only; fails like zkhip_fri16_view_shard): per query the trace row's path and the quotient row's path, [Q][H][8] each, as the
+ * proof holds them, and the two roots; refuses proofs with lookup pairs, with a preprocessed commitment of their own (the trace leaf is then not the whole row)
+ * and with the width-16 hash.  zkhip_fri16_rowpaths_describe / _key_host (no GPU) / _key / _proof_size: as the _openings_ entries; the key takes the final
+ * coefficients, the layer roots, the trace root and the quotient root.  zkhip_fri16_rowpaths_gen_trace: P24R's main trace on the device (dense [2^lr][552],
+ * 16-byte aligned) from raw rows, indices and siblings alone, one launch (a wave per path); ends [2 Q][8] receives where every path ends, in tag order (query q's
+ * trace path, then its quotient path; canonical).  zkhip_prove_fri16_rowpaths takes the openings machine's arguments, the two trees' paths and the two roots, and
+ * refuses before anything is proven, each with a message that names query and tree: everything zkhip_prove_fri16_openings refuses, a path that does not end in its
+ * root, path words that are not canonical.  zkhip_verify_fri16_rowpaths is host only: shape, W, inner_pow_bits, the 40 public values, the key.
+ * STILL OUTSIDE after this machine: the transcript before the commit phase (so the eight constants and where the two roots come from), lookups, the AIR identity
+ * at zeta, the wiring into the shard verifier machines (shard_verifier.inl). */
+int zkhip_fri16_view_row_paths(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                               uint32_t* trace_paths, uint32_t* quotient_paths, uint32_t trace_root[8], uint32_t quotient_root[8]);
+size_t zkhip_fri16_rowpaths_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
+                                     size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_rowpaths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
+                                  const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_rowpaths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                             zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_rowpaths_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm);
+int zkhip_fri16_rowpaths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
+                                   const uint32_t* quotient_rows, const uint32_t* indices, const uint32_t* trace_paths, const uint32_t* quotient_paths, uint32_t* d_trace,
+                                   uint32_t* ends);
+int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness,
+                               const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths,
+                               const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint8_t* proof,
+                               size_t cap, size_t* len);
+int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that

@@ -57,6 +57,8 @@ EXPORTS = [
     "zkhip_fri16_indices_gen_traces", "zkhip_fri16_samples_gen_trace", "zkhip_prove_fri16_indices", "zkhip_verify_fri16_indices",
     "zkhip_fri16_view_openings", "zkhip_fri16_openings_describe", "zkhip_fri16_openings_key_host", "zkhip_fri16_openings_key", "zkhip_fri16_openings_proof_size",
     "zkhip_fri16_openings_gen_traces", "zkhip_prove_fri16_openings", "zkhip_verify_fri16_openings",
+    "zkhip_fri16_view_row_paths", "zkhip_fri16_rowpaths_describe", "zkhip_fri16_rowpaths_key_host", "zkhip_fri16_rowpaths_key", "zkhip_fri16_rowpaths_proof_size",
+    "zkhip_fri16_rowpaths_gen_trace", "zkhip_prove_fri16_rowpaths", "zkhip_verify_fri16_rowpaths",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -392,6 +394,18 @@ def load():
     L.zkhip_prove_fri16_openings.argtypes = [C.c_void_p, C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
                                                                                         C.POINTER(Params), u8p, C.c_size_t, szp]
     L.zkhip_verify_fri16_openings.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
+    # the fold-16 row-paths machine: the openings machine with the opened rows' Merkle paths proven (the key takes roots, no row)
+    L.zkhip_fri16_view_row_paths.argtypes = [u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), u32p, u32p, u32p, u32p]
+    L.zkhip_fri16_rowpaths_describe.restype = C.c_size_t
+    L.zkhip_fri16_rowpaths_describe.argtypes = L.zkhip_fri16_openings_describe.argtypes
+    L.zkhip_fri16_rowpaths_key_host.argtypes = fri16_oshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), u32p]    # final_poly, layer roots, trace root, quotient root
+    L.zkhip_fri16_rowpaths_key.argtypes = [C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_rowpaths_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_rowpaths_proof_size.argtypes = L.zkhip_fri16_openings_proof_size.argtypes
+    L.zkhip_fri16_rowpaths_gen_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, u32p, u32p, u32p, u32p, u32p, C.c_void_p, u32p]
+    L.zkhip_prove_fri16_rowpaths.argtypes = [C.c_void_p, C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
+                                                                                        u32p, u32p, u32p, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16_rowpaths.argtypes = L.zkhip_verify_fri16_openings.argtypes
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -32,6 +32,9 @@
 // The OPENINGS machine (zkhip_prove_fri16_openings) is the indices machine with the reduced openings computed in-circuit: ROWSUM16 sums the opened trace row and quotient
 // row in fa, QUERY16 puts the three quotients together at the point FOLD16C hands it; the key holds the opened rows and no reduced opening; the eight constants of the
 // formula are PUBLIC VALUES in this step -- the step that brings them in over buses is a later one (tests/fri16_openings_air.py).
+// The ROW-PATHS machine (zkhip_prove_fri16_rowpaths) is the openings machine with the Merkle paths of the opened trace row and quotient row proven: P24R, a second
+// layer-paths-style variant of the width-24 chip, stands where the preprocessed ROWS table stood; the key holds roots and final coefficients only, no opened word
+// (tests/fri16_rowpaths_air.py).
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -53,6 +56,7 @@
 namespace zk {
 extern std::atomic<uint64_t> g_p2_generation;      // params.cpp
 namespace p24chip { std::shared_ptr<const std::vector<uint32_t>> program_fri16_layers(uint32_t n_public); }      // poseidon2_chip.cpp
+namespace p24chip { std::shared_ptr<const std::vector<uint32_t>> program_fri16_rows(uint32_t n_public); }
 namespace p2chip { std::vector<uint32_t> permutation_body(uint32_t col_offset, uint32_t* count); }                // poseidon2_chip.cpp: the permutation's constraints behind preprocessed columns
 namespace frichip {                                                                                               // fri_chip.hip: the SAMPLES chip
 std::shared_ptr<const std::vector<uint32_t>> samples_chip_program(int index_bits, int pow_bits, uint32_t n_public);
@@ -758,9 +762,11 @@ void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots
 //   ROWSUM16 one row per 8 words of an opened row, per query the trace blocks from the last to the first, then the quotient block: V[8] ACCIN[4] T[8][4] FA[4], FA tied
 //            to the public values; preprocessed TAG = 2 q + tree, ACT, NOTFIRST, LAST0, LAST1, QN, K0 = 2 block, K1 = K0 + 1.  Sends (TAG, K0, V0..V3) and
 //            (TAG, K1, V4..V7) to ROWS, (QN, T_0) to QUERY16 on a trace's block 0 (LAST0) and on the quotient block (LAST1)
-//   ROWS     preprocessed (TAG, K, w0..w3, 1): one row per 4-word group of every opened row, the tuple form in which P24L's sponge rows receive theirs -- THE TABLE A
-//            WIDTH-24 CHIP VARIANT ON THE SAME BUS REPLACES: until then the Merkle paths of the trace and quotient rows are NOT proven
-// STILL OUTSIDE: those paths, the transcript before the commit phase (so the eight constants), lookups, the AIR identity.  tests/fri16_openings_air.py writes it again.
+//   ROWS     preprocessed (TAG, K, w0..w3, 1): one row per 4-word group of every opened row, the tuple form in which P24L's sponge rows receive theirs.  In THIS
+//            machine the Merkle paths of the trace and quotient rows are NOT proven: the ROW-PATHS machine below is this one with the width-24 chip variant P24R
+//            on the same bus where ROWS stands here
+// STILL OUTSIDE: those paths (proven by the row-paths machine), the transcript before the commit phase (so the eight constants), lookups, the AIR identity.
+// tests/fri16_openings_air.py writes it again.
 constexpr uint32_t BUS_ROW16 = 81, BUS_AT16 = 82, BUS_AQ16 = 83, N_PUBLIC_O = 40, Q16_PRE = 8, QP_QN = 0, QP_ACT = 1, RS16_PRE = 8, ROWS_PRE16 = 8, QROW16 = 8;
 constexpr uint32_t RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST0 = 3, RP_LAST1 = 4, RP_QN = 5, RP_K0 = 6, RP_K1 = 7;
 constexpr uint32_t PUB_FA = 8, PUB_ZETA = 12;       // public values: FA, then ZETA ZNX YL YN YQ OFFN OFFQ in QUERY16's column order
@@ -940,29 +946,36 @@ std::shared_ptr<const OMachine> openings_machine_of(const OShape& s) {
     cache.emplace(key, m);
     return m;
 }
+// ROWSUM16's schedule: per query the trace blocks from the last to the first, then the quotient block
+void rowsum16_schedule(size_t Q, size_t W, int log_rows, std::vector<uint32_t>& t) {
+    const size_t WB = W / 8;
+    t.assign((size_t)RS16_PRE << log_rows, 0u);
+    size_t r = 0;
+    for (size_t q = 0; q < Q; q++)
+        for (size_t pos = 0; pos <= WB; pos++) {
+            const bool quot = pos == WB;
+            const size_t blk = quot ? 0 : WB - 1 - pos;
+            uint32_t* w = t.data() + RS16_PRE * r++;
+            w[RP_TAG] = to_monty((uint32_t)(2 * q + (quot ? 1 : 0))); w[RP_ACT] = MONTY_R1; w[RP_NOTFIRST] = pos == 0 || quot ? 0u : MONTY_R1;
+            w[RP_LAST0] = !quot && blk == 0 ? MONTY_R1 : 0u; w[RP_LAST1] = quot ? MONTY_R1 : 0u; w[RP_QN] = to_monty((uint32_t)q);
+            w[RP_K0] = to_monty((uint32_t)(2 * blk)); w[RP_K1] = to_monty((uint32_t)(2 * blk + 1));
+        }
+}
 // the key's tables by table number: the indices machine's (QUERY16's schedule where its QUERIES stood), ROWSUM16's schedule and ROWS -- the rows go in, no reduced opening
 int build_openings_key_tables(const OShape& s, const uint32_t* final_poly, const uint32_t* trows, const uint32_t* qrows, const uint32_t* roots, std::vector<uint32_t> pre[N_OT],
                               const char* who) {
     const Shape& b = s.i.p.base;
-    const size_t Q = b.Q, W = s.W, WB = W / 8;
+    const size_t Q = b.Q, W = s.W;
     if (!trows || !qrows) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     if (!canonical(trows, Q * W) || !canonical(qrows, Q * QROW16)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     const std::vector<uint32_t> no_values(4 * Q, 0u);
     ZK_TRY(build_indices_key_tables(s.i, final_poly, no_values.data(), roots, pre, who));
     pre[T_QUERY16].assign((size_t)Q16_PRE << s.log_rows[T_QUERY16], 0u);
     for (size_t q = 0; q < Q; q++) { pre[T_QUERY16][Q16_PRE * q + QP_QN] = to_monty((uint32_t)q); pre[T_QUERY16][Q16_PRE * q + QP_ACT] = MONTY_R1; }
-    pre[T_ROWSUM16].assign((size_t)RS16_PRE << s.log_rows[T_ROWSUM16], 0u);
+    rowsum16_schedule(Q, W, s.log_rows[T_ROWSUM16], pre[T_ROWSUM16]);
     pre[T_ROWS].assign((size_t)ROWS_PRE16 << s.log_rows[T_ROWS], 0u);
-    size_t r = 0, g = 0;
+    size_t g = 0;
     for (size_t q = 0; q < Q; q++) {
-        for (size_t pos = 0; pos <= WB; pos++) {
-            const bool quot = pos == WB;
-            const size_t blk = quot ? 0 : WB - 1 - pos;
-            uint32_t* w = pre[T_ROWSUM16].data() + RS16_PRE * r++;
-            w[RP_TAG] = to_monty((uint32_t)(2 * q + (quot ? 1 : 0))); w[RP_ACT] = MONTY_R1; w[RP_NOTFIRST] = pos == 0 || quot ? 0u : MONTY_R1;
-            w[RP_LAST0] = !quot && blk == 0 ? MONTY_R1 : 0u; w[RP_LAST1] = quot ? MONTY_R1 : 0u; w[RP_QN] = to_monty((uint32_t)q);
-            w[RP_K0] = to_monty((uint32_t)(2 * blk)); w[RP_K1] = to_monty((uint32_t)(2 * blk + 1));
-        }
         for (int tree = 0; tree < 2; tree++) {
             const uint32_t* row = tree ? qrows + QROW16 * q : trows + W * q;
             for (size_t k = 0; k < (tree ? QROW16 : W) / 4; k++) {
@@ -984,6 +997,118 @@ int check_openings_constants(const OShape& s, const uint32_t* consts, const char
     if (!ext_eq(ext_from_canon(consts + 8), ext_mul_base(zeta, two_adic_generator(b.H - b.b))) || !ext_eq(ext_from_canon(consts + 24), ext_pow(fa, s.W)) ||
         !ext_eq(ext_from_canon(consts + 28), ext_pow(fa, 2 * (uint64_t)s.W)))
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constants do not match each other (zeta g_N, OFFN = fa^W, OFFQ = fa^(2W))");
+    return ZKHIP_OK;
+}
+
+// ---------------------------------------------------------------- the ROW-PATHS machine: the openings machine with the opened rows' Merkle paths proven
+// Table numbers as in the openings machine with P24R at 9; the 40 public values stay.  FOLD16C, FINAL, P24L, COEFFS, ROOTS, P2T, SAMPLES and ROWSUM16: the openings
+// machine's programs and interaction tables word for word (taken from it, not built again).  The key commits the layer roots, the final coefficients, the trace root
+// and the quotient root: NO opened word.
+//   ROOTS    key table: two more rows, (LN = R, DEP = H, trace root, LISTED = 0) and (LN = R + 1, DEP = H, quotient root, LISTED = 0) -- not listed: nothing comes from
+//            the transcript, and FOLDROWS (1 - LISTED) = 0 keeps them from handing FOLD16C a challenge; their path-end count is the prover's main column
+//   QUERY16  program unchanged; preprocessed (q, ACT, TG0 = 2 q, TG1 = 2 q + 1, LN0 = R, LN1 = R + 1); two more sends on BUS_TAG16, (TG0, LN0, IDX) and (TG1, LN1, IDX),
+//            multiplicity ACT: which tree a tag belongs to and at which index it is opened (the parity of a tag means nothing in the field)
+//   P24R     p24chip.h's row-paths variant, main only: one path per (query, tree), 2 Q paths, none shared; a sponge row receives (TAG, K_i, IN[4 i .. 4 i + 4]) with the
+//            multiplicities M0, G1, G2, G3 on ROWSUM16's bus, the SS row (TAG, LNR, IX) from QUERY16, the END row sends (LNR, DEP, digest) in two halves to ROOTS.
+//            The leaf's length is pinned by the bus: ROWSUM16's sends are preprocessed, every group (TAG, k) is sent once, and with K_i = 4 BL + i and BL restarting at
+//            0 on SS it can be received in block k / 4 of a chain that starts at SS only
+// P24R has lg(Q (ceil(W / 16) + 1 + 2 H)) rows, at least 2^6 as ROWS had.  STILL OUTSIDE: the transcript before the commit phase (so the eight constants and where the
+// two roots come from), lookups, the AIR identity at zeta.  tests/fri16_rowpaths_air.py writes it again.
+constexpr uint32_t BUS_TAG16 = 84, QP_TG0 = 2, QP_TG1 = 3, QP_LN0 = 4, QP_LN1 = 5;
+enum : int { T_P24R = 9, MAX_SAME_HEIGHT = 8 };
+struct RShape {
+    OShape o;
+    int log_rows[N_OT], order[N_OT];
+    uint32_t main_w[N_OT], pre_w[N_OT];
+};
+int rowpaths_shape_of(int R, int F, int b, size_t Q, int pow_bits, uint32_t W, RShape& s) {
+    ZK_TRY(openings_shape_of(R, F, b, Q, pow_bits, W, s.o));
+    const size_t per_query = (size_t)(W + 15) / 16 + 1 + 2 * (size_t)s.o.i.p.base.H;
+    for (int t = 0; t < N_OT; t++) {
+        const bool r = t == T_P24R;
+        s.log_rows[t] = r ? std::max(6, lg(Q * per_query)) : s.o.log_rows[t];
+        s.main_w[t] = r ? p24chip::WIDTH_R : s.o.main_w[t]; s.pre_w[t] = r ? 0u : s.o.pre_w[t]; s.order[t] = t;
+    }
+    std::stable_sort(s.order, s.order + N_OT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    for (int t = 0; t < N_OT; t++)
+        if (std::count(s.log_rows, s.log_rows + N_OT, s.log_rows[t]) > MAX_SAME_HEIGHT)
+            return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
+    return ZKHIP_OK;
+}
+std::vector<uint32_t> build_rowpaths_interactions(int R, int lf, int table) {
+    std::vector<uint32_t> v = table == T_P24R ? std::vector<uint32_t>{LOOKUP_MAGIC, 0u, 0u} : build_openings_interactions(R, lf, table);
+    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
+        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
+        v.insert(v.end(), cols.begin(), cols.end());
+        v[1]++;
+    };
+    if (table == T_QUERY16) {
+        add(0u, QP_ACT, BUS_TAG16, {QP_TG0, QP_LN0, QC_IDX});
+        add(0u, QP_ACT, BUS_TAG16, {QP_TG1, QP_LN1, QC_IDX});
+    } else if (table == T_P24R) {
+        using namespace p24chip;
+        const uint32_t o7 = oute(7), mult[4] = {R_M0, p24chip::G(1), p24chip::G(2), p24chip::G(3)};
+        for (uint32_t i = 0; i < 4; i++) add(1u, mult[i], BUS_ROW16, {R_TAG, R_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
+        add(1u, SS, BUS_TAG16, {R_TAG, R_LNR, R_IX});
+        add(0u, END, BUS_RT0, {R_LNR, R_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
+        add(0u, END, BUS_RT1, {R_LNR, R_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
+    }
+    v[2] = (uint32_t)v.size();
+    return v;
+}
+struct RMachine {
+    RShape s;
+    std::vector<uint32_t> prog[N_OT], tab[N_OT];
+    int32_t log_ns[N_OT]; uint32_t widths[N_OT], pre_widths[N_OT];
+    const uint32_t* progs[N_OT]; size_t prog_words[N_OT]; const uint32_t* tabs[N_OT]; size_t tab_words[N_OT];
+};
+std::shared_ptr<const RMachine> rowpaths_machine_of(const RShape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 6>, std::shared_ptr<const RMachine>> cache;
+    static uint64_t cached_gen = ~0ull;
+    const auto om = openings_machine_of(s.o);                  // (before the lock: it drops its own cache on the same generation)
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
+    const Shape& b = s.o.i.p.base;
+    const std::array<uint64_t, 6> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.o.i.pow_bits, (uint64_t)s.o.W};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<RMachine>();
+    m->s = s;
+    for (int i = 0; i < N_OT; i++) {
+        const int t = s.order[i];
+        if (t == T_P24R) m->prog[i] = *p24chip::program_fri16_rows(N_PUBLIC_O);
+        else m->prog[i] = om->prog[std::find(s.o.order, s.o.order + N_OT, t) - s.o.order];
+        m->tab[i] = t == T_P24R || t == T_QUERY16 ? build_rowpaths_interactions(b.R, b.lf, t) : om->tab[std::find(s.o.order, s.o.order + N_OT, t) - s.o.order];
+        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
+        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
+    }
+    cache.emplace(key, m);
+    return m;
+}
+// the key's tables by table number: the indices machine's, QUERY16's schedule with the tags and tree numbers, ROWSUM16's schedule, the two roots in ROOTS -- no row
+int build_rowpaths_key_tables(const RShape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root,
+                              std::vector<uint32_t> pre[N_OT], const char* who) {
+    const Shape& b = s.o.i.p.base;
+    const size_t Q = b.Q, R = (size_t)b.R;
+    if (!trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(trace_root, 8) || !canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    const std::vector<uint32_t> no_values(4 * Q, 0u);
+    ZK_TRY(build_indices_key_tables(s.o.i, final_poly, no_values.data(), roots, pre, who));
+    pre[T_QUERY16].assign((size_t)Q16_PRE << s.log_rows[T_QUERY16], 0u);
+    for (size_t q = 0; q < Q; q++) {
+        uint32_t* w = pre[T_QUERY16].data() + Q16_PRE * q;
+        w[QP_QN] = to_monty((uint32_t)q); w[QP_ACT] = MONTY_R1; w[QP_TG0] = to_monty((uint32_t)(2 * q)); w[QP_TG1] = to_monty((uint32_t)(2 * q + 1));
+        w[QP_LN0] = to_monty((uint32_t)R); w[QP_LN1] = to_monty((uint32_t)R + 1u);
+    }
+    for (size_t tree = 0; tree < 2; tree++) {                  // (R + 2 <= 7 rows of 2^5; column 10, LISTED, stays zero)
+        uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (R + tree);
+        w[RT_LN] = to_monty((uint32_t)(R + tree)); w[RT_DEP] = to_monty((uint32_t)b.H);
+        for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty((tree ? quotient_root : trace_root)[j]);
+    }
+    rowsum16_schedule(Q, s.o.W, s.log_rows[T_ROWSUM16], pre[T_ROWSUM16]);
+    pre[T_P24R].clear();
     return ZKHIP_OK;
 }
 
@@ -1537,7 +1662,8 @@ int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_b
 // canonical, where the fold kernel reads its chains' first values); status[0] / status[1]: the least query whose opening differs from view_values / whose point has no
 // inverse (0xFFFFFFFF: none)
 static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices,
-                                    const uint32_t* view_values, uint32_t* d_rowsum, uint32_t* d_query, uint32_t** d_openings, uint32_t status[2], const uint32_t** d_indices = nullptr) {
+                                    const uint32_t* view_values, uint32_t* d_rowsum, uint32_t* d_query, uint32_t** d_openings, uint32_t status[2], const uint32_t** d_indices = nullptr,
+                                    const uint32_t** d_rows = nullptr) {      // d_rows: where the raw rows lie on the device, [Q][W] then [Q][8]
     const fri16::Shape& b = s.i.p.base;
     const size_t Q = b.Q, W = s.W, nt = Q * W, nq = Q * fri16::QROW16, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q;
     const size_t o_q = nt, o_c = o_q + nq, o_i = o_c + 32, o_v = o_i + ni, o_open = o_v + nv, o_status = o_open + nv, words = o_status + 4;
@@ -1571,6 +1697,7 @@ static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::OShape& s, cons
     status[0] = st[0]; status[1] = st[1];
     *d_openings = a.openings;
     if (d_indices) *d_indices = a.indices;
+    if (d_rows) *d_rows = d;
     return ZKHIP_OK;
 }
 static int fri16_openings_check_rows(const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices, const char* who) {
@@ -1749,6 +1876,242 @@ int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, 
         return fail(ZKHIP_ERR_VERIFY, "verify_fri16_openings: bad arguments");
     }
     const auto m = fri16::openings_machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, public_values,
+                                      fri16::N_PUBLIC_O, prm, reason);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the row-paths machine's entries
+// P24R in one launch: a path per (query, tree), tag order.  d_rows: the raw rows where fri16_openings_rows_impl left them on the device ([Q][W], then [Q][8]), or null:
+// they are uploaded here.  ends [2 Q][8]: where every path ends (canonical).
+static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::RShape& s, const uint32_t* d_rows, const uint32_t* trows, const uint32_t* qrows, const uint32_t* indices,
+                                        const uint32_t* tpaths, const uint32_t* qpaths, uint32_t* d_trace, size_t ld, std::vector<uint32_t>& ends) {
+    const fri16::Shape& b = s.o.i.p.base;
+    const size_t Q = b.Q, W = s.o.W, H = (size_t)b.H, n = 2 * Q, blocks = (W + 15) / 16, rows = (size_t)1 << s.log_rows[fri16::T_P24R];
+    const size_t nd = 8 * n, ns = 8 * H * n, nr = d_rows ? 0 : Q * (W + fri16::QROW16), up_words = nd + ns + nr;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 8 * n) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    size_t used = 0;
+    {
+        std::vector<uint32_t> up(up_words, 0u);
+        for (size_t q = 0; q < Q; q++)
+            for (size_t tree = 0; tree < 2; tree++) {
+                const size_t p = 2 * q + tree;
+                const uint32_t desc[8] = {(uint32_t)p, (uint32_t)((size_t)b.R + tree), indices[q], (uint32_t)(tree ? fri16::QROW16 : W), (uint32_t)used,
+                                          (uint32_t)(tree ? Q * W + fri16::QROW16 * q : W * q), (uint32_t)(8 * H * p), 0u};
+                std::memcpy(up.data() + 8 * p, desc, 32);
+                std::memcpy(up.data() + nd + 8 * H * p, (tree ? qpaths : tpaths) + 8 * H * q, 32 * H);
+                used += (tree ? 1 : blocks) + H;
+            }
+        if (!d_rows) {
+            std::memcpy(up.data() + nd + ns, trows, Q * W * 4);
+            std::memcpy(up.data() + nd + ns + Q * W, qrows, Q * fri16::QROW16 * 4);
+        }
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
+    }
+    if (used > rows) return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: the paths do not fit the table");
+    p24chip::RowPathsArgs a{};
+    a.desc = d; a.siblings = d + nd; a.rows = d_rows ? d_rows : d + nd + ns; a.n_paths = n; a.trace_rows = rows; a.used_rows = used; a.depth = (uint32_t)H;
+    a.trace = d_trace; a.ld = ld; a.ends = d + up_words;
+    ZK_HIP(launch_p24chip_row_paths(a, ctx->stream));
+    ends.resize(8 * n);
+    return dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4);
+}
+// refused before anything is hashed: null or non-canonical path words, by query and tree
+static int fri16_rowpaths_check_paths(const fri16::RShape& s, const uint32_t* tpaths, const uint32_t* qpaths, const uint32_t* troot, const uint32_t* qroot, const char* who) {
+    const fri16::Shape& b = s.o.i.p.base;
+    if (!tpaths || !qpaths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (troot && (!qroot || !fri16::canonical(troot, 8) || !fri16::canonical(qroot, 8))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+    const size_t per = 8 * (size_t)b.H;
+    for (size_t q = 0; q < b.Q; q++)
+        for (int tree = 0; tree < 2; tree++)
+            if (!fri16::canonical((tree ? qpaths : tpaths) + per * q, per))
+                return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(q) + ", " + (tree ? "quotient" : "trace") + " tree: path words must be canonical");
+    return ZKHIP_OK;
+}
+
+extern "C" {
+
+size_t zkhip_fri16_rowpaths_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
+                                     size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
+    fri16::RShape s;
+    if (which < 0 || which >= fri16::N_OT || kind < 0 || kind > 1 || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::rowpaths_machine_of(s);
+    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+
+int zkhip_fri16_rowpaths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
+                                  const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::RShape s;
+    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::N_OT];
+    ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key_host"));
+    const auto m = fri16::rowpaths_machine_of(s);
+    const uint32_t* h[fri16::N_OT];
+    for (int i = 0; i < fri16::N_OT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_OT, prm, vk);
+}
+
+int zkhip_fri16_rowpaths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                             zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::RShape s;
+    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key: null argument");
+    std::vector<uint32_t> pre[fri16::N_OT];
+    ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key"));
+    const auto m = fri16::rowpaths_machine_of(s);
+    const int slots[fri16::N_OT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, -1};      // by table number: the seven tables with preprocessed columns
+    zkhip_chip chips[fri16::N_OT]{};
+    for (int i = 0; i < fri16::N_OT; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips, fri16::N_OT, prm, key, vk);
+}
+
+size_t zkhip_fri16_rowpaths_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
+    fri16::RShape s;
+    if (!prm || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
+    const auto m = fri16::rowpaths_machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, prm, fri16::N_PUBLIC_O);
+}
+
+int zkhip_fri16_rowpaths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
+                                   const uint32_t* quotient_rows, const uint32_t* indices, const uint32_t* trace_paths, const uint32_t* quotient_paths, uint32_t* d_trace,
+                                   uint32_t* ends) {
+    CHECK_CTX(ctx);
+    fri16::RShape s;
+    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    const fri16::Shape& b = s.o.i.p.base;
+    if (!trace_rows || !quotient_rows || !indices || !d_trace || !ends || (uintptr_t)d_trace % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: null argument, or a trace that is not 16-byte aligned (dense, 552 columns)");
+    if (!fri16::canonical(trace_rows, b.Q * (size_t)s.o.W) || !fri16::canonical(quotient_rows, b.Q * fri16::QROW16))
+        return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: values must be canonical");
+    for (size_t q = 0; q < b.Q; q++) if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: a query index has more bits than the proof's domain");
+    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, nullptr, nullptr, "fri16_rowpaths_gen_trace"));
+    std::vector<uint32_t> e;
+    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, nullptr, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, d_trace, p24chip::WIDTH_R, e));
+    std::memcpy(ends, e.data(), e.size() * 4);
+    return ZKHIP_OK;
+}
+
+int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness,
+                               const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths,
+                               const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint8_t* proof,
+                               size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    fri16::RShape s;
+    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: null argument");
+    const fri16::OShape& os = s.o;
+    const fri16::IShape& is = os.i;
+    const fri16::PShape& ps = is.p;
+    ZK_TRY(fri16_paths_check_view(ps.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_rowpaths"));
+    ZK_TRY(fri16_indices_check_inputs(is, capacity, roots, final_poly, witness, "prove_fri16_rowpaths"));
+    ZK_TRY(fri16_openings_check_rows(os, trace_rows, quotient_rows, constants, indices, "prove_fri16_rowpaths"));
+    ZK_TRY(fri16::check_openings_constants(os, constants, "prove_fri16_rowpaths"));
+    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, "prove_fri16_rowpaths"));
+    const auto m = fri16::rowpaths_machine_of(s);
+    using namespace fri16;
+    const size_t ld_fold = s.main_w[T_FOLD16], Q = ps.base.Q;
+    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp, *t_rs, *t_q, *t_p24r;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, (ld_fold << s.log_rows[T_FOLD16]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[T_FINAL] << s.log_rows[T_FINAL]) * 4, &t_final));
+    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[T_P24L]) * 4, &t_p24));
+    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[T_P2T]) * 4, &t_p2t));
+    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[T_SAMPLES]) * 4, &t_smp));
+    ZK_TRY(ctx_reserve(ctx, S_REC_F, ((size_t)RS_MAIN16 << s.log_rows[T_ROWSUM16]) * 4, &t_rs));
+    ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
+    ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
+    // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; a scratch QUERIES block the transcript kernel fills
+    size_t zoff[N_OT] = {0}, zwords = 0;
+    for (int t : {(int)T_QUERIES, (int)T_COEFFS, (int)T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)(t == T_QUERIES ? TAB_MAIN : s.main_w[t]) << s.log_rows[t]; }
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
+    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_COEFFS], 0, ((size_t)s.main_w[T_COEFFS] << s.log_rows[T_COEFFS]) * 4));
+    // refused here, before anything is proven: all zkhip_prove_fri16_openings refuses; then row paths that do not end in their roots
+    Chain c;
+    walk_chain(is, capacity, roots, final_poly, witness, c);
+    PathPlan pl;
+    ZK_TRY(plan_paths(ps.base, indices, paths, pl));
+    uint32_t status = 0;
+    ZK_TRY(fri16_transcript_impl(ctx, is, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[T_QUERIES],
+                                 (uint32_t*)t_tabs + zoff[T_ROOTS], &status));
+    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the challenges are not the ones the transcript draws from these roots and this capacity");
+    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the witness does not satisfy the proof of work");
+    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the query indices are not the ones the transcript draws");
+    {
+        const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
+        for (size_t tree = 0; tree < 2; tree++)
+            ZK_TRY(dev_h2d(ctx, (uint32_t*)t_tabs + zoff[T_ROOTS] + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
+    }
+    uint32_t ost[2], *d_open = nullptr;
+    const uint32_t *d_idx = nullptr, *d_rows = nullptr;
+    ZK_TRY(fri16_openings_rows_impl(ctx, os, trace_rows, quotient_rows, constants, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx, &d_rows));
+    if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse("prove_fri16_rowpaths", ost[1]);
+    if (ost[0] != 0xFFFFFFFFu)
+        return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
+    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, ld_fold, (uint32_t*)t_final, s.main_w[T_FINAL], d_open));
+    {
+        XqColsArgs xa{};
+        xa.indices = d_idx; xa.Q = (uint32_t)Q; xa.R = (uint32_t)R; xa.H = (uint32_t)ps.base.H;
+        xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = (uint32_t*)t_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
+        ZK_LAUNCH(fri16_xq_cols_kernel, fri16_xq_cols_kernel_batch, xq_cols_bargs, dim3((unsigned)((xa.rows + 63) / 64)), dim3(64), 0, ctx->stream, xa);
+        ZK_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    for (size_t p = 0; p < pl.n; p++)
+        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " does not open: its path does not end in the layer's root");
+    // P24R from the raw rows the openings launch left on the device (the staging block of S_REC_J is not reserved again before this)
+    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
+    for (size_t p = 0; p < 2 * Q; p++)
+        if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") +
+                                               " tree: the opened row's path does not end in the root");
+    zkhip_chip chips[N_OT]{};
+    for (int i = 0; i < N_OT; i++) {
+        const int t = s.order[i];
+        chips[i].d_trace = t == T_FOLD16 ? (const uint32_t*)t_fold : t == T_FINAL ? (const uint32_t*)t_final : t == T_P24L ? (const uint32_t*)t_p24
+                         : t == T_P2T ? (const uint32_t*)t_p2t : t == T_SAMPLES ? (const uint32_t*)t_smp : t == T_ROWSUM16 ? (const uint32_t*)t_rs
+                         : t == T_QUERY16 ? (const uint32_t*)t_q : t == T_P24R ? (const uint32_t*)t_p24r : (const uint32_t*)t_tabs + zoff[t];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    uint32_t pub[N_PUBLIC_O];
+    std::memcpy(pub, capacity, 32);
+    std::memcpy(pub + 8, constants, 128);
+    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, N_OT, pub, N_PUBLIC_O, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    fri16::RShape s;
+    if (!proof || !public_values || !vk || !prm || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_rowpaths: bad arguments");
+    }
+    const auto m = fri16::rowpaths_machine_of(s);
     return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, public_values,
                                       fri16::N_PUBLIC_O, prm, reason);
 }

@@ -183,8 +183,9 @@ hipError_t stark_upload_p2_tables(const P2Tables& t, hipStream_t s);
 namespace p2chip { struct MerkleTraceArgs; struct LayerPathsArgs; struct P2RArgs; struct MrecChainArgs; struct Fri16TranscriptArgs; }
 hipError_t launch_p2chip_merkle(const p2chip::MerkleTraceArgs& a, hipStream_t s);
 // ... and of the width-24 chip (p24chip.h)
-namespace p24chip { struct MerkleTraceArgs; struct LayerPathsArgs; }
+namespace p24chip { struct MerkleTraceArgs; struct LayerPathsArgs; struct RowPathsArgs; }
 hipError_t launch_p24chip_merkle(const p24chip::MerkleTraceArgs& a, hipStream_t s);
+hipError_t launch_p24chip_row_paths(const p24chip::RowPathsArgs& a, hipStream_t s);       // the fold-16 row-paths machine's P24R table: one launch, both trees
 hipError_t launch_p24chip_layer_paths(const p24chip::LayerPathsArgs& a, hipStream_t s);   // the fold-16 paths machine's P24L table: one launch, all layers
 hipError_t launch_fri16_transcript(const p2chip::Fri16TranscriptArgs& a, hipStream_t s);    // the fold-16 indices machine: P2T, SAMPLES and the main columns of QUERIES and ROOTS, one launch
 hipError_t launch_p2chip_layer_paths(const p2chip::LayerPathsArgs& a, hipStream_t s);     // the FRI-layers variant: paths of different depths

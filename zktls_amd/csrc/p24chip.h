@@ -57,5 +57,21 @@ struct LayerPathsArgs {
     uint32_t* differs;           // [n_paths]: 0, or 1 + the number (within the path's readers) of the first reader whose 64 words are not the first reader's
 };
 
+// The ROW-PATHS variant (the fold-16 row-paths machine, fri16_chip.hip: P24R stands where the ROWS table stood).  The 540 columns keep their positions; the tail:
+// TAG 2 query + tree | LNR the tree's number in ROOTS | KP index walk | DEP compression rows so far | IX the index | BL block number | LSP last sponge row | M0 sponge
+// row | K0..K3 = 4 BL + i the bus keys of the row's four groups.  A path = ceil(width / 16) sponge rows over the opened row (the last one absorbs 2 groups when
+// width mod 16 = 8; KP = 2 index, DEP = 0), then `depth` compression rows (KP = index >> level, DEP = level + 1, the other tail cells but TAG and LNR zero).
+constexpr uint32_t R_TAG = 540, R_LNR = 541, R_KP = 542, R_DEP = 543, R_IX = 544, R_BL = 545, R_LSP = 546, R_M0 = 547, R_K = 548, WIDTH_R = 552;
+static_assert(R_TAG == WIDTH && WIDTH_R == WIDTH_L, "p24chip row-paths tail: the layer-paths variant's width, so that its row writer serves both");
+struct RowPathsArgs {
+    const uint32_t* desc;        // [n_paths][8]: tag, tree number, index, leaf width, first trace row, word offset of the leaf in `rows`, word offset into `siblings`, 0
+    const uint32_t* rows;        // the raw opened rows (canonical words) already on the device
+    const uint32_t* siblings;    // canonical digests, `depth` of them per path from its offset
+    uint64_t n_paths, trace_rows, used_rows;
+    uint32_t depth;
+    uint32_t* trace; uint64_t ld;   // [trace_rows][ld], Montgomery; 16-byte aligned, ld % 4 == 0
+    uint32_t* ends;              // [n_paths][8] canonical: where each path ends
+};
+
 }  // namespace p24chip
 }  // namespace zk

@@ -409,7 +409,9 @@ struct Layout24 {
 
 // layers: the layer-paths variant P24L of the fold-16 paths machine (p24chip.h: the tail columns; fri16_chip.hip: the machine) -- no public root and
 // count, n_public public values of the machine's, and the constraints of leaf shape, path shape, index, depth and bus keys at the end
-std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_PUBLIC) {
+// rows: the row-paths variant P24R of the fold-16 row-paths machine (p24chip.h: its tail columns) -- the same chip part, then the sponge chain of floating length (BL
+// counts the blocks from SS on, LSP marks the last one), path shape, tag and tree, index, depth and bus keys.  The leaf's LENGTH is pinned by the bus, not here.
+std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_PUBLIC, bool rows = false) {
     using p2chip::ALL; using p2chip::FIRST; using p2chip::LAST; using p2chip::TRANSITION;
     Builder b;
     uint32_t ME[24][24], rc_e[8][24], rc_i[21], diag[24];
@@ -440,10 +442,10 @@ std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_P
         for (uint32_t j = 4 * k; j < 4 * k + 4; j++)
             b.add(TRANSITION, Terms{{1u, {var(C(k), true), var(IN + j, true)}}, {P - 1, {var(C(k), true), var(o7 + j)}}});
     for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(CH, true), var(D + j, true)}}, {P - 1, {var(CH, true), var(o7 + j)}}});
-    if (!layers) for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(END), var(o7 + j)}}, {P - 1, {var(END), pub(j)}}});
+    if (!layers && !rows) for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(END), var(o7 + j)}}, {P - 1, {var(END), pub(j)}}});
     b.add(FIRST, Terms{{1u, {var(CNT)}}, {P - 1, {var(END)}}});
     b.add(TRANSITION, Terms{{1u, {var(CNT, true)}}, {P - 1, {var(CNT)}}, {P - 1, {var(END, true)}}});
-    if (!layers) b.add(LAST, Terms{{1u, {var(CNT)}}, {P - 1, {pub(8)}}});
+    if (!layers && !rows) b.add(LAST, Terms{{1u, {var(CNT)}}, {P - 1, {pub(8)}}});
     if (layers) {
         const uint32_t Z0 = L_Z, Z1 = L_Z + 1, Z2 = L_Z + 2, Z3 = L_Z + 3;
         // leaf shape: Z_k one-hot number of a sponge row, Z0 = SS, SPG = Z1 + Z2 + Z3, stepping 0 1 2 3; every block is full
@@ -474,7 +476,43 @@ std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_P
             b.add(ALL, Terms{{1u, {var(L_K + i)}}, {P - 8, {var(SS), var(L_KP)}}, {P - 8, {var(SPG), var(L_KP)}}, {neg(i), {var(Z0)}}, {neg(4 + i), {var(Z1)}},
                              {neg(8 + i), {var(Z2)}}, {neg(12 + i), {var(Z3)}}});
     }
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, layers ? WIDTH_L : WIDTH, b.count, n_public, (uint32_t)(6 + b.body.size())};
+    if (rows) {
+        const uint32_t M0 = R_M0, LSP = R_LSP, BL = R_BL, IX = R_IX, KP = R_KP, DEP = R_DEP;
+        // the sponge chain: M0 marks a sponge row; blocks count from SS on; a sponge row that is not the last one is followed by a continuing one, and no other row is
+        b.add(ALL, Terms{{1u, {var(M0)}}, {P - 1, {var(SS)}}, {P - 1, {var(SPG)}}});
+        b.add(ALL, Terms{{1u, {var(SS), var(SPG)}}});
+        for (uint32_t k = 1; k <= 3; k++) b.add(ALL, Terms{{1u, {var(G(k))}}, {P - 1, {var(G(k)), var(M0)}}});
+        b.add(ALL, Terms{{1u, {var(LSP), var(LSP)}}, {P - 1, {var(LSP)}}});
+        b.add(ALL, Terms{{1u, {var(LSP)}}, {P - 1, {var(LSP), var(M0)}}});
+        b.add(ALL, Terms{{1u, {var(SS), var(BL)}}});
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true), var(BL, true)}}, {P - 1, {var(SPG, true), var(BL)}}, {P - 1, {var(SPG, true)}}});
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true)}}, {P - 1, {var(M0)}}, {1u, {var(LSP)}}});
+        // path shape
+        b.add(TRANSITION, Terms{{1u, {var(CH, true)}}, {P - 1, {var(LSP)}}, {P - 1, {var(CH)}}, {1u, {var(END)}}});
+        b.add(LAST, Terms{{1u, {var(M0)}}, {1u, {var(CH)}}, {P - 1, {var(END)}}});
+        b.add(ALL, Terms{{1u, {var(END)}}, {P - 1, {var(END), var(CH)}}});
+        b.add(ALL, Terms{{1u, {var(M0), var(CH)}}});
+        b.add(ALL, Terms{{1u, {var(M0), var(BIT)}}});
+        for (uint32_t col : {R_TAG, R_LNR})                                                                       // one tag and one tree per path
+            b.add(TRANSITION, Terms{{1u, {var(CH, true), var(col, true)}}, {P - 1, {var(CH, true), var(col)}},
+                                    {1u, {var(SPG, true), var(col, true)}}, {P - 1, {var(SPG, true), var(col)}}});
+        // index: KP = 2 IX on the leaf, then the recurrence of the layer-paths variant
+        b.add(ALL, Terms{{1u, {var(M0), var(KP)}}, {P - 2, {var(M0), var(IX)}}});
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true), var(KP, true)}}, {P - 1, {var(SPG, true), var(KP)}}});
+        b.add(TRANSITION, Terms{{1u, {var(SPG, true), var(IX, true)}}, {P - 1, {var(SPG, true), var(IX)}}});
+        b.add(TRANSITION, Terms{{1u, {var(CH, true), var(KP)}}, {P - 2, {var(CH, true), var(KP, true)}}, {P - 1, {var(CH, true), var(BIT)}}});
+        b.add(ALL, Terms{{1u, {var(END), var(KP)}}, {P - 1, {var(END), var(BIT)}}});
+        // depth
+        b.add(ALL, Terms{{1u, {var(M0), var(DEP)}}});
+        b.add(TRANSITION, Terms{{1u, {var(CH, true), var(DEP, true)}}, {P - 1, {var(CH, true), var(DEP)}}, {P - 1, {var(CH, true)}}});
+        // bus keys: group i of block BL is the row's group 4 BL + i
+        for (uint32_t i = 0; i < 4; i++) {
+            Terms t{{1u, {var(R_K + i)}}, {P - 4, {var(M0), var(BL)}}};
+            if (i) t.push_back(Term{neg(i), {var(M0)}});
+            b.add(ALL, t);
+        }
+    }
+    std::vector<uint32_t> p{AIR_MAGIC, 1u, layers ? WIDTH_L : rows ? WIDTH_R : WIDTH, b.count, n_public, (uint32_t)(6 + b.body.size())};
     p.insert(p.end(), b.body.begin(), b.body.end());
     return p;
 }
@@ -501,6 +539,18 @@ std::shared_ptr<const std::vector<uint32_t>> program_fri16_layers(uint32_t n_pub
     if (cached_gen != gen) { cache.clear(); cached_gen = gen; }
     auto it = cache.find(n_public);
     if (it == cache.end()) it = cache.emplace(n_public, std::make_shared<const std::vector<uint32_t>>(build_program(true, n_public))).first;
+    return it->second;
+}
+// the row-paths variant P24R for a machine with n_public public values (fri16_chip.hip)
+std::shared_ptr<const std::vector<uint32_t>> program_fri16_rows(uint32_t n_public) {
+    static std::mutex mu;
+    static std::map<uint32_t, std::shared_ptr<const std::vector<uint32_t>>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen) { cache.clear(); cached_gen = gen; }
+    auto it = cache.find(n_public);
+    if (it == cache.end()) it = cache.emplace(n_public, std::make_shared<const std::vector<uint32_t>>(build_program(false, n_public, true))).first;
     return it->second;
 }
 namespace {

@@ -177,6 +177,8 @@ struct FriViewSink {
     // openings (zkhip_fri16_view_openings): per query the opened trace row (width words) and quotient row as the proof holds them, and the eight constants
     // of the reduced opening -- fa, zeta, zeta g_N, y_loc, y_nxt, y_q, fa^width, fa^(2 width), four words each
     uint32_t *trace_rows = nullptr, *quotient_rows = nullptr, *constants = nullptr;
+    // row paths (zkhip_fri16_view_row_paths): per query the trace row's and the quotient row's Merkle path ([Q][H][8] each) as the proof holds them, and the two roots
+    uint32_t *trace_paths = nullptr, *quotient_paths = nullptr, *trace_root = nullptr, *quotient_root = nullptr;
 };
 
 static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
@@ -365,6 +367,7 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
         else for (int i = 0; i < 4; i++) sink->final_value[i] = from_monty(final_poly[0].c[i]);
         for (int q = 0; q < NQ_; q++) sink->indices[q] = (uint32_t)indices[q];
         if (sink->roots) for (int l = 0; l < RL; l++) for (int i = 0; i < 8; i++) sink->roots[8 * l + i] = from_monty(commits[8 * l + i]);
+        if (sink->trace_root) for (int i = 0; i < 8; i++) { sink->trace_root[i] = from_monty(troot[i]); sink->quotient_root[i] = from_monty(qroot[i]); }
     }
     const size_t pos0 = pos, words_total = len / 4;
     if ((words_total - pos0) % (size_t)NQ_ != 0) return reject(5);
@@ -394,6 +397,10 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
             if (sink && sink->trace_rows) {
                 std::memcpy(sink->trace_rows + (size_t)(q0 + j) * width, trow[j], 4 * (size_t)width);
                 std::memcpy(sink->quotient_rows + (size_t)(q0 + j) * QW, qrow[j], 4 * QW);
+            }
+            if (sink && sink->trace_paths) {
+                std::memcpy(sink->trace_paths + (size_t)(q0 + j) * 8 * (size_t)H, tpath[j], 32 * (size_t)H);
+                std::memcpy(sink->quotient_paths + (size_t)(q0 + j) * 8 * (size_t)H, qpath[j], 32 * (size_t)H);
             }
         }
         auto batch = [&](const uint32_t* const* rows, size_t row_off, const uint32_t* const* paths, const size_t* idx) {
@@ -593,6 +600,29 @@ int zkhip_fri16_view_openings(const uint8_t* proof, size_t len, int log_n, uint3
     sink.fold16 = true;
     sink.final_poly = final_poly.data();
     sink.trace_rows = trace_rows; sink.quotient_rows = quotient_rows; sink.constants = constants;
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
+}
+
+// ... and the Merkle paths of those rows (the row-paths machine of fri16_chip.hip): per query the trace row's path and the quotient row's path, [Q][H][8] each, H =
+// log_n + log_blowup, as the proof holds them, and the trace root and the quotient root.  Refused: lookup pairs; a preprocessed commitment of the proof's own (the
+// trace leaf is then not the whole row); the width-16 hash (the machine's chip is the width-24 one).
+int zkhip_fri16_view_row_paths(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                               uint32_t* trace_paths, uint32_t* quotient_paths, uint32_t trace_root[8], uint32_t quotient_root[8]) {
+    if (!prm || !trace_paths || !quotient_paths || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "fri16_view_row_paths: null argument");
+    Shape sh;
+    if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_row_paths: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    if (prm->logup_pairs) return fail(ZKHIP_ERR_INVALID, "fri16_view_row_paths: proofs with lookup pairs are not taken (logup_pairs = 0 only)");
+    if (sh.cw) return fail(ZKHIP_ERR_INVALID, "fri16_view_row_paths: proofs with a preprocessed commitment of their own are not taken (the trace leaf is not the whole row)");
+    if (sh.hw != 24) return fail(ZKHIP_ERR_INVALID, "fri16_view_row_paths: proofs with the width-16 hash are not taken (the row-paths machine opens width-24 Poseidon2 commitments)");
+    const size_t Q = (size_t)prm->num_queries;
+    std::vector<uint32_t> betas(4 * (size_t)sh.R), final_poly((size_t)4 << sh.F), indices(Q), values(4 * Q), siblings(60 * Q * (size_t)sh.R);
+    FriViewSink sink{betas.data(), nullptr, indices.data(), values.data(), siblings.data(), sh.R, nullptr, nullptr, nullptr};
+    sink.fold16 = true;
+    sink.final_poly = final_poly.data();
+    sink.trace_paths = trace_paths; sink.quotient_paths = quotient_paths; sink.trace_root = trace_root; sink.quotient_root = quotient_root;
     int why = 0;
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }

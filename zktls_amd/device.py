@@ -851,6 +851,53 @@ class Context:
                                                   qrows.ctypes.data_as(u32p), consts.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 ROW-PATHS machine (the opened rows' Merkle paths in-circuit: P24R where ROWS stood)
+    def fri16_rowpaths_key(self, view, params=None):
+        """zkhip_fri16_rowpaths_key: the key of the fold-16 row-paths machine, committed on the device -- from the shape, the inner proof's grinding bits and trace
+        width, the final coefficients, the layer roots, the trace root and the quotient root: no row, no index, no value -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+        _, _, troot, qroot = _fri16_rowpaths_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_rowpaths_key(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)],
+                                                C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_rowpaths_gen_trace(self, R, F, log_blowup, n_queries, pow_bits, W, trows, qrows, indices, tpaths, qpaths):
+        """zkhip_fri16_rowpaths_gen_trace: P24R's main trace from raw rows [Q][W] and [Q][8], the indices and the siblings [Q][H][8] of either tree alone, one launch
+        -> (P24R [2^lr][552] (canonical words, downloaded), the path ends [2 Q][8] in tag order: query q's trace path, then its quotient path)"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        lns = {d[4]: d[1] for d in (fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, 0) for which in range(10))}
+        H = 4 * R + F + log_blowup
+        tr, qr, ix, tp, qp = u(trows), u(qrows), u(indices), u(tpaths), u(qpaths)
+        assert tr.size == n_queries * W and qr.size == 8 * n_queries and ix.size == n_queries and tp.size == qp.size == 8 * H * n_queries
+        trace = self.alloc(552 << lns[9])
+        ends = np.zeros(16 * n_queries, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_rowpaths_gen_trace(self.handle, R, F, log_blowup, n_queries, pow_bits, W, *[a.ctypes.data_as(u32p) for a in (tr, qr, ix, tp, qp)],
+                                                      C.c_void_p(trace.ptr), ends.ctypes.data_as(u32p)))
+        return trace.download().reshape(-1, 552), ends.reshape(-1, 8)
+
+    def prove_fri16_rowpaths(self, key, view, params=None):
+        """zkhip_prove_fri16_rowpaths: everything prove_fri16_openings states, and "the rows from which AT_q and AQ_q are summed are the leaves at the index drawn for
+        q of the trees whose roots the key lists as the trace root and the quotient root".  view: an openings view with "tpaths" / "qpaths" [Q][H][8] and "troot" /
+        "qroot" [8].  Refused before anything is proven, each naming query and tree: all prove_fri16_openings refuses, a path that does not end in its root,
+        path words that are not canonical"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
+        W, trows, qrows, consts = _fri16_openings_arrays(view)
+        tpaths, qpaths, troot, qroot = _fri16_rowpaths_arrays(view)
+        pb = int(view["pow_bits"])
+        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
+        assert cap.size == 8
+        size = self.lib.zkhip_fri16_rowpaths_proof_size(*shape, pb, W, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_rowpaths(self.handle, key.handle, *shape, hw, pb, W, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+                                                  paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]),
+                                                  *[a.ctypes.data_as(u32p) for a in (trows, qrows, consts, tpaths, qpaths, troot, qroot)], C.byref(params),
+                                                  buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1747,6 +1794,69 @@ def verify_fri16_openings(proof, public_values, R, F, log_blowup, n_queries, pow
     k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
     reason = C.c_int(0)
     rc = lib.zkhip_verify_fri16_openings(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, W, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
+                                         C.byref(params), C.byref(reason))
+    return rc, reason.value
+
+
+def _fri16_rowpaths_arrays(view):
+    """a row-paths view -> (trace paths [Q][H][8] flat, quotient paths [Q][H][8] flat, trace root [8], quotient root [8])"""
+    u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+    Q, H = len(view["queries"]), int(view["H"])
+    tpaths, qpaths, troot, qroot = u(view["tpaths"]), u(view["qpaths"]), u(view["troot"]), u(view["qroot"])
+    assert tpaths.size == qpaths.size == 8 * H * Q and troot.size == qroot.size == 8
+    return tpaths, qpaths, troot, qroot
+
+
+def fri16_view_row_paths(proof, log_n, width, public_values=(), params=None):
+    """zkhip_fri16_view_row_paths: the Merkle paths of the rows a fold-by-16 proof opens -> {"tpaths": [Q][H][8], "qpaths": [Q][H][8], "troot": [8], "qroot": [8]},
+    or raises if the proof is rejected, has lookup pairs, a preprocessed commitment of its own or the width-16 hash.  Host only."""
+    params = params or _lib.segment_params()
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+    Q, H = int(params.num_queries), log_n + int(params.log_blowup)
+    tp, qp, tr, qr = np.zeros(Q * H * 8, dtype=np.uint32), np.zeros(Q * H * 8, dtype=np.uint32), np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
+    check(lib.zkhip_fri16_view_row_paths(pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size, C.byref(params),
+                                         *[a.ctypes.data_as(u32p) for a in (tp, qp, tr, qr)]))
+    return {"tpaths": tp.reshape(Q, H, 8).tolist(), "qpaths": qp.reshape(Q, H, 8).tolist(), "troot": tr.tolist(), "qroot": qr.tolist()}
+
+
+def fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind):
+    """zkhip_fri16_rowpaths_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..9) of the fold-16 row-paths machine
+    -> (words, log rows, main width, preprocessed width, table number: the openings machine's with 9 P24R); raises with the library's message for a shape it refuses"""
+    lib = _lib.load()
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    n = lib.zkhip_fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    if n == 0:
+        raise _lib.ZkHipError(-1, "fri16_rowpaths_describe: " + lib.zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib.zkhip_fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
+                                             C.byref(tb)) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def fri16_rowpaths_key_host(view, params=None):
+    """zkhip_fri16_rowpaths_key_host: the fold-16 row-paths machine's key of a view (with "pow_bits", "W", "troot", "qroot"), without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+    _, _, troot, qroot = _fri16_rowpaths_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_rowpaths_key_host(*shape, hw, int(view["pow_bits"]), int(view["W"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)],
+                                                    C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_rowpaths(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
+    """zkhip_verify_fri16_rowpaths: the shape, the inner proof's grinding bits and trace width, the 40 public values (capacity, then the eight constants), the key
+    -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32).reshape(-1))
+    assert pv.size == 40
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = lib.zkhip_verify_fri16_rowpaths(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, W, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
                                          C.byref(params), C.byref(reason))
     return rc, reason.value
 
