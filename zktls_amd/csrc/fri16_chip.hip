@@ -24,17 +24,27 @@
 //   3 QUERIES  preprocessed: distinct (index, reduced opening) with multiplicity.       4 COEFFS  preprocessed: (j, c_j, queries).
 // NOT in this machine: the Merkle paths of the layer rows, the transcript (challenges, query indices), the reduced openings.  tests/fri16_air.py writes
 // the programs, tables and traces independently; the words must be equal.
-// The PATHS machine (further down; zkhip_prove_fri16_paths) is this machine with P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands,
-// and a preprocessed ROOTS table: there the layer rows' Merkle paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py).
-// The INDICES machine (last; zkhip_prove_fri16_indices) is the paths machine with the Fiat-Shamir transcript inside: a transcript-only width-16 Poseidon2 table (P2T)
-// walks the duplex challenger from the commit phase on, the SAMPLES chip of fri_chip.hip takes the bits of the words it hands out; the challenges reach FOLD16 over a
-// bus and the key holds neither a challenge nor an index (tests/fri16_transcript_air.py).
-// The OPENINGS machine (zkhip_prove_fri16_openings) is the indices machine with the reduced openings computed in-circuit: ROWSUM16 sums the opened trace row and quotient
-// row in fa, QUERY16 puts the three quotients together at the point FOLD16C hands it; the key holds the opened rows and no reduced opening; the eight constants of the
-// formula are PUBLIC VALUES in this step -- the step that brings them in over buses is a later one (tests/fri16_openings_air.py).
-// The ROW-PATHS machine (zkhip_prove_fri16_rowpaths) is the openings machine with the Merkle paths of the opened trace row and quotient row proven: P24R, a second
-// layer-paths-style variant of the width-24 chip, stands where the preprocessed ROWS table stood; the key holds roots and final coefficients only, no opened word
-// (tests/fri16_rowpaths_air.py).
+// FIVE machines are kept here as ONE description read at five kinds (enum Kind), each kind the one before it with a step more of the inner verifier inside:
+//   LAYERS   (zkhip_prove_fri16)           the five tables above
+//   PATHS    (zkhip_prove_fri16_paths)     P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands, and a preprocessed ROOTS table: the layer rows' Merkle
+//                                          paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py)
+//   INDICES  (zkhip_prove_fri16_indices)   the Fiat-Shamir transcript inside: a transcript-only width-16 Poseidon2 table (P2T) walks the duplex challenger from the commit phase
+//                                          on, the SAMPLES chip of fri_chip.hip takes the bits of the words it hands out; the challenges reach FOLD16 over a bus and the key
+//                                          holds neither a challenge nor an index (tests/fri16_transcript_air.py)
+//   OPENINGS (zkhip_prove_fri16_openings)  the reduced openings computed in-circuit: ROWSUM16 sums the opened trace row and quotient row in fa, QUERY16 puts the three quotients
+//                                          together at the point FOLD16C hands it; the key holds the opened rows and no reduced opening; the eight constants of the formula are
+//                                          PUBLIC VALUES in this step -- the step that brings them in over buses is a later one (tests/fri16_openings_air.py)
+//   ROWPATHS (zkhip_prove_fri16_rowpaths)  the Merkle paths of the opened trace row and quotient row proven: P24R, a second layer-paths-style variant of the width-24 chip,
+//                                          stands where the preprocessed ROWS table stood; the key holds roots and final coefficients only, no opened word
+//                                          (tests/fri16_rowpaths_air.py)
+// The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
+// table number the height and widths, the machine order), shape_of (every kind's validity checks, one sort), program_of and interactions_of (per TABLE, what each kind adds
+// to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape) -- and what every entry does with it (describe, key_host, key_upload,
+// proof_size, prove, verify); then the kernels' launchers, the provers' stages (transcript, openings, layer paths) and the extern "C" entries, which are a shape call,
+// their own argument checks and those helpers.  The builders of constraint programs and interaction tables are air_builder.h's, shared with the other chips.
+// ADDING A KIND: a value of Kind and its table count in N_TABLES; its new or replaced tables in shape_of (with its checks), program_of and interactions_of -- one `if` on
+// the kind in the case of every table it touches; its public values in n_public_of; a builder of its key tables beside the others; a stage for what its prover launches;
+// its entries.  Machine, machine_of and the helpers take no new case.
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -46,6 +56,7 @@
 #include <vector>
 
 #include "air.h"
+#include "air_builder.h"
 #include "context.h"
 #include "batch.h"
 #include "fri16_rows.cuh"
@@ -66,64 +77,30 @@ void samples_chip_pre(size_t nq, int log_rows, int first_row, std::vector<uint32
 }
 namespace fri16 {
 namespace {
+using namespace airb;
 
 constexpr uint32_t BUS_L16 = 70, BUS_Q16 = 71, BUS_FIN16 = 72, BUS_COEF = 73;
 constexpr uint32_t FJ = 0, FFIRST = 1, FLAST = 2, FACT = 3, FNL = 4;                                  // FINAL's schedule; its main columns in the combined row:
 constexpr uint32_t CFC = FIN_PRE + FC, CFACC = FIN_PRE + FACC, CFAX = FIN_PRE + FAX, CFX = FIN_PRE + FX;
 constexpr uint32_t LAY_PRE = 84, LAY_LN = 0, LAY_KEY = 1, LAY_M = 17, LAY_E = 20, Q_PRE = 8, C_PRE = 8, TAB_MAIN = 4;
-enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_QUERIES = 3, T_COEFFS = 4 };
-
-struct Term { uint32_t coeff; std::vector<uint32_t> vars; };
-typedef std::vector<Term> Terms;
-inline uint32_t var(uint32_t col, bool next = false) { return next ? ((1u << 30) | col) : col; }
-inline uint32_t pub(uint32_t idx) { return (2u << 30) | idx; }
-inline uint32_t neg(uint64_t c) { c %= P; return c ? (uint32_t)(P - c) : 0u; }
-inline uint32_t mulm(uint64_t a, uint64_t b) { return (uint32_t)((a % P) * (b % P) % P); }
-enum : uint32_t { ALL = 0, FIRST = 1, LAST = 2, TRANSITION = 3 };
-struct Builder {
-    std::vector<uint32_t> body;
-    uint32_t count = 0;
-    void add(uint32_t selector, const Terms& terms) {
-        body.push_back(selector);
-        const size_t at = body.size();
-        body.push_back(0u);
-        uint32_t kept = 0;
-        for (const Term& t : terms) {
-            if (t.coeff % P == 0) continue;
-            body.push_back(t.coeff % P);
-            body.push_back((uint32_t)t.vars.size());
-            for (uint32_t v : t.vars) body.push_back(v);
-            kept++;
-        }
-        body[at] = kept;
-        count++;
-    }
-    std::vector<uint32_t> finish(uint32_t width, uint32_t n_public) const {
-        std::vector<uint32_t> p{AIR_MAGIC, 1u, width, count, n_public, (uint32_t)(6 + body.size())};
-        p.insert(p.end(), body.begin(), body.end());
-        return p;
-    }
-};
+// ONE numbering of the tables for the five kinds: a later kind appends tables (5; 6, 7; 8, 9) or puts a chip where a key table stood (2, 3, 9)
+enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_P24L = 2, T_QUERIES = 3, T_QUERY16 = 3, T_COEFFS = 4, T_ROOTS = 5, T_P2T = 6, T_SAMPLES = 7, T_ROWSUM16 = 8, T_ROWS = 9,
+              T_P24R = 9, MAX_TABLES = 10 };
 inline uint32_t canon_nibble_factor(uint32_t first_bit, uint32_t nbits, uint32_t j) { return from_monty(nibble_factor(first_bit, nbits, j)); }
 
+// The five machines are ONE description read at five kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
+// (pow_bits, C S NT from INDICES on; W from OPENINGS on) stays zero below it.  shape_of, program_of, interactions_of and machine_of are further down, behind the chips.
+enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS };
 struct Shape {
-    int R = 0, F = 0, b = 0, lf = 0, H = 0;
-    size_t Q = 0;
-    int log_rows[5];            // by table number
-    int order[5];               // machine position -> table number
-    uint32_t main_w[5], pre_w[5];
+    Kind kind = LAYERS;
+    int R = 0, F = 0, b = 0, lf = 0, H = 0, pow_bits = 0, n_tables = 0;
+    size_t Q = 0, C = 0, S = 0, NT = 0;      // C, S, NT: coefficient rows, rows that hand words out, rows of the transcript's chain
+    uint32_t W = 0;                          // the inner proof's trace width
+    int log_rows[MAX_TABLES];                // by table number
+    int order[MAX_TABLES];                   // machine position -> table number
+    uint32_t main_w[MAX_TABLES], pre_w[MAX_TABLES];
 };
 inline int lg(size_t n) { int l = 5; while (((size_t)1 << l) < n) l++; return l; }
-int shape_of(int R, int F, int b, size_t Q, Shape& s) {
-    if (R < 1 || R > MAX_R || F < 0 || F > MAX_F || b < 1 || b > 3 || F + b > MAX_LF || Q < 1 || Q > MAX_Q || 4 * R + F + b > TWO_ADICITY)
-        return fail(ZKHIP_ERR_INVALID, "fri16: 1..5 layers, log_final 0..8, log_blowup 1..3 (log_final + log_blowup <= 11), 1..1024 queries, and a domain of at most 2^27 points");
-    s.R = R; s.F = F; s.b = b; s.lf = F + b; s.H = 4 * R + s.lf; s.Q = Q;
-    const int lr[5] = {lg(Q * (size_t)R), lg(Q << F), lg(Q * (size_t)R), lg(Q), lg((size_t)1 << F)};
-    const uint32_t mw[5] = {fold16_width((uint32_t)s.lf), FIN_MAIN, TAB_MAIN, TAB_MAIN, TAB_MAIN}, pw[5] = {0u, FIN_PRE, LAY_PRE, Q_PRE, C_PRE};
-    for (int i = 0; i < 5; i++) { s.log_rows[i] = lr[i]; s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
-    std::stable_sort(s.order, s.order + 5, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
-    return ZKHIP_OK;
-}
 
 std::vector<uint32_t> build_fold16_program(int R, int lf, bool beta_bus = false, uint32_t n_public = 0) {      // beta_bus: FOLD16B, BETA is received, not public
     Builder b;
@@ -267,60 +244,6 @@ std::vector<uint32_t> build_final_program(uint32_t n_public) {
 std::vector<uint32_t> build_table_program(uint32_t n_public, uint32_t pre_width, uint32_t main_width = TAB_MAIN) {          // the contents are fixed by the KEY: one harmless identity
     return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + main_width, 1u, n_public, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + main_width - 1u)};
 }
-std::vector<uint32_t> build_interactions(int R, int table) {
-    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
-    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
-        v.insert(v.end(), cols.begin(), cols.end());
-        v[1]++;
-    };
-    switch (table) {
-    case T_FOLD16:
-        for (uint32_t j = 0; j < 16; j++) add(0u, ACTIVE, BUS_L16, {LN, KJ + j, E + 4 * j, E + 4 * j + 1, E + 4 * j + 2, E + 4 * j + 3});
-        add(0u, L, BUS_Q16, {IDX, OWN, OWN + 1, OWN + 2, OWN + 3});
-        add(0u, L + (uint32_t)R - 1u, BUS_FIN16, {X16, FOLD, FOLD + 1, FOLD + 2, FOLD + 3});
-        break;
-    case T_FINAL:
-        add(1u, FACT, BUS_COEF, {FJ, CFC, CFC + 1, CFC + 2, CFC + 3});
-        add(1u, FLAST, BUS_FIN16, {CFX, CFACC, CFACC + 1, CFACC + 2, CFACC + 3});
-        break;
-    case T_LAYERS:
-        for (uint32_t j = 0; j < 16; j++) add(1u, LAY_M, BUS_L16, {LAY_LN, LAY_KEY + j, LAY_E + 4 * j, LAY_E + 4 * j + 1, LAY_E + 4 * j + 2, LAY_E + 4 * j + 3});
-        break;
-    case T_QUERIES: add(1u, 5u, BUS_Q16, {0u, 1u, 2u, 3u, 4u}); break;
-    default: add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u}); break;
-    }
-    v[2] = (uint32_t)v.size();
-    return v;
-}
-
-// programs and interaction tables of a shape, in MACHINE order, with the arrays the keyed-machine entries take
-struct Machine {
-    Shape s;
-    std::vector<uint32_t> prog[5], tab[5];
-    int32_t log_ns[5]; uint32_t widths[5], pre_widths[5];
-    const uint32_t* progs[5]; size_t prog_words[5]; const uint32_t* tabs[5]; size_t tab_words[5];
-};
-std::shared_ptr<const Machine> machine_of(const Shape& s) {
-    static std::mutex mu;
-    static std::map<std::array<uint64_t, 4>, std::shared_ptr<const Machine>> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    const std::array<uint64_t, 4> key{(uint64_t)s.R, (uint64_t)s.F, (uint64_t)s.b, (uint64_t)s.Q};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto m = std::make_shared<Machine>();
-    m->s = s;
-    for (int i = 0; i < 5; i++) {
-        const int t = s.order[i];
-        m->prog[i] = t == T_FOLD16 ? build_fold16_program(s.R, s.lf) : t == T_FINAL ? build_final_program(4u * (uint32_t)s.R) : build_table_program(4u * (uint32_t)s.R, s.pre_w[t]);
-        m->tab[i] = build_interactions(s.R, t);
-        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
-        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
-    }
-    if (cache.size() > 64) cache.clear();
-    cache.emplace(key, m);
-    return m;
-}
 
 inline Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
 bool canonical(const uint32_t* v, size_t n) { for (size_t i = 0; i < n; i++) if (v[i] >= P) return false; return true; }
@@ -374,7 +297,7 @@ void fill_schedule_queries_coeffs(const Shape& s, const uint32_t* final_poly, co
 // The three key tables and FINAL's schedule from a view (host, canonical -> Montgomery), by table number.  Walks every chain: queries that meet must
 // agree about the row, and every chain must end in the final polynomial at its last point -- a view taken from an accepted proof always does.
 int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings,
-                 std::vector<uint32_t> pre[5]) {
+                 std::vector<uint32_t> pre[]) {
     const size_t R = (size_t)s.R, n = (size_t)1 << s.F;
     std::map<std::pair<uint32_t, uint32_t>, std::pair<std::array<uint32_t, 64>, uint32_t>> layers;      // (layer, row) -> entries (Montgomery), count
     std::map<std::array<uint32_t, 5>, uint32_t> queries;                                                 // (index, value) canonical -> count
@@ -424,94 +347,25 @@ int build_tables(const Shape& s, const uint32_t* betas, const uint32_t* final_po
 // width-24 chip's layer-paths variant (p24chip.h, poseidon2_chip.cpp): its sponge rows receive on BUS_L16 what FOLD16 sends, its END rows send
 // (layer, depth, digest) in two halves to ROOTS (preprocessed layer, depth, root[8]; main: the number of path ends of the layer, the prover's).
 constexpr uint32_t BUS_RT0 = 74, BUS_RT1 = 75, ROOTS_PRE16 = 12, RT_LN = 0, RT_DEP = 1, RT_ROOT = 2;
-enum : int { T_P24L = 2, T_ROOTS = 5, N_PT = 6 };
-struct PShape {
-    Shape base;
-    int log_rows[N_PT], order[N_PT];
-    uint32_t main_w[N_PT], pre_w[N_PT];
-};
-int paths_shape_of(int R, int F, int b, size_t Q, PShape& s) {
-    ZK_TRY(shape_of(R, F, b, Q, s.base));
-    size_t per_query = 0;
-    for (int l = 0; l < R; l++) per_query += (size_t)p24chip::LEAF_ROWS + (size_t)(s.base.H - 4 * (l + 1));
-    const int lr[N_PT] = {s.base.log_rows[0], s.base.log_rows[1], lg(Q * per_query), s.base.log_rows[3], s.base.log_rows[4], lg((size_t)R)};
-    const uint32_t mw[N_PT] = {s.base.main_w[0], FIN_MAIN, p24chip::WIDTH_L, TAB_MAIN, TAB_MAIN, TAB_MAIN}, pw[N_PT] = {0u, FIN_PRE, 0u, Q_PRE, C_PRE, ROOTS_PRE16};
-    for (int i = 0; i < N_PT; i++) { s.log_rows[i] = lr[i]; s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
-    std::stable_sort(s.order, s.order + N_PT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
-    return ZKHIP_OK;
-}
-std::vector<uint32_t> build_paths_interactions(int R, int table) {
-    if (table != T_P24L && table != T_ROOTS) return build_interactions(R, table);          // FOLD16, FINAL, QUERIES, COEFFS: the numbers and the words of the machine above
-    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
-    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
-        v.insert(v.end(), cols.begin(), cols.end());
-        v[1]++;
-    };
-    if (table == T_P24L) {
-        using namespace p24chip;
-        const uint32_t o7 = oute(7);
-        for (uint32_t i = 0; i < 4; i++) add(1u, L_M, BUS_L16, {L_LN, L_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
-        add(0u, END, BUS_RT0, {L_LN, L_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
-        add(0u, END, BUS_RT1, {L_LN, L_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
-    } else {
-        add(1u, ROOTS_PRE16, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
-        add(1u, ROOTS_PRE16, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
-    }
-    v[2] = (uint32_t)v.size();
-    return v;
-}
-struct PMachine {
-    PShape s;
-    std::vector<uint32_t> prog[N_PT], tab[N_PT];
-    int32_t log_ns[N_PT]; uint32_t widths[N_PT], pre_widths[N_PT];
-    const uint32_t* progs[N_PT]; size_t prog_words[N_PT]; const uint32_t* tabs[N_PT]; size_t tab_words[N_PT];
-};
-// (P24L's program follows the width-24 tables in effect: the cache is dropped when they change)
-std::shared_ptr<const PMachine> paths_machine_of(const PShape& s) {
-    static std::mutex mu;
-    static std::map<std::array<uint64_t, 4>, std::shared_ptr<const PMachine>> cache;
-    static uint64_t cached_gen = ~0ull;
-    std::lock_guard<std::mutex> lk(mu);
-    const uint64_t gen = g_p2_generation.load();
-    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
-    const std::array<uint64_t, 4> key{(uint64_t)s.base.R, (uint64_t)s.base.F, (uint64_t)s.base.b, (uint64_t)s.base.Q};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto m = std::make_shared<PMachine>();
-    m->s = s;
-    const int R = s.base.R;
-    for (int i = 0; i < N_PT; i++) {
-        const int t = s.order[i];
-        m->prog[i] = t == T_FOLD16 ? build_fold16_program(R, s.base.lf) : t == T_FINAL ? build_final_program(4u * (uint32_t)R)
-                   : t == T_P24L ? *p24chip::program_fri16_layers(4u * (uint32_t)R) : build_table_program(4u * (uint32_t)R, s.pre_w[t]);
-        m->tab[i] = build_paths_interactions(R, t);
-        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
-        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
-    }
-    cache.emplace(key, m);
-    return m;
-}
 int check_hash_width(int inner_hash_width, const char* who) {
     if (inner_hash_width == 24) return ZKHIP_OK;
     return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the paths machine opens width-24 Poseidon2 commitments (inner hash_width 24); a fold-16 proof with the width-16 hash is taken by zkhip_prove_fri16 only");
 }
 // the key's tables by table number: FINAL's schedule, QUERIES, COEFFS, ROOTS -- from the shape, the final coefficients, the queries and the layer roots alone
-int build_paths_key_tables(const PShape& s, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[N_PT],
+int build_paths_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[],
                            const char* who) {
-    const Shape& b = s.base;
     if (!final_poly || !indices || !values || !roots) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!canonical(final_poly, (size_t)4 << b.F) || !canonical(values, 4 * b.Q) || !canonical(roots, 8 * (size_t)b.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    if (!canonical(final_poly, (size_t)4 << s.F) || !canonical(values, 4 * s.Q) || !canonical(roots, 8 * (size_t)s.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     std::map<std::array<uint32_t, 5>, uint32_t> queries;
-    for (size_t q = 0; q < b.Q; q++) {
-        if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    for (size_t q = 0; q < s.Q; q++) {
+        if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
         queries[std::array<uint32_t, 5>{indices[q], values[4 * q], values[4 * q + 1], values[4 * q + 2], values[4 * q + 3]}]++;
     }
-    for (int t = 0; t < N_PT; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
-    fill_schedule_queries_coeffs(b, final_poly, queries, pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
-    for (int l = 0; l < b.R; l++) {
+    for (int t = 0; t < s.n_tables; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
+    fill_schedule_queries_coeffs(s, final_poly, queries, pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
+    for (int l = 0; l < s.R; l++) {
         uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (size_t)l;
-        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(b.H - 4 * (l + 1)));
+        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(s.H - 4 * (l + 1)));
         for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty(roots[8 * l + j]);
     }
     return ZKHIP_OK;
@@ -522,19 +376,19 @@ struct PathPlan {
     std::vector<uint32_t> desc, readers, layer_of, first_query, counts;     // [n][8], [Q R], [n], [n], [R]
     size_t n = 0, used_rows = 0, path_words = 0;
 };
-int plan_paths(const Shape& b, const uint32_t* indices, const uint32_t* paths, PathPlan& pl) {
-    const size_t R = (size_t)b.R;
+int plan_paths(const Shape& s, const uint32_t* indices, const uint32_t* paths, PathPlan& pl) {
+    const size_t R = (size_t)s.R;
     std::vector<size_t> off(R + 1, 0);
-    for (size_t l = 0; l < R; l++) off[l + 1] = off[l] + 8 * (size_t)(b.H - 4 * ((int)l + 1));
+    for (size_t l = 0; l < R; l++) off[l + 1] = off[l] + 8 * (size_t)(s.H - 4 * ((int)l + 1));
     pl.path_words = off[R];
-    if (!canonical(paths, b.Q * pl.path_words)) return fail(ZKHIP_ERR_INVALID, "fri16 paths: values must be canonical");
+    if (!canonical(paths, s.Q * pl.path_words)) return fail(ZKHIP_ERR_INVALID, "fri16 paths: values must be canonical");
     std::map<std::pair<uint32_t, uint32_t>, std::vector<uint32_t>> rows;
-    for (size_t q = 0; q < b.Q; q++)
+    for (size_t q = 0; q < s.Q; q++)
         for (size_t l = 0; l < R; l++) rows[{(uint32_t)l, indices[q] >> (4 * (l + 1))}].push_back((uint32_t)q);
     pl.n = rows.size();
     pl.counts.assign(R, 0u);
     for (const auto& e : rows) {
-        const uint32_t l = e.first.first, depth = (uint32_t)(b.H - 4 * ((int)l + 1)), q0 = e.second[0];
+        const uint32_t l = e.first.first, depth = (uint32_t)(s.H - 4 * ((int)l + 1)), q0 = e.second[0];
         const uint32_t* mine = paths + q0 * pl.path_words + off[l];
         for (uint32_t q : e.second)
             if (std::memcmp(mine, paths + q * pl.path_words + off[l], 32 * (size_t)depth) != 0)
@@ -564,27 +418,8 @@ int plan_paths(const Shape& b, const uint32_t* indices, const uint32_t* paths, P
 // root and beta received from the layer's root row, beta sent on to the fold rows -- by listed rows only (build_roots_program); SAMPLES: fri_chip.hip's chip with H index bits, first row number R + C.
 constexpr uint32_t BUS_TR0 = 76, BUS_TR1 = 77, BUS_TB = 78, BUS_BF16 = 79, BUS_CT = 80, N_PUBLIC_I = 8, ROOTS_MAIN_I = 8;
 constexpr uint32_t PT_PRE = 20, PT_SPG = 0, PT_K = 1, PT_ROOT = 9, PT_LN = 10, PT_C0 = 11, PT_KEY0 = 12, PT_C1 = 13, PT_KEY1 = 14, PT_SMP = 15, PT_ROW = 16;
-enum : int { T_P2T = 6, T_SAMPLES = 7, N_IT = 8 };
-struct IShape {
-    PShape p;
-    int pow_bits = 0;
-    size_t C = 0, S = 0, NT = 0;        // coefficient rows, rows that hand words out, rows of the chain
-    int log_rows[N_IT], order[N_IT];
-    uint32_t main_w[N_IT], pre_w[N_IT];
-};
-int indices_shape_of(int R, int F, int b, size_t Q, int pow_bits, IShape& s) {
-    ZK_TRY(paths_shape_of(R, F, b, Q, s.p));
-    if (pow_bits < 0 || pow_bits > 30) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
-    s.pow_bits = pow_bits;
-    s.C = F >= 1 ? (size_t)1 << (F - 1) : 0; s.S = frichip::samples_chip_rows(Q); s.NT = (size_t)R + s.C + s.S;
-    const uint32_t mw[N_IT] = {s.p.main_w[0], FIN_MAIN, p24chip::WIDTH_L, TAB_MAIN, TAB_MAIN, ROOTS_MAIN_I, p2chip::T_WIDTH, frichip::S_MAIN};
-    const uint32_t pw[N_IT] = {0u, FIN_PRE, 0u, Q_PRE, C_PRE, ROOTS_PRE16, PT_PRE, frichip::S_PRE};
-    for (int i = 0; i < N_IT; i++) { s.log_rows[i] = i < N_PT ? s.p.log_rows[i] : i == T_P2T ? lg(s.NT) : lg(s.S); s.main_w[i] = mw[i]; s.pre_w[i] = pw[i]; s.order[i] = i; }
-    std::stable_sort(s.order, s.order + N_IT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
-    return ZKHIP_OK;
-}
 // P2T's program: the permutation; D and BIT pinned (no path in this table); the chain behind the preprocessed schedule
-std::vector<uint32_t> build_p2t_program() {
+std::vector<uint32_t> build_p2t_program(uint32_t n_public) {
     using namespace p2chip;
     const uint32_t M0 = PT_PRE, OUT = M0 + oute(7);
     Builder b;
@@ -594,116 +429,36 @@ std::vector<uint32_t> build_p2t_program() {
     for (uint32_t j = 0; j < 8; j++) b.add(FIRST, Terms{{1u, {var(M0 + IN + 8 + j)}}, {P - 1, {pub(j)}}});
     for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_SPG, true), var(M0 + IN + 8 + j, true)}}, {P - 1, {var(PT_SPG, true), var(OUT + 8 + j)}}});
     for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_K + j, true), var(M0 + IN + j, true)}}, {P - 1, {var(PT_K + j, true), var(OUT + j)}}});
-    return b.finish(PT_PRE + T_WIDTH, N_PUBLIC_I);
+    return b.finish(PT_PRE + T_WIDTH, n_public);
 }
 // ROOTS' program: the harmless identity of a key table, and FOLDROWS (1 - LISTED) = 0 -- the multiplicity of the send (layer, beta) to FOLD16B is a MAIN column, and a
 // padding row's preprocessed cells are zero (layer 0, nothing received from the transcript): without this a padding row could hand layer 0 a challenge of the prover's choice
-std::vector<uint32_t> build_roots_program() {
+std::vector<uint32_t> build_roots_program(uint32_t n_public) {
     Builder b;
     b.add(FIRST, Terms{{1u, {var(ROOTS_PRE16 + ROOTS_MAIN_I - 1u)}}});
     b.add(ALL, Terms{{1u, {var(ROOTS_PRE16 + 5u)}}, {P - 1, {var(ROOTS_PRE16 + 5u), var(10u)}}});
-    return b.finish(ROOTS_PRE16 + ROOTS_MAIN_I, N_PUBLIC_I);
-}
-std::vector<uint32_t> build_indices_interactions(int R, int table) {
-    if (table == T_FINAL || table == T_P24L) return build_paths_interactions(R, table);
-    if (table == T_SAMPLES) return frichip::samples_chip_interactions();
-    std::vector<uint32_t> v = table == T_FOLD16 ? build_interactions(R, T_FOLD16) : std::vector<uint32_t>{LOOKUP_MAGIC, 0u, 0u};
-    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
-        v.insert(v.end(), cols.begin(), cols.end());
-        v[1]++;
-    };
-    const uint32_t RM = ROOTS_PRE16, in = PT_PRE + p2chip::IN, o = PT_PRE + p2chip::oute(7);
-    switch (table) {
-    case T_FOLD16: add(1u, ACTIVE, BUS_BF16, {LN, BETA, BETA + 1, BETA + 2, BETA + 3}); break;
-    case T_QUERIES:
-        add(1u, 5u, BUS_Q16, {Q_PRE, 1u, 2u, 3u, 4u});
-        add(1u, 5u, frichip::BUS_I, {0u, Q_PRE});
-        break;
-    case T_COEFFS:
-        add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u});
-        add(0u, 6u, BUS_CT, {0u, 1u, 2u, 3u, 4u});
-        break;
-    case T_ROOTS:
-        add(1u, RM, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
-        add(1u, RM, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
-        add(1u, 10u, BUS_TR0, {RT_LN, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
-        add(1u, 10u, BUS_TR1, {RT_LN, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
-        add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
-        add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
-        break;
-    default:        // P2T
-        add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
-        add(1u, PT_C1, BUS_CT, {PT_KEY1, in + 4, in + 5, in + 6, in + 7});
-        add(0u, PT_ROOT, BUS_TR0, {PT_LN, in, in + 1, in + 2, in + 3});
-        add(0u, PT_ROOT, BUS_TR1, {PT_LN, in + 4, in + 5, in + 6, in + 7});
-        add(0u, PT_ROOT, BUS_TB, {PT_LN, o + 7, o + 6, o + 5, o + 4});
-        add(0u, PT_SMP, frichip::BUS_S0, {PT_ROW, o + 7, o + 6, o + 5, o + 4});
-        add(0u, PT_SMP, frichip::BUS_S1, {PT_ROW, o + 3, o + 2, o + 1, o});
-        break;
-    }
-    v[2] = (uint32_t)v.size();
-    return v;
-}
-struct IMachine {
-    IShape s;
-    std::vector<uint32_t> prog[N_IT], tab[N_IT];
-    int32_t log_ns[N_IT]; uint32_t widths[N_IT], pre_widths[N_IT];
-    const uint32_t* progs[N_IT]; size_t prog_words[N_IT]; const uint32_t* tabs[N_IT]; size_t tab_words[N_IT];
-};
-// (P24L's and P2T's programs follow the Poseidon2 tables in effect: the cache is dropped when they change)
-std::shared_ptr<const IMachine> indices_machine_of(const IShape& s) {
-    static std::mutex mu;
-    static std::map<std::array<uint64_t, 5>, std::shared_ptr<const IMachine>> cache;
-    static uint64_t cached_gen = ~0ull;
-    std::lock_guard<std::mutex> lk(mu);
-    const uint64_t gen = g_p2_generation.load();
-    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
-    const Shape& b = s.p.base;
-    const std::array<uint64_t, 5> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.pow_bits};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto m = std::make_shared<IMachine>();
-    m->s = s;
-    for (int i = 0; i < N_IT; i++) {
-        const int t = s.order[i];
-        switch (t) {
-        case T_FOLD16: m->prog[i] = build_fold16_program(b.R, b.lf, true, N_PUBLIC_I); break;
-        case T_FINAL: m->prog[i] = build_final_program(N_PUBLIC_I); break;
-        case T_P24L: m->prog[i] = *p24chip::program_fri16_layers(N_PUBLIC_I); break;
-        case T_P2T: m->prog[i] = build_p2t_program(); break;
-        case T_SAMPLES: m->prog[i] = *frichip::samples_chip_program(b.H, s.pow_bits, N_PUBLIC_I); break;
-        case T_ROOTS: m->prog[i] = build_roots_program(); break;
-        default: m->prog[i] = build_table_program(N_PUBLIC_I, s.pre_w[t], s.main_w[t]); break;
-        }
-        m->tab[i] = build_indices_interactions(b.R, t);
-        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
-        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
-    }
-    cache.emplace(key, m);
-    return m;
+    return b.finish(ROOTS_PRE16 + ROOTS_MAIN_I, n_public);
 }
 // the key's tables by table number: FINAL's schedule, QUERIES by query number, COEFFS, ROOTS, and the schedules of P2T and SAMPLES -- no index and no challenge
-int build_indices_key_tables(const IShape& s, const uint32_t* final_poly, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[N_IT], const char* who) {
-    const Shape& b = s.p.base;
+int build_indices_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[], const char* who) {
     if (!final_poly || !values || !roots) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!canonical(final_poly, (size_t)4 << b.F) || !canonical(values, 4 * b.Q) || !canonical(roots, 8 * (size_t)b.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
-    for (int t = 0; t < N_IT; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
-    fill_schedule_queries_coeffs(b, final_poly, std::map<std::array<uint32_t, 5>, uint32_t>(), pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
-    for (size_t q = 0; q < b.Q; q++) {
+    if (!canonical(final_poly, (size_t)4 << s.F) || !canonical(values, 4 * s.Q) || !canonical(roots, 8 * (size_t)s.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (int t = 0; t < s.n_tables; t++) pre[t].assign((size_t)s.pre_w[t] << s.log_rows[t], 0u);
+    fill_schedule_queries_coeffs(s, final_poly, std::map<std::array<uint32_t, 5>, uint32_t>(), pre[T_FINAL], pre[T_QUERIES], pre[T_COEFFS]);
+    for (size_t q = 0; q < s.Q; q++) {
         uint32_t* w = pre[T_QUERIES].data() + Q_PRE * q;
         w[0] = to_monty((uint32_t)q);
         for (int i = 0; i < 4; i++) w[1 + i] = to_monty(values[4 * q + i]);
         w[5] = MONTY_R1;
     }
-    for (size_t j = 0; j < ((size_t)1 << b.F); j++) pre[T_COEFFS][C_PRE * j + 6] = MONTY_R1;
-    for (int l = 0; l < b.R; l++) {
+    for (size_t j = 0; j < ((size_t)1 << s.F); j++) pre[T_COEFFS][C_PRE * j + 6] = MONTY_R1;
+    for (int l = 0; l < s.R; l++) {
         uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (size_t)l;
-        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(b.H - 4 * (l + 1)));
+        w[RT_LN] = to_monty((uint32_t)l); w[RT_DEP] = to_monty((uint32_t)(s.H - 4 * (l + 1)));
         for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty(roots[8 * l + j]);
         w[10] = MONTY_R1;
     }
-    const size_t R = (size_t)b.R;
+    const size_t R = (size_t)s.R;
     for (size_t r = 0; r < s.NT; r++) {
         uint32_t* w = pre[T_P2T].data() + PT_PRE * r;
         if (r) w[PT_SPG] = MONTY_R1;
@@ -713,20 +468,19 @@ int build_indices_key_tables(const IShape& s, const uint32_t* final_poly, const 
             const uint32_t i = (uint32_t)(r - R);
             w[PT_C0] = w[PT_C1] = MONTY_R1; w[PT_KEY0] = to_monty(2u * i); w[PT_KEY1] = to_monty(2u * i + 1u);
         } else if (r == R + s.C) {
-            if (b.F == 0) { w[PT_C0] = MONTY_R1; kept_from = 5; } else kept_from = 1;
+            if (s.F == 0) { w[PT_C0] = MONTY_R1; kept_from = 5; } else kept_from = 1;
         } else kept_from = 0;
         for (uint32_t j = kept_from; j < 8; j++) w[PT_K + j] = MONTY_R1;
         if (r >= R + s.C) { w[PT_SMP] = MONTY_R1; w[PT_ROW] = to_monty((uint32_t)r); }
     }
-    frichip::samples_chip_pre(b.Q, s.log_rows[T_SAMPLES], (int)(R + s.C), pre[T_SAMPLES]);
+    frichip::samples_chip_pre(s.Q, s.log_rows[T_SAMPLES], (int)(R + s.C), pre[T_SAMPLES]);
     return ZKHIP_OK;
 }
 // the chain walked on the host (NT permutations): every row's input state, the challenges and the words it hands out -- canonical
 struct Chain { std::vector<uint32_t> inputs, words, betas, drawn; };
-void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, Chain& c) {
-    const Shape& b = s.p.base;
-    const size_t R = (size_t)b.R;
-    c.inputs.assign(16 * s.NT, 0u); c.words.assign(8 * s.S, 0u); c.betas.assign(4 * R, 0u); c.drawn.assign(b.Q, 0u);
+void walk_chain(const Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, Chain& c) {
+    const size_t R = (size_t)s.R;
+    c.inputs.assign(16 * s.NT, 0u); c.words.assign(8 * s.S, 0u); c.betas.assign(4 * R, 0u); c.drawn.assign(s.Q, 0u);
     uint32_t st[16];
     size_t r = 0;
     auto step = [&]() { for (int j = 0; j < 16; j++) c.inputs[16 * r + j] = from_monty(st[j]); r++; p2_permute(st); };
@@ -740,14 +494,14 @@ void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots
         for (int j = 0; j < 8; j++) st[j] = to_monty(final_poly[8 * i + j]);
         step();
     }
-    if (b.F == 0) { for (int j = 0; j < 4; j++) st[j] = to_monty(final_poly[j]); st[4] = to_monty(witness); }
+    if (s.F == 0) { for (int j = 0; j < 4; j++) st[j] = to_monty(final_poly[j]); st[4] = to_monty(witness); }
     else st[0] = to_monty(witness);
     for (size_t i = 0; i < s.S; i++) {
         step();
         for (int j = 0; j < 8; j++) c.words[8 * i + j] = from_monty(st[7 - j]);
     }
-    const uint32_t mask = (1u << b.H) - 1u;
-    for (size_t q = 0; q < b.Q; q++) c.drawn[q] = c.words[q + 1] & mask;
+    const uint32_t mask = (1u << s.H) - 1u;
+    for (size_t q = 0; q < s.Q; q++) c.drawn[q] = c.words[q + 1] & mask;
 }
 
 // ---------------------------------------------------------------- the OPENINGS machine: the indices machine with the reduced openings computed in-circuit
@@ -770,29 +524,6 @@ void walk_chain(const IShape& s, const uint32_t* capacity, const uint32_t* roots
 constexpr uint32_t BUS_ROW16 = 81, BUS_AT16 = 82, BUS_AQ16 = 83, N_PUBLIC_O = 40, Q16_PRE = 8, QP_QN = 0, QP_ACT = 1, RS16_PRE = 8, ROWS_PRE16 = 8, QROW16 = 8;
 constexpr uint32_t RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST0 = 3, RP_LAST1 = 4, RP_QN = 5, RP_K0 = 6, RP_K1 = 7;
 constexpr uint32_t PUB_FA = 8, PUB_ZETA = 12;       // public values: FA, then ZETA ZNX YL YN YQ OFFN OFFQ in QUERY16's column order
-enum : int { T_QUERY16 = 3, T_ROWSUM16 = 8, T_ROWS = 9, N_OT = 10 };
-struct OShape {
-    IShape i;
-    uint32_t W = 0;
-    int log_rows[N_OT], order[N_OT];
-    uint32_t main_w[N_OT], pre_w[N_OT];
-};
-int openings_shape_of(int R, int F, int b, size_t Q, int pow_bits, uint32_t W, OShape& s) {
-    ZK_TRY(indices_shape_of(R, F, b, Q, pow_bits, s.i));
-    if (W < 8 || W > MAX_OPEN_W || W % 8)
-        return fail(ZKHIP_ERR_INVALID, "fri16 openings: a trace width of 8 .. 1024 in multiples of 8 (inner proofs without lookup pairs and with a quotient row of 8 words)");
-    s.W = W;
-    const uint32_t mw[N_OT] = {s.i.main_w[0] + 4u, FIN_MAIN, p24chip::WIDTH_L, Q16_MAIN, TAB_MAIN, ROOTS_MAIN_I, p2chip::T_WIDTH, frichip::S_MAIN, RS_MAIN16, TAB_MAIN};
-    const uint32_t pw[N_OT] = {0u, FIN_PRE, 0u, Q16_PRE, C_PRE, ROOTS_PRE16, PT_PRE, frichip::S_PRE, RS16_PRE, ROWS_PRE16};
-    for (int t = 0; t < N_OT; t++) {
-        // (ROWSUM16 and ROWS: at least 2^6 rows -- a keyed machine takes at most 8 tables of one height, and the other eight can all have 2^5 rows; from 2^6 rows
-        // on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting)
-        s.log_rows[t] = t < N_IT ? s.i.log_rows[t] : std::max(6, t == T_ROWSUM16 ? lg(Q * (size_t)(W / 8 + 1)) : lg(Q * (size_t)(W + QROW16) / 4));
-        s.main_w[t] = mw[t]; s.pre_w[t] = pw[t]; s.order[t] = t;
-    }
-    std::stable_sort(s.order, s.order + N_OT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
-    return ZKHIP_OK;
-}
 // polynomials over columns, as in shard_verifier.inl: a list of (coefficient, variables), an extension expression = four of them; the order in which terms are
 // produced IS the program (tests/recursion_air.py's helpers produce them in the same order)
 typedef std::array<Terms, 4> EE;
@@ -826,7 +557,6 @@ inline EE emul(const EE& a, const EE& b) {
 }
 inline EE egate(const Terms& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
 inline void add_ext(Builder& b, uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) b.add(sel, e[i]); }
-inline std::vector<uint32_t> with_public(std::vector<uint32_t> prog, uint32_t n_public) { prog[4] = n_public; return prog; }
 
 std::vector<uint32_t> build_fold16c_program(int R, int lf) {
     const std::vector<uint32_t> p = build_fold16_program(R, lf, true, N_PUBLIC_O);
@@ -873,79 +603,6 @@ std::vector<uint32_t> build_rowsum16_program() {
     add_ext(b, ALL, egate(padd(pv(RP_ACT), pneg(pv(RP_NOTFIRST))), ev(M0 + RS_ACCIN)));
     return b.finish(RS16_PRE + RS_MAIN16, N_PUBLIC_O);
 }
-std::vector<uint32_t> build_openings_interactions(int R, int lf, int table) {
-    if (table == T_FINAL || table == T_P24L) return build_paths_interactions(R, table);
-    if (table != T_FOLD16 && table != T_QUERY16 && table < N_IT) return build_indices_interactions(R, table);
-    std::vector<uint32_t> v{LOOKUP_MAGIC, 0u, 0u};
-    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
-        v.insert(v.end(), cols.begin(), cols.end());
-        v[1]++;
-    };
-    const uint32_t XQ = fold16_width((uint32_t)lf), rv = RS16_PRE + RS_V, rt = RS16_PRE + RS_T;
-    switch (table) {
-    case T_FOLD16:
-        for (uint32_t j = 0; j < 16; j++) add(0u, ACTIVE, BUS_L16, {LN, KJ + j, E + 4 * j, E + 4 * j + 1, E + 4 * j + 2, E + 4 * j + 3});
-        add(0u, L, BUS_Q16, {IDX, XQ, OWN, OWN + 1, OWN + 2, OWN + 3});
-        add(0u, L + (uint32_t)R - 1u, BUS_FIN16, {X16, FOLD, FOLD + 1, FOLD + 2, FOLD + 3});
-        add(1u, ACTIVE, BUS_BF16, {LN, BETA, BETA + 1, BETA + 2, BETA + 3});
-        break;
-    case T_QUERY16:
-        add(1u, QP_ACT, frichip::BUS_I, {QP_QN, QC_IDX});
-        add(1u, QP_ACT, BUS_Q16, {QC_IDX, QC_XQ, QC_RO, QC_RO + 1, QC_RO + 2, QC_RO + 3});
-        add(1u, QP_ACT, BUS_AT16, {QP_QN, QC_AT, QC_AT + 1, QC_AT + 2, QC_AT + 3});
-        add(1u, QP_ACT, BUS_AQ16, {QP_QN, QC_AQ, QC_AQ + 1, QC_AQ + 2, QC_AQ + 3});
-        break;
-    case T_ROWSUM16:
-        add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
-        add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K1, rv + 4, rv + 5, rv + 6, rv + 7});
-        add(0u, RP_LAST0, BUS_AT16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
-        add(0u, RP_LAST1, BUS_AQ16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
-        break;
-    default: add(1u, 6u, BUS_ROW16, {0u, 1u, 2u, 3u, 4u, 5u}); break;          // ROWS
-    }
-    v[2] = (uint32_t)v.size();
-    return v;
-}
-struct OMachine {
-    OShape s;
-    std::vector<uint32_t> prog[N_OT], tab[N_OT];
-    int32_t log_ns[N_OT]; uint32_t widths[N_OT], pre_widths[N_OT];
-    const uint32_t* progs[N_OT]; size_t prog_words[N_OT]; const uint32_t* tabs[N_OT]; size_t tab_words[N_OT];
-};
-std::shared_ptr<const OMachine> openings_machine_of(const OShape& s) {
-    static std::mutex mu;
-    static std::map<std::array<uint64_t, 6>, std::shared_ptr<const OMachine>> cache;
-    static uint64_t cached_gen = ~0ull;
-    std::lock_guard<std::mutex> lk(mu);
-    const uint64_t gen = g_p2_generation.load();
-    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
-    const Shape& b = s.i.p.base;
-    const std::array<uint64_t, 6> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.i.pow_bits, (uint64_t)s.W};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto m = std::make_shared<OMachine>();
-    m->s = s;
-    for (int i = 0; i < N_OT; i++) {
-        const int t = s.order[i];
-        switch (t) {
-        case T_FOLD16: m->prog[i] = build_fold16c_program(b.R, b.lf); break;
-        case T_FINAL: m->prog[i] = build_final_program(N_PUBLIC_O); break;
-        case T_P24L: m->prog[i] = *p24chip::program_fri16_layers(N_PUBLIC_O); break;
-        case T_QUERY16: m->prog[i] = build_query16_program(); break;
-        case T_P2T: m->prog[i] = with_public(build_p2t_program(), N_PUBLIC_O); break;
-        case T_SAMPLES: m->prog[i] = *frichip::samples_chip_program(b.H, s.i.pow_bits, N_PUBLIC_O); break;
-        case T_ROOTS: m->prog[i] = with_public(build_roots_program(), N_PUBLIC_O); break;
-        case T_ROWSUM16: m->prog[i] = build_rowsum16_program(); break;
-        default: m->prog[i] = build_table_program(N_PUBLIC_O, s.pre_w[t], s.main_w[t]); break;         // COEFFS, ROWS
-        }
-        m->tab[i] = build_openings_interactions(b.R, b.lf, t);
-        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
-        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
-    }
-    cache.emplace(key, m);
-    return m;
-}
 // ROWSUM16's schedule: per query the trace blocks from the last to the first, then the quotient block
 void rowsum16_schedule(size_t Q, size_t W, int log_rows, std::vector<uint32_t>& t) {
     const size_t WB = W / 8;
@@ -962,14 +619,13 @@ void rowsum16_schedule(size_t Q, size_t W, int log_rows, std::vector<uint32_t>& 
         }
 }
 // the key's tables by table number: the indices machine's (QUERY16's schedule where its QUERIES stood), ROWSUM16's schedule and ROWS -- the rows go in, no reduced opening
-int build_openings_key_tables(const OShape& s, const uint32_t* final_poly, const uint32_t* trows, const uint32_t* qrows, const uint32_t* roots, std::vector<uint32_t> pre[N_OT],
+int build_openings_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* trows, const uint32_t* qrows, const uint32_t* roots, std::vector<uint32_t> pre[],
                               const char* who) {
-    const Shape& b = s.i.p.base;
-    const size_t Q = b.Q, W = s.W;
+    const size_t Q = s.Q, W = s.W;
     if (!trows || !qrows) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     if (!canonical(trows, Q * W) || !canonical(qrows, Q * QROW16)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     const std::vector<uint32_t> no_values(4 * Q, 0u);
-    ZK_TRY(build_indices_key_tables(s.i, final_poly, no_values.data(), roots, pre, who));
+    ZK_TRY(build_indices_key_tables(s, final_poly, no_values.data(), roots, pre, who));
     pre[T_QUERY16].assign((size_t)Q16_PRE << s.log_rows[T_QUERY16], 0u);
     for (size_t q = 0; q < Q; q++) { pre[T_QUERY16][Q16_PRE * q + QP_QN] = to_monty((uint32_t)q); pre[T_QUERY16][Q16_PRE * q + QP_ACT] = MONTY_R1; }
     rowsum16_schedule(Q, W, s.log_rows[T_ROWSUM16], pre[T_ROWSUM16]);
@@ -989,12 +645,11 @@ int build_openings_key_tables(const OShape& s, const uint32_t* final_poly, const
     return ZKHIP_OK;
 }
 // the constants among themselves: zeta g_N, fa^W, fa^(2W)
-int check_openings_constants(const OShape& s, const uint32_t* consts, const char* who) {
+int check_openings_constants(const Shape& s, const uint32_t* consts, const char* who) {
     if (!consts) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     if (!canonical(consts, 32)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
-    const Shape& b = s.i.p.base;
     const Ext fa = ext_from_canon(consts), zeta = ext_from_canon(consts + 4);
-    if (!ext_eq(ext_from_canon(consts + 8), ext_mul_base(zeta, two_adic_generator(b.H - b.b))) || !ext_eq(ext_from_canon(consts + 24), ext_pow(fa, s.W)) ||
+    if (!ext_eq(ext_from_canon(consts + 8), ext_mul_base(zeta, two_adic_generator(s.H - s.b))) || !ext_eq(ext_from_canon(consts + 24), ext_pow(fa, s.W)) ||
         !ext_eq(ext_from_canon(consts + 28), ext_pow(fa, 2 * (uint64_t)s.W)))
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constants do not match each other (zeta g_N, OFFN = fa^W, OFFQ = fa^(2W))");
     return ZKHIP_OK;
@@ -1002,7 +657,7 @@ int check_openings_constants(const OShape& s, const uint32_t* consts, const char
 
 // ---------------------------------------------------------------- the ROW-PATHS machine: the openings machine with the opened rows' Merkle paths proven
 // Table numbers as in the openings machine with P24R at 9; the 40 public values stay.  FOLD16C, FINAL, P24L, COEFFS, ROOTS, P2T, SAMPLES and ROWSUM16: the openings
-// machine's programs and interaction tables word for word (taken from it, not built again).  The key commits the layer roots, the final coefficients, the trace root
+// machine's programs and interaction tables word for word (program_of and interactions_of have no case for this kind there).  The key commits the layer roots, the final coefficients, the trace root
 // and the quotient root: NO opened word.
 //   ROOTS    key table: two more rows, (LN = R, DEP = H, trace root, LISTED = 0) and (LN = R + 1, DEP = H, quotient root, LISTED = 0) -- not listed: nothing comes from
 //            the transcript, and FOLDROWS (1 - LISTED) = 0 keeps them from handing FOLD16C a challenge; their path-end count is the prover's main column
@@ -1015,87 +670,15 @@ int check_openings_constants(const OShape& s, const uint32_t* consts, const char
 // P24R has lg(Q (ceil(W / 16) + 1 + 2 H)) rows, at least 2^6 as ROWS had.  STILL OUTSIDE: the transcript before the commit phase (so the eight constants and where the
 // two roots come from), lookups, the AIR identity at zeta.  tests/fri16_rowpaths_air.py writes it again.
 constexpr uint32_t BUS_TAG16 = 84, QP_TG0 = 2, QP_TG1 = 3, QP_LN0 = 4, QP_LN1 = 5;
-enum : int { T_P24R = 9, MAX_SAME_HEIGHT = 8 };
-struct RShape {
-    OShape o;
-    int log_rows[N_OT], order[N_OT];
-    uint32_t main_w[N_OT], pre_w[N_OT];
-};
-int rowpaths_shape_of(int R, int F, int b, size_t Q, int pow_bits, uint32_t W, RShape& s) {
-    ZK_TRY(openings_shape_of(R, F, b, Q, pow_bits, W, s.o));
-    const size_t per_query = (size_t)(W + 15) / 16 + 1 + 2 * (size_t)s.o.i.p.base.H;
-    for (int t = 0; t < N_OT; t++) {
-        const bool r = t == T_P24R;
-        s.log_rows[t] = r ? std::max(6, lg(Q * per_query)) : s.o.log_rows[t];
-        s.main_w[t] = r ? p24chip::WIDTH_R : s.o.main_w[t]; s.pre_w[t] = r ? 0u : s.o.pre_w[t]; s.order[t] = t;
-    }
-    std::stable_sort(s.order, s.order + N_OT, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
-    for (int t = 0; t < N_OT; t++)
-        if (std::count(s.log_rows, s.log_rows + N_OT, s.log_rows[t]) > MAX_SAME_HEIGHT)
-            return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
-    return ZKHIP_OK;
-}
-std::vector<uint32_t> build_rowpaths_interactions(int R, int lf, int table) {
-    std::vector<uint32_t> v = table == T_P24R ? std::vector<uint32_t>{LOOKUP_MAGIC, 0u, 0u} : build_openings_interactions(R, lf, table);
-    auto add = [&](uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        v.push_back(sign); v.push_back(mult); v.push_back(bus); v.push_back((uint32_t)cols.size());
-        v.insert(v.end(), cols.begin(), cols.end());
-        v[1]++;
-    };
-    if (table == T_QUERY16) {
-        add(0u, QP_ACT, BUS_TAG16, {QP_TG0, QP_LN0, QC_IDX});
-        add(0u, QP_ACT, BUS_TAG16, {QP_TG1, QP_LN1, QC_IDX});
-    } else if (table == T_P24R) {
-        using namespace p24chip;
-        const uint32_t o7 = oute(7), mult[4] = {R_M0, p24chip::G(1), p24chip::G(2), p24chip::G(3)};
-        for (uint32_t i = 0; i < 4; i++) add(1u, mult[i], BUS_ROW16, {R_TAG, R_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
-        add(1u, SS, BUS_TAG16, {R_TAG, R_LNR, R_IX});
-        add(0u, END, BUS_RT0, {R_LNR, R_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
-        add(0u, END, BUS_RT1, {R_LNR, R_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
-    }
-    v[2] = (uint32_t)v.size();
-    return v;
-}
-struct RMachine {
-    RShape s;
-    std::vector<uint32_t> prog[N_OT], tab[N_OT];
-    int32_t log_ns[N_OT]; uint32_t widths[N_OT], pre_widths[N_OT];
-    const uint32_t* progs[N_OT]; size_t prog_words[N_OT]; const uint32_t* tabs[N_OT]; size_t tab_words[N_OT];
-};
-std::shared_ptr<const RMachine> rowpaths_machine_of(const RShape& s) {
-    static std::mutex mu;
-    static std::map<std::array<uint64_t, 6>, std::shared_ptr<const RMachine>> cache;
-    static uint64_t cached_gen = ~0ull;
-    const auto om = openings_machine_of(s.o);                  // (before the lock: it drops its own cache on the same generation)
-    std::lock_guard<std::mutex> lk(mu);
-    const uint64_t gen = g_p2_generation.load();
-    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
-    const Shape& b = s.o.i.p.base;
-    const std::array<uint64_t, 6> key{(uint64_t)b.R, (uint64_t)b.F, (uint64_t)b.b, (uint64_t)b.Q, (uint64_t)s.o.i.pow_bits, (uint64_t)s.o.W};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto m = std::make_shared<RMachine>();
-    m->s = s;
-    for (int i = 0; i < N_OT; i++) {
-        const int t = s.order[i];
-        if (t == T_P24R) m->prog[i] = *p24chip::program_fri16_rows(N_PUBLIC_O);
-        else m->prog[i] = om->prog[std::find(s.o.order, s.o.order + N_OT, t) - s.o.order];
-        m->tab[i] = t == T_P24R || t == T_QUERY16 ? build_rowpaths_interactions(b.R, b.lf, t) : om->tab[std::find(s.o.order, s.o.order + N_OT, t) - s.o.order];
-        m->log_ns[i] = s.log_rows[t]; m->widths[i] = s.main_w[t]; m->pre_widths[i] = s.pre_w[t];
-        m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size();
-    }
-    cache.emplace(key, m);
-    return m;
-}
+enum : int { MAX_SAME_HEIGHT = 8 };
 // the key's tables by table number: the indices machine's, QUERY16's schedule with the tags and tree numbers, ROWSUM16's schedule, the two roots in ROOTS -- no row
-int build_rowpaths_key_tables(const RShape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root,
-                              std::vector<uint32_t> pre[N_OT], const char* who) {
-    const Shape& b = s.o.i.p.base;
-    const size_t Q = b.Q, R = (size_t)b.R;
+int build_rowpaths_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root,
+                              std::vector<uint32_t> pre[], const char* who) {
+    const size_t Q = s.Q, R = (size_t)s.R;
     if (!trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     if (!canonical(trace_root, 8) || !canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     const std::vector<uint32_t> no_values(4 * Q, 0u);
-    ZK_TRY(build_indices_key_tables(s.o.i, final_poly, no_values.data(), roots, pre, who));
+    ZK_TRY(build_indices_key_tables(s, final_poly, no_values.data(), roots, pre, who));
     pre[T_QUERY16].assign((size_t)Q16_PRE << s.log_rows[T_QUERY16], 0u);
     for (size_t q = 0; q < Q; q++) {
         uint32_t* w = pre[T_QUERY16].data() + Q16_PRE * q;
@@ -1104,12 +687,264 @@ int build_rowpaths_key_tables(const RShape& s, const uint32_t* final_poly, const
     }
     for (size_t tree = 0; tree < 2; tree++) {                  // (R + 2 <= 7 rows of 2^5; column 10, LISTED, stays zero)
         uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE16 * (R + tree);
-        w[RT_LN] = to_monty((uint32_t)(R + tree)); w[RT_DEP] = to_monty((uint32_t)b.H);
+        w[RT_LN] = to_monty((uint32_t)(R + tree)); w[RT_DEP] = to_monty((uint32_t)s.H);
         for (int j = 0; j < 8; j++) w[RT_ROOT + j] = to_monty((tree ? quotient_root : trace_root)[j]);
     }
-    rowsum16_schedule(Q, s.o.W, s.log_rows[T_ROWSUM16], pre[T_ROWSUM16]);
+    rowsum16_schedule(Q, s.W, s.log_rows[T_ROWSUM16], pre[T_ROWSUM16]);
     pre[T_P24R].clear();
     return ZKHIP_OK;
+}
+
+// ---------------------------------------------------------------- the one description: shape, programs, interaction tables, machine, and what every entry does with them
+constexpr int N_TABLES[5] = {5, 6, 8, 10, 10};
+inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : N_PUBLIC_O; }
+
+// pow_bits is read from INDICES on, W from OPENINGS on.  ROWSUM16, ROWS and P24R have at least 2^6 rows: a keyed machine takes at most 8 tables of one height, and the
+// other eight can all have 2^5 rows; from 2^6 rows on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting where ROWS stands --
+// P24R can still meet eight others, and that shape is refused
+int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s) {
+    if (R < 1 || R > MAX_R || F < 0 || F > MAX_F || b < 1 || b > 3 || F + b > MAX_LF || Q < 1 || Q > MAX_Q || 4 * R + F + b > TWO_ADICITY)
+        return fail(ZKHIP_ERR_INVALID, "fri16: 1..5 layers, log_final 0..8, log_blowup 1..3 (log_final + log_blowup <= 11), 1..1024 queries, and a domain of at most 2^27 points");
+    if (kind >= INDICES && (pow_bits < 0 || pow_bits > 30)) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
+    if (kind >= OPENINGS && (W < 8 || W > MAX_OPEN_W || W % 8))
+        return fail(ZKHIP_ERR_INVALID, "fri16 openings: a trace width of 8 .. 1024 in multiples of 8 (inner proofs without lookup pairs and with a quotient row of 8 words)");
+    s = Shape{};
+    s.kind = kind; s.R = R; s.F = F; s.b = b; s.lf = F + b; s.H = 4 * R + s.lf; s.Q = Q; s.n_tables = N_TABLES[kind];
+    if (kind >= INDICES) { s.pow_bits = pow_bits; s.C = F >= 1 ? (size_t)1 << (F - 1) : 0; s.S = frichip::samples_chip_rows(Q); s.NT = (size_t)R + s.C + s.S; }
+    if (kind >= OPENINGS) s.W = W;
+    size_t layer_paths = 0;                                      // rows of P24L per query: every layer's leaf and path
+    for (int l = 0; l < R; l++) layer_paths += (size_t)p24chip::LEAF_ROWS + (size_t)(s.H - 4 * (l + 1));
+    const size_t row_paths = (size_t)(W + 15) / 16 + 1 + 2 * (size_t)s.H;      // rows of P24R per query: the two leaves and the two paths
+    auto table = [&](int t, int log_rows, uint32_t main_w, uint32_t pre_w) { s.log_rows[t] = log_rows; s.main_w[t] = main_w; s.pre_w[t] = pre_w; };
+    table(T_FOLD16, lg(Q * (size_t)R), fold16_width((uint32_t)s.lf) + (kind >= OPENINGS ? 4u : 0u), 0u);
+    table(T_FINAL, lg(Q << F), FIN_MAIN, FIN_PRE);
+    if (kind == LAYERS) table(T_LAYERS, lg(Q * (size_t)R), TAB_MAIN, LAY_PRE);
+    else table(T_P24L, lg(Q * layer_paths), p24chip::WIDTH_L, 0u);
+    if (kind < OPENINGS) table(T_QUERIES, lg(Q), TAB_MAIN, Q_PRE);
+    else table(T_QUERY16, lg(Q), Q16_MAIN, Q16_PRE);
+    table(T_COEFFS, lg((size_t)1 << F), TAB_MAIN, C_PRE);
+    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, ROOTS_PRE16);
+    table(T_P2T, lg(s.NT), p2chip::T_WIDTH, PT_PRE);
+    table(T_SAMPLES, lg(s.S), frichip::S_MAIN, frichip::S_PRE);
+    table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, RS16_PRE);
+    if (kind == OPENINGS) table(T_ROWS, std::max(6, lg(Q * (size_t)(W + QROW16) / 4)), TAB_MAIN, ROWS_PRE16);
+    else table(T_P24R, std::max(6, lg(Q * row_paths)), p24chip::WIDTH_R, 0u);
+    for (int t = 0; t < s.n_tables; t++) s.order[t] = t;
+    std::stable_sort(s.order, s.order + s.n_tables, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
+    for (int t = 0; kind == ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
+        if (std::count(s.log_rows, s.log_rows + s.n_tables, s.log_rows[t]) > MAX_SAME_HEIGHT)
+            return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
+    return ZKHIP_OK;
+}
+
+// the program of table t: per table, from which kind on it is which chip
+std::vector<uint32_t> program_of(const Shape& s, int t) {
+    const Kind k = s.kind;
+    const uint32_t np = n_public_of(s);
+    switch (t) {
+    case T_FOLD16: return k >= OPENINGS ? build_fold16c_program(s.R, s.lf) : build_fold16_program(s.R, s.lf, k >= INDICES, np);
+    case T_FINAL: return build_final_program(np);
+    case T_P24L: if (k >= PATHS) return *p24chip::program_fri16_layers(np); break;                                 // (LAYERS: a key table)
+    case T_QUERY16: if (k >= OPENINGS) return build_query16_program(); break;                                     // (below: QUERIES, a key table)
+    case T_ROOTS: if (k >= INDICES) return build_roots_program(np); break;                                        // (PATHS: a key table)
+    case T_P2T: return build_p2t_program(np);
+    case T_SAMPLES: return *frichip::samples_chip_program(s.H, s.pow_bits, np);
+    case T_ROWSUM16: return build_rowsum16_program();
+    case T_P24R: if (k == ROWPATHS) return *p24chip::program_fri16_rows(np); break;                               // (OPENINGS: ROWS, a key table)
+    default: break;                                                                                                // COEFFS
+    }
+    return build_table_program(np, s.pre_w[t], s.main_w[t]);
+}
+
+// the interaction table of table t: per table, what each kind adds to or changes in the kind before it -- the ORDER of the entries is part of the words
+std::vector<uint32_t> interactions_of(const Shape& s, int t) {
+    if (t == T_SAMPLES) return frichip::samples_chip_interactions();
+    const Kind k = s.kind;
+    const uint32_t R = (uint32_t)s.R, XQ = fold16_width((uint32_t)s.lf), RM = ROOTS_PRE16, in = PT_PRE + p2chip::IN, o = PT_PRE + p2chip::oute(7), rv = RS16_PRE + RS_V,
+                   rt = RS16_PRE + RS_T;
+    Interactions v;
+    switch (t) {
+    case T_FOLD16:
+        for (uint32_t j = 0; j < 16; j++) v.add(0u, ACTIVE, BUS_L16, {LN, KJ + j, E + 4 * j, E + 4 * j + 1, E + 4 * j + 2, E + 4 * j + 3});
+        if (k < OPENINGS) v.add(0u, L, BUS_Q16, {IDX, OWN, OWN + 1, OWN + 2, OWN + 3});
+        else v.add(0u, L, BUS_Q16, {IDX, XQ, OWN, OWN + 1, OWN + 2, OWN + 3});                                     // FOLD16C: the query's point goes with it
+        v.add(0u, L + R - 1u, BUS_FIN16, {X16, FOLD, FOLD + 1, FOLD + 2, FOLD + 3});
+        if (k >= INDICES) v.add(1u, ACTIVE, BUS_BF16, {LN, BETA, BETA + 1, BETA + 2, BETA + 3});                   // FOLD16B: the challenge is received
+        break;
+    case T_FINAL:
+        v.add(1u, FACT, BUS_COEF, {FJ, CFC, CFC + 1, CFC + 2, CFC + 3});
+        v.add(1u, FLAST, BUS_FIN16, {CFX, CFACC, CFACC + 1, CFACC + 2, CFACC + 3});
+        break;
+    case T_LAYERS:
+        if (k == LAYERS) {
+            for (uint32_t j = 0; j < 16; j++) v.add(1u, LAY_M, BUS_L16, {LAY_LN, LAY_KEY + j, LAY_E + 4 * j, LAY_E + 4 * j + 1, LAY_E + 4 * j + 2, LAY_E + 4 * j + 3});
+        } else {                                                                                                   // P24L
+            using namespace p24chip;
+            const uint32_t o7 = oute(7);
+            for (uint32_t i = 0; i < 4; i++) v.add(1u, L_M, BUS_L16, {L_LN, L_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
+            v.add(0u, END, BUS_RT0, {L_LN, L_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
+            v.add(0u, END, BUS_RT1, {L_LN, L_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
+        }
+        break;
+    case T_QUERIES:
+        if (k < INDICES) v.add(1u, 5u, BUS_Q16, {0u, 1u, 2u, 3u, 4u});
+        else if (k == INDICES) {                                                                                   // by query number; the index is a main column, from SAMPLES
+            v.add(1u, 5u, BUS_Q16, {Q_PRE, 1u, 2u, 3u, 4u});
+            v.add(1u, 5u, frichip::BUS_I, {0u, Q_PRE});
+        } else {                                                                                                   // QUERY16
+            v.add(1u, QP_ACT, frichip::BUS_I, {QP_QN, QC_IDX});
+            v.add(1u, QP_ACT, BUS_Q16, {QC_IDX, QC_XQ, QC_RO, QC_RO + 1, QC_RO + 2, QC_RO + 3});
+            v.add(1u, QP_ACT, BUS_AT16, {QP_QN, QC_AT, QC_AT + 1, QC_AT + 2, QC_AT + 3});
+            v.add(1u, QP_ACT, BUS_AQ16, {QP_QN, QC_AQ, QC_AQ + 1, QC_AQ + 2, QC_AQ + 3});
+            if (k == ROWPATHS) {                                                                                   // which tree a tag belongs to and at which index it is opened
+                v.add(0u, QP_ACT, BUS_TAG16, {QP_TG0, QP_LN0, QC_IDX});
+                v.add(0u, QP_ACT, BUS_TAG16, {QP_TG1, QP_LN1, QC_IDX});
+            }
+        }
+        break;
+    case T_COEFFS:
+        v.add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u});
+        if (k >= INDICES) v.add(0u, 6u, BUS_CT, {0u, 1u, 2u, 3u, 4u});                                             // one more send, to P2T
+        break;
+    case T_ROOTS:
+        v.add(1u, RM, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
+        v.add(1u, RM, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+        if (k >= INDICES) {                                                                                        // root and beta from the layer's root row, beta on to the fold rows
+            v.add(1u, 10u, BUS_TR0, {RT_LN, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
+            v.add(1u, 10u, BUS_TR1, {RT_LN, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+            v.add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
+            v.add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
+        }
+        break;
+    case T_P2T:
+        v.add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
+        v.add(1u, PT_C1, BUS_CT, {PT_KEY1, in + 4, in + 5, in + 6, in + 7});
+        v.add(0u, PT_ROOT, BUS_TR0, {PT_LN, in, in + 1, in + 2, in + 3});
+        v.add(0u, PT_ROOT, BUS_TR1, {PT_LN, in + 4, in + 5, in + 6, in + 7});
+        v.add(0u, PT_ROOT, BUS_TB, {PT_LN, o + 7, o + 6, o + 5, o + 4});
+        v.add(0u, PT_SMP, frichip::BUS_S0, {PT_ROW, o + 7, o + 6, o + 5, o + 4});
+        v.add(0u, PT_SMP, frichip::BUS_S1, {PT_ROW, o + 3, o + 2, o + 1, o});
+        break;
+    case T_ROWSUM16:
+        v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
+        v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K1, rv + 4, rv + 5, rv + 6, rv + 7});
+        v.add(0u, RP_LAST0, BUS_AT16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
+        v.add(0u, RP_LAST1, BUS_AQ16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
+        break;
+    default:
+        if (k == OPENINGS) v.add(1u, 6u, BUS_ROW16, {0u, 1u, 2u, 3u, 4u, 5u});                                     // ROWS
+        else {                                                                                                     // P24R
+            using namespace p24chip;
+            const uint32_t o7 = oute(7), mult[4] = {R_M0, p24chip::G(1), p24chip::G(2), p24chip::G(3)};
+            for (uint32_t i = 0; i < 4; i++) v.add(1u, mult[i], BUS_ROW16, {R_TAG, R_K + i, IN + 4 * i, IN + 4 * i + 1, IN + 4 * i + 2, IN + 4 * i + 3});
+            v.add(1u, SS, BUS_TAG16, {R_TAG, R_LNR, R_IX});
+            v.add(0u, END, BUS_RT0, {R_LNR, R_DEP, o7, o7 + 1, o7 + 2, o7 + 3});
+            v.add(0u, END, BUS_RT1, {R_LNR, R_DEP, o7 + 4, o7 + 5, o7 + 6, o7 + 7});
+        }
+        break;
+    }
+    return v.finish();
+}
+
+// programs and interaction tables of a shape in MACHINE order (tallest table first), with the arrays the keyed-machine entries take
+struct Machine {
+    Shape s;
+    std::vector<std::vector<uint32_t>> prog, tab;
+    std::vector<int32_t> log_ns;
+    std::vector<uint32_t> widths, pre_widths;
+    std::vector<const uint32_t*> progs, tabs;
+    std::vector<size_t> prog_words, tab_words;
+};
+// (P24L's, P24R's and P2T's programs follow the Poseidon2 tables in effect: the cache is dropped when they change)
+std::shared_ptr<const Machine> machine_of(const Shape& s) {
+    static std::mutex mu;
+    static std::map<std::array<uint64_t, 7>, std::shared_ptr<const Machine>> cache;
+    static uint64_t cached_gen = ~0ull;
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t gen = g_p2_generation.load();
+    if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
+    const std::array<uint64_t, 7> key{(uint64_t)s.kind, (uint64_t)s.R, (uint64_t)s.F, (uint64_t)s.b, (uint64_t)s.Q, (uint64_t)s.pow_bits, (uint64_t)s.W};
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    auto m = std::make_shared<Machine>();
+    m->s = s;
+    for (int i = 0; i < s.n_tables; i++) {
+        const int t = s.order[i];
+        m->prog.push_back(program_of(s, t)); m->tab.push_back(interactions_of(s, t));
+        m->log_ns.push_back(s.log_rows[t]); m->widths.push_back(s.main_w[t]); m->pre_widths.push_back(s.pre_w[t]);
+    }
+    for (int i = 0; i < s.n_tables; i++) {
+        m->progs.push_back(m->prog[i].data()); m->prog_words.push_back(m->prog[i].size()); m->tabs.push_back(m->tab[i].data()); m->tab_words.push_back(m->tab[i].size());
+    }
+    cache.emplace(key, m);
+    return m;
+}
+
+// what the entries of every kind do with a shape
+size_t describe(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, int which, int what, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                uint32_t* pre_width, int* table) {
+    Shape s;
+    if (which < 0 || which >= N_TABLES[kind] || what < 0 || what > 1 || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
+    const auto m = machine_of(s);
+    const std::vector<uint32_t>& w = what == 0 ? m->prog[which] : m->tab[which];
+    if (log_rows) *log_rows = m->log_ns[which];
+    if (main_width) *main_width = m->widths[which];
+    if (pre_width) *pre_width = m->pre_widths[which];
+    if (table) *table = s.order[which];
+    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
+    return w.size();
+}
+// pre: the key's tables by table number (host, Montgomery)
+int key_host(const Shape& s, const std::vector<uint32_t>* pre, const zkhip_params* prm, uint32_t vk[8]) {
+    const auto m = machine_of(s);
+    std::vector<const uint32_t*> h(s.n_tables);
+    for (int i = 0; i < s.n_tables; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
+    return zkhip_machine_key_host(h.data(), m->log_ns.data(), m->pre_widths.data(), s.n_tables, prm, vk);
+}
+// ... uploaded, each table with preprocessed columns into its scratch slot (slots: by table number)
+int key_upload(zkhip_ctx* ctx, const Shape& s, const std::vector<uint32_t>* pre, const int* slots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    const auto m = machine_of(s);
+    std::vector<zkhip_chip> chips(s.n_tables, zkhip_chip{});
+    for (int i = 0; i < s.n_tables; i++) {
+        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
+        if (!m->pre_widths[i]) continue;
+        const std::vector<uint32_t>& t = pre[s.order[i]];
+        void* dp;
+        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
+        chips[i].d_trace = (const uint32_t*)dp;
+    }
+    return zkhip_machine_setup(ctx, chips.data(), s.n_tables, prm, key, vk);
+}
+size_t proof_size(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const zkhip_params* prm) {
+    Shape s;
+    if (!prm || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
+    const auto m = machine_of(s);
+    return zkhip_machine_proof_size_keyed(m->log_ns.data(), m->widths.data(), m->pre_widths.data(), m->progs.data(), m->prog_words.data(), m->tabs.data(), m->tab_words.data(),
+                                          s.n_tables, prm, n_public_of(s));
+}
+// traces: the main traces on the device (dense) by table number
+int prove(zkhip_ctx* ctx, const zkhip_machine_key* key, const Shape& s, const uint32_t* const* traces, const uint32_t* public_values, const zkhip_params* prm, uint8_t* proof,
+          size_t cap, size_t* len) {
+    const auto m = machine_of(s);
+    std::vector<zkhip_chip> chips(s.n_tables, zkhip_chip{});
+    for (int i = 0; i < s.n_tables; i++) {
+        chips[i].d_trace = traces[s.order[i]];
+        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
+    }
+    return zkhip_prove_machine_keyed(ctx, key, chips.data(), m->progs.data(), m->prog_words.data(), m->tabs.data(), m->tab_words.data(), s.n_tables, public_values, n_public_of(s),
+                                     prm, proof, cap, len);
+}
+int verify(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const uint8_t* proof, size_t len, const uint32_t* public_values, const uint32_t vk[8],
+           const zkhip_params* prm, int* reason, const char* who) {
+    Shape s;
+    if (!proof || !public_values || !vk || !prm || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) {
+        if (reason) *reason = 1;
+        return fail(ZKHIP_ERR_VERIFY, std::string(who) + ": bad arguments");
+    }
+    const auto m = machine_of(s);
+    return zkhip_verify_machine_keyed(proof, len, m->log_ns.data(), m->widths.data(), m->pre_widths.data(), vk, m->progs.data(), m->prog_words.data(), m->tabs.data(),
+                                      m->tab_words.data(), s.n_tables, public_values, n_public_of(s), prm, reason);
 }
 
 struct fold_rows_bargs { FoldRowsArgs a; static fold_rows_bargs make(FoldRowsArgs a) { return fold_rows_bargs{a}; } };
@@ -1153,7 +988,7 @@ static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const ui
     // (d_values: the chains start from values already on the device -- the openings machine's, computed there from the opened rows)
     fri16::ViewArgs v{d, d + nb, d + nb + nf, d_values ? d_values : d + nb + nf + ni, d + nb + nf + ni + nv, (uint32_t)Q, (uint32_t)s.R, (uint32_t)s.F, (uint32_t)s.lf, (uint32_t)s.H};
     uint32_t* d_ends = d + up_words;
-    fri16::FoldRowsArgs fa{v, s.main_w[0], (uint64_t)1 << s.log_rows[0], d_fold, ld_fold, d_ends};
+    fri16::FoldRowsArgs fa{v, fri16::fold16_width((uint32_t)s.lf), (uint64_t)1 << s.log_rows[0], d_fold, ld_fold, d_ends};
     const size_t pad = (size_t)fa.rows - Q * R, fold_lanes = Q * R + (pad < 4096 ? pad : 4096);        // the padding rows are shared among up to 4096 extra lanes
     ZK_LAUNCH(fri16::fri16_fold_rows_kernel, fri16::fri16_fold_rows_kernel_batch, fri16::fold_rows_bargs, dim3((unsigned)((fold_lanes + 63) / 64)), dim3(64), 0, ctx->stream, fa);
     ZK_HIP(hipGetLastError());
@@ -1171,12 +1006,11 @@ static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const ui
 
 // P24L from the caller's plan of the view's paths (fri16::plan_paths, which refuses queries that disagree about the path of a shared row) and the FOLD16 trace already on
 // the device (its E columns are the leaves); ends [n][8]: where every path ends.  Refused here: two queries that disagree about a shared row.
-static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::PShape& s, const uint32_t* paths, const uint32_t* d_fold, size_t ld_fold, uint32_t* d_trace, size_t ld,
+static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* paths, const uint32_t* d_fold, size_t ld_fold, uint32_t* d_trace, size_t ld,
                                      const fri16::PathPlan& pl, std::vector<uint32_t>& ends) {
-    const fri16::Shape& b = s.base;
     const size_t rows = (size_t)1 << s.log_rows[fri16::T_P24L];
     if (pl.used_rows > rows) return fail(ZKHIP_ERR_INVALID, "fri16 paths: the paths do not fit the table");
-    const size_t nd = 8 * pl.n, nr = (pl.readers.size() + 3) & ~(size_t)3, ns = b.Q * pl.path_words, up_words = nd + nr + ns;
+    const size_t nd = 8 * pl.n, nr = (pl.readers.size() + 3) & ~(size_t)3, ns = s.Q * pl.path_words, up_words = nd + nr + ns;
     void* stage;
     ZK_TRY(ctx_reserve(ctx, S_REC_I, (up_words + 9 * pl.n) * 4, &stage));
     uint32_t* d = (uint32_t*)stage;
@@ -1195,7 +1029,7 @@ static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::PShape& s, con
     ZK_TRY(dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4));
     for (size_t p = 0; p < pl.n; p++)
         if (const uint32_t k = ends[8 * pl.n + p])
-            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.readers[pl.desc[8 * p + 5] + k - 1] / (uint32_t)b.R) + " layer " + std::to_string(pl.layer_of[p]) +
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.readers[pl.desc[8 * p + 5] + k - 1] / (uint32_t)s.R) + " layer " + std::to_string(pl.layer_of[p]) +
                                                " disagrees with query " + std::to_string(pl.first_query[p]) + " about a shared row");
     ends.resize(8 * pl.n);
     return ZKHIP_OK;
@@ -1207,153 +1041,10 @@ static int fri16_paths_check_view(const fri16::Shape& s, int inner_hash_width, c
     return fri16::check_view(s, betas, final_poly, indices, values, siblings, who);
 }
 
-extern "C" {
-
-size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
-                                  uint32_t* pre_width, int* table) {
-    fri16::PShape s;
-    if (which < 0 || which >= fri16::N_PT || kind < 0 || kind > 1 || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::paths_machine_of(s);
-    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
-}
-
-int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                               const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::PShape s;
-    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::N_PT];
-    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key_host"));
-    const auto m = fri16::paths_machine_of(s);
-    const uint32_t* h[fri16::N_PT];
-    for (int i = 0; i < fri16::N_PT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_PT, prm, vk);
-}
-
-int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
-                          const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
-    CHECK_CTX(ctx);
-    fri16::PShape s;
-    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key: null argument");
-    std::vector<uint32_t> pre[fri16::N_PT];
-    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key"));
-    const auto m = fri16::paths_machine_of(s);
-    const int slots[fri16::N_PT] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
-    zkhip_chip chips[fri16::N_PT]{};
-    for (int i = 0; i < fri16::N_PT; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
-        void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[i], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
-    }
-    return zkhip_machine_setup(ctx, chips, fri16::N_PT, prm, key, vk);
-}
-
-int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly,
-                                const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* paths, uint32_t* d_trace, size_t ld,
-                                uint32_t* ends, size_t cap_paths, size_t* n_paths) {
-    CHECK_CTX(ctx);
-    fri16::PShape s;
-    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
-    ZK_TRY(fri16_paths_check_view(s.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "fri16_paths_gen_trace"));
-    if (!d_trace || !ends || !n_paths || ld < p24chip::WIDTH_L || ld % 4 || (uintptr_t)d_trace % 16)
-        return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: a 16-byte aligned trace, a leading dimension that is a multiple of 4 and holds 552 columns, ends and n_paths");
-    void *t_fold, *t_final;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
-    ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
-    fri16::PathPlan pl;
-    std::vector<uint32_t> e;
-    ZK_TRY(fri16::plan_paths(s.base, indices, paths, pl));
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, (const uint32_t*)t_fold, s.main_w[0], d_trace, ld, pl, e));
-    *n_paths = pl.n;
-    if (cap_paths < pl.n) return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: more paths than `ends` holds");
-    std::memcpy(ends, e.data(), e.size() * 4);
-    return ZKHIP_OK;
-}
-
-size_t zkhip_fri16_paths_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
-    fri16::PShape s;
-    if (!prm || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::paths_machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, prm, 4 * (size_t)R);
-}
-
-int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas,
-                            const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
-                            const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    fri16::PShape s;
-    ZK_TRY(fri16::paths_shape_of(R, F, log_blowup, n_queries, s));
-    if (!key || !prm || !proof || !len || !roots) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: null argument");
-    ZK_TRY(fri16_paths_check_view(s.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_paths"));
-    if (!fri16::canonical(roots, 8 * (size_t)R)) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: values must be canonical");
-    const auto m = fri16::paths_machine_of(s);
-    void *t_fold, *t_final, *t_p24, *t_tabs;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
-    // the three tables' main columns: QUERIES and COEFFS unused, zero; ROOTS the number of path ends per layer
-    size_t zoff[fri16::N_PT] = {0}, zwords = 0;
-    for (int t : {(int)fri16::T_QUERIES, (int)fri16::T_COEFFS, (int)fri16::T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)fri16::TAB_MAIN << s.log_rows[t]; }
-    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
-    // refused here, before anything is proven: chains that do not end in the final polynomial, queries that disagree, paths that do not end in their layer's root
-    ZK_TRY(fri16_gen_traces_impl(ctx, s.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
-    fri16::PathPlan pl;
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16::plan_paths(s.base, indices, paths, pl));
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
-    for (size_t p = 0; p < pl.n; p++)
-        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
-                                               " does not open: its path does not end in the layer's root");
-    {
-        std::vector<uint32_t> tabs(zwords, 0u);
-        for (int l = 0; l < R; l++) tabs[zoff[fri16::T_ROOTS] + (size_t)fri16::TAB_MAIN * l] = to_monty(pl.counts[l]);
-        ZK_TRY(dev_h2d(ctx, t_tabs, tabs.data(), zwords * 4));
-    }
-    zkhip_chip chips[fri16::N_PT]{};
-    for (int i = 0; i < fri16::N_PT; i++) {
-        const int t = s.order[i];
-        chips[i].d_trace = t == fri16::T_FOLD16 ? (const uint32_t*)t_fold : t == fri16::T_FINAL ? (const uint32_t*)t_final : t == fri16::T_P24L ? (const uint32_t*)t_p24
-                                                                                                                           : (const uint32_t*)t_tabs + zoff[t];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
-    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, betas, 4 * (size_t)R, prm, proof, cap, len);
-}
-
-int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
-                             const zkhip_params* prm, int* reason) {
-    fri16::PShape s;
-    if (!proof || !betas || !vk || !prm || fri16::paths_shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) {
-        if (reason) *reason = 1;
-        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_paths: bad arguments");
-    }
-    const auto m = fri16::paths_machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_PT, betas, 4 * (size_t)R, prm,
-                                      reason);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the indices machine's entries
 // P2T, SAMPLES and (non-null) the main columns of QUERIES and ROOTS in one launch from one staging block; status: what the kernel found different from the view
-static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::IShape& s, const fri16::Chain& c, const uint32_t* view_betas, const uint32_t* view_indices, const uint32_t* counts,
+static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::Chain& c, const uint32_t* view_betas, const uint32_t* view_indices, const uint32_t* counts,
                                  uint32_t* d_p2t, uint32_t* d_samples, uint32_t* d_qmain, uint32_t* d_rmain, uint32_t* status) {
-    const fri16::Shape& b = s.p.base;
-    const size_t R = (size_t)b.R, Q = b.Q, ni = (Q + 3) & ~(size_t)3, nr = (R + 3) & ~(size_t)3;
+    const size_t R = (size_t)s.R, Q = s.Q, ni = (Q + 3) & ~(size_t)3, nr = (R + 3) & ~(size_t)3;
     const size_t o_words = 16 * s.NT, o_betas = o_words + 8 * s.S, o_vbetas = o_betas + 4 * R, o_vidx = o_vbetas + 4 * R, o_counts = o_vidx + ni, o_status = o_counts + nr, up_words = o_status + 4;
     void* stage;
     ZK_TRY(ctx_reserve(ctx, S_REC_E, up_words * 4, &stage));
@@ -1371,87 +1062,416 @@ static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::IShape& s, const f
     p2chip::Fri16TranscriptArgs a{};
     a.chain_inputs = d; a.words = d + o_words; a.drawn_betas = d + o_betas; a.view_betas = view_betas ? d + o_vbetas : nullptr; a.view_indices = view_indices ? d + o_vidx : nullptr;
     a.counts = counts ? d + o_counts : nullptr;
-    a.n_chain = (uint32_t)s.NT; a.n_sample_rows = (uint32_t)s.S; a.R = (uint32_t)R; a.Q = (uint32_t)Q; a.index_bits = (uint32_t)b.H;
+    a.n_chain = (uint32_t)s.NT; a.n_sample_rows = (uint32_t)s.S; a.R = (uint32_t)R; a.Q = (uint32_t)Q; a.index_bits = (uint32_t)s.H;
     a.p2t_rows = d_p2t ? (uint64_t)1 << s.log_rows[fri16::T_P2T] : 0; a.samples_rows = (uint64_t)1 << s.log_rows[fri16::T_SAMPLES];
     a.queries_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERIES]; a.roots_rows = (uint64_t)1 << s.log_rows[fri16::T_ROOTS];
     a.p2t = d_p2t; a.samples = d_samples; a.queries_main = d_qmain; a.roots_main = d_rmain; a.status = d + o_status;
     ZK_HIP(launch_fri16_transcript(a, ctx->stream));
     return dev_d2h(ctx, status, a.status, 4);
 }
-static int fri16_indices_check_inputs(const fri16::IShape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, const char* who) {
-    const fri16::Shape& b = s.p.base;
+static int fri16_indices_check_inputs(const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, const char* who) {
     if (!capacity || !roots || !final_poly) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!fri16::canonical(capacity, 8) || !fri16::canonical(roots, 8 * (size_t)b.R) || !fri16::canonical(final_poly, (size_t)4 << b.F) || witness >= P)
+    if (!fri16::canonical(capacity, 8) || !fri16::canonical(roots, 8 * (size_t)s.R) || !fri16::canonical(final_poly, (size_t)4 << s.F) || witness >= P)
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     return ZKHIP_OK;
 }
 
+// ROWSUM16 and QUERY16 in one launch from one staging block (rows, constants, indices, the view's values); the reduced openings stay on the device (*d_openings,
+// canonical, where the fold kernel reads its chains' first values); status[0] / status[1]: the least query whose opening differs from view_values / whose point has no
+// inverse (0xFFFFFFFF: none)
+static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices,
+                                    const uint32_t* view_values, uint32_t* d_rowsum, uint32_t* d_query, uint32_t** d_openings, uint32_t status[2], const uint32_t** d_indices = nullptr,
+                                    const uint32_t** d_rows = nullptr) {      // d_rows: where the raw rows lie on the device, [Q][W] then [Q][8]
+    const size_t Q = s.Q, W = s.W, nt = Q * W, nq = Q * fri16::QROW16, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q;
+    const size_t o_q = nt, o_c = o_q + nq, o_i = o_c + 32, o_v = o_i + ni, o_open = o_v + nv, o_status = o_open + nv, words = o_status + 4;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_REC_J, words * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(words, 0u);
+        std::memcpy(up.data(), trows, nt * 4);
+        std::memcpy(up.data() + o_q, qrows, nq * 4);
+        std::memcpy(up.data() + o_c, consts, 32 * 4);
+        std::memcpy(up.data() + o_i, indices, Q * 4);
+        if (view_values) std::memcpy(up.data() + o_v, view_values, nv * 4);
+        for (int i = 0; i < 4; i++) up[o_status + i] = 0xFFFFFFFFu;
+        ZK_TRY(dev_h2d(ctx, d, up.data(), words * 4));
+    }
+    fri16::OpeningsRowsArgs a{};
+    a.trows = d; a.qrows = d + o_q; a.consts = d + o_c; a.indices = d + o_i; a.view_values = view_values ? d + o_v : nullptr;
+    a.Q = (uint32_t)Q; a.W = (uint32_t)W; a.H = (uint32_t)s.H;
+    a.rowsum_rows = (uint64_t)1 << s.log_rows[fri16::T_ROWSUM16]; a.query_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERY16];
+    a.rowsum = d_rowsum; a.query = d_query; a.openings = d + o_open; a.status = d + o_status;
+    const size_t per = W / 8 + 1;
+    if (per <= 64) {
+        const size_t qpw = 64 / per;
+        ZK_LAUNCH(fri16::fri16_openings_rows_kernel, fri16::fri16_openings_rows_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)((Q + qpw - 1) / qpw)), dim3(64), 0, ctx->stream, a);
+    } else
+        ZK_LAUNCH(fri16::fri16_openings_rows_tall_kernel, fri16::fri16_openings_rows_tall_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)Q), dim3(64), 0, ctx->stream, a);
+    ZK_HIP(hipGetLastError());
+    uint32_t st[4];
+    ZK_TRY(dev_d2h(ctx, st, a.status, 16));
+    status[0] = st[0]; status[1] = st[1];
+    *d_openings = a.openings;
+    if (d_indices) *d_indices = a.indices;
+    if (d_rows) *d_rows = d;
+    return ZKHIP_OK;
+}
+static int fri16_openings_check_rows(const fri16::Shape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices, const char* who) {
+    if (!trows || !qrows || !consts || !indices) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(trows, s.Q * (size_t)s.W) || !fri16::canonical(qrows, s.Q * fri16::QROW16) || !fri16::canonical(consts, 32))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    return ZKHIP_OK;
+}
+static int fri16_openings_no_inverse(const char* who, uint32_t q) {
+    return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the point of query " + std::to_string(q) + " is zeta or zeta g: its reduced opening has no inverse");
+}
+
+// P24R in one launch: a path per (query, tree), tag order.  d_rows: the raw rows where fri16_openings_rows_impl left them on the device ([Q][W], then [Q][8]), or null:
+// they are uploaded here.  ends [2 Q][8]: where every path ends (canonical).
+static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* d_rows, const uint32_t* trows, const uint32_t* qrows, const uint32_t* indices,
+                                        const uint32_t* tpaths, const uint32_t* qpaths, uint32_t* d_trace, size_t ld, std::vector<uint32_t>& ends) {
+    const size_t Q = s.Q, W = s.W, H = (size_t)s.H, n = 2 * Q, blocks = (W + 15) / 16, rows = (size_t)1 << s.log_rows[fri16::T_P24R];
+    const size_t nd = 8 * n, ns = 8 * H * n, nr = d_rows ? 0 : Q * (W + fri16::QROW16), up_words = nd + ns + nr;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 8 * n) * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    size_t used = 0;
+    {
+        std::vector<uint32_t> up(up_words, 0u);
+        for (size_t q = 0; q < Q; q++)
+            for (size_t tree = 0; tree < 2; tree++) {
+                const size_t p = 2 * q + tree;
+                const uint32_t desc[8] = {(uint32_t)p, (uint32_t)((size_t)s.R + tree), indices[q], (uint32_t)(tree ? fri16::QROW16 : W), (uint32_t)used,
+                                          (uint32_t)(tree ? Q * W + fri16::QROW16 * q : W * q), (uint32_t)(8 * H * p), 0u};
+                std::memcpy(up.data() + 8 * p, desc, 32);
+                std::memcpy(up.data() + nd + 8 * H * p, (tree ? qpaths : tpaths) + 8 * H * q, 32 * H);
+                used += (tree ? 1 : blocks) + H;
+            }
+        if (!d_rows) {
+            std::memcpy(up.data() + nd + ns, trows, Q * W * 4);
+            std::memcpy(up.data() + nd + ns + Q * W, qrows, Q * fri16::QROW16 * 4);
+        }
+        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
+    }
+    if (used > rows) return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: the paths do not fit the table");
+    p24chip::RowPathsArgs a{};
+    a.desc = d; a.siblings = d + nd; a.rows = d_rows ? d_rows : d + nd + ns; a.n_paths = n; a.trace_rows = rows; a.used_rows = used; a.depth = (uint32_t)H;
+    a.trace = d_trace; a.ld = ld; a.ends = d + up_words;
+    ZK_HIP(launch_p24chip_row_paths(a, ctx->stream));
+    ends.resize(8 * n);
+    return dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4);
+}
+// refused before anything is hashed: null or non-canonical path words, by query and tree
+static int fri16_rowpaths_check_paths(const fri16::Shape& s, const uint32_t* tpaths, const uint32_t* qpaths, const uint32_t* troot, const uint32_t* qroot, const char* who) {
+    if (!tpaths || !qpaths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (troot && (!qroot || !fri16::canonical(troot, 8) || !fri16::canonical(qroot, 8))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+    const size_t per = 8 * (size_t)s.H;
+    for (size_t q = 0; q < s.Q; q++)
+        for (int tree = 0; tree < 2; tree++)
+            if (!fri16::canonical((tree ? qpaths : tpaths) + per * q, per))
+                return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(q) + ", " + (tree ? "quotient" : "trace") + " tree: path words must be canonical");
+    return ZKHIP_OK;
+}
+
+// ---------------------------------------------------------------- the provers' stages.  Each reserves what it makes, launches, and refuses in the caller's name (who).
+// FOLD16's and FINAL's traces (S_REC_A, S_REC_B): what every prover starts with
+static int fri16_reserve_fold_final(zkhip_ctx* ctx, const fri16::Shape& s, uint32_t** d_fold, uint32_t** d_final) {
+    void *t_fold, *t_final;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[fri16::T_FOLD16] << s.log_rows[fri16::T_FOLD16]) * 4, &t_fold));
+    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[fri16::T_FINAL] << s.log_rows[fri16::T_FINAL]) * 4, &t_final));
+    *d_fold = (uint32_t*)t_fold; *d_final = (uint32_t*)t_final;
+    return ZKHIP_OK;
+}
+// the small tables' main columns, one region each of one block (S_CHIP).  QUERIES from OPENINGS on is no table of the machine (QUERY16 holds the index in its own row):
+// a scratch block of the plain table's width, which the transcript kernel fills with the indices
+struct Fri16SmallTables {
+    uint32_t* d = nullptr;
+    size_t off[fri16::MAX_TABLES] = {0}, words[fri16::MAX_TABLES] = {0}, total = 0;
+    uint32_t* at(int t) const { return d + off[t]; }
+};
+static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std::initializer_list<int> tables, Fri16SmallTables& z) {
+    for (int t : tables) {
+        z.off[t] = z.total;
+        z.words[t] = (size_t)(t == fri16::T_QUERIES && s.kind >= fri16::OPENINGS ? fri16::TAB_MAIN : s.main_w[t]) << s.log_rows[t];
+        z.total += z.words[t];
+    }
+    void* p;
+    ZK_TRY(ctx_reserve(ctx, S_CHIP, z.total * 4, &p));
+    z.d = (uint32_t*)p;
+    return ZKHIP_OK;
+}
+// P2T and SAMPLES (S_REC_C, S_REC_D) and the main columns of QUERIES and ROOTS from the chain walked on the host.  Refused: challenges and indices the chain does not
+// draw, a witness that fails the proof of work
+static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness,
+                                  const uint32_t* betas, const uint32_t* indices, const fri16::PathPlan& pl, uint32_t* d_qmain, uint32_t* d_rmain, const uint32_t** d_p2t,
+                                  const uint32_t** d_samples, const char* who) {
+    void *t_p2t, *t_smp;
+    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
+    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
+    fri16::Chain c;
+    fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
+    uint32_t status = 0;
+    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status));
+    if (status & 1u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges are not the ones the transcript draws from these roots and this capacity");
+    if (s.pow_bits && (c.words[0] & ((1u << s.pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the witness does not satisfy the proof of work");
+    if (status & 2u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the query indices are not the ones the transcript draws");
+    *d_p2t = (const uint32_t*)t_p2t; *d_samples = (const uint32_t*)t_smp;
+    return ZKHIP_OK;
+}
+// P24L (S_REC_H) from the plan of the view's paths and the FOLD16 trace.  Refused: queries that disagree about a shared row, paths that do not end in their layer's root.
+// (The plan is the caller's: from INDICES on the transcript stage, which comes first, takes the path counts from it.)
+static int fri16_layer_paths_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* paths, const uint32_t* roots, const uint32_t* d_fold, size_t ld_fold,
+                                   const fri16::PathPlan& pl, const uint32_t** d_p24) {
+    void* t_p24;
+    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, d_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    for (size_t p = 0; p < pl.n; p++)
+        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
+                                               " does not open: its path does not end in the layer's root");
+    *d_p24 = (const uint32_t*)t_p24;
+    return ZKHIP_OK;
+}
+// ROWSUM16 and QUERY16 (S_REC_F, S_REC_G), then FOLD16C and FINAL with the chains starting from the openings the device computed, XQ beside the fold kernel's columns.
+// Refused: points without an inverse, openings the rows do not give, chains that do not end in the final polynomial.  d_rows: where the raw rows stay on the device
+static int fri16_openings_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                                const uint32_t* siblings, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, uint32_t* d_fold, uint32_t* d_final,
+                                const uint32_t** d_rowsum, const uint32_t** d_query, const uint32_t** d_rows, const char* who) {
+    using namespace fri16;
+    const size_t ld_fold = s.main_w[T_FOLD16];
+    void *t_rs, *t_q;
+    ZK_TRY(ctx_reserve(ctx, S_REC_F, ((size_t)RS_MAIN16 << s.log_rows[T_ROWSUM16]) * 4, &t_rs));
+    ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
+    uint32_t ost[2], *d_open = nullptr;
+    const uint32_t* d_idx = nullptr;
+    ZK_TRY(fri16_openings_rows_impl(ctx, s, trows, qrows, consts, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx, d_rows));
+    if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse(who, ost[1]);
+    if (ost[0] != 0xFFFFFFFFu)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, s.main_w[T_FINAL], d_open));
+    XqColsArgs xa{};
+    xa.indices = d_idx; xa.Q = (uint32_t)s.Q; xa.R = (uint32_t)s.R; xa.H = (uint32_t)s.H;
+    xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = d_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
+    ZK_LAUNCH(fri16_xq_cols_kernel, fri16_xq_cols_kernel_batch, xq_cols_bargs, dim3((unsigned)((xa.rows + 63) / 64)), dim3(64), 0, ctx->stream, xa);
+    ZK_HIP(hipGetLastError());
+    *d_rowsum = (const uint32_t*)t_rs; *d_query = (const uint32_t*)t_q;
+    return ZKHIP_OK;
+}
+// the 40 public values from OPENINGS on: the capacity, then the eight constants
+static void fri16_openings_public(const uint32_t capacity[8], const uint32_t constants[32], uint32_t pub[fri16::N_PUBLIC_O]) {
+    std::memcpy(pub, capacity, 32);
+    std::memcpy(pub + 8, constants, 128);
+}
+
 extern "C" {
 
+// ---------------------------------------------------------------- LAYERS: the first machine's entries
+size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                            uint32_t* pre_width, int* table) {
+    return fri16::describe(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+}
+
+int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                         const uint32_t* siblings, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key_host: null argument");
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key_host"));
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
+    return fri16::key_host(s, pre, prm, vk);
+}
+
+int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                    const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key: null argument");
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key"));
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
+    const int by_position[5] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G};      // this machine and PATHS give the slots out by machine position
+    int slots[fri16::MAX_TABLES];
+    for (int i = 0; i < s.n_tables; i++) slots[s.order[i]] = by_position[i];
+    return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
+}
+
+int zkhip_fri16_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
+                           const uint32_t* values, const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
+    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_gen_traces"));
+    if (!d_fold || !d_final || ld_fold < s.main_w[0] || ld_final < fri16::FIN_MAIN || ld_fold % 4 || ld_final % 4 || ((uintptr_t)d_fold | (uintptr_t)d_final) % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_gen_traces: 16-byte aligned traces, leading dimensions multiples of 4 that hold the tables' widths");
+    return fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, ld_final);
+}
+
+size_t zkhip_fri16_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
+    return fri16::proof_size(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, prm);
+}
+
+int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly,
+                      const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    using namespace fri16;
+    Shape s;
+    ZK_TRY(shape_of(LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
+    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16: null argument");
+    ZK_TRY(check_view(s, betas, final_poly, indices, values, siblings, "prove_fri16"));
+    uint32_t *t_fold, *t_final;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    Fri16SmallTables z;          // the three key tables' main columns: unused, zero
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_LAYERS, T_QUERIES, T_COEFFS}, z));
+    ZK_TRY(dev_memset(ctx, z.d, 0, z.total * 4));
+    // refused here, before anything is proven: a view whose chains do not end in the final polynomial
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, z.at(T_LAYERS), z.at(T_QUERIES), z.at(T_COEFFS)};
+    return prove(ctx, key, s, traces, betas, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
+                       int* reason) {
+    return fri16::verify(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, proof, len, betas, vk, prm, reason, "verify_fri16");
+}
+
+// ---------------------------------------------------------------- PATHS
+size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
+                                  uint32_t* pre_width, int* table) {
+    return fri16::describe(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+}
+
+int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key_host"));
+    return fri16::key_host(s, pre, prm, vk);
+}
+
+int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
+                          const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key"));
+    const int by_position[6] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
+    int slots[fri16::MAX_TABLES];
+    for (int i = 0; i < s.n_tables; i++) slots[s.order[i]] = by_position[i];
+    return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
+}
+
+int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly,
+                                const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* paths, uint32_t* d_trace, size_t ld,
+                                uint32_t* ends, size_t cap_paths, size_t* n_paths) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "fri16_paths_gen_trace"));
+    if (!d_trace || !ends || !n_paths || ld < p24chip::WIDTH_L || ld % 4 || (uintptr_t)d_trace % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: a 16-byte aligned trace, a leading dimension that is a multiple of 4 and holds 552 columns, ends and n_paths");
+    uint32_t *t_fold, *t_final;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
+    fri16::PathPlan pl;
+    std::vector<uint32_t> e;
+    ZK_TRY(fri16::plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, t_fold, s.main_w[0], d_trace, ld, pl, e));
+    *n_paths = pl.n;
+    if (cap_paths < pl.n) return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: more paths than `ends` holds");
+    std::memcpy(ends, e.data(), e.size() * 4);
+    return ZKHIP_OK;
+}
+
+size_t zkhip_fri16_paths_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
+    return fri16::proof_size(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, prm);
+}
+
+int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas,
+                            const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
+                            const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    using namespace fri16;
+    Shape s;
+    ZK_TRY(shape_of(PATHS, R, F, log_blowup, n_queries, 0, 0, s));
+    if (!key || !prm || !proof || !len || !roots) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: null argument");
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_paths"));
+    if (!canonical(roots, 8 * (size_t)R)) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: values must be canonical");
+    uint32_t *t_fold, *t_final;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    Fri16SmallTables z;          // the three tables' main columns: QUERIES and COEFFS unused, zero; ROOTS the number of path ends per layer
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
+    // refused here, before anything is proven: chains that do not end in the final polynomial, queries that disagree, paths that do not end in their layer's root
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
+    PathPlan pl;
+    const uint32_t* t_p24;
+    ZK_TRY(plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[0], pl, &t_p24));
+    {
+        std::vector<uint32_t> tabs(z.total, 0u);
+        for (int l = 0; l < R; l++) tabs[z.off[T_ROOTS] + (size_t)TAB_MAIN * l] = to_monty(pl.counts[l]);
+        ZK_TRY(dev_h2d(ctx, z.d, tabs.data(), z.total * 4));
+    }
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS)};
+    return prove(ctx, key, s, traces, betas, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
+                             const zkhip_params* prm, int* reason) {
+    return fri16::verify(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, proof, len, betas, vk, prm, reason, "verify_fri16_paths");
+}
+
+// ---------------------------------------------------------------- INDICES
 size_t zkhip_fri16_indices_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows,
                                     uint32_t* main_width, uint32_t* pre_width, int* table) {
-    fri16::IShape s;
-    if (which < 0 || which >= fri16::N_IT || kind < 0 || kind > 1 || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::indices_machine_of(s);
-    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
+    return fri16::describe(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_indices_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly, const uint32_t* values,
                                  const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::IShape s;
-    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key_host"));
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::N_IT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key_host"));
-    const auto m = fri16::indices_machine_of(s);
-    const uint32_t* h[fri16::N_IT];
-    for (int i = 0; i < fri16::N_IT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_IT, prm, vk);
+    return fri16::key_host(s, pre, prm, vk);
 }
+
+// (INDICES on: the key's slots by table number -- the tables with preprocessed columns)
+static const int FRI16_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B};
 
 int zkhip_fri16_indices_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly,
                             const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::IShape s;
-    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key"));
     if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key: null argument");
-    std::vector<uint32_t> pre[fri16::N_IT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key"));
-    const auto m = fri16::indices_machine_of(s);
-    const int slots[fri16::N_IT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};         // by table number: the six tables with preprocessed columns
-    zkhip_chip chips[fri16::N_IT]{};
-    for (int i = 0; i < fri16::N_IT; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
-        void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
-    }
-    return zkhip_machine_setup(ctx, chips, fri16::N_IT, prm, key, vk);
+    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);
 }
 
 size_t zkhip_fri16_indices_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const zkhip_params* prm) {
-    fri16::IShape s;
-    if (!prm || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::indices_machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, prm, fri16::N_PUBLIC_I);
+    return fri16::proof_size(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, prm);
 }
 
 int zkhip_fri16_indices_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8], const uint32_t* roots,
                                    const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2t, uint32_t* d_samples, uint32_t* betas, uint32_t* indices) {
     CHECK_CTX(ctx);
-    fri16::IShape s;
-    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
     ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, "fri16_indices_gen_traces"));
     if (!d_p2t || !d_samples || !betas || !indices || ((uintptr_t)d_p2t | (uintptr_t)d_samples) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_indices_gen_traces: 16-byte aligned dense traces (352 and 288 columns), betas and indices");
@@ -1489,297 +1509,74 @@ int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int 
                               const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
                               const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
     CHECK_CTX(ctx);
-    fri16::IShape s;
-    ZK_TRY(fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s));
+    using namespace fri16;
+    const char* who = "prove_fri16_indices";
+    Shape s;
+    ZK_TRY(shape_of(INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
     if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: null argument");
-    ZK_TRY(fri16_paths_check_view(s.p.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_indices"));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, "prove_fri16_indices"));
-    const auto m = fri16::indices_machine_of(s);
-    const fri16::PShape& ps = s.p;
-    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
-    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
-    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
-    // the three tables' main columns: QUERIES the indices, COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer
-    size_t zoff[fri16::N_IT] = {0}, zwords = 0;
-    for (int t : {(int)fri16::T_QUERIES, (int)fri16::T_COEFFS, (int)fri16::T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)s.main_w[t] << s.log_rows[t]; }
-    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
-    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[fri16::T_COEFFS], 0, ((size_t)s.main_w[fri16::T_COEFFS] << s.log_rows[fri16::T_COEFFS]) * 4));
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
+    uint32_t *t_fold, *t_final;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    Fri16SmallTables z;          // the three tables' main columns: QUERIES the indices, COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
+    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
     // refused here, before anything is proven: challenges and indices the chain does not draw, a witness that fails the proof of work; then all the paths machine refuses
-    fri16::Chain c;
-    fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
-    fri16::PathPlan pl;
-    ZK_TRY(fri16::plan_paths(ps.base, indices, paths, pl));
-    uint32_t status = 0;
-    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[fri16::T_QUERIES],
-                                 (uint32_t*)t_tabs + zoff[fri16::T_ROOTS], &status));
-    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the challenges are not the ones the transcript draws from these roots and this capacity");
-    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the witness does not satisfy the proof of work");
-    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: the query indices are not the ones the transcript draws");
-    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
-    for (size_t p = 0; p < pl.n; p++)
-        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
-                                               " does not open: its path does not end in the layer's root");
-    zkhip_chip chips[fri16::N_IT]{};
-    for (int i = 0; i < fri16::N_IT; i++) {
-        const int t = s.order[i];
-        chips[i].d_trace = t == fri16::T_FOLD16 ? (const uint32_t*)t_fold : t == fri16::T_FINAL ? (const uint32_t*)t_final : t == fri16::T_P24L ? (const uint32_t*)t_p24
-                         : t == fri16::T_P2T ? (const uint32_t*)t_p2t : t == fri16::T_SAMPLES ? (const uint32_t*)t_smp : (const uint32_t*)t_tabs + zoff[t];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
-    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, capacity, fri16::N_PUBLIC_I, prm, proof, cap, len);
+    PathPlan pl;
+    const uint32_t *t_p2t, *t_smp, *t_p24;
+    ZK_TRY(plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
+    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[0], pl, &t_p24));
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp};
+    return prove(ctx, key, s, traces, capacity, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
                                const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    fri16::IShape s;
-    if (!proof || !capacity || !vk || !prm || fri16::indices_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, s) != ZKHIP_OK) {
-        if (reason) *reason = 1;
-        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_indices: bad arguments");
-    }
-    const auto m = fri16::indices_machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_IT, capacity,
-                                      fri16::N_PUBLIC_I, prm, reason);
+    return fri16::verify(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, proof, len, capacity, vk, prm, reason, "verify_fri16_indices");
 }
 
-size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
-                            uint32_t* pre_width, int* table) {
-    fri16::Shape s;
-    if (which < 0 || which > 4 || kind < 0 || kind > 1 || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::machine_of(s);
-    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
-}
-
-int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                         const uint32_t* siblings, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key_host: null argument");
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key_host"));
-    std::vector<uint32_t> pre[5];
-    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
-    const auto m = fri16::machine_of(s);
-    const uint32_t* h[5];
-    for (int i = 0; i < 5; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, 5, prm, vk);
-}
-
-int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
-                    const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
-    CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key: null argument");
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key"));
-    std::vector<uint32_t> pre[5];
-    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
-    const auto m = fri16::machine_of(s);
-    const int slots[5] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G};
-    zkhip_chip chips[5]{};
-    for (int i = 0; i < 5; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
-        void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[i], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
-    }
-    return zkhip_machine_setup(ctx, chips, 5, prm, key, vk);
-}
-
-int zkhip_fri16_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
-                           const uint32_t* values, const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
-    CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_gen_traces"));
-    if (!d_fold || !d_final || ld_fold < s.main_w[0] || ld_final < fri16::FIN_MAIN || ld_fold % 4 || ld_final % 4 || ((uintptr_t)d_fold | (uintptr_t)d_final) % 16)
-        return fail(ZKHIP_ERR_INVALID, "fri16_gen_traces: 16-byte aligned traces, leading dimensions multiples of 4 that hold the tables' widths");
-    return fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, ld_final);
-}
-
-size_t zkhip_fri16_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
-    fri16::Shape s;
-    if (!prm || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, 5, prm, 4 * (size_t)R);
-}
-
-int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly,
-                      const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(R, F, log_blowup, n_queries, s));
-    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16: null argument");
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "prove_fri16"));
-    const auto m = fri16::machine_of(s);
-    void *t_fold, *t_final, *t_zero;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, ((size_t)s.main_w[0] << s.log_rows[0]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[1] << s.log_rows[1]) * 4, &t_final));
-    // the three key tables' main columns: unused, zero; one region each
-    size_t zoff[5] = {0}, zwords = 0;
-    for (int t = 2; t < 5; t++) { zoff[t] = zwords; zwords += (size_t)fri16::TAB_MAIN << s.log_rows[t]; }
-    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_zero));
-    ZK_TRY(dev_memset(ctx, t_zero, 0, zwords * 4));
-    // refused here, before anything is proven: a view whose chains do not end in the final polynomial
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, s.main_w[0], (uint32_t*)t_final, s.main_w[1]));
-    zkhip_chip chips[5]{};
-    for (int i = 0; i < 5; i++) {
-        const int t = s.order[i];
-        chips[i].d_trace = t == 0 ? (const uint32_t*)t_fold : t == 1 ? (const uint32_t*)t_final : (const uint32_t*)t_zero + zoff[t];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
-    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, 5, betas, 4 * (size_t)R, prm, proof, cap, len);
-}
-
-int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
-                       int* reason) {
-    fri16::Shape s;
-    if (!proof || !betas || !vk || !prm || fri16::shape_of(R, F, log_blowup, n_queries, s) != ZKHIP_OK) {
-        if (reason) *reason = 1;
-        return fail(ZKHIP_ERR_VERIFY, "verify_fri16: bad arguments");
-    }
-    const auto m = fri16::machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, 5, betas, 4 * (size_t)R, prm, reason);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the openings machine's entries
-// ROWSUM16 and QUERY16 in one launch from one staging block (rows, constants, indices, the view's values); the reduced openings stay on the device (*d_openings,
-// canonical, where the fold kernel reads its chains' first values); status[0] / status[1]: the least query whose opening differs from view_values / whose point has no
-// inverse (0xFFFFFFFF: none)
-static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices,
-                                    const uint32_t* view_values, uint32_t* d_rowsum, uint32_t* d_query, uint32_t** d_openings, uint32_t status[2], const uint32_t** d_indices = nullptr,
-                                    const uint32_t** d_rows = nullptr) {      // d_rows: where the raw rows lie on the device, [Q][W] then [Q][8]
-    const fri16::Shape& b = s.i.p.base;
-    const size_t Q = b.Q, W = s.W, nt = Q * W, nq = Q * fri16::QROW16, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q;
-    const size_t o_q = nt, o_c = o_q + nq, o_i = o_c + 32, o_v = o_i + ni, o_open = o_v + nv, o_status = o_open + nv, words = o_status + 4;
-    void* stage;
-    ZK_TRY(ctx_reserve(ctx, S_REC_J, words * 4, &stage));
-    uint32_t* d = (uint32_t*)stage;
-    {
-        std::vector<uint32_t> up(words, 0u);
-        std::memcpy(up.data(), trows, nt * 4);
-        std::memcpy(up.data() + o_q, qrows, nq * 4);
-        std::memcpy(up.data() + o_c, consts, 32 * 4);
-        std::memcpy(up.data() + o_i, indices, Q * 4);
-        if (view_values) std::memcpy(up.data() + o_v, view_values, nv * 4);
-        for (int i = 0; i < 4; i++) up[o_status + i] = 0xFFFFFFFFu;
-        ZK_TRY(dev_h2d(ctx, d, up.data(), words * 4));
-    }
-    fri16::OpeningsRowsArgs a{};
-    a.trows = d; a.qrows = d + o_q; a.consts = d + o_c; a.indices = d + o_i; a.view_values = view_values ? d + o_v : nullptr;
-    a.Q = (uint32_t)Q; a.W = (uint32_t)W; a.H = (uint32_t)b.H;
-    a.rowsum_rows = (uint64_t)1 << s.log_rows[fri16::T_ROWSUM16]; a.query_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERY16];
-    a.rowsum = d_rowsum; a.query = d_query; a.openings = d + o_open; a.status = d + o_status;
-    const size_t per = W / 8 + 1;
-    if (per <= 64) {
-        const size_t qpw = 64 / per;
-        ZK_LAUNCH(fri16::fri16_openings_rows_kernel, fri16::fri16_openings_rows_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)((Q + qpw - 1) / qpw)), dim3(64), 0, ctx->stream, a);
-    } else
-        ZK_LAUNCH(fri16::fri16_openings_rows_tall_kernel, fri16::fri16_openings_rows_tall_kernel_batch, fri16::openings_rows_bargs, dim3((unsigned)Q), dim3(64), 0, ctx->stream, a);
-    ZK_HIP(hipGetLastError());
-    uint32_t st[4];
-    ZK_TRY(dev_d2h(ctx, st, a.status, 16));
-    status[0] = st[0]; status[1] = st[1];
-    *d_openings = a.openings;
-    if (d_indices) *d_indices = a.indices;
-    if (d_rows) *d_rows = d;
-    return ZKHIP_OK;
-}
-static int fri16_openings_check_rows(const fri16::OShape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices, const char* who) {
-    const fri16::Shape& b = s.i.p.base;
-    if (!trows || !qrows || !consts || !indices) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!fri16::canonical(trows, b.Q * (size_t)s.W) || !fri16::canonical(qrows, b.Q * fri16::QROW16) || !fri16::canonical(consts, 32))
-        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
-    for (size_t q = 0; q < b.Q; q++) if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
-    return ZKHIP_OK;
-}
-static int fri16_openings_no_inverse(const char* who, uint32_t q) {
-    return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the point of query " + std::to_string(q) + " is zeta or zeta g: its reduced opening has no inverse");
-}
-
-extern "C" {
-
+// ---------------------------------------------------------------- OPENINGS
 size_t zkhip_fri16_openings_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
                                      size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    fri16::OShape s;
-    if (which < 0 || which >= fri16::N_OT || kind < 0 || kind > 1 || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::openings_machine_of(s);
-    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
+    return fri16::describe(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_openings_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
                                   const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::OShape s;
-    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key_host"));
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::N_OT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key_host"));
-    const auto m = fri16::openings_machine_of(s);
-    const uint32_t* h[fri16::N_OT];
-    for (int i = 0; i < fri16::N_OT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_OT, prm, vk);
+    return fri16::key_host(s, pre, prm, vk);
 }
 
 int zkhip_fri16_openings_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                              const uint32_t* final_poly, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm,
                              zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::OShape s;
-    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key"));
     if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key: null argument");
-    std::vector<uint32_t> pre[fri16::N_OT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key"));
-    const auto m = fri16::openings_machine_of(s);
-    const int slots[fri16::N_OT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B};      // by table number: the eight tables with preprocessed columns
-    zkhip_chip chips[fri16::N_OT]{};
-    for (int i = 0; i < fri16::N_OT; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
-        void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
-    }
-    return zkhip_machine_setup(ctx, chips, fri16::N_OT, prm, key, vk);
+    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);
 }
 
 size_t zkhip_fri16_openings_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
-    fri16::OShape s;
-    if (!prm || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::openings_machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, prm, fri16::N_PUBLIC_O);
+    return fri16::proof_size(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm);
 }
 
 int zkhip_fri16_openings_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
                                     const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* indices, uint32_t* d_rowsum, uint32_t* d_query,
                                     uint32_t* openings) {
     CHECK_CTX(ctx);
-    fri16::OShape s;
-    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, "fri16_openings_gen_traces"));
     if (!d_rowsum || !d_query || !openings || ((uintptr_t)d_rowsum | (uintptr_t)d_query) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_openings_gen_traces: 16-byte aligned dense traces (48 and 72 columns) and the openings");
@@ -1795,217 +1592,84 @@ int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const zkhip_params* prm, uint8_t* proof, size_t cap,
                                size_t* len) {
     CHECK_CTX(ctx);
-    fri16::OShape s;
-    ZK_TRY(fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: null argument");
-    const fri16::IShape& is = s.i;
-    const fri16::PShape& ps = is.p;
-    ZK_TRY(fri16_paths_check_view(ps.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_openings"));
-    ZK_TRY(fri16_indices_check_inputs(is, capacity, roots, final_poly, witness, "prove_fri16_openings"));
-    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, "prove_fri16_openings"));
-    ZK_TRY(fri16::check_openings_constants(s, constants, "prove_fri16_openings"));
-    const auto m = fri16::openings_machine_of(s);
     using namespace fri16;
-    const size_t ld_fold = s.main_w[T_FOLD16];
-    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp, *t_rs, *t_q;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, (ld_fold << s.log_rows[T_FOLD16]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[T_FINAL] << s.log_rows[T_FINAL]) * 4, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[T_P24L]) * 4, &t_p24));
-    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[T_P2T]) * 4, &t_p2t));
-    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[T_SAMPLES]) * 4, &t_smp));
-    ZK_TRY(ctx_reserve(ctx, S_REC_F, ((size_t)RS_MAIN16 << s.log_rows[T_ROWSUM16]) * 4, &t_rs));
-    ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
-    // the small tables' main columns: COEFFS and ROWS unused (zero), ROOTS path ends, challenge and fold rows per layer; a scratch QUERIES block the transcript kernel
-    // fills with the indices (this machine's QUERY16 holds them in its own row)
-    size_t zoff[N_OT] = {0}, zwords = 0;
-    for (int t : {(int)T_QUERIES, (int)T_COEFFS, (int)T_ROOTS, (int)T_ROWS}) { zoff[t] = zwords; zwords += (size_t)(t == T_QUERIES ? TAB_MAIN : s.main_w[t]) << s.log_rows[t]; }
-    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
-    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_COEFFS], 0, ((size_t)s.main_w[T_COEFFS] << s.log_rows[T_COEFFS]) * 4));
-    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_ROWS], 0, ((size_t)s.main_w[T_ROWS] << s.log_rows[T_ROWS]) * 4));
+    const char* who = "prove_fri16_openings";
+    Shape s;
+    ZK_TRY(shape_of(OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: null argument");
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
+    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
+    ZK_TRY(check_openings_constants(s, constants, who));
+    uint32_t *t_fold, *t_final;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    Fri16SmallTables z;          // the small tables' main columns: COEFFS and ROWS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_ROWS}, z));
+    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
+    ZK_TRY(dev_memset(ctx, z.at(T_ROWS), 0, z.words[T_ROWS] * 4));
     // refused here, before anything is proven: all zkhip_prove_fri16_indices refuses; then openings the rows do not give, points without an inverse
-    Chain c;
-    walk_chain(is, capacity, roots, final_poly, witness, c);
     PathPlan pl;
-    ZK_TRY(plan_paths(ps.base, indices, paths, pl));
-    uint32_t status = 0;
-    ZK_TRY(fri16_transcript_impl(ctx, is, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[T_QUERIES],
-                                 (uint32_t*)t_tabs + zoff[T_ROOTS], &status));
-    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the challenges are not the ones the transcript draws from these roots and this capacity");
-    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the witness does not satisfy the proof of work");
-    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the query indices are not the ones the transcript draws");
-    uint32_t ost[2], *d_open = nullptr;
-    const uint32_t* d_idx = nullptr;
-    ZK_TRY(fri16_openings_rows_impl(ctx, s, trace_rows, quotient_rows, constants, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx));
-    if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse("prove_fri16_openings", ost[1]);
-    if (ost[0] != 0xFFFFFFFFu)
-        return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
-    // the fold chains start from the openings the device computed; XQ beside the fold kernel's columns
-    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, ld_fold, (uint32_t*)t_final, s.main_w[T_FINAL], d_open));
-    {
-        XqColsArgs xa{};
-        xa.indices = d_idx; xa.Q = (uint32_t)ps.base.Q; xa.R = (uint32_t)R; xa.H = (uint32_t)ps.base.H;
-        xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = (uint32_t*)t_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
-        ZK_LAUNCH(fri16_xq_cols_kernel, fri16_xq_cols_kernel_batch, xq_cols_bargs, dim3((unsigned)((xa.rows + 63) / 64)), dim3(64), 0, ctx->stream, xa);
-        ZK_HIP(hipGetLastError());
-    }
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
-    for (size_t p = 0; p < pl.n; p++)
-        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
-                                               " does not open: its path does not end in the layer's root");
-    zkhip_chip chips[N_OT]{};
-    for (int i = 0; i < N_OT; i++) {
-        const int t = s.order[i];
-        chips[i].d_trace = t == T_FOLD16 ? (const uint32_t*)t_fold : t == T_FINAL ? (const uint32_t*)t_final : t == T_P24L ? (const uint32_t*)t_p24
-                         : t == T_P2T ? (const uint32_t*)t_p2t : t == T_SAMPLES ? (const uint32_t*)t_smp : t == T_ROWSUM16 ? (const uint32_t*)t_rs
-                         : t == T_QUERY16 ? (const uint32_t*)t_q : (const uint32_t*)t_tabs + zoff[t];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
+    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24;
+    ZK_TRY(plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
+    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, constants, t_fold, t_final, &t_rs, &t_q, nullptr, who));
+    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, z.at(T_ROWS)};
     uint32_t pub[N_PUBLIC_O];
-    std::memcpy(pub, capacity, 32);
-    std::memcpy(pub + 8, constants, 128);
-    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, N_OT, pub, N_PUBLIC_O, prm, proof, cap, len);
+    fri16_openings_public(capacity, constants, pub);
+    return prove(ctx, key, s, traces, pub, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    fri16::OShape s;
-    if (!proof || !public_values || !vk || !prm || fri16::openings_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) {
-        if (reason) *reason = 1;
-        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_openings: bad arguments");
-    }
-    const auto m = fri16::openings_machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, public_values,
-                                      fri16::N_PUBLIC_O, prm, reason);
+    return fri16::verify(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, public_values, vk, prm, reason, "verify_fri16_openings");
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- the row-paths machine's entries
-// P24R in one launch: a path per (query, tree), tag order.  d_rows: the raw rows where fri16_openings_rows_impl left them on the device ([Q][W], then [Q][8]), or null:
-// they are uploaded here.  ends [2 Q][8]: where every path ends (canonical).
-static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::RShape& s, const uint32_t* d_rows, const uint32_t* trows, const uint32_t* qrows, const uint32_t* indices,
-                                        const uint32_t* tpaths, const uint32_t* qpaths, uint32_t* d_trace, size_t ld, std::vector<uint32_t>& ends) {
-    const fri16::Shape& b = s.o.i.p.base;
-    const size_t Q = b.Q, W = s.o.W, H = (size_t)b.H, n = 2 * Q, blocks = (W + 15) / 16, rows = (size_t)1 << s.log_rows[fri16::T_P24R];
-    const size_t nd = 8 * n, ns = 8 * H * n, nr = d_rows ? 0 : Q * (W + fri16::QROW16), up_words = nd + ns + nr;
-    void* stage;
-    ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 8 * n) * 4, &stage));
-    uint32_t* d = (uint32_t*)stage;
-    size_t used = 0;
-    {
-        std::vector<uint32_t> up(up_words, 0u);
-        for (size_t q = 0; q < Q; q++)
-            for (size_t tree = 0; tree < 2; tree++) {
-                const size_t p = 2 * q + tree;
-                const uint32_t desc[8] = {(uint32_t)p, (uint32_t)((size_t)b.R + tree), indices[q], (uint32_t)(tree ? fri16::QROW16 : W), (uint32_t)used,
-                                          (uint32_t)(tree ? Q * W + fri16::QROW16 * q : W * q), (uint32_t)(8 * H * p), 0u};
-                std::memcpy(up.data() + 8 * p, desc, 32);
-                std::memcpy(up.data() + nd + 8 * H * p, (tree ? qpaths : tpaths) + 8 * H * q, 32 * H);
-                used += (tree ? 1 : blocks) + H;
-            }
-        if (!d_rows) {
-            std::memcpy(up.data() + nd + ns, trows, Q * W * 4);
-            std::memcpy(up.data() + nd + ns + Q * W, qrows, Q * fri16::QROW16 * 4);
-        }
-        ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
-    }
-    if (used > rows) return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: the paths do not fit the table");
-    p24chip::RowPathsArgs a{};
-    a.desc = d; a.siblings = d + nd; a.rows = d_rows ? d_rows : d + nd + ns; a.n_paths = n; a.trace_rows = rows; a.used_rows = used; a.depth = (uint32_t)H;
-    a.trace = d_trace; a.ld = ld; a.ends = d + up_words;
-    ZK_HIP(launch_p24chip_row_paths(a, ctx->stream));
-    ends.resize(8 * n);
-    return dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4);
-}
-// refused before anything is hashed: null or non-canonical path words, by query and tree
-static int fri16_rowpaths_check_paths(const fri16::RShape& s, const uint32_t* tpaths, const uint32_t* qpaths, const uint32_t* troot, const uint32_t* qroot, const char* who) {
-    const fri16::Shape& b = s.o.i.p.base;
-    if (!tpaths || !qpaths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (troot && (!qroot || !fri16::canonical(troot, 8) || !fri16::canonical(qroot, 8))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
-    const size_t per = 8 * (size_t)b.H;
-    for (size_t q = 0; q < b.Q; q++)
-        for (int tree = 0; tree < 2; tree++)
-            if (!fri16::canonical((tree ? qpaths : tpaths) + per * q, per))
-                return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(q) + ", " + (tree ? "quotient" : "trace") + " tree: path words must be canonical");
-    return ZKHIP_OK;
-}
-
-extern "C" {
-
+// ---------------------------------------------------------------- ROWPATHS
 size_t zkhip_fri16_rowpaths_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
                                      size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    fri16::RShape s;
-    if (which < 0 || which >= fri16::N_OT || kind < 0 || kind > 1 || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::rowpaths_machine_of(s);
-    const std::vector<uint32_t>& w = kind == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
+    return fri16::describe(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_rowpaths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
                                   const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::RShape s;
-    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key_host"));
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::N_OT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key_host"));
-    const auto m = fri16::rowpaths_machine_of(s);
-    const uint32_t* h[fri16::N_OT];
-    for (int i = 0; i < fri16::N_OT; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h, m->log_ns, m->pre_widths, fri16::N_OT, prm, vk);
+    return fri16::key_host(s, pre, prm, vk);
 }
 
 int zkhip_fri16_rowpaths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                              const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
                              zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::RShape s;
-    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key"));
     if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key: null argument");
-    std::vector<uint32_t> pre[fri16::N_OT];
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key"));
-    const auto m = fri16::rowpaths_machine_of(s);
-    const int slots[fri16::N_OT] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, -1};      // by table number: the seven tables with preprocessed columns
-    zkhip_chip chips[fri16::N_OT]{};
-    for (int i = 0; i < fri16::N_OT; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
-        void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
-    }
-    return zkhip_machine_setup(ctx, chips, fri16::N_OT, prm, key, vk);
+    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);          // (P24R has no preprocessed columns: its slot is not read)
 }
 
 size_t zkhip_fri16_rowpaths_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
-    fri16::RShape s;
-    if (!prm || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) return 0;
-    const auto m = fri16::rowpaths_machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, prm, fri16::N_PUBLIC_O);
+    return fri16::proof_size(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm);
 }
 
 int zkhip_fri16_rowpaths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
                                    const uint32_t* quotient_rows, const uint32_t* indices, const uint32_t* trace_paths, const uint32_t* quotient_paths, uint32_t* d_trace,
                                    uint32_t* ends) {
     CHECK_CTX(ctx);
-    fri16::RShape s;
-    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    const fri16::Shape& b = s.o.i.p.base;
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
     if (!trace_rows || !quotient_rows || !indices || !d_trace || !ends || (uintptr_t)d_trace % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: null argument, or a trace that is not 16-byte aligned (dense, 552 columns)");
-    if (!fri16::canonical(trace_rows, b.Q * (size_t)s.o.W) || !fri16::canonical(quotient_rows, b.Q * fri16::QROW16))
+    if (!fri16::canonical(trace_rows, s.Q * (size_t)s.W) || !fri16::canonical(quotient_rows, s.Q * fri16::QROW16))
         return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: values must be canonical");
-    for (size_t q = 0; q < b.Q; q++) if (indices[q] >> b.H) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: a query index has more bits than the proof's domain");
+    for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: a query index has more bits than the proof's domain");
     ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, nullptr, nullptr, "fri16_rowpaths_gen_trace"));
     std::vector<uint32_t> e;
     ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, nullptr, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, d_trace, p24chip::WIDTH_R, e));
@@ -2020,100 +1684,51 @@ int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint8_t* proof,
                                size_t cap, size_t* len) {
     CHECK_CTX(ctx);
-    fri16::RShape s;
-    ZK_TRY(fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: null argument");
-    const fri16::OShape& os = s.o;
-    const fri16::IShape& is = os.i;
-    const fri16::PShape& ps = is.p;
-    ZK_TRY(fri16_paths_check_view(ps.base, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_rowpaths"));
-    ZK_TRY(fri16_indices_check_inputs(is, capacity, roots, final_poly, witness, "prove_fri16_rowpaths"));
-    ZK_TRY(fri16_openings_check_rows(os, trace_rows, quotient_rows, constants, indices, "prove_fri16_rowpaths"));
-    ZK_TRY(fri16::check_openings_constants(os, constants, "prove_fri16_rowpaths"));
-    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, "prove_fri16_rowpaths"));
-    const auto m = fri16::rowpaths_machine_of(s);
     using namespace fri16;
-    const size_t ld_fold = s.main_w[T_FOLD16], Q = ps.base.Q;
-    void *t_fold, *t_final, *t_p24, *t_tabs, *t_p2t, *t_smp, *t_rs, *t_q, *t_p24r;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, (ld_fold << s.log_rows[T_FOLD16]) * 4, &t_fold));
-    ZK_TRY(ctx_reserve(ctx, S_REC_B, ((size_t)s.main_w[T_FINAL] << s.log_rows[T_FINAL]) * 4, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[T_P24L]) * 4, &t_p24));
-    ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[T_P2T]) * 4, &t_p2t));
-    ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[T_SAMPLES]) * 4, &t_smp));
-    ZK_TRY(ctx_reserve(ctx, S_REC_F, ((size_t)RS_MAIN16 << s.log_rows[T_ROWSUM16]) * 4, &t_rs));
-    ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
+    const char* who = "prove_fri16_rowpaths";
+    Shape s;
+    ZK_TRY(shape_of(ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: null argument");
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
+    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
+    ZK_TRY(check_openings_constants(s, constants, who));
+    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, who));
+    const size_t Q = s.Q;
+    uint32_t *t_fold, *t_final;
+    void* t_p24r;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
     ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
-    // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; a scratch QUERIES block the transcript kernel fills
-    size_t zoff[N_OT] = {0}, zwords = 0;
-    for (int t : {(int)T_QUERIES, (int)T_COEFFS, (int)T_ROOTS}) { zoff[t] = zwords; zwords += (size_t)(t == T_QUERIES ? TAB_MAIN : s.main_w[t]) << s.log_rows[t]; }
-    ZK_TRY(ctx_reserve(ctx, S_CHIP, zwords * 4, &t_tabs));
-    ZK_TRY(dev_memset(ctx, (uint32_t*)t_tabs + zoff[T_COEFFS], 0, ((size_t)s.main_w[T_COEFFS] << s.log_rows[T_COEFFS]) * 4));
+    Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
+    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
     // refused here, before anything is proven: all zkhip_prove_fri16_openings refuses; then row paths that do not end in their roots
-    Chain c;
-    walk_chain(is, capacity, roots, final_poly, witness, c);
     PathPlan pl;
-    ZK_TRY(plan_paths(ps.base, indices, paths, pl));
-    uint32_t status = 0;
-    ZK_TRY(fri16_transcript_impl(ctx, is, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, (uint32_t*)t_tabs + zoff[T_QUERIES],
-                                 (uint32_t*)t_tabs + zoff[T_ROOTS], &status));
-    if (status & 1u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the challenges are not the ones the transcript draws from these roots and this capacity");
-    if (inner_pow_bits && (c.words[0] & ((1u << inner_pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the witness does not satisfy the proof of work");
-    if (status & 2u) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the query indices are not the ones the transcript draws");
+    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr;
+    ZK_TRY(plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
     {
         const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
-        for (size_t tree = 0; tree < 2; tree++)
-            ZK_TRY(dev_h2d(ctx, (uint32_t*)t_tabs + zoff[T_ROOTS] + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
+        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, z.at(T_ROOTS) + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
     }
-    uint32_t ost[2], *d_open = nullptr;
-    const uint32_t *d_idx = nullptr, *d_rows = nullptr;
-    ZK_TRY(fri16_openings_rows_impl(ctx, os, trace_rows, quotient_rows, constants, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx, &d_rows));
-    if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse("prove_fri16_rowpaths", ost[1]);
-    if (ost[0] != 0xFFFFFFFFu)
-        return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
-    ZK_TRY(fri16_gen_traces_impl(ctx, ps.base, betas, final_poly, indices, values, siblings, (uint32_t*)t_fold, ld_fold, (uint32_t*)t_final, s.main_w[T_FINAL], d_open));
-    {
-        XqColsArgs xa{};
-        xa.indices = d_idx; xa.Q = (uint32_t)Q; xa.R = (uint32_t)R; xa.H = (uint32_t)ps.base.H;
-        xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = (uint32_t*)t_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
-        ZK_LAUNCH(fri16_xq_cols_kernel, fri16_xq_cols_kernel_batch, xq_cols_bargs, dim3((unsigned)((xa.rows + 63) / 64)), dim3(64), 0, ctx->stream, xa);
-        ZK_HIP(hipGetLastError());
-    }
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, ps, paths, (const uint32_t*)t_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
-    for (size_t p = 0; p < pl.n; p++)
-        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
-                                               " does not open: its path does not end in the layer's root");
+    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, constants, t_fold, t_final, &t_rs, &t_q, &d_rows, who));
+    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
     // P24R from the raw rows the openings launch left on the device (the staging block of S_REC_J is not reserved again before this)
+    std::vector<uint32_t> ends;
     ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
     for (size_t p = 0; p < 2 * Q; p++)
         if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
             return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") +
                                                " tree: the opened row's path does not end in the root");
-    zkhip_chip chips[N_OT]{};
-    for (int i = 0; i < N_OT; i++) {
-        const int t = s.order[i];
-        chips[i].d_trace = t == T_FOLD16 ? (const uint32_t*)t_fold : t == T_FINAL ? (const uint32_t*)t_final : t == T_P24L ? (const uint32_t*)t_p24
-                         : t == T_P2T ? (const uint32_t*)t_p2t : t == T_SAMPLES ? (const uint32_t*)t_smp : t == T_ROWSUM16 ? (const uint32_t*)t_rs
-                         : t == T_QUERY16 ? (const uint32_t*)t_q : t == T_P24R ? (const uint32_t*)t_p24r : (const uint32_t*)t_tabs + zoff[t];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r};
     uint32_t pub[N_PUBLIC_O];
-    std::memcpy(pub, capacity, 32);
-    std::memcpy(pub + 8, constants, 128);
-    return zkhip_prove_machine_keyed(ctx, key, chips, m->progs, m->prog_words, m->tabs, m->tab_words, N_OT, pub, N_PUBLIC_O, prm, proof, cap, len);
+    fri16_openings_public(capacity, constants, pub);
+    return prove(ctx, key, s, traces, pub, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    fri16::RShape s;
-    if (!proof || !public_values || !vk || !prm || fri16::rowpaths_shape_of(R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s) != ZKHIP_OK) {
-        if (reason) *reason = 1;
-        return fail(ZKHIP_ERR_VERIFY, "verify_fri16_rowpaths: bad arguments");
-    }
-    const auto m = fri16::rowpaths_machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, fri16::N_OT, public_values,
-                                      fri16::N_PUBLIC_O, prm, reason);
+    return fri16::verify(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, public_values, vk, prm, reason, "verify_fri16_rowpaths");
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "air.h"
+#include "air_builder.h"
 #include "context.h"
 #include "batch.h"
 #include "p2chip.h"
@@ -67,29 +68,7 @@ inline uint32_t n_public_of(int layers, bool transcript = false) { return transc
 
 namespace {
 inline Ext ext_from_canon(const uint32_t* p);
-struct Term { uint32_t coeff; std::vector<uint32_t> vars; };
-typedef std::vector<Term> Terms;
-inline uint32_t var(uint32_t col, bool next = false) { return next ? ((1u << 30) | col) : col; }
-inline uint32_t pub(uint32_t idx) { return (2u << 30) | idx; }
-inline uint32_t neg(uint64_t c) { c %= P; return c ? (uint32_t)(P - c) : 0u; }
-inline uint32_t mulm(uint64_t a, uint64_t b) { return (uint32_t)((a % P) * (b % P) % P); }
-enum : uint32_t { ALL = 0, FIRST = 1, LAST = 2, TRANSITION = 3 };
-struct Builder {
-    std::vector<uint32_t> body;
-    uint32_t count = 0;
-    void add(uint32_t selector, const Terms& terms) {
-        Terms kept;
-        for (const Term& t : terms) if (t.coeff % P) kept.push_back(t);
-        body.push_back(selector);
-        body.push_back((uint32_t)kept.size());
-        for (const Term& t : kept) {
-            body.push_back(t.coeff % P);
-            body.push_back((uint32_t)t.vars.size());
-            for (uint32_t v : t.vars) body.push_back(v);
-        }
-        count++;
-    }
-};
+using namespace airb;
 // c_l = w_{2^(l+1)} canonical: the factor bit l of a query index contributes to its evaluation point
 inline uint32_t root_const(int l) { return from_monty(two_adic_generator(l + 1)); }
 
@@ -182,9 +161,7 @@ std::vector<uint32_t> build_program(int RL, bool wired, bool transcript = false,
         b.add(ALL, Terms{{1u, {var(LNX)}}, {P - 1, {var(PT)}}, {P - 1, {var(LN)}}});
         b.add(TRANSITION, gated(Terms{{1u, {var(PT)}}, {P - 1, {var(PT, true)}}}));
     }
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, W, b.count, NP, (uint32_t)(6 + b.body.size())};
-    p.insert(p.end(), b.body.begin(), b.body.end());
-    return p;
+    return b.finish(W, NP);
 }
 std::shared_ptr<const std::vector<uint32_t>> program(int RL, bool wired = false, bool transcript = false, int rec_public = -1) {
     static std::mutex mu;
@@ -346,9 +323,7 @@ std::shared_ptr<const std::vector<uint32_t>> samples_program(int RL, int pow_bit
         for (uint32_t i = 0; i < (uint32_t)pow_bits; i++) c.push_back(Term{1u, {var(S_POW), var(M0 + S_BITS + i)}});
         b.add(ALL, c);
     }
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, S_PRE + S_MAIN, b.count, n_public, (uint32_t)(6 + b.body.size())};
-    p.insert(p.end(), b.body.begin(), b.body.end());
-    return cache.emplace(key, std::make_shared<const std::vector<uint32_t>>(std::move(p))).first->second;
+    return cache.emplace(key, std::make_shared<const std::vector<uint32_t>>(b.finish(S_PRE + S_MAIN, n_public))).first->second;
 }
 // the chip's preprocessed rows (Montgomery): fixed by the shape alone
 void samples_pre(int RL, size_t nq, int log_rows, std::vector<uint32_t>& t, int base = -1) {      // base: the number of the first query-phase sponge row (default: RL)

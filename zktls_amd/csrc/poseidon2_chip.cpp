@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "air.h"
+#include "air_builder.h"
 #include "context.h"
 #include "p24chip.h"
 #include "p2chip.h"
@@ -35,30 +36,7 @@ extern std::atomic<uint64_t> g_p2_generation;      // params.cpp
 namespace p2chip {
 namespace {
 
-struct Term { uint32_t coeff; std::vector<uint32_t> vars; };
-typedef std::vector<Term> Terms;
-inline uint32_t var(uint32_t col, bool next = false) { return next ? ((1u << 30) | col) : col; }
-inline uint32_t pub(uint32_t idx) { return (2u << 30) | idx; }
-inline uint32_t neg(uint64_t c) { c %= P; return c ? (uint32_t)(P - c) : 0u; }
-inline uint32_t mulm(uint64_t a, uint64_t b) { return (uint32_t)((a % P) * (b % P) % P); }
-enum : uint32_t { ALL = 0, FIRST = 1, LAST = 2, TRANSITION = 3 };
-
-struct Builder {
-    std::vector<uint32_t> body;
-    uint32_t count = 0;
-    void add(uint32_t selector, const Terms& terms) {          // terms with coefficient 0 are omitted
-        Terms kept;
-        for (const Term& t : terms) if (t.coeff % P) kept.push_back(t);
-        body.push_back(selector);
-        body.push_back((uint32_t)kept.size());
-        for (const Term& t : kept) {
-            body.push_back(t.coeff % P);
-            body.push_back((uint32_t)t.vars.size());
-            for (uint32_t v : t.vars) body.push_back(v);
-        }
-        count++;
-    }
-};
+using namespace airb;
 // x3 - (c + k)^3
 Terms cube_def(uint32_t x3, uint32_t c, uint32_t k) {
     return Terms{{1u, {var(x3)}}, {P - 1, {var(c), var(c), var(c)}}, {neg(3ull * k), {var(c), var(c)}}, {neg(3ull * mulm(k, k)), {var(c)}}, {neg(mulm(mulm(k, k), k)), {}}};
@@ -202,9 +180,7 @@ std::vector<uint32_t> build_program(bool fri_layers = false, uint32_t n_public =
             b.add(ALL, Terms{{1u, {var(QF), var(IN + j)}}, {P - 1, {var(QF), pub((uint32_t)queries + j)}}});
         for (uint32_t f : {CH, END, SS, BIT, M}) b.add(ALL, Terms{{1u, {var(QP), var(f)}}});
     }
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, transcript >= 0 ? WIDTH_T : WIDTH, b.count, n_public, (uint32_t)(6 + b.body.size())};
-    p.insert(p.end(), b.body.begin(), b.body.end());
-    return p;
+    return b.finish(transcript >= 0 ? WIDTH_T : WIDTH, n_public);
 }
 
 // the program of the Poseidon2 tables in effect (rebuilt when zkhip_load_poseidon2_params / _reset_ changes them)
@@ -512,9 +488,7 @@ std::vector<uint32_t> build_program(bool layers = false, uint32_t n_public = N_P
             b.add(ALL, t);
         }
     }
-    std::vector<uint32_t> p{AIR_MAGIC, 1u, layers ? WIDTH_L : rows ? WIDTH_R : WIDTH, b.count, n_public, (uint32_t)(6 + b.body.size())};
-    p.insert(p.end(), b.body.begin(), b.body.end());
-    return p;
+    return b.finish(layers ? WIDTH_L : rows ? WIDTH_R : WIDTH, n_public);
 }
 
 // the program of the width-24 tables in effect (rebuilt when zkhip_load_poseidon2_params / _reset_ changes them)

@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "air.h"
+#include "air_builder.h"
 #include "context.h"
 #include "batch.h"
 namespace zk { int lockstep_selftest_observe(int members); }      // prover.cpp: the members' transcripts absorbing side by side (LaunchBatcher::host_merge) against one after the other
@@ -121,11 +122,7 @@ inline PadPlace padding_publics(uint64_t L, uint64_t first, uint64_t n_active, u
 }
 
 // ---- the constraint program ------------------------------------------------------------------------------------------
-struct Term { uint32_t coeff; std::vector<uint32_t> vars; };
-typedef std::vector<Term> Terms;
-inline uint32_t var(uint32_t col, bool next = false) { return next ? ((1u << 30) | col) : col; }
-inline uint32_t pub(uint32_t idx) { return (2u << 30) | idx; }
-inline uint32_t neg(uint32_t c) { return c ? P - c : 0u; }
+using namespace airb;
 __host__ __device__ inline uint32_t xl(int j) { return XL + 2 * (j >= 14 ? j - 2 : j - 1); }          // limb pair of W_{t+j}, j in 1..12, 14, 15
 
 struct Word { bool bits; uint32_t base; };
@@ -146,22 +143,6 @@ inline Terms xor3(uint32_t x, uint32_t y, uint32_t z) {
     return Terms{{1, {x}}, {1, {y}}, {1, {z}}, {P - 2, {x, y}}, {P - 2, {y, z}}, {P - 2, {x, z}}, {4, {x, y, z}}};
 }
 inline Terms xor2(uint32_t x, uint32_t y) { return Terms{{1, {x}}, {1, {y}}, {P - 2, {x, y}}}; }
-
-struct Builder {
-    std::vector<uint32_t> body;
-    uint32_t count = 0;
-    void add(uint32_t selector, const Terms& terms) {
-        body.push_back(selector);
-        body.push_back((uint32_t)terms.size());
-        for (const Term& t : terms) {
-            body.push_back(t.coeff % P);
-            body.push_back((uint32_t)t.vars.size());
-            for (uint32_t v : t.vars) body.push_back(v);
-        }
-        count++;
-    }
-};
-enum : uint32_t { ALL = 0, FIRST = 1, LAST = 2, TRANSITION = 3 };
 
 // chained = false: the chaining value of the first row is the standard IV (16 public values: the final chaining value's limbs);
 // chained = true: it is PUBLIC too (32 public values: final limbs, then initial limbs) -- a shard of a longer message
@@ -331,9 +312,7 @@ static std::vector<uint32_t> build_program(bool chained) {
                     b.add(ALL, t);
                 }
         }
-        std::vector<uint32_t> p{AIR_MAGIC, 1u, WIDTH, b.count, chained ? N_PUBLIC_CHAINED : N_PUBLIC, (uint32_t)(6 + b.body.size())};
-        p.insert(p.end(), b.body.begin(), b.body.end());
-        return p;
+        return b.finish(WIDTH, chained ? N_PUBLIC_CHAINED : N_PUBLIC);
     }
 }
 static const std::vector<uint32_t>& program() { static const std::vector<uint32_t> prog = build_program(false); return prog; }

@@ -79,9 +79,7 @@ struct Cons {
     }
     void ext(uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) add(sel, e[i]); }
     std::vector<uint32_t> program(uint32_t width, uint32_t n_public) const {
-        std::vector<uint32_t> p{AIR_MAGIC, 1u, width, b.count, n_public, (uint32_t)(6 + b.body.size())};
-        p.insert(p.end(), b.body.begin(), b.body.end());
-        return p;
+        return b.finish(width, n_public);
     }
 };
 inline uint32_t rup4(uint32_t n) { return (n + 3u) & ~3u; }
@@ -242,13 +240,7 @@ std::vector<uint32_t> p2r_program(const Shape& sh) {
     return c.program(P2_PRE + P2_MAIN, sh.npub_total());
 }
 // interaction tables: {sign, multiplicity column, bus, n, columns...}
-struct Tab {
-    std::vector<uint32_t> w{LOOKUP_MAGIC, 0u, 0u};
-    void add(uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {
-        w.push_back(sign); w.push_back(mult); w.push_back(bus); w.push_back((uint32_t)cols.size());
-        for (uint32_t c : cols) w.push_back(c);
-        w[1]++; w[2] = (uint32_t)w.size();
-    }
+struct Tab : airb::Interactions {
     void add8(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a, uint32_t b) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3, b, b + 1, b + 2, b + 3}); }
     void add4(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3}); }
     void add5(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t key, uint32_t a) { add(sign, mult, bus, {key, a, a + 1, a + 2, a + 3}); }

@@ -1599,17 +1599,37 @@ def fri16_view_shard(proof, log_n, width, public_values=(), params=None):
             "paths": [[paths[q * pw + offs[l]:q * pw + offs[l + 1]].tolist() for l in range(R)] for q in range(Q)]}
 
 
+def _describe(entry_name, *shape_args, which, kind):
+    """zkhip_<entry_name> of a fold-16 machine: the words of the program (kind 0) or interaction table (kind 1) at machine position `which`
+    -> (words, log rows, main width, preprocessed width, table number); raises with the library's message for a shape or position it refuses"""
+    entry = getattr(_lib.load(), "zkhip_" + entry_name)
+    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    refs = (C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
+    n = entry(*shape_args, which, kind, None, 0, *refs)
+    if n == 0:
+        raise _lib.ZkHipError(-1, entry_name + ": " + _lib.load().zkhip_last_error().decode())
+    out = np.zeros(n, dtype=np.uint32)
+    assert entry(*shape_args, which, kind, out.ctypes.data_as(u32p), n, *refs) == n
+    return out, ln.value, mw.value, pw.value, tb.value
+
+
+def _verify(entry_name, proof, public_values, *shape_args, vk, params, n_public=None):
+    """zkhip_<entry_name> of a fold-16 machine: the proof, the shape, the public values, the key -> (rc, reason).  Host only."""
+    params = params or Params(1, 100, 16)
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32).reshape(-1))
+    assert n_public is None or pv.size == n_public
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = getattr(_lib.load(), "zkhip_" + entry_name)(pr.ctypes.data_as(u8p), pr.size, *shape_args, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params),
+                                                     C.byref(reason))
+    return rc, reason.value
+
+
 def fri16_describe(R, F, log_blowup, n_queries, which, kind):
     """zkhip_fri16_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` of the fold-16 FRI machine
     -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16, 1 FINAL, 2 LAYERS, 3 QUERIES, 4 COEFFS)"""
-    lib = _lib.load()
-    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
-    n = lib.zkhip_fri16_describe(R, F, log_blowup, n_queries, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
-    if n == 0:
-        raise _lib.ZkHipError(-1, "fri16_describe: " + lib.zkhip_last_error().decode())
-    out = np.zeros(n, dtype=np.uint32)
-    assert lib.zkhip_fri16_describe(R, F, log_blowup, n_queries, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb)) == n
-    return out, ln.value, mw.value, pw.value, tb.value
+    return _describe("fri16_describe", R, F, log_blowup, n_queries, which=which, kind=kind)
 
 
 def fri16_key_host(view, params=None):
@@ -1623,14 +1643,7 @@ def fri16_key_host(view, params=None):
 
 def verify_fri16(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
     """zkhip_verify_fri16: the challenges, the key, the shape -> (rc, reason).  Host only."""
-    params = params or Params(1, 100, 16)
-    lib = _lib.load()
-    pr = np.ascontiguousarray(proof, dtype=np.uint8)
-    bt = np.ascontiguousarray(np.array(betas, dtype=np.uint32).reshape(-1))
-    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
-    reason = C.c_int(0)
-    rc = lib.zkhip_verify_fri16(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params), C.byref(reason))
-    return rc, reason.value
+    return _verify("verify_fri16", proof, betas, R, F, log_blowup, n_queries, vk=vk, params=params)
 
 
 def _fri16_paths_arrays(view):
@@ -1647,14 +1660,7 @@ def _fri16_paths_arrays(view):
 def fri16_paths_describe(R, F, log_blowup, n_queries, which, kind):
     """zkhip_fri16_paths_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..5) of the fold-16 paths
     machine -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS)"""
-    lib = _lib.load()
-    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
-    n = lib.zkhip_fri16_paths_describe(R, F, log_blowup, n_queries, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
-    if n == 0:
-        raise _lib.ZkHipError(-1, "fri16_paths_describe: " + lib.zkhip_last_error().decode())
-    out = np.zeros(n, dtype=np.uint32)
-    assert lib.zkhip_fri16_paths_describe(R, F, log_blowup, n_queries, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb)) == n
-    return out, ln.value, mw.value, pw.value, tb.value
+    return _describe("fri16_paths_describe", R, F, log_blowup, n_queries, which=which, kind=kind)
 
 
 def fri16_paths_key_host(view, params=None):
@@ -1668,15 +1674,7 @@ def fri16_paths_key_host(view, params=None):
 
 def verify_fri16_paths(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
     """zkhip_verify_fri16_paths: the challenges, the key, the shape -> (rc, reason).  Host only."""
-    params = params or Params(1, 100, 16)
-    lib = _lib.load()
-    pr = np.ascontiguousarray(proof, dtype=np.uint8)
-    bt = np.ascontiguousarray(np.array(betas, dtype=np.uint32).reshape(-1))
-    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
-    reason = C.c_int(0)
-    rc = lib.zkhip_verify_fri16_paths(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, bt.ctypes.data_as(u32p), k.ctypes.data_as(u32p), C.byref(params),
-                                      C.byref(reason))
-    return rc, reason.value
+    return _verify("verify_fri16_paths", proof, betas, R, F, log_blowup, n_queries, vk=vk, params=params)
 
 
 def fri16_view_transcript(proof, log_n, width, public_values=(), params=None):
@@ -1697,15 +1695,7 @@ def fri16_view_transcript(proof, log_n, width, public_values=(), params=None):
 def fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind):
     """zkhip_fri16_indices_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..7) of the fold-16 indices
     machine -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16B, 1 FINAL, 2 P24L, 3 QUERIES, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES)"""
-    lib = _lib.load()
-    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
-    n = lib.zkhip_fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
-    if n == 0:
-        raise _lib.ZkHipError(-1, "fri16_indices_describe: " + lib.zkhip_last_error().decode())
-    out = np.zeros(n, dtype=np.uint32)
-    assert lib.zkhip_fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
-                                            C.byref(tb)) == n
-    return out, ln.value, mw.value, pw.value, tb.value
+    return _describe("fri16_indices_describe", R, F, log_blowup, n_queries, pow_bits, which=which, kind=kind)
 
 
 def fri16_indices_key_host(view, params=None):
@@ -1720,16 +1710,7 @@ def fri16_indices_key_host(view, params=None):
 
 def verify_fri16_indices(proof, capacity, R, F, log_blowup, n_queries, pow_bits, vk, params=None):
     """zkhip_verify_fri16_indices: the shape, the inner proof's grinding bits, the capacity, the key -> (rc, reason).  Host only."""
-    params = params or Params(1, 100, 16)
-    lib = _lib.load()
-    pr = np.ascontiguousarray(proof, dtype=np.uint8)
-    cp = np.ascontiguousarray(np.array(capacity, dtype=np.uint32).reshape(-1))
-    assert cp.size == 8
-    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
-    reason = C.c_int(0)
-    rc = lib.zkhip_verify_fri16_indices(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, cp.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
-                                        C.byref(params), C.byref(reason))
-    return rc, reason.value
+    return _verify("verify_fri16_indices", proof, capacity, R, F, log_blowup, n_queries, pow_bits, vk=vk, params=params, n_public=8)
 
 
 FRI16_OPENING_CONSTANTS = ("FA", "ZETA", "ZNX", "YL", "YN", "YQ", "OFFN", "OFFQ")          # the order of the openings machine's public values behind the capacity
@@ -1761,15 +1742,7 @@ def fri16_view_openings(proof, log_n, width, public_values=(), params=None):
 def fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind):
     """zkhip_fri16_openings_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..9) of the fold-16 openings machine
     -> (words, log rows, main width, preprocessed width, table number: 0 FOLD16C, 1 FINAL, 2 P24L, 3 QUERY16, 4 COEFFS, 5 ROOTS, 6 P2T, 7 SAMPLES, 8 ROWSUM16, 9 ROWS)"""
-    lib = _lib.load()
-    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
-    n = lib.zkhip_fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
-    if n == 0:
-        raise _lib.ZkHipError(-1, "fri16_openings_describe: " + lib.zkhip_last_error().decode())
-    out = np.zeros(n, dtype=np.uint32)
-    assert lib.zkhip_fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
-                                             C.byref(tb)) == n
-    return out, ln.value, mw.value, pw.value, tb.value
+    return _describe("fri16_openings_describe", R, F, log_blowup, n_queries, pow_bits, W, which=which, kind=kind)
 
 
 def fri16_openings_key_host(view, params=None):
@@ -1786,16 +1759,7 @@ def fri16_openings_key_host(view, params=None):
 def verify_fri16_openings(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
     """zkhip_verify_fri16_openings: the shape, the inner proof's grinding bits and trace width, the 40 public values (capacity, then the eight constants), the key
     -> (rc, reason).  Host only."""
-    params = params or Params(1, 100, 16)
-    lib = _lib.load()
-    pr = np.ascontiguousarray(proof, dtype=np.uint8)
-    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32).reshape(-1))
-    assert pv.size == 40
-    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
-    reason = C.c_int(0)
-    rc = lib.zkhip_verify_fri16_openings(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, W, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
-                                         C.byref(params), C.byref(reason))
-    return rc, reason.value
+    return _verify("verify_fri16_openings", proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk=vk, params=params, n_public=40)
 
 
 def _fri16_rowpaths_arrays(view):
@@ -1824,15 +1788,7 @@ def fri16_view_row_paths(proof, log_n, width, public_values=(), params=None):
 def fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind):
     """zkhip_fri16_rowpaths_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..9) of the fold-16 row-paths machine
     -> (words, log rows, main width, preprocessed width, table number: the openings machine's with 9 P24R); raises with the library's message for a shape it refuses"""
-    lib = _lib.load()
-    ln, mw, pw, tb = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
-    n = lib.zkhip_fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, None, 0, C.byref(ln), C.byref(mw), C.byref(pw), C.byref(tb))
-    if n == 0:
-        raise _lib.ZkHipError(-1, "fri16_rowpaths_describe: " + lib.zkhip_last_error().decode())
-    out = np.zeros(n, dtype=np.uint32)
-    assert lib.zkhip_fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kind, out.ctypes.data_as(u32p), n, C.byref(ln), C.byref(mw), C.byref(pw),
-                                             C.byref(tb)) == n
-    return out, ln.value, mw.value, pw.value, tb.value
+    return _describe("fri16_rowpaths_describe", R, F, log_blowup, n_queries, pow_bits, W, which=which, kind=kind)
 
 
 def fri16_rowpaths_key_host(view, params=None):
@@ -1849,16 +1805,7 @@ def fri16_rowpaths_key_host(view, params=None):
 def verify_fri16_rowpaths(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
     """zkhip_verify_fri16_rowpaths: the shape, the inner proof's grinding bits and trace width, the 40 public values (capacity, then the eight constants), the key
     -> (rc, reason).  Host only."""
-    params = params or Params(1, 100, 16)
-    lib = _lib.load()
-    pr = np.ascontiguousarray(proof, dtype=np.uint8)
-    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32).reshape(-1))
-    assert pv.size == 40
-    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
-    reason = C.c_int(0)
-    rc = lib.zkhip_verify_fri16_rowpaths(pr.ctypes.data_as(u8p), pr.size, R, F, log_blowup, n_queries, pow_bits, W, pv.ctypes.data_as(u32p), k.ctypes.data_as(u32p),
-                                         C.byref(params), C.byref(reason))
-    return rc, reason.value
+    return _verify("verify_fri16_rowpaths", proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk=vk, params=params, n_public=40)
 
 
 def fri_view_transcript(proof, log_n, width, public_values=(), params=None):
