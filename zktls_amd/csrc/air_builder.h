@@ -1,9 +1,10 @@
 // air_builder.h -- how every chip of this library writes its constraint program and its interaction table: ONE definition of the term list, the variable words,
-// the selectors and the two builders.  A chip file includes this and says `using namespace airb;` where its builders live.
+// the selectors, the two builders and the expression algebra over term lists.  A chip file includes this and says `using namespace airb;` where its builders live.
 //   program (air.h):            {AIR_MAGIC, 1, width, constraints, public values, words} then per constraint {selector, terms, per term {coefficient, degree, variables...}}
 //   interaction table (air.h):  {LOOKUP_MAGIC, entries, words} then per entry {sign (0 send, 1 receive), multiplicity column, bus, n, columns...}
 // The ORDER in which terms and entries are added is the program: the Python restatements under tests/ add them in the same order, and the words must be equal.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <initializer_list>
 #include <vector>
@@ -46,6 +47,44 @@ struct Builder {
         return p;
     }
 };
+
+// ---- polynomials over columns: a list of (coefficient, variables); an extension expression = four of them (x^4 = 11).  No merging of
+// like terms: the order in which terms are produced IS the program (tests/recursion_air.py's helpers produce them in the same order).
+typedef std::array<Terms, 4> EE;
+inline Terms pc(uint64_t c) { c %= P; return c ? Terms{Term{(uint32_t)c, {}}} : Terms{}; }
+inline Terms pv(uint32_t col, bool nxt = false) { return Terms{Term{1u, {var(col, nxt)}}}; }
+inline Terms ppub(uint32_t i) { return Terms{Term{1u, {pub(i)}}}; }
+inline Terms padd(const Terms& a, const Terms& b) { Terms o = a; o.insert(o.end(), b.begin(), b.end()); return o; }
+inline Terms pscale(const Terms& a, uint64_t k) { Terms o; for (const Term& t : a) { const uint32_t c = mulm(t.coeff, k); if (c) o.push_back(Term{c, t.vars}); } return o; }
+inline Terms pneg(const Terms& a) { return pscale(a, P - 1); }
+inline Terms pmul(const Terms& a, const Terms& b) {
+    Terms o;
+    for (const Term& x : a) for (const Term& y : b) { const uint32_t c = mulm(x.coeff, y.coeff); if (!c) continue; Term t{c, x.vars}; t.vars.insert(t.vars.end(), y.vars.begin(), y.vars.end()); o.push_back(t); }
+    return o;
+}
+inline EE ev(uint32_t col, bool nxt = false) { return EE{pv(col, nxt), pv(col + 1, nxt), pv(col + 2, nxt), pv(col + 3, nxt)}; }
+inline EE ec(uint64_t c0, uint64_t c1 = 0, uint64_t c2 = 0, uint64_t c3 = 0) { return EE{pc(c0), pc(c1), pc(c2), pc(c3)}; }
+inline EE eb(const Terms& p) { return EE{p, Terms{}, Terms{}, Terms{}}; }
+inline EE epub(uint32_t idx) { return EE{ppub(idx), ppub(idx + 1), ppub(idx + 2), ppub(idx + 3)}; }
+inline EE eone() { return ec(1); }
+inline EE eadd(const EE& a, const EE& b) { return EE{padd(a[0], b[0]), padd(a[1], b[1]), padd(a[2], b[2]), padd(a[3], b[3])}; }
+inline EE eadd(const EE& a, const EE& b, const EE& c) { return eadd(eadd(a, b), c); }
+inline EE esub(const EE& a, const EE& b) { return EE{padd(a[0], pneg(b[0])), padd(a[1], pneg(b[1])), padd(a[2], pneg(b[2])), padd(a[3], pneg(b[3]))}; }
+inline EE escale(const EE& a, uint64_t k) { return EE{pscale(a[0], k), pscale(a[1], k), pscale(a[2], k), pscale(a[3], k)}; }
+inline EE emul(const EE& a, const EE& b) {
+    EE o;
+    for (int j = 0; j < 4; j++)
+        for (int i = 0; i < 4; i++)
+            for (int k = 0; k < 4; k++) {
+                if ((i + k) % 4 != j) continue;
+                Terms t = pmul(a[i], b[k]);
+                if (i + k >= 4) t = pscale(t, EXT_W);
+                o[j].insert(o[j].end(), t.begin(), t.end());
+            }
+    return o;
+}
+inline EE egate(const Terms& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
+inline void add_ext(Builder& b, uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) b.add(sel, e[i]); }
 
 struct Interactions {
     std::vector<uint32_t> w{LOOKUP_MAGIC, 0u, 0u};

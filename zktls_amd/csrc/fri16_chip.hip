@@ -38,10 +38,10 @@
 //                                          stands where the preprocessed ROWS table stood; the key holds roots and final coefficients only, no opened word
 //                                          (tests/fri16_rowpaths_air.py)
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
-// table number the height and widths, the machine order), shape_of (every kind's validity checks, one sort), program_of and interactions_of (per TABLE, what each kind adds
-// to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape) -- and what every entry does with it (describe, key_host, key_upload,
-// proof_size, prove, verify); then the kernels' launchers, the provers' stages (transcript, openings, layer paths) and the extern "C" entries, which are a shape call,
-// their own argument checks and those helpers.  The builders of constraint programs and interaction tables are air_builder.h's, shared with the other chips.
+// table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
+// to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
+// and what every entry does with it (describe, key_upload, proof_size, verify, and keyed_machine.h's key_host and prove directly); then the kernels' launchers, the provers' stages (transcript, openings, layer paths) and the extern "C" entries, which are a shape call,
+// their own argument checks and those helpers.  The builders of constraint programs and interaction tables and the expression algebra are air_builder.h's, shared with the other chips.
 // ADDING A KIND: a value of Kind and its table count in N_TABLES; its new or replaced tables in shape_of (with its checks), program_of and interactions_of -- one `if` on
 // the kind in the case of every table it touches; its public values in n_public_of; a builder of its key tables beside the others; a stage for what its prover launches;
 // its entries.  Machine, machine_of and the helpers take no new case.
@@ -60,6 +60,7 @@
 #include "context.h"
 #include "batch.h"
 #include "fri16_rows.cuh"
+#include "keyed_machine.h"
 #include "kernels.h"
 #include "p24chip.h"
 #include "p2chip.h"
@@ -97,7 +98,6 @@ struct Shape {
     size_t Q = 0, C = 0, S = 0, NT = 0;      // C, S, NT: coefficient rows, rows that hand words out, rows of the transcript's chain
     uint32_t W = 0;                          // the inner proof's trace width
     int log_rows[MAX_TABLES];                // by table number
-    int order[MAX_TABLES];                   // machine position -> table number
     uint32_t main_w[MAX_TABLES], pre_w[MAX_TABLES];
 };
 inline int lg(size_t n) { int l = 5; while (((size_t)1 << l) < n) l++; return l; }
@@ -524,39 +524,6 @@ void walk_chain(const Shape& s, const uint32_t* capacity, const uint32_t* roots,
 constexpr uint32_t BUS_ROW16 = 81, BUS_AT16 = 82, BUS_AQ16 = 83, N_PUBLIC_O = 40, Q16_PRE = 8, QP_QN = 0, QP_ACT = 1, RS16_PRE = 8, ROWS_PRE16 = 8, QROW16 = 8;
 constexpr uint32_t RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST0 = 3, RP_LAST1 = 4, RP_QN = 5, RP_K0 = 6, RP_K1 = 7;
 constexpr uint32_t PUB_FA = 8, PUB_ZETA = 12;       // public values: FA, then ZETA ZNX YL YN YQ OFFN OFFQ in QUERY16's column order
-// polynomials over columns, as in shard_verifier.inl: a list of (coefficient, variables), an extension expression = four of them; the order in which terms are
-// produced IS the program (tests/recursion_air.py's helpers produce them in the same order)
-typedef std::array<Terms, 4> EE;
-inline Terms pv(uint32_t col, bool nxt = false) { return Terms{Term{1u, {var(col, nxt)}}}; }
-inline Terms pc(uint64_t c) { c %= P; return c ? Terms{Term{(uint32_t)c, {}}} : Terms{}; }
-inline Terms padd(const Terms& a, const Terms& b) { Terms o = a; o.insert(o.end(), b.begin(), b.end()); return o; }
-inline Terms pscale(const Terms& a, uint64_t k) { Terms o; for (const Term& t : a) { const uint32_t c = mulm(t.coeff, k); if (c) o.push_back(Term{c, t.vars}); } return o; }
-inline Terms pneg(const Terms& a) { return pscale(a, P - 1); }
-inline Terms pmul(const Terms& a, const Terms& b) {
-    Terms o;
-    for (const Term& x : a) for (const Term& y : b) { const uint32_t c = mulm(x.coeff, y.coeff); if (!c) continue; Term t{c, x.vars}; t.vars.insert(t.vars.end(), y.vars.begin(), y.vars.end()); o.push_back(t); }
-    return o;
-}
-inline EE ev(uint32_t col, bool nxt = false) { return EE{pv(col, nxt), pv(col + 1, nxt), pv(col + 2, nxt), pv(col + 3, nxt)}; }
-inline EE epub(uint32_t idx) { return EE{Terms{Term{1u, {pub(idx)}}}, Terms{Term{1u, {pub(idx + 1)}}}, Terms{Term{1u, {pub(idx + 2)}}}, Terms{Term{1u, {pub(idx + 3)}}}}; }
-inline EE eone() { return EE{pc(1), Terms{}, Terms{}, Terms{}}; }
-inline EE eb(const Terms& p) { return EE{p, Terms{}, Terms{}, Terms{}}; }
-inline EE eadd(const EE& a, const EE& b) { return EE{padd(a[0], b[0]), padd(a[1], b[1]), padd(a[2], b[2]), padd(a[3], b[3])}; }
-inline EE esub(const EE& a, const EE& b) { return EE{padd(a[0], pneg(b[0])), padd(a[1], pneg(b[1])), padd(a[2], pneg(b[2])), padd(a[3], pneg(b[3]))}; }
-inline EE emul(const EE& a, const EE& b) {
-    EE o;
-    for (int j = 0; j < 4; j++)
-        for (int i = 0; i < 4; i++)
-            for (int k = 0; k < 4; k++) {
-                if ((i + k) % 4 != j) continue;
-                Terms t = pmul(a[i], b[k]);
-                if (i + k >= 4) t = pscale(t, EXT_W);
-                o[j].insert(o[j].end(), t.begin(), t.end());
-            }
-    return o;
-}
-inline EE egate(const Terms& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
-inline void add_ext(Builder& b, uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) b.add(sel, e[i]); }
 
 std::vector<uint32_t> build_fold16c_program(int R, int lf) {
     const std::vector<uint32_t> p = build_fold16_program(R, lf, true, N_PUBLIC_O);
@@ -729,8 +696,6 @@ int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W,
     table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, RS16_PRE);
     if (kind == OPENINGS) table(T_ROWS, std::max(6, lg(Q * (size_t)(W + QROW16) / 4)), TAB_MAIN, ROWS_PRE16);
     else table(T_P24R, std::max(6, lg(Q * row_paths)), p24chip::WIDTH_R, 0u);
-    for (int t = 0; t < s.n_tables; t++) s.order[t] = t;
-    std::stable_sort(s.order, s.order + s.n_tables, [&](int x, int y) { return s.log_rows[x] > s.log_rows[y]; });
     for (int t = 0; kind == ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
         if (std::count(s.log_rows, s.log_rows + s.n_tables, s.log_rows[t]) > MAX_SAME_HEIGHT)
             return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
@@ -846,15 +811,8 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
     return v.finish();
 }
 
-// programs and interaction tables of a shape in MACHINE order (tallest table first), with the arrays the keyed-machine entries take
-struct Machine {
-    Shape s;
-    std::vector<std::vector<uint32_t>> prog, tab;
-    std::vector<int32_t> log_ns;
-    std::vector<uint32_t> widths, pre_widths;
-    std::vector<const uint32_t*> progs, tabs;
-    std::vector<size_t> prog_words, tab_words;
-};
+// a shape and its keyed machine (keyed_machine.h: programs and interaction tables in MACHINE order, tallest table first)
+struct Machine { Shape s; keyed::KeyedMachine km; };
 // (P24L's, P24R's and P2T's programs follow the Poseidon2 tables in effect: the cache is dropped when they change)
 std::shared_ptr<const Machine> machine_of(const Shape& s) {
     static std::mutex mu;
@@ -868,14 +826,7 @@ std::shared_ptr<const Machine> machine_of(const Shape& s) {
     if (it != cache.end()) return it->second;
     auto m = std::make_shared<Machine>();
     m->s = s;
-    for (int i = 0; i < s.n_tables; i++) {
-        const int t = s.order[i];
-        m->prog.push_back(program_of(s, t)); m->tab.push_back(interactions_of(s, t));
-        m->log_ns.push_back(s.log_rows[t]); m->widths.push_back(s.main_w[t]); m->pre_widths.push_back(s.pre_w[t]);
-    }
-    for (int i = 0; i < s.n_tables; i++) {
-        m->progs.push_back(m->prog[i].data()); m->prog_words.push_back(m->prog[i].size()); m->tabs.push_back(m->tab[i].data()); m->tab_words.push_back(m->tab[i].size());
-    }
+    keyed::build(m->km, s.n_tables, s.log_rows, s.main_w, s.pre_w, [&](int t, std::vector<uint32_t>& prog, std::vector<uint32_t>& tab) { prog = program_of(s, t); tab = interactions_of(s, t); });
     cache.emplace(key, m);
     return m;
 }
@@ -886,54 +837,27 @@ size_t describe(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t
     Shape s;
     if (which < 0 || which >= N_TABLES[kind] || what < 0 || what > 1 || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
     const auto m = machine_of(s);
-    const std::vector<uint32_t>& w = what == 0 ? m->prog[which] : m->tab[which];
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    if (table) *table = s.order[which];
-    if (out && cap_words >= w.size()) std::memcpy(out, w.data(), w.size() * 4);
-    return w.size();
+    if (table) *table = m->km.order[which];
+    return keyed::describe(m->km, which, what, [](int, int, std::vector<uint32_t>&) {}, out, cap_words, log_rows, main_width, pre_width);
 }
-// pre: the key's tables by table number (host, Montgomery)
-int key_host(const Shape& s, const std::vector<uint32_t>* pre, const zkhip_params* prm, uint32_t vk[8]) {
-    const auto m = machine_of(s);
-    std::vector<const uint32_t*> h(s.n_tables);
-    for (int i = 0; i < s.n_tables; i++) h[i] = m->pre_widths[i] ? pre[s.order[i]].data() : nullptr;
-    return zkhip_machine_key_host(h.data(), m->log_ns.data(), m->pre_widths.data(), s.n_tables, prm, vk);
-}
-// ... uploaded, each table with preprocessed columns into its scratch slot (slots: by table number)
+// pre: the key's tables by table number (host, Montgomery), uploaded each with preprocessed columns into its scratch slot (slots: by table number)
 int key_upload(zkhip_ctx* ctx, const Shape& s, const std::vector<uint32_t>* pre, const int* slots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     const auto m = machine_of(s);
-    std::vector<zkhip_chip> chips(s.n_tables, zkhip_chip{});
+    const uint32_t* d_pre[MAX_TABLES] = {};
     for (int i = 0; i < s.n_tables; i++) {
-        chips[i].log_n = m->log_ns[i]; chips[i].width = m->pre_widths[i]; chips[i].ld = m->pre_widths[i]; chips[i].partner = -1;
-        if (!m->pre_widths[i]) continue;
-        const std::vector<uint32_t>& t = pre[s.order[i]];
+        const int t = m->km.order[i];
+        if (!s.pre_w[t]) continue;
         void* dp;
-        ZK_TRY(ctx_reserve(ctx, slots[s.order[i]], t.size() * 4, &dp));
-        ZK_TRY(dev_h2d(ctx, dp, t.data(), t.size() * 4));
-        chips[i].d_trace = (const uint32_t*)dp;
+        ZK_TRY(ctx_reserve(ctx, slots[t], pre[t].size() * 4, &dp));
+        ZK_TRY(dev_h2d(ctx, dp, pre[t].data(), pre[t].size() * 4));
+        d_pre[t] = (const uint32_t*)dp;
     }
-    return zkhip_machine_setup(ctx, chips.data(), s.n_tables, prm, key, vk);
+    return keyed::key_setup(ctx, m->km, d_pre, prm, key, vk);
 }
 size_t proof_size(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const zkhip_params* prm) {
     Shape s;
     if (!prm || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
-    const auto m = machine_of(s);
-    return zkhip_machine_proof_size_keyed(m->log_ns.data(), m->widths.data(), m->pre_widths.data(), m->progs.data(), m->prog_words.data(), m->tabs.data(), m->tab_words.data(),
-                                          s.n_tables, prm, n_public_of(s));
-}
-// traces: the main traces on the device (dense) by table number
-int prove(zkhip_ctx* ctx, const zkhip_machine_key* key, const Shape& s, const uint32_t* const* traces, const uint32_t* public_values, const zkhip_params* prm, uint8_t* proof,
-          size_t cap, size_t* len) {
-    const auto m = machine_of(s);
-    std::vector<zkhip_chip> chips(s.n_tables, zkhip_chip{});
-    for (int i = 0; i < s.n_tables; i++) {
-        chips[i].d_trace = traces[s.order[i]];
-        chips[i].ld = m->widths[i]; chips[i].log_n = m->log_ns[i]; chips[i].width = m->widths[i]; chips[i].partner = -1;
-    }
-    return zkhip_prove_machine_keyed(ctx, key, chips.data(), m->progs.data(), m->prog_words.data(), m->tabs.data(), m->tab_words.data(), s.n_tables, public_values, n_public_of(s),
-                                     prm, proof, cap, len);
+    return keyed::proof_size(machine_of(s)->km, prm, n_public_of(s));
 }
 int verify(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const uint8_t* proof, size_t len, const uint32_t* public_values, const uint32_t vk[8],
            const zkhip_params* prm, int* reason, const char* who) {
@@ -942,9 +866,7 @@ int verify(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, c
         if (reason) *reason = 1;
         return fail(ZKHIP_ERR_VERIFY, std::string(who) + ": bad arguments");
     }
-    const auto m = machine_of(s);
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns.data(), m->widths.data(), m->pre_widths.data(), vk, m->progs.data(), m->prog_words.data(), m->tabs.data(),
-                                      m->tab_words.data(), s.n_tables, public_values, n_public_of(s), prm, reason);
+    return keyed::verify(machine_of(s)->km, proof, len, vk, public_values, n_public_of(s), prm, reason);
 }
 
 struct fold_rows_bargs { FoldRowsArgs a; static fold_rows_bargs make(FoldRowsArgs a) { return fold_rows_bargs{a}; } };
@@ -1282,7 +1204,7 @@ int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const u
     ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key_host"));
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
-    return fri16::key_host(s, pre, prm, vk);
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
 }
 
 int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
@@ -1295,8 +1217,9 @@ int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queri
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
     const int by_position[5] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G};      // this machine and PATHS give the slots out by machine position
+    const auto m = fri16::machine_of(s);
     int slots[fri16::MAX_TABLES];
-    for (int i = 0; i < s.n_tables; i++) slots[s.order[i]] = by_position[i];
+    for (int i = 0; i < s.n_tables; i++) slots[m->km.order[i]] = by_position[i];
     return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
 }
 
@@ -1331,7 +1254,7 @@ int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F
     // refused here, before anything is proven: a view whose chains do not end in the final polynomial
     ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, z.at(T_LAYERS), z.at(T_QUERIES), z.at(T_COEFFS)};
-    return prove(ctx, key, s, traces, betas, prm, proof, cap, len);
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, betas, n_public_of(s), prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
@@ -1353,7 +1276,7 @@ int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, i
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key_host: null argument");
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key_host"));
-    return fri16::key_host(s, pre, prm, vk);
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
 }
 
 int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
@@ -1366,8 +1289,9 @@ int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key"));
     const int by_position[6] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
+    const auto m = fri16::machine_of(s);
     int slots[fri16::MAX_TABLES];
-    for (int i = 0; i < s.n_tables; i++) slots[s.order[i]] = by_position[i];
+    for (int i = 0; i < s.n_tables; i++) slots[m->km.order[i]] = by_position[i];
     return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
 }
 
@@ -1423,7 +1347,7 @@ int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R,
         ZK_TRY(dev_h2d(ctx, z.d, tabs.data(), z.total * 4));
     }
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS)};
-    return prove(ctx, key, s, traces, betas, prm, proof, cap, len);
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, betas, n_public_of(s), prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
@@ -1445,7 +1369,7 @@ int zkhip_fri16_indices_key_host(int R, int F, int log_blowup, size_t n_queries,
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key_host: null argument");
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key_host"));
-    return fri16::key_host(s, pre, prm, vk);
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
 }
 
 // (INDICES on: the key's slots by table number -- the tables with preprocessed columns)
@@ -1529,7 +1453,7 @@ int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int 
     ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
     ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[0], pl, &t_p24));
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp};
-    return prove(ctx, key, s, traces, capacity, prm, proof, cap, len);
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, capacity, n_public_of(s), prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
@@ -1551,7 +1475,7 @@ int zkhip_fri16_openings_key_host(int R, int F, int log_blowup, size_t n_queries
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key_host: null argument");
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key_host"));
-    return fri16::key_host(s, pre, prm, vk);
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
 }
 
 int zkhip_fri16_openings_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
@@ -1617,7 +1541,7 @@ int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, z.at(T_ROWS)};
     uint32_t pub[N_PUBLIC_O];
     fri16_openings_public(capacity, constants, pub);
-    return prove(ctx, key, s, traces, pub, prm, proof, cap, len);
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, pub, n_public_of(s), prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
@@ -1639,7 +1563,7 @@ int zkhip_fri16_rowpaths_key_host(int R, int F, int log_blowup, size_t n_queries
     if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key_host: null argument");
     std::vector<uint32_t> pre[fri16::MAX_TABLES];
     ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key_host"));
-    return fri16::key_host(s, pre, prm, vk);
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
 }
 
 int zkhip_fri16_rowpaths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
@@ -1723,7 +1647,7 @@ int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r};
     uint32_t pub[N_PUBLIC_O];
     fri16_openings_public(capacity, constants, pub);
-    return prove(ctx, key, s, traces, pub, prm, proof, cap, len);
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, pub, n_public_of(s), prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,

@@ -38,6 +38,7 @@
 #include "air_builder.h"
 #include "context.h"
 #include "batch.h"
+#include "keyed_machine.h"
 #include "p2chip.h"
 #include "p2_x16.h"
 

@@ -18,7 +18,6 @@ namespace zk {
 namespace mrec {
 namespace {
 using namespace zk::rec;
-using frichip::ALL; using frichip::TRANSITION;
 
 constexpr uint32_t BUS_DG0 = 90, BUS_DG1 = 91, BUS_TC2 = 92, BUS_PW = 93, BUS_CS = 98, BUS_ACC = 100, BUS_KL = 101, BUS_ZH0 = 104, BUS_ZH1 = 105, BUS_KFA_M = 106,
                    BUS_YH0 = 107, BUS_YH1 = 108, BUS_AH0 = 109, BUS_AH1 = 110;
@@ -268,8 +267,8 @@ constexpr uint32_t PP_SS = 0, PP_SPG = 1, PP_CH = 2, PP_END = 3, PP_K = 4, PP_RI
 std::vector<uint32_t> p2r_program(const MShape& sh) {
     using namespace p2chip;
     const uint32_t M0 = P2_PRE, IN_ = M0 + IN, OUT = M0 + oute(7), D_ = M0 + D, BIT_ = M0 + BIT, KP_ = M0 + R_KP;
-    Cons c;
-    c.b.body = permutation_body(M0, &c.b.count);
+    Builder c;
+    c.body = permutation_body(M0, &c.count);
     for (uint32_t j = 0; j < 8; j++) c.add(ALL, padd(padd(pv(D_ + j), pneg(pv(IN_ + j))), padd(pmul(pv(BIT_), pv(IN_ + j)), pneg(pmul(pv(BIT_), pv(IN_ + 8 + j))))));
     c.add(ALL, padd(pmul(pv(BIT_), pv(BIT_)), pneg(pv(BIT_))));
     c.add(ALL, pmul(padd(padd(pv(PP_SS), pv(PP_SPG)), pv(PP_RDG)), pv(BIT_)));
@@ -281,7 +280,7 @@ std::vector<uint32_t> p2r_program(const MShape& sh) {
     c.add(TRANSITION, pmul(pv(PP_CH, true), padd(padd(pv(KP_), pscale(pv(KP_, true), P - 2)), pneg(pv(BIT_)))));
     c.add(TRANSITION, pmul(pv(PP_CHN, true), padd(pv(KP_), pneg(pv(KP_, true)))));
     c.add(ALL, pmul(pv(PP_END), padd(pv(KP_), pneg(pv(BIT_)))));
-    return c.program(P2_PRE + P2_MAIN, sh.npub_total());
+    return c.finish(P2_PRE + P2_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> p2r_table() {
     using namespace p2chip;
@@ -378,22 +377,6 @@ TsCols ts_cols(const MShape& sh) {
     c.W = c.pre; c.TR = c.pre + 8; c.CH = c.pre + 16; c.CH2 = c.pre + 20;
     return c;
 }
-int pub_row_index(const MShape& sh, int row) { for (size_t i = 0; i < sh.pub_rows.size(); i++) if (sh.pub_rows[i] == row) return (int)i; return -1; }
-std::vector<uint32_t> ts_program(const MShape& sh) {
-    const TsCols c = ts_cols(sh);
-    Cons k;
-    for (uint32_t j = 0; j < 8; j++) k.add(ALL, pmul(pv(c.CF + j), padd(pv(c.W + j), pneg(pv(c.CV + j)))));
-    const int npr = (int)sh.pub_rows.size();
-    for (int p = 0; p < sh.NP; p++)
-        for (int i = 0; i < sh.NPUB; i++) {
-            const int pos = sh.HL + 8 + i;
-            k.add(ALL, pmul(pv(c.IP + (uint32_t)(p * npr + pub_row_index(sh, pos / 8))), padd(pv(c.W + (uint32_t)(pos % 8)), pneg(ppub((uint32_t)(p * sh.NPUB + i))))));
-        }
-    const uint32_t o = (uint32_t)(sh.HL % 8);
-    for (uint32_t j = 0; j < 8 - o; j++) k.add(ALL, pmul(pv(c.IND0), padd(pv(c.W + o + j), pneg(pv(c.TR + j)))));
-    for (uint32_t j = 0; j < o; j++) k.add(TRANSITION, pmul(pv(c.IND0), padd(pv(c.W + j, true), pneg(pv(c.TR + 8 - o + j)))));
-    return k.program(c.pre + TS_MAIN, sh.npub_total());
-}
 std::vector<uint32_t> ts_table(const MShape& sh) {
     const TsCols c = ts_cols(sh);
     Tab t;
@@ -442,14 +425,14 @@ constexpr uint32_t EV_PRE = 12, EP_COEF = 0, EP_K0 = 1, EP_FIRSTC = 4, EP_ACT = 
 constexpr uint32_t EV_F0 = 0, EV_M = 12, EV_TV = 16, EV_ACCIN = 20, EV_ACCO = 24, EV_ALPHA = 28, EV_MAIN = 32;
 std::vector<uint32_t> eval_program(const MShape& sh) {
     const uint32_t M0 = EV_PRE;
-    Cons c;
+    Builder c;
     const EE f0 = ev(M0 + EV_F0), f1 = ev(M0 + EV_F0 + 4), f2 = ev(M0 + EV_F0 + 8), mm = ev(M0 + EV_M), tv = ev(M0 + EV_TV), ai = ev(M0 + EV_ACCIN), ao = ev(M0 + EV_ACCO), al = ev(M0 + EV_ALPHA);
-    c.ext(ALL, esub(mm, emul(f0, f1)));
-    c.ext(ALL, esub(tv, egate(pv(EP_COEF), emul(mm, f2))));
-    c.ext(ALL, esub(ao, eadd(ai, egate(pv(EP_FIRSTC), esub(emul(ai, al), ai)), tv)));
-    c.ext(TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ACCIN, true), ao)));
-    c.ext(ALL, egate(pv(EP_CFIRST), ai));
-    return c.program(EV_PRE + EV_MAIN, sh.npub_total());
+    add_ext(c, ALL, esub(mm, emul(f0, f1)));
+    add_ext(c, ALL, esub(tv, egate(pv(EP_COEF), emul(mm, f2))));
+    add_ext(c, ALL, esub(ao, eadd(ai, egate(pv(EP_FIRSTC), esub(emul(ai, al), ai)), tv)));
+    add_ext(c, TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ACCIN, true), ao)));
+    add_ext(c, ALL, egate(pv(EP_CFIRST), ai));
+    return c.finish(EV_PRE + EV_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> eval_table() {
     const uint32_t M0 = EV_PRE;
@@ -495,7 +478,7 @@ EE from_columns(uint32_t first) {       // sum_k X^k column_k
         const EE e = ev(first + 4 * k);
         for (uint32_t i = 0; i < 4; i++) {
             const uint32_t j = i + k;
-            const Poly t = j >= 4 ? pscale(e[i], EXT_W) : e[i];
+            const Terms t = j >= 4 ? pscale(e[i], EXT_W) : e[i];
             out[j % 4].insert(out[j % 4].end(), t.begin(), t.end());
         }
     }
@@ -503,33 +486,33 @@ EE from_columns(uint32_t first) {       // sum_k X^k column_k
 }
 std::vector<uint32_t> logup_program(const MShape& sh) {
     const LgCols m = lg_cols();
-    Cons c;
+    Builder c;
     const uint32_t consts[2] = {m.ALPHA, m.GAMMA};
-    for (uint32_t col : consts) c.ext(TRANSITION, egate(pv(LP_NFP, true), esub(ev(col, true), ev(col))));
-    for (uint32_t k = 0; k < 8; k++) c.ext(TRANSITION, egate(pv(LP_NFP, true), esub(ev(m.BP + 4 * k, true), ev(m.BP + 4 * k))));
-    for (uint32_t k = 1; k < 8; k++) c.ext(ALL, esub(ev(m.BP + 4 * k), emul(ev(m.BP + 4 * (k - 1)), ev(m.BP))));
-    c.ext(ALL, esub(ev(m.PHI), from_columns(m.PH)));
-    c.ext(ALL, esub(ev(m.PHIN), from_columns(m.PN)));
+    for (uint32_t col : consts) add_ext(c, TRANSITION, egate(pv(LP_NFP, true), esub(ev(col, true), ev(col))));
+    for (uint32_t k = 0; k < 8; k++) add_ext(c, TRANSITION, egate(pv(LP_NFP, true), esub(ev(m.BP + 4 * k, true), ev(m.BP + 4 * k))));
+    for (uint32_t k = 1; k < 8; k++) add_ext(c, ALL, esub(ev(m.BP + 4 * k), emul(ev(m.BP + 4 * (k - 1)), ev(m.BP))));
+    add_ext(c, ALL, esub(ev(m.PHI), from_columns(m.PH)));
+    add_ext(c, ALL, esub(ev(m.PHIN), from_columns(m.PN)));
     for (int side = 0; side < 2; side++) {
         const uint32_t V_ = side ? m.VB : m.VA, D_ = side ? m.DB : m.DA, BUS_ = side ? LP_BUSB : LP_BUSA, F_ = side ? LP_FB : LP_FA;
         EE d = eadd(egate(side ? pv(LP_HASB) : pv(LP_ISP), ev(m.GAMMA)), eb(pv(BUS_)));
         if (side) d = eadd(d, eb(pv(LP_NOB)));
         for (uint32_t t = 0; t < 8; t++) d = eadd(d, egate(pv(F_ + t), emul(ev(m.BP + 4 * t), ev(V_ + 4 * t))));
-        c.ext(ALL, esub(ev(D_), d));
+        add_ext(c, ALL, esub(ev(D_), d));
     }
     const EE ma = egate(pv(LP_SA), ev(m.MA)), mb = egate(pv(LP_SB), ev(m.MB));
-    c.ext(ALL, esub(ev(m.CST), esub(emul(emul(ev(m.PHI), ev(m.DA)), ev(m.DB)), eadd(emul(ma, ev(m.DB)), emul(mb, ev(m.DA))))));
+    add_ext(c, ALL, esub(ev(m.CST), esub(emul(emul(ev(m.PHI), ev(m.DA)), ev(m.DB)), eadd(emul(ma, ev(m.DB)), emul(mb, ev(m.DA))))));
     const EE al = ev(m.ALPHA);
-    c.ext(ALL, esub(ev(m.U1), eadd(emul(ev(m.ACCIN), al), emul(ev(m.VA), esub(ev(m.PHI), ev(m.SUML))))));
-    c.ext(ALL, esub(ev(m.U2), eadd(emul(ev(m.U1), al), emul(ev(m.VA + 8), esub(esub(ev(m.PHIN), ev(m.PHI)), ev(m.SUMN))))));
-    c.ext(ALL, esub(ev(m.ACCO), eadd(egate(pv(LP_ISP), eadd(emul(ev(m.ACCIN), al), ev(m.CST))),
+    add_ext(c, ALL, esub(ev(m.U1), eadd(emul(ev(m.ACCIN), al), emul(ev(m.VA), esub(ev(m.PHI), ev(m.SUML))))));
+    add_ext(c, ALL, esub(ev(m.U2), eadd(emul(ev(m.U1), al), emul(ev(m.VA + 8), esub(esub(ev(m.PHIN), ev(m.PHI)), ev(m.SUMN))))));
+    add_ext(c, ALL, esub(ev(m.ACCO), eadd(egate(pv(LP_ISP), eadd(emul(ev(m.ACCIN), al), ev(m.CST))),
                                       egate(pv(LP_ISB), eadd(emul(ev(m.U2), al), emul(ev(m.VA + 4), esub(ev(m.PHI), ev(m.CUM))))))));
-    c.ext(TRANSITION, egate(pv(LP_NF, true), esub(ev(m.ACCIN, true), ev(m.ACCO))));
-    c.ext(TRANSITION, egate(pv(LP_NF, true), esub(ev(m.SUML, true), eadd(ev(m.SUML), ev(m.PHI)))));
-    c.ext(TRANSITION, egate(pv(LP_NF, true), esub(ev(m.SUMN, true), eadd(ev(m.SUMN), ev(m.PHIN)))));
-    c.ext(ALL, egate(pv(LP_CFIRST), ev(m.SUML)));
-    c.ext(ALL, egate(pv(LP_CFIRST), ev(m.SUMN)));
-    return c.program(LG_PRE + LG_MAIN, sh.npub_total());
+    add_ext(c, TRANSITION, egate(pv(LP_NF, true), esub(ev(m.ACCIN, true), ev(m.ACCO))));
+    add_ext(c, TRANSITION, egate(pv(LP_NF, true), esub(ev(m.SUML, true), eadd(ev(m.SUML), ev(m.PHI)))));
+    add_ext(c, TRANSITION, egate(pv(LP_NF, true), esub(ev(m.SUMN, true), eadd(ev(m.SUMN), ev(m.PHIN)))));
+    add_ext(c, ALL, egate(pv(LP_CFIRST), ev(m.SUML)));
+    add_ext(c, ALL, egate(pv(LP_CFIRST), ev(m.SUMN)));
+    return c.finish(LG_PRE + LG_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> logup_table() {
     const LgCols m = lg_cols();
@@ -594,39 +577,39 @@ ScCols sc_cols(const MShape& sh) {
 }
 std::vector<uint32_t> scalars_program(const MShape& sh) {
     const ScCols c = sc_cols(sh);
-    Cons k;
+    Builder k;
     const uint32_t consts[5] = {c.ALPHA, c.ZETA, c.FA, c.GAMMA, c.BETA};
-    for (uint32_t col : consts) k.ext(TRANSITION, egate(pv(c.NFP, true), esub(ev(col, true), ev(col))));
+    for (uint32_t col : consts) add_ext(k, TRANSITION, egate(pv(c.NFP, true), esub(ev(col, true), ev(col))));
     std::vector<EE> zp{ev(c.ZETA)};
     for (int i = 0; i < sh.R; i++) zp.push_back(ev(c.ZP + 4 * (uint32_t)i));
-    for (int i = 0; i < sh.R; i++) k.ext(ALL, esub(zp[(size_t)i + 1], emul(zp[(size_t)i], zp[(size_t)i])));
+    for (int i = 0; i < sh.R; i++) add_ext(k, ALL, esub(zp[(size_t)i + 1], emul(zp[(size_t)i], zp[(size_t)i])));
     EE zn;
     for (int i = 0; i <= sh.R; i++) zn = eadd(zn, egate(pv(c.OH + (uint32_t)i), zp[(size_t)i]));
-    k.ext(ALL, esub(ev(c.ZN), zn));
+    add_ext(k, ALL, esub(ev(c.ZN), zn));
     const EE zh = esub(ev(c.ZN), eb(pv(c.ACT))), one = eb(pv(c.ACT));
-    k.ext(ALL, esub(emul(esub(ev(c.ZETA), one), ev(c.INVF)), one));
-    k.ext(ALL, esub(emul(esub(ev(c.ZETA), eb(pv(c.WINV))), ev(c.INVT)), one));
-    k.ext(ALL, esub(ev(c.SELF), emul(zh, ev(c.INVF))));
-    k.ext(ALL, esub(ev(c.SELL), emul(zh, ev(c.INVT))));
-    k.ext(ALL, esub(ev(c.SELT), esub(ev(c.ZETA), eb(pv(c.WINV)))));
-    k.ext(ALL, esub(ev(c.ZNX), egate(pv(c.WN), ev(c.ZETA))));
+    add_ext(k, ALL, esub(emul(esub(ev(c.ZETA), one), ev(c.INVF)), one));
+    add_ext(k, ALL, esub(emul(esub(ev(c.ZETA), eb(pv(c.WINV))), ev(c.INVT)), one));
+    add_ext(k, ALL, esub(ev(c.SELF), emul(zh, ev(c.INVF))));
+    add_ext(k, ALL, esub(ev(c.SELL), emul(zh, ev(c.INVT))));
+    add_ext(k, ALL, esub(ev(c.SELT), esub(ev(c.ZETA), eb(pv(c.WINV)))));
+    add_ext(k, ALL, esub(ev(c.ZNX), egate(pv(c.WN), ev(c.ZETA))));
     for (uint32_t h = 0; h < 2; h++) {
         EE q;
         for (uint32_t j = 0; j < 4; j++) {
             const EE v = ev(c.QZ + 16 * h + 4 * j);
-            for (uint32_t i = 0; i < 4; i++) { const Poly t = i + j >= 4 ? pscale(v[i], EXT_W) : v[i]; q[(i + j) % 4].insert(q[(i + j) % 4].end(), t.begin(), t.end()); }
+            for (uint32_t i = 0; i < 4; i++) { const Terms t = i + j >= 4 ? pscale(v[i], EXT_W) : v[i]; q[(i + j) % 4].insert(q[(i + j) % 4].end(), t.begin(), t.end()); }
         }
-        k.ext(ALL, esub(ev(h ? c.Q1 : c.Q0), q));
+        add_ext(k, ALL, esub(ev(h ? c.Q1 : c.Q0), q));
     }
     const EE zps0 = eadd(egate(pv(c.ZA0), ev(c.ZN)), eb(pv(c.ZB0))), zps1 = eadd(egate(pv(c.ZA1), ev(c.ZN)), eb(pv(c.ZB1)));
-    k.ext(ALL, esub(ev(c.QUO), eadd(emul(zps0, ev(c.Q0)), emul(zps1, ev(c.Q1)))));
-    k.ext(ALL, esub(ev(c.ACC), emul(ev(c.QUO), zh)));
-    k.ext(ALL, egate(pv(c.PFIRST), ev(c.TOTIN)));
-    k.ext(ALL, esub(ev(c.TOTO), eadd(ev(c.TOTIN), ev(c.CUM))));
-    k.ext(TRANSITION, egate(pv(c.NFP, true), esub(ev(c.TOTIN, true), ev(c.TOTO))));
-    k.ext(ALL, egate(pv(c.LASTC), ev(c.TOTO)));
+    add_ext(k, ALL, esub(ev(c.QUO), eadd(emul(zps0, ev(c.Q0)), emul(zps1, ev(c.Q1)))));
+    add_ext(k, ALL, esub(ev(c.ACC), emul(ev(c.QUO), zh)));
+    add_ext(k, ALL, egate(pv(c.PFIRST), ev(c.TOTIN)));
+    add_ext(k, ALL, esub(ev(c.TOTO), eadd(ev(c.TOTIN), ev(c.CUM))));
+    add_ext(k, TRANSITION, egate(pv(c.NFP, true), esub(ev(c.TOTIN, true), ev(c.TOTO))));
+    add_ext(k, ALL, egate(pv(c.LASTC), ev(c.TOTO)));
     for (uint32_t j = 0; j < 8; j++) k.add(ALL, pmul(pv(c.PFIRST), padd(pv(c.KR + j), pc(P - sh.key_root[j]))));
-    return k.program(c.pre + rup4(c.end - c.pre), sh.npub_total());
+    return k.finish(c.pre + rup4(c.end - c.pre), sh.npub_total());
 }
 std::vector<uint32_t> scalars_table(const MShape& sh) {
     const ScCols c = sc_cols(sh);
@@ -701,22 +684,22 @@ std::vector<StreamRow> stream_rows(const MShape& sh) {
 bool is_next_kind(int kind) { return kind == K_EN || kind == K_TN || kind == K_PN; }
 std::vector<uint32_t> opened_program(const MShape& sh) {
     const uint32_t M0 = OS_PRE;
-    Cons c;
+    Builder c;
     const EE v0 = ev(M0 + OS_W), v1 = ev(M0 + OS_W + 4), fa = ev(M0 + OS_FA), fa2 = ev(M0 + OS_FA2), pw = ev(M0 + OS_PW), mm = ev(M0 + OS_M);
     const uint32_t consts[2] = {OS_FA, OS_FA2};
-    for (uint32_t col : consts) c.ext(TRANSITION, egate(pv(OS_NFP, true), esub(ev(M0 + col, true), ev(M0 + col))));
-    c.ext(ALL, esub(fa2, emul(fa, fa)));
-    c.ext(ALL, esub(mm, eadd(v0, emul(fa, v1))));
-    c.ext(ALL, egate(pv(OS_RST), esub(pw, ec(1))));
-    c.ext(ALL, esub(ev(M0 + OS_PWN), emul(pw, fa2)));
-    c.ext(TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_PW, true), ev(M0 + OS_PWN))));
-    c.ext(ALL, esub(ev(M0 + OS_YZO), eadd(ev(M0 + OS_YZIN), egate(pv(OS_NISN), emul(pw, mm)))));
-    c.ext(ALL, esub(ev(M0 + OS_YNO), eadd(ev(M0 + OS_YNIN), egate(pv(OS_ISN), emul(pw, mm)))));
-    c.ext(TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_YZIN, true), ev(M0 + OS_YZO))));
-    c.ext(TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_YNIN, true), ev(M0 + OS_YNO))));
-    c.ext(ALL, egate(pv(OS_RST), ev(M0 + OS_YZIN)));
-    c.ext(ALL, egate(pv(OS_RST), ev(M0 + OS_YNIN)));
-    return c.program(OS_PRE + OS_MAIN, sh.npub_total());
+    for (uint32_t col : consts) add_ext(c, TRANSITION, egate(pv(OS_NFP, true), esub(ev(M0 + col, true), ev(M0 + col))));
+    add_ext(c, ALL, esub(fa2, emul(fa, fa)));
+    add_ext(c, ALL, esub(mm, eadd(v0, emul(fa, v1))));
+    add_ext(c, ALL, egate(pv(OS_RST), esub(pw, ec(1))));
+    add_ext(c, ALL, esub(ev(M0 + OS_PWN), emul(pw, fa2)));
+    add_ext(c, TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_PW, true), ev(M0 + OS_PWN))));
+    add_ext(c, ALL, esub(ev(M0 + OS_YZO), eadd(ev(M0 + OS_YZIN), egate(pv(OS_NISN), emul(pw, mm)))));
+    add_ext(c, ALL, esub(ev(M0 + OS_YNO), eadd(ev(M0 + OS_YNIN), egate(pv(OS_ISN), emul(pw, mm)))));
+    add_ext(c, TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_YZIN, true), ev(M0 + OS_YZO))));
+    add_ext(c, TRANSITION, egate(pv(OS_NRST, true), esub(ev(M0 + OS_YNIN, true), ev(M0 + OS_YNO))));
+    add_ext(c, ALL, egate(pv(OS_RST), ev(M0 + OS_YZIN)));
+    add_ext(c, ALL, egate(pv(OS_RST), ev(M0 + OS_YNIN)));
+    return c.finish(OS_PRE + OS_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> opened_table() {
     const uint32_t M0 = OS_PRE, W = M0 + OS_W;
@@ -786,28 +769,28 @@ std::vector<RsRow> rowsum_rows(const MShape& sh) {
 }
 std::vector<uint32_t> rowsum_program(const MShape& sh) {
     const uint32_t M0 = RS_PRE;
-    Cons c;
+    Builder c;
     const EE fa = ev(M0 + RS_FA);
-    c.ext(TRANSITION, egate(pv(RP_NFP, true), esub(ev(M0 + RS_FA, true), fa)));
+    add_ext(c, TRANSITION, egate(pv(RP_NFP, true), esub(ev(M0 + RS_FA, true), fa)));
     EE prev = ev(M0 + RS_ACCIN);
     for (int s = 7; s >= 0; s--) {
         const EE cur = ev(M0 + RS_T + 4 * (uint32_t)s);
         EE carried = emul(prev, fa);
         if (s == 7) carried = egate(pv(RP_NR7), carried);
         if (s == 3) carried = egate(pv(RP_NR3), carried);
-        c.ext(ALL, esub(cur, eadd(carried, eb(pv(M0 + RS_V + (uint32_t)s)))));
+        add_ext(c, ALL, esub(cur, eadd(carried, eb(pv(M0 + RS_V + (uint32_t)s)))));
         prev = cur;
     }
-    c.ext(TRANSITION, egate(pv(RP_NR7, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
+    add_ext(c, TRANSITION, egate(pv(RP_NR7, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
     for (uint32_t j = 0; j < 4; j++) c.add(ALL, pmul(pv(RP_HALF), pv(M0 + RS_V + 4 + j)));
     const EE t0 = ev(M0 + RS_T), t4 = ev(M0 + RS_T + 16);
-    c.ext(ALL, esub(ev(M0 + RS_AZO), eadd(ev(M0 + RS_AZIN), egate(pv(RP_F0), emul(ev(M0 + RS_KZ0), t0)), egate(pv(RP_F4), emul(ev(M0 + RS_KZ4), t4)))));
-    c.ext(ALL, esub(ev(M0 + RS_ANO), eadd(ev(M0 + RS_ANIN), egate(pv(RP_N0), emul(ev(M0 + RS_KN0), t0)), egate(pv(RP_N4), emul(ev(M0 + RS_KN4), t4)))));
-    c.ext(TRANSITION, egate(pv(RP_NG, true), esub(ev(M0 + RS_AZIN, true), ev(M0 + RS_AZO))));
-    c.ext(TRANSITION, egate(pv(RP_NG, true), esub(ev(M0 + RS_ANIN, true), ev(M0 + RS_ANO))));
-    c.ext(ALL, egate(pv(RP_GFIRST), ev(M0 + RS_AZIN)));
-    c.ext(ALL, egate(pv(RP_GFIRST), ev(M0 + RS_ANIN)));
-    return c.program(RS_PRE + RS_MAIN, sh.npub_total());
+    add_ext(c, ALL, esub(ev(M0 + RS_AZO), eadd(ev(M0 + RS_AZIN), egate(pv(RP_F0), emul(ev(M0 + RS_KZ0), t0)), egate(pv(RP_F4), emul(ev(M0 + RS_KZ4), t4)))));
+    add_ext(c, ALL, esub(ev(M0 + RS_ANO), eadd(ev(M0 + RS_ANIN), egate(pv(RP_N0), emul(ev(M0 + RS_KN0), t0)), egate(pv(RP_N4), emul(ev(M0 + RS_KN4), t4)))));
+    add_ext(c, TRANSITION, egate(pv(RP_NG, true), esub(ev(M0 + RS_AZIN, true), ev(M0 + RS_AZO))));
+    add_ext(c, TRANSITION, egate(pv(RP_NG, true), esub(ev(M0 + RS_ANIN, true), ev(M0 + RS_ANO))));
+    add_ext(c, ALL, egate(pv(RP_GFIRST), ev(M0 + RS_AZIN)));
+    add_ext(c, ALL, egate(pv(RP_GFIRST), ev(M0 + RS_ANIN)));
+    return c.finish(RS_PRE + RS_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> rowsum_table() {
     const uint32_t M0 = RS_PRE, v = M0 + RS_V;
@@ -850,17 +833,17 @@ constexpr uint32_t QM_IDX = Q_PRE, QM_XQ = Q_PRE + 1, QM_IDX0 = Q_PRE + 2, QM_RO
                    QM_I1 = QM_ZNX + 4, QM_I2 = QM_I1 + 4, QM_P1 = QM_I2 + 4, QM_P2 = QM_P1 + 4, QM_END = QM_P2 + 4;
 constexpr uint32_t Q_MAIN = ((QM_END - Q_PRE) + 3u) & ~3u;
 std::vector<uint32_t> query_program(const MShape& sh) {
-    Cons c;
+    Builder c;
     const EE x = eb(pscale(pv(QM_XQ), from_monty(MONTY_GEN))), one = eb(pv(QP_ACT));
-    c.ext(ALL, esub(emul(esub(x, ev(QM_ZETA)), ev(QM_I1)), one));
-    c.ext(ALL, esub(emul(esub(x, ev(QM_ZNX)), ev(QM_I2)), one));
-    c.ext(ALL, esub(ev(QM_P1), emul(esub(ev(QM_AZ), ev(QM_YZ)), ev(QM_I1))));
-    c.ext(ALL, esub(ev(QM_P2), emul(esub(ev(QM_AN), ev(QM_YN)), ev(QM_I2))));
-    c.ext(ALL, esub(ev(QM_RO), eadd(ev(QM_P1), ev(QM_P2))));
+    add_ext(c, ALL, esub(emul(esub(x, ev(QM_ZETA)), ev(QM_I1)), one));
+    add_ext(c, ALL, esub(emul(esub(x, ev(QM_ZNX)), ev(QM_I2)), one));
+    add_ext(c, ALL, esub(ev(QM_P1), emul(esub(ev(QM_AZ), ev(QM_YZ)), ev(QM_I1))));
+    add_ext(c, ALL, esub(ev(QM_P2), emul(esub(ev(QM_AN), ev(QM_YN)), ev(QM_I2))));
+    add_ext(c, ALL, esub(ev(QM_RO), eadd(ev(QM_P1), ev(QM_P2))));
     // the rows of a query carry its index: what the fold chain hands a LOWER height is named by the query (two heights of two queries cannot be exchanged)
     c.add(ALL, pmul(pv(QP_TOP), padd(pv(QM_IDX0), pneg(pv(QM_IDX)))));
     c.add(TRANSITION, pmul(pv(QP_NQ, true), padd(pv(QM_IDX0, true), pneg(pv(QM_IDX0)))));
-    return c.program(Q_PRE + Q_MAIN, sh.npub_total());
+    return c.finish(Q_PRE + Q_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> query_table() {
     Tab t;
@@ -891,27 +874,12 @@ void query_pre(const MShape& sh, int log_rows, std::vector<uint32_t>& t) {
 
 // ============================================================================================================ FOLD
 std::vector<int> inject_layers(const MShape& sh) { std::vector<int> o; for (size_t i = sh.hs.size(); i-- > 0;) if (sh.hs[i] != sh.H) o.push_back(sh.H - sh.hs[i]); std::sort(o.begin(), o.end()); return o; }
-std::vector<uint32_t> fold_table(const MShape& sh) {
-    using namespace frichip;
-    const uint32_t INJ = width_of(sh.R, true, true), INJF = INJ + 4;
-    Tab t;
-    t.add(SEND, ACTIVE, BUS_E0, {LNX, K2, E0, E0 + 1, E0 + 2, E0 + 3}); t.add(SEND, ACTIVE, BUS_E1, {LNX, K2, E1, E1 + 1, E1 + 2, E1 + 3});
-    t.add(SEND, L_REC, BUS_Q, {frichip::PT, IDX, XS, OWN, OWN + 1, OWN + 2, OWN + 3}); t.add(SEND, INJF, BUS_Q, {LNX, INJF + 1, IDX, XS, INJ, INJ + 1, INJ + 2, INJ + 3});
-    t.add5(RECV, ACTIVE, BUS_BETA, LNX, BETA);
-    t.add5(SEND, L_REC + (uint32_t)sh.R - 1u, BUS_FIN, frichip::PT, FOLD);
-    return t.w;
-}
 
 // ============================================================================================================ the machine
 enum MChipId : int { C_P2R, C_ROWSUM, C_FOLD, C_TS, C_QUERY, C_OPENED, C_SAMPLES, C_SCALARS, C_EVAL, C_LOGUP, N_CHIPS };
 struct Machine {
     MShape sh;
-    int order[N_CHIPS];
-    int32_t log_ns[N_CHIPS]; uint32_t widths[N_CHIPS], pre_widths[N_CHIPS];
-    std::vector<uint32_t> prog[N_CHIPS], tab[N_CHIPS];                  // by position
-    const uint32_t* progs[N_CHIPS]; size_t prog_words[N_CHIPS]; const uint32_t* tabs[N_CHIPS]; size_t tab_words[N_CHIPS];
-    int height[N_CHIPS];                                                // by chip
-    uint32_t w_main[N_CHIPS], w_pre[N_CHIPS];                           // by chip
+    keyed::KeyedMachine km;
     std::vector<std::vector<uint32_t>> programs_kept, tables_kept;      // the inner machine's own words (the description's pointers need not outlive the call)
 };
 void heights_of(const MShape& sh, int h[N_CHIPS]) {
@@ -975,31 +943,26 @@ std::shared_ptr<const Machine> machine_of_impl(const zkhip_machine_desc* d, size
     const MShape& sh = m->sh;
     int h[N_CHIPS];
     heights_of(sh, h);
-    for (int c = 0; c < N_CHIPS; c++) { m->height[c] = h[c]; m->order[c] = c; }
-    std::stable_sort(m->order, m->order + N_CHIPS, [&](int a, int b) { return h[a] > h[b]; });
     const std::vector<int> inj = inject_layers(sh);
     const ScCols scc = sc_cols(sh);
     const TsCols tsc = ts_cols(sh);
-    const uint32_t w_main[N_CHIPS] = {P2_MAIN, RS_MAIN, frichip::width_of(sh.R, true, true) + 8u, TS_MAIN, Q_MAIN, OS_MAIN, frichip::S_MAIN, rup4(scc.end - scc.pre), EV_MAIN, LG_MAIN};
+    const uint32_t INJ = frichip::width_of(sh.R, true, true);            // the fold chip's injection columns stand behind its `rec` form
+    const uint32_t w_main[N_CHIPS] = {P2_MAIN, RS_MAIN, INJ + 8u, TS_MAIN, Q_MAIN, OS_MAIN, frichip::S_MAIN, rup4(scc.end - scc.pre), EV_MAIN, LG_MAIN};
     const uint32_t w_pre[N_CHIPS] = {P2_PRE, RS_PRE, 0u, tsc.pre, Q_PRE, OS_PRE, frichip::S_PRE, scc.pre, EV_PRE, LG_PRE};
-    for (int c = 0; c < N_CHIPS; c++) { m->w_main[c] = w_main[c]; m->w_pre[c] = w_pre[c]; }
-    for (int i = 0; i < N_CHIPS; i++) {
-        const int c = m->order[i];
+    keyed::build(m->km, N_CHIPS, h, w_main, w_pre, [&](int c, std::vector<uint32_t>& prog, std::vector<uint32_t>& tab) {
         switch (c) {
-            case C_P2R: m->prog[i] = p2r_program(sh); m->tab[i] = p2r_table(); break;
-            case C_ROWSUM: m->prog[i] = rowsum_program(sh); m->tab[i] = rowsum_table(); break;
-            case C_FOLD: m->prog[i] = frichip::build_program(sh.R, true, true, (int)sh.npub_total(), &inj); m->tab[i] = fold_table(sh); break;
-            case C_TS: m->prog[i] = ts_program(sh); m->tab[i] = ts_table(sh); break;
-            case C_QUERY: m->prog[i] = query_program(sh); m->tab[i] = query_table(); break;
-            case C_OPENED: m->prog[i] = opened_program(sh); m->tab[i] = opened_table(); break;
-            case C_SAMPLES: m->prog[i] = *frichip::samples_program(sh.R, sh.PB, sh.npub_total()); m->tab[i] = frichip::samples_interactions(); break;
-            case C_SCALARS: m->prog[i] = scalars_program(sh); m->tab[i] = scalars_table(sh); break;
-            case C_EVAL: m->prog[i] = eval_program(sh); m->tab[i] = eval_table(); break;
-            default: m->prog[i] = logup_program(sh); m->tab[i] = logup_table(); break;
+            case C_P2R: prog = p2r_program(sh); tab = p2r_table(); break;
+            case C_ROWSUM: prog = rowsum_program(sh); tab = rowsum_table(); break;
+            case C_FOLD: prog = frichip::build_program(sh.R, true, true, (int)sh.npub_total(), &inj); tab = fold_table(sh.R, INJ); break;
+            case C_TS: prog = ts_program(sh, TS_MAIN); tab = ts_table(sh); break;
+            case C_QUERY: prog = query_program(sh); tab = query_table(); break;
+            case C_OPENED: prog = opened_program(sh); tab = opened_table(); break;
+            case C_SAMPLES: prog = *frichip::samples_program(sh.R, sh.PB, sh.npub_total()); tab = frichip::samples_interactions(); break;
+            case C_SCALARS: prog = scalars_program(sh); tab = scalars_table(sh); break;
+            case C_EVAL: prog = eval_program(sh); tab = eval_table(); break;
+            default: prog = logup_program(sh); tab = logup_table(); break;
         }
-        m->log_ns[i] = h[c]; m->widths[i] = w_main[c]; m->pre_widths[i] = w_pre[c];
-    }
-    for (int i = 0; i < N_CHIPS; i++) { m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size(); }
+    });
     std::lock_guard<std::mutex> lk(mu);
     if (cache.size() > 8) cache.clear();
     cache.emplace(key, m);
@@ -1014,24 +977,9 @@ std::shared_ptr<const Machine> machine_of(const zkhip_machine_desc* d, size_t n_
     catch (const std::exception& e) { *rc = fail(ZKHIP_ERR_INTERNAL, std::string("machine verifier: ") + e.what()); }
     return nullptr;
 }
-void samples_pre_all(const MShape& sh, int log_rows, std::vector<uint32_t>& t) {
-    t.assign((size_t)frichip::S_PRE << log_rows, 0u);
-    std::vector<uint32_t> one;
-    for (int p = 0; p < sh.NP; p++) {
-        frichip::samples_pre(sh.R, (size_t)sh.Q, lg((size_t)sh.NS), one, (int)sh.ttag(p, sh.TP));
-        for (int r = 0; r < sh.NS; r++) {
-            uint32_t* row = one.data() + (size_t)frichip::S_PRE * (size_t)r;
-            for (uint32_t j = 0; j < 8; j++) if (row[frichip::S_ACT + j]) row[frichip::S_KQ + j] = fadd(row[frichip::S_KQ + j], to_monty((uint32_t)(p * sh.Q)));
-        }
-        std::memcpy(t.data() + (size_t)frichip::S_PRE * (size_t)p * (size_t)sh.NS, one.data(), (size_t)frichip::S_PRE * (size_t)sh.NS * 4);
-    }
-}
-void all_pre(const Machine& m, std::vector<uint32_t> pre[N_CHIPS]) {
-    const MShape& sh = m.sh;
-    p2r_pre(sh, m.height[C_P2R], pre[C_P2R]); rowsum_pre(sh, m.height[C_ROWSUM], pre[C_ROWSUM]); ts_pre(sh, m.height[C_TS], pre[C_TS]); query_pre(sh, m.height[C_QUERY], pre[C_QUERY]);
-    opened_pre(sh, m.height[C_OPENED], pre[C_OPENED]); samples_pre_all(sh, m.height[C_SAMPLES], pre[C_SAMPLES]); scalars_pre(sh, m.height[C_SCALARS], pre[C_SCALARS]);
-    eval_pre(sh, m.height[C_EVAL], pre[C_EVAL]); logup_pre(sh, m.height[C_LOGUP], pre[C_LOGUP]);
-}
+// every chip's preprocessed-trace builder, by chip (the fold chip has no preprocessed columns)
+typedef void (*PreFn)(const MShape&, int, std::vector<uint32_t>&);
+const PreFn PRE[N_CHIPS] = {p2r_pre, rowsum_pre, nullptr, ts_pre, query_pre, opened_pre, samples_pre_all<MShape>, scalars_pre, eval_pre, logup_pre};
 
 // ============================================================================================================ the witness and the main traces (host)
 // Everything below reads the inner proof's words by their position (docs/PROTOCOL.md section 6, version 11) and recomputes what the host
@@ -1058,7 +1006,6 @@ struct HostTabs {
                             p2_in.release(), p2_bit.release(), p2_kp.release()});
     }
 };
-inline Ext ext_at(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
 inline Ext recombine4(const Ext* four) {            // sum_k X^k four[k]
     Ext acc = ext_zero();
     for (int k = 0; k < 4; k++) { Ext basis = ext_zero(); basis.c[k] = MONTY_R1; acc = ext_add(acc, ext_mul(basis, four[k])); }
@@ -1275,7 +1222,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
         if ((int)wt.indices.size() != Q) return fail(ZKHIP_ERR_INTERNAL, "prove_machine_verifier: query indices");
     }
     sec("samples");
-    auto stream_ext = [&](uint32_t posv) { return ext_at(w + wt.o_stream + 4 * (size_t)posv); };
+    auto stream_ext = [&](uint32_t posv) { return ext_canon(w + wt.o_stream + 4 * (size_t)posv); };
     // ---- SCALARS values per chip
     std::vector<ScVals> sc((size_t)C);
     std::vector<Ext> zp{wt.zeta};
@@ -1299,10 +1246,10 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
             const Ext zps0 = ext_add_base(ext_mul_base(v.zn, to_monty(zw[0])), to_monty(zw[1])), zps1 = ext_add_base(ext_mul_base(v.zn, to_monty(zw[2])), to_monty(zw[3]));
             v.quo = ext_add(ext_mul(zps0, v.q0), ext_mul(zps1, v.q1));
             v.acc = ext_mul(v.quo, zh);
-            v.cum = ext_at(w + wt.o_cum + 4 * (size_t)ch); v.totin = tot;
+            v.cum = ext_canon(w + wt.o_cum + 4 * (size_t)ch); v.totin = tot;
             tot = ext_add(tot, v.cum);
             v.toto = tot;
-            uint32_t* r = ht.sc.data() + (size_t)m.w_main[C_SCALARS] * ((size_t)p * (size_t)C + (size_t)ch);
+            uint32_t* r = ht.sc.data() + (size_t)m.km.w_main[C_SCALARS] * ((size_t)p * (size_t)C + (size_t)ch);
             auto put = [&](uint32_t col, const Ext& e) { put_ext(r, col - cc.pre, e); };
             put(cc.ALPHA, wt.alpha); put(cc.ZETA, wt.zeta); put(cc.FA, wt.fa); put(cc.GAMMA, wt.gamma); put(cc.BETA, wt.beta);
             for (int i = 0; i < R; i++) put(cc.ZP + 4 * (uint32_t)i, zp[(size_t)i + 1]);
@@ -1381,7 +1328,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
             const Ext cst = ext_sub(ext_mul(ext_mul(phi, da), db), ext_add(ext_mul(sma, db), ext_mul(smb, da)));
             const Ext u1 = ext_add(ext_mul(acc, wt.alpha), ext_mul(va[0], ext_sub(phi, suml)));
             const Ext u2 = ext_add(ext_mul(u1, wt.alpha), ext_mul(va[2], ext_sub(ext_sub(phin, phi), sumn)));
-            const Ext cum = row.bnd ? ext_at(w + wt.o_cum + 4 * (size_t)c) : ext_zero();
+            const Ext cum = row.bnd ? ext_canon(w + wt.o_cum + 4 * (size_t)c) : ext_zero();
             const Ext acco = row.bnd ? ext_add(ext_mul(u2, wt.alpha), ext_mul(va[1], ext_sub(phi, cum))) : ext_add(ext_mul(acc, wt.alpha), cst);
             put(lc.DA, da); put(lc.DB, db); put(lc.CST, cst); put(lc.U1, u1); put(lc.U2, u2); put(lc.CUM, cum); put(lc.ACCO, acco);
             acc = acco; suml = ext_add(suml, phi); sumn = ext_add(sumn, phin);
@@ -1403,7 +1350,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
             if (s.first) { pw = ext_one(); yz = ext_zero(); yn = ext_zero(); }
             const uint32_t* words = w + wt.o_stream + 8 * i;
             for (int j = 0; j < 8; j++) r[OS_W + j] = to_monty(words[j]);
-            const Ext v0 = ext_at(words), v1 = ext_at(words + 4), mm = ext_add(v0, ext_mul(wt.fa, v1));
+            const Ext v0 = ext_canon(words), v1 = ext_canon(words + 4), mm = ext_add(v0, ext_mul(wt.fa, v1));
             put_ext(r, OS_FA, wt.fa); put_ext(r, OS_FA2, fa2); put_ext(r, OS_PW, pw); put_ext(r, OS_M, mm); put_ext(r, OS_YZIN, yz); put_ext(r, OS_YNIN, yn);
             const Ext add = ext_mul(pw, mm);
             if (is_next_kind(s.kind)) yn = ext_add(yn, add); else yz = ext_add(yz, add);
@@ -1506,7 +1453,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
     // ---- FOLD rows (host: the recursion form with what joins on the way down) and the Poseidon2 rows of the FRI layers
     {
         using namespace frichip;
-        const uint32_t FW = m.w_main[C_FOLD], INJ = width_of(R, true, true), INJF = INJ + 4;
+        const uint32_t FW = m.km.w_main[C_FOLD], INJ = width_of(R, true, true), INJF = INJ + 4;
         // (the queries are independent: a few threads per proof walk them -- one scalar permutation per Poseidon2 row is most of this function's time)
         std::vector<int> qerr((size_t)Q, 0);
         const bool x16 = p2x16_available();                 // sixteen queries walked in lockstep, one per AVX-512 lane (p2_x16.h); else one scalar permutation per row
@@ -1528,7 +1475,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
                     if (inj) { const Ext v = wt.roh[(size_t)q * 32 + (size_t)hh]; put_ext(row, INJ, v); row[INJF] = MONTY_R1; own = ext_add(own, v); }
                 }
                 const uint32_t bit = idx & 1u, k = idx >> 1;
-                const Ext sib = ext_at(w + fat), beta = wt.betas[(size_t)l];
+                const Ext sib = ext_canon(w + fat), beta = wt.betas[(size_t)l];
                 const uint32_t* path = w + fat + 4;
                 fat += 4 + 8 * (size_t)(H - 1 - l);
                 const Ext e0 = bit ? sib : own, e1 = bit ? own : sib;
@@ -1902,22 +1849,10 @@ int m_machine_verifier_setup(zkhip_ctx* ctx, const zkhip_machine_desc* inner, si
     if (!mp) return rc;
     const Machine& m = *mp;
     std::vector<uint32_t> pre[N_CHIPS];
-    all_pre(m, pre);
-    size_t total = 0;
-    for (int c = 0; c < N_CHIPS; c++) total += pre[c].size();
-    void* d;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, total * 4, &d));
-    zkhip_chip chips[N_CHIPS]{};
-    size_t at = 0;
-    for (int i = 0; i < N_CHIPS; i++) {
-        const int c = m.order[i];
-        chips[i].log_n = m.height[c]; chips[i].width = m.pre_widths[i]; chips[i].ld = m.pre_widths[i]; chips[i].partner = -1;
-        if (pre[c].empty()) continue;
-        ZK_TRY(dev_h2d(ctx, (uint32_t*)d + at, pre[c].data(), pre[c].size() * 4));
-        chips[i].d_trace = (const uint32_t*)d + at;
-        at += pre[c].size();
-    }
-    return zkhip_machine_setup(ctx, chips, N_CHIPS, outer, key, vk);
+    all_pre(m.sh, m.km, PRE, pre);
+    const uint32_t* d_pre[N_CHIPS];
+    ZK_TRY(stage_pre(ctx, m.km, pre, d_pre));
+    return keyed::key_setup(ctx, m.km, d_pre, outer, key, vk);
 }
 int m_machine_verifier_key_host(const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, uint32_t vk[8]) {
     try {
@@ -1925,16 +1860,9 @@ int m_machine_verifier_key_host(const zkhip_machine_desc* inner, size_t n_proofs
         int rc = ZKHIP_OK;
         const auto mp = machine_of(inner, n_proofs, &rc);
         if (!mp) return rc;
-        const Machine& m = *mp;
         std::vector<uint32_t> pre[N_CHIPS];
-        all_pre(m, pre);
-        const uint32_t* traces[N_CHIPS]; int32_t lns[N_CHIPS]; uint32_t pws[N_CHIPS];
-        for (int i = 0; i < N_CHIPS; i++) {
-            const int c = m.order[i];
-            lns[i] = m.height[c]; pws[i] = pre[c].empty() ? 0u : m.pre_widths[i];
-            traces[i] = pre[c].empty() ? nullptr : pre[c].data();
-        }
-        return zkhip_machine_key_host(traces, lns, pws, N_CHIPS, outer, vk);
+        all_pre(mp->sh, mp->km, PRE, pre);
+        return keyed::key_host(mp->km, pre, outer, vk);
     } catch (const std::bad_alloc&) {
         return fail(ZKHIP_ERR_NOMEM, "machine_verifier_key_host: out of host memory");
     }
@@ -1943,7 +1871,7 @@ size_t m_machine_verifier_proof_size(const zkhip_machine_desc* inner, size_t n_p
     int rc = ZKHIP_OK;
     const auto mp = machine_of(inner, n_proofs, &rc);
     if (!mp || !outer) return 0;
-    return zkhip_machine_proof_size_keyed(mp->log_ns, mp->widths, mp->pre_widths, mp->progs, mp->prog_words, mp->tabs, mp->tab_words, N_CHIPS, outer, mp->sh.npub_total());
+    return keyed::proof_size(mp->km, outer, mp->sh.npub_total());
 }
 // what the machine is made of, for tests and for a verifier that wants to look: position `which` of the ten chips (tallest first): kind 0 its program,
 // 1 its interaction table, 2 its preprocessed trace (canonical words).  Returns the word count; out may be null
@@ -1951,26 +1879,8 @@ size_t m_machine_verifier_describe(const zkhip_machine_desc* inner, size_t n_pro
                                        uint32_t* pre_width) {
     int rc = ZKHIP_OK;
     const auto mp = machine_of(inner, n_proofs, &rc);
-    if (!mp || which < 0 || which >= N_CHIPS || kind < 0 || kind > 2) return 0;
-    const Machine& m = *mp;
-    if (log_rows) *log_rows = m.log_ns[which];
-    if (main_width) *main_width = m.widths[which];
-    if (pre_width) *pre_width = m.pre_widths[which];
-    std::vector<uint32_t> pre;
-    const std::vector<uint32_t>* src = kind == 0 ? &m.prog[which] : &m.tab[which];
-    if (kind == 2) {
-        const int c = m.order[which], h = m.height[c];
-        const MShape& sh = m.sh;
-        switch (c) {
-            case C_P2R: p2r_pre(sh, h, pre); break; case C_ROWSUM: rowsum_pre(sh, h, pre); break; case C_TS: ts_pre(sh, h, pre); break; case C_QUERY: query_pre(sh, h, pre); break;
-            case C_OPENED: opened_pre(sh, h, pre); break; case C_SAMPLES: samples_pre_all(sh, h, pre); break; case C_SCALARS: scalars_pre(sh, h, pre); break;
-            case C_EVAL: eval_pre(sh, h, pre); break; case C_LOGUP: logup_pre(sh, h, pre); break; default: break;
-        }
-        for (uint32_t& v : pre) v = from_monty(v);
-        src = &pre;
-    }
-    if (out && cap >= src->size()) std::memcpy(out, src->data(), src->size() * 4);
-    return src->size();
+    if (!mp) return 0;
+    return keyed::describe(mp->km, which, kind, [&](int c, int h, std::vector<uint32_t>& pre) { if (PRE[c]) PRE[c](mp->sh, h, pre); }, out, cap, log_rows, main_width, pre_width);
 }
 
 // The top in three steps, so that a caller that makes the inner proofs itself (zkhip_prove_shard_tree: the joins of a tree) fills a proof's tables the
@@ -2002,9 +1912,9 @@ int top_begin(const zkhip_machine_desc* inner, size_t n_proofs, size_t n_public,
     ZeroedWords* tabs[N_CHIPS] = {nullptr, &ht.rs, &ht.fold, &ht.ts, &ht.q, &ht.op, &ht.sm, &ht.sc, &ht.evl, &ht.lgu};
     for (int c = 0; c < N_CHIPS; c++) {
         if (!tabs[c] || (s.device && (c == C_ROWSUM || c == C_FOLD || c == C_QUERY))) continue;       // (device mode: those three never exist on the host)
-        if (!tabs[c]->reset((size_t)m.w_main[c] << m.height[c])) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory for the machine's tables");
+        if (!tabs[c]->reset((size_t)m.km.w_main[c] << m.km.height[c])) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory for the machine's tables");
     }
-    if (!s.device) for (size_t r = 0; r < ((size_t)1 << m.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;      // (the fold chip's padding rows: T = 1)
+    if (!s.device) for (size_t r = 0; r < ((size_t)1 << m.km.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.km.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;      // (the fold chip's padding rows: T = 1)
     s.used = (size_t)sh.NP * sh.p2_rows;
     const size_t walked = s.device ? (size_t)sh.NP * (size_t)sh.NT : s.used;                          // Poseidon2 rows whose input states the host walks
     if (!ht.p2_in.reset(16 * walked) || !ht.p2_bit.reset(walked) || !ht.p2_kp.reset(walked)) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory");
@@ -2057,9 +1967,30 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
     HostTabs& ht = s.ht;
     const size_t used = s.used;
     ZeroedWords* tabs[N_CHIPS] = {nullptr, &ht.rs, &ht.fold, &ht.ts, &ht.q, &ht.op, &ht.sm, &ht.sc, &ht.evl, &ht.lgu};
-    void* dev[N_CHIPS] = {nullptr};
+    uint32_t* dev[N_CHIPS] = {nullptr};      // the main traces on the device, by chip
     const int slots[N_CHIPS] = {S_REC_A, S_REC_C, S_REC_B, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_H, S_REC_I, S_REC_J};
-    for (int c = 0; c < N_CHIPS; c++) ZK_TRY(ctx_reserve(ctx, slots[c], ((size_t)m.w_main[c] << m.height[c]) * 4, &dev[c]));
+    for (int c = 0; c < N_CHIPS; c++) ZK_TRY(ctx_reserve(ctx, slots[c], ((size_t)m.km.w_main[c] << m.km.height[c]) * 4, (void**)&dev[c]));
+    // a launch that fills the 360 columns of n rows of the Poseidon2 chip from (input state [16], direction bit, KP) per row; trows: which rows (null: in order)
+    auto p2r_args = [&](const uint32_t* in, const uint32_t* bits, const uint32_t* kps, const uint32_t* trows, size_t n, uint64_t used_rows) {
+        p2chip::P2RArgs a{};
+        a.chain_inputs = in; a.trows = trows; a.n_chains = 0; a.n_transcript = (uint32_t)n;
+        a.rows = (uint64_t)1 << m.km.height[C_P2R]; a.used_rows = used_rows; a.trace = dev[C_P2R]; a.ld = P2_MAIN; a.roots = nullptr;
+        a.row_bits = bits; a.row_kps = kps;
+        return a;
+    };
+    // the host's rows up -- input states | bits | KP | row numbers, the first trows.size() of each -- and that launch over them
+    auto p2r_upload = [&](const std::vector<uint32_t>& trows) -> int {
+        const size_t n = trows.size();
+        void* stage;
+        ZK_TRY(ctx_reserve(ctx, S_STAGE, (16 * n + 3 * n) * 4, &stage));
+        uint32_t* d = (uint32_t*)stage;
+        ZK_TRY(dev_h2d(ctx, d, ht.p2_in.data(), 16 * n * 4));
+        ZK_TRY(dev_h2d(ctx, d + 16 * n, ht.p2_bit.data(), n * 4));
+        ZK_TRY(dev_h2d(ctx, d + 17 * n, ht.p2_kp.data(), n * 4));
+        ZK_TRY(dev_h2d(ctx, d + 18 * n, trows.data(), n * 4));
+        ZK_HIP(launch_p2r_rows(p2r_args(d, d + 16 * n, d + 17 * n, d + 18 * n, n, used), ctx->stream));
+        return ZKHIP_OK;
+    };
     if (s.device) {
         // ---- the per-query tables on the device: the inner proofs' words up once, then four launches (ROWSUM + QUERY rows, the fold chains, the
         // Poseidon2 chains) fill ROWSUM, QUERY, FOLD and the queries' rows of the Poseidon2 chip in place
@@ -2114,9 +2045,9 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         ZK_HIP(hipMemcpyAsync(dprf, hp, NPs * s.proof_len, hipMemcpyHostToDevice, ctx->stream));
         ZK_HIP(hipMemcpyAsync(db, hp + NPs * s.proof_len, up_bytes, hipMemcpyHostToDevice, ctx->stream));
         ZK_HIP(hipMemsetAsync(db + up_bytes, 0, b_roh + b_pairs + b_pk + b_err, ctx->stream));
-        ZK_HIP(hipMemsetAsync(dev[C_ROWSUM], 0, ((size_t)m.w_main[C_ROWSUM] << m.height[C_ROWSUM]) * 4, ctx->stream));
-        ZK_HIP(hipMemsetAsync(dev[C_QUERY], 0, ((size_t)m.w_main[C_QUERY] << m.height[C_QUERY]) * 4, ctx->stream));
-        ZK_HIP(hipMemsetAsync(dev[C_FOLD], 0, ((size_t)m.w_main[C_FOLD] << m.height[C_FOLD]) * 4, ctx->stream));
+        ZK_HIP(hipMemsetAsync(dev[C_ROWSUM], 0, ((size_t)m.km.w_main[C_ROWSUM] << m.km.height[C_ROWSUM]) * 4, ctx->stream));
+        ZK_HIP(hipMemsetAsync(dev[C_QUERY], 0, ((size_t)m.km.w_main[C_QUERY] << m.km.height[C_QUERY]) * 4, ctx->stream));
+        ZK_HIP(hipMemsetAsync(dev[C_FOLD], 0, ((size_t)m.km.w_main[C_FOLD] << m.km.height[C_FOLD]) * 4, ctx->stream));
         WitArgs a{};
         a.proofs = (const uint32_t*)dprf; a.proof_words = pwords; a.vals = (const uint32_t*)db; a.vals_stride = vstride;
         a.v_betas = (uint32_t)Q; a.v_fa = a.v_betas + 4u * (uint32_t)R; a.v_zeta = a.v_fa + 4; a.v_h = a.v_zeta + 4; a.v_pw = a.v_h + 12u * (uint32_t)nh;
@@ -2127,7 +2058,7 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         const int32_t* d_src = (const int32_t*)(db + at);
         a.nh = (uint32_t)nh; a.nq = (uint32_t)nq; a.NP = (uint32_t)NP; a.Q = (uint32_t)Q; a.R = (uint32_t)R; a.H = (uint32_t)sh.H; a.NTREES = sh.NTREES;
         a.o_queries = (uint32_t)o_queries; a.per_query = (uint32_t)perq; a.o_final = (uint32_t)o_final; a.fri_off = pl.fri_off;
-        a.rs = (uint32_t*)dev[C_ROWSUM]; a.qt = (uint32_t*)dev[C_QUERY]; a.fold = (uint32_t*)dev[C_FOLD]; a.fw = m.w_main[C_FOLD]; a.inj_col = frichip::width_of(sh.R, true, true);
+        a.rs = (uint32_t*)dev[C_ROWSUM]; a.qt = (uint32_t*)dev[C_QUERY]; a.fold = (uint32_t*)dev[C_FOLD]; a.fw = m.km.w_main[C_FOLD]; a.inj_col = frichip::width_of(sh.R, true, true);
         a.roh = (uint32_t*)(db + up_bytes); a.pairs = (uint32_t*)(db + up_bytes + b_roh); a.pair_k = (uint32_t*)(db + up_bytes + b_roh + b_pairs);
         a.err = (uint32_t*)(db + up_bytes + b_roh + b_pairs + b_pk);
         const unsigned gq = (unsigned)((NPs * Q * nh + 63) / 64), gf = (unsigned)((NPs * Q + 63) / 64);
@@ -2135,7 +2066,7 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         hipLaunchKernelGGL(mrec_rowsum_accin_kernel, dim3(gq), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(mrec_fold_kernel, dim3(gf), dim3(64), 0, ctx->stream, a);
         {
-            const uint64_t frows = (uint64_t)1 << m.height[C_FOLD], fused = NPs * Q * R;
+            const uint64_t frows = (uint64_t)1 << m.km.height[C_FOLD], fused = NPs * Q * R;
             if (frows > fused) hipLaunchKernelGGL(mrec_fold_pad_kernel, dim3((unsigned)((frows - fused + 255) / 256)), dim3(256), 0, ctx->stream, a.fold, a.fw, fused, frows);
         }
         ZK_HIP(hipGetLastError());
@@ -2151,29 +2082,15 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         ca.trace = (uint32_t*)dev[C_P2R]; ca.ld = P2_MAIN;              // sixteen lanes per chain write the queries' rows themselves (hash.hip mrec_chains16_kernel)
         ZK_HIP(launch_mrec_chains(ca, ctx->stream));
         if (!(ca.trace && ca.ld == p2chip::R_WIDTH)) {   // the one-lane form: 360 columns each from (state, bit, KP), one lane per row; the transcripts' rows are skipped here
-            p2chip::P2RArgs qa{};
-            qa.chain_inputs = ca.row_in; qa.trows = nullptr; qa.n_chains = 0; qa.n_transcript = (uint32_t)used;
-            qa.rows = (uint64_t)1 << m.height[C_P2R]; qa.used_rows = qa.rows;      // (no padding rows from this launch)
-            qa.trace = (uint32_t*)dev[C_P2R]; qa.ld = P2_MAIN; qa.roots = nullptr; qa.row_bits = ca.row_bit; qa.row_kps = ca.row_kp;
+            p2chip::P2RArgs qa = p2r_args(ca.row_in, ca.row_bit, ca.row_kp, nullptr, used, (uint64_t)1 << m.km.height[C_P2R]);      // (no padding rows from this launch)
             qa.inputs_monty = 1; qa.seg_rows = (uint32_t)sh.p2_rows; qa.skip_first = (uint32_t)sh.NT;
             ZK_HIP(launch_p2r_rows(qa, ctx->stream));
         }
         // the transcripts' rows (walked on the host: a serial sponge chain per proof) and the padding rows
         const size_t nt = NPs * (size_t)sh.NT;
-        void* stage;
-        ZK_TRY(ctx_reserve(ctx, S_STAGE, (16 * nt + 3 * nt) * 4, &stage));
-        uint32_t* d = (uint32_t*)stage;
         std::vector<uint32_t> trows(nt);
         for (size_t p = 0; p < NPs; p++) for (size_t T = 0; T < (size_t)sh.NT; T++) trows[p * (size_t)sh.NT + T] = (uint32_t)(p * sh.p2_rows + T);
-        ZK_TRY(dev_h2d(ctx, d, ht.p2_in.data(), 16 * nt * 4));
-        ZK_TRY(dev_h2d(ctx, d + 16 * nt, ht.p2_bit.data(), nt * 4));
-        ZK_TRY(dev_h2d(ctx, d + 17 * nt, ht.p2_kp.data(), nt * 4));
-        ZK_TRY(dev_h2d(ctx, d + 18 * nt, trows.data(), nt * 4));
-        p2chip::P2RArgs pa{};
-        pa.desc = nullptr; pa.data = nullptr; pa.chain_inputs = d; pa.trows = d + 18 * nt; pa.n_chains = 0; pa.n_transcript = (uint32_t)nt;
-        pa.rows = (uint64_t)1 << m.height[C_P2R]; pa.used_rows = used; pa.trace = (uint32_t*)dev[C_P2R]; pa.ld = P2_MAIN; pa.roots = nullptr;
-        pa.row_bits = d + 16 * nt; pa.row_kps = d + 17 * nt;
-        ZK_HIP(launch_p2r_rows(pa, ctx->stream));
+        ZK_TRY(p2r_upload(trows));
         std::vector<uint32_t> errs(NPs, 0u);
         ZK_TRY(dev_d2h(ctx, errs.data(), a.err, NPs * 4));
         for (size_t p = 0; p < NPs; p++) {
@@ -2182,33 +2099,16 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
             return fail(ZKHIP_ERR_VERIFY, "prove_machine_verifier: proof " + std::to_string(p) + " rejected: " + what);
         }
     } else {   // the Poseidon2 rows: input states, bits, indices up; one launch fills the 360 columns of every row
-        const size_t words = 16 * used + 3 * used;
-        void* stage;
-        ZK_TRY(ctx_reserve(ctx, S_STAGE, words * 4, &stage));
-        uint32_t* d = (uint32_t*)stage;
         std::vector<uint32_t> trows(used);
         for (size_t r = 0; r < used; r++) trows[r] = (uint32_t)r;
-        ZK_TRY(dev_h2d(ctx, d, ht.p2_in.data(), 16 * used * 4));
-        ZK_TRY(dev_h2d(ctx, d + 16 * used, ht.p2_bit.data(), used * 4));
-        ZK_TRY(dev_h2d(ctx, d + 17 * used, ht.p2_kp.data(), used * 4));
-        ZK_TRY(dev_h2d(ctx, d + 18 * used, trows.data(), used * 4));
-        p2chip::P2RArgs a{};
-        a.desc = nullptr; a.data = nullptr; a.chain_inputs = d; a.trows = d + 18 * used; a.n_chains = 0; a.n_transcript = (uint32_t)used;
-        a.rows = (uint64_t)1 << m.height[C_P2R]; a.used_rows = used; a.trace = (uint32_t*)dev[C_P2R]; a.ld = P2_MAIN; a.roots = nullptr;
-        a.row_bits = d + 16 * used; a.row_kps = d + 17 * used;
-        ZK_HIP(launch_p2r_rows(a, ctx->stream));
+        ZK_TRY(p2r_upload(trows));
     }
     lap("device: Poseidon2 rows");
     for (int c = 0; c < N_CHIPS; c++) if (tabs[c] && tabs[c]->size()) ZK_TRY(dev_h2d(ctx, dev[c], tabs[c]->data(), tabs[c]->size() * 4));
     lap("upload: host tables");
-    zkhip_chip chips[N_CHIPS]{};
-    for (int i = 0; i < N_CHIPS; i++) {
-        const int c = m.order[i];
-        chips[i].d_trace = (const uint32_t*)dev[c]; chips[i].ld = m.w_main[c]; chips[i].log_n = m.height[c]; chips[i].width = m.w_main[c]; chips[i].partner = -1;
-    }
     std::vector<uint32_t> pv((size_t)NP * n_public);
     for (size_t i = 0; i < pv.size(); i++) pv[i] = public_values[i] % P;
-    const int prc = zkhip_prove_machine_keyed(ctx, key, chips, m.progs, m.prog_words, m.tabs, m.tab_words, N_CHIPS, pv.data(), pv.size(), outer, proof, cap, len);
+    const int prc = keyed::prove(ctx, key, m.km, dev, pv.data(), pv.size(), outer, proof, cap, len);
     lap("the machine's proof");
     return prc;
 }
@@ -2217,19 +2117,7 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
                                  const uint32_t* public_values, size_t n_public, const zkhip_params* outer, uint8_t* proof, size_t cap, size_t* len) {
     CHECK_CTX(ctx);
     if (!key || !inner || !proofs || !proof_lens || !outer || !proof || !len || (n_public && !public_values)) return fail(ZKHIP_ERR_INVALID, "prove_machine_verifier: null argument");
-#ifdef ZKHIP_AB_HOOKS
-    static const bool timing = getenv("ZKHIP_REC_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "  [machine verifier] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-#else
-    auto lap = [](const char*) {};
-#endif
+    Lap lap(ctx, "machine verifier", 34);
     TopSession s;
     ZK_TRY(top_begin(inner, n_proofs, n_public, s));
     const int NP = s.mp->sh.NP;
@@ -2245,7 +2133,7 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
 #endif
             const int r = top_fill(s, p, proofs[p], proof_lens[p], public_values + (size_t)p * n_public);
 #ifdef ZKHIP_AB_HOOKS
-            if (timing) std::fprintf(stderr, "    [machine verifier] proof %d: tables filled in %.2f ms\n", p, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv).count());
+            if (rec_timing()) std::fprintf(stderr, "    [machine verifier] proof %d: tables filled in %.2f ms\n", p, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv).count());
 #endif
             rcs[(size_t)p] = r;
             if (r != ZKHIP_OK) msgs[(size_t)p] = zkhip_last_error();
@@ -2302,14 +2190,14 @@ size_t m_machine_verifier_host_tables(const zkhip_machine_desc* inner, const uin
     const MShape& sh = m.sh;
     HostTabs ht;
     ZeroedWords* tabs[N_CHIPS] = {nullptr, &ht.rs, &ht.fold, &ht.ts, &ht.q, &ht.op, &ht.sm, &ht.sc, &ht.evl, &ht.lgu};
-    for (int c = 0; c < N_CHIPS; c++) if (tabs[c] && !tabs[c]->reset((size_t)m.w_main[c] << m.height[c])) { (void)fail(ZKHIP_ERR_NOMEM, "machine_verifier_host_tables: no host memory"); return 0; }
-    for (size_t r = 0; r < ((size_t)1 << m.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;
+    for (int c = 0; c < N_CHIPS; c++) if (tabs[c] && !tabs[c]->reset((size_t)m.km.w_main[c] << m.km.height[c])) { (void)fail(ZKHIP_ERR_NOMEM, "machine_verifier_host_tables: no host memory"); return 0; }
+    for (size_t r = 0; r < ((size_t)1 << m.km.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.km.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;
     const size_t used = (size_t)sh.NP * sh.p2_rows;
     if (!ht.p2_in.reset(16 * used) || !ht.p2_bit.reset(used) || !ht.p2_kp.reset(used)) { (void)fail(ZKHIP_ERR_NOMEM, "machine_verifier_host_tables: no host memory"); return 0; }
     try {
         for (int p = 0; p < sh.NP; p++) if (!proofs[p] || fill_proof(m, p, proofs[p], proof_lens[p], public_values + (size_t)p * n_public, ht) != ZKHIP_OK) return 0;
     } catch (const std::exception& e) { (void)fail(ZKHIP_ERR_NOMEM, std::string("machine_verifier_host_tables: ") + e.what()); return 0; }
-    const int c = m.order[which];
+    const int c = m.km.order[which];
     if (c == C_P2R) {
         const size_t n = 18 * used;
         if (out && cap >= n)
@@ -2330,7 +2218,7 @@ int m_verify_machine_recursive(const zkhip_machine_desc* inner, const uint8_t* p
     const Machine& m = *mp;
     std::vector<uint32_t> pv(n_proofs * n_public);
     for (size_t i = 0; i < pv.size(); i++) pv[i] = public_values[i] % P;
-    return zkhip_verify_machine_keyed(proof, len, m.log_ns, m.widths, m.pre_widths, vk, m.progs, m.prog_words, m.tabs, m.tab_words, N_CHIPS, pv.data(), pv.size(), outer, reason);
+    return keyed::verify(m.km, proof, len, vk, pv.data(), pv.size(), outer, reason);
 }
 
 }  // namespace mrec

@@ -30,58 +30,7 @@
 namespace zk {
 namespace rec {
 namespace {
-using frichip::Builder;
-using frichip::ALL; using frichip::FIRST; using frichip::LAST; using frichip::TRANSITION;
-
-// ---- polynomials over columns: a list of (coefficient, variables); an extension expression = four of them (x^4 = 11).  No merging of
-// like terms: the order in which terms are produced IS the program (tests/recursion_air.py produces them in the same order).
-struct PT { uint32_t c; std::vector<uint32_t> v; };
-typedef std::vector<PT> Poly;
-typedef std::array<Poly, 4> EE;
-inline uint32_t mulp(uint64_t a, uint64_t b) { return (uint32_t)((a % P) * (b % P) % P); }
-inline Poly pc(uint64_t c) { c %= P; return c ? Poly{PT{(uint32_t)c, {}}} : Poly{}; }
-inline Poly pv(uint32_t col, bool nxt = false) { return Poly{PT{1u, {nxt ? ((1u << 30) | col) : col}}}; }
-inline Poly ppub(uint32_t i) { return Poly{PT{1u, {(2u << 30) | i}}}; }
-inline Poly padd(const Poly& a, const Poly& b) { Poly o = a; o.insert(o.end(), b.begin(), b.end()); return o; }
-inline Poly pscale(const Poly& a, uint64_t k) { Poly o; for (const PT& t : a) { const uint32_t c = mulp(t.c, k); if (c) o.push_back(PT{c, t.v}); } return o; }
-inline Poly pneg(const Poly& a) { return pscale(a, P - 1); }
-inline Poly pmul(const Poly& a, const Poly& b) {
-    Poly o;
-    for (const PT& x : a) for (const PT& y : b) { const uint32_t c = mulp(x.c, y.c); if (!c) continue; PT t{c, x.v}; t.v.insert(t.v.end(), y.v.begin(), y.v.end()); o.push_back(t); }
-    return o;
-}
-inline EE ev(uint32_t col, bool nxt = false) { return EE{pv(col, nxt), pv(col + 1, nxt), pv(col + 2, nxt), pv(col + 3, nxt)}; }
-inline EE ec(uint64_t c0, uint64_t c1 = 0, uint64_t c2 = 0, uint64_t c3 = 0) { return EE{pc(c0), pc(c1), pc(c2), pc(c3)}; }
-inline EE eb(const Poly& p) { return EE{p, Poly{}, Poly{}, Poly{}}; }
-inline EE eadd(const EE& a, const EE& b) { return EE{padd(a[0], b[0]), padd(a[1], b[1]), padd(a[2], b[2]), padd(a[3], b[3])}; }
-inline EE eadd(const EE& a, const EE& b, const EE& c) { return eadd(eadd(a, b), c); }
-inline EE esub(const EE& a, const EE& b) { return EE{padd(a[0], pneg(b[0])), padd(a[1], pneg(b[1])), padd(a[2], pneg(b[2])), padd(a[3], pneg(b[3]))}; }
-inline EE escale(const EE& a, uint64_t k) { return EE{pscale(a[0], k), pscale(a[1], k), pscale(a[2], k), pscale(a[3], k)}; }
-inline EE emul(const EE& a, const EE& b) {
-    EE o;
-    for (int j = 0; j < 4; j++)
-        for (int i = 0; i < 4; i++)
-            for (int k = 0; k < 4; k++) {
-                if ((i + k) % 4 != j) continue;
-                Poly t = pmul(a[i], b[k]);
-                if (i + k >= 4) t = pscale(t, EXT_W);
-                o[j].insert(o[j].end(), t.begin(), t.end());
-            }
-    return o;
-}
-inline EE egate(const Poly& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
-struct Cons {
-    Builder b;
-    void add(uint32_t sel, const Poly& p) {
-        frichip::Terms ts;
-        for (const PT& t : p) ts.push_back(frichip::Term{t.c, t.v});
-        b.add(sel, ts);
-    }
-    void ext(uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) add(sel, e[i]); }
-    std::vector<uint32_t> program(uint32_t width, uint32_t n_public) const {
-        return b.finish(width, n_public);
-    }
-};
+using namespace airb;      // (the fold chip says so too: frichip's names stay qualified here)
 inline uint32_t rup4(uint32_t n) { return (n + 3u) & ~3u; }
 inline int lg(size_t n, int lo = 5) { int l = lo; while (((size_t)1 << l) < n) l++; return l; }
 
@@ -93,6 +42,107 @@ constexpr uint32_t BUS_K0 = 70, BUS_KFA = 77, BUS_KO0 = 78, BUS_OY = 83, BUS_OA 
 constexpr uint32_t BUS_VAL = 86, BUS_EA = 87;
 using frichip::BUS_FIN; using frichip::BUS_E0; using frichip::BUS_E1; using frichip::BUS_R0; using frichip::BUS_R1; using frichip::BUS_Q;
 using frichip::BUS_S0; using frichip::BUS_S1; using frichip::BUS_I;
+
+// ---- what this file and machine_verifier.inl (namespace mrec, which takes this one whole) say in the same words: once, as templates on the shape type (Shape
+// here, MShape there) or over the few numbers read.  What differs in content between the two machines stays two functions.
+// interaction tables: {sign, multiplicity column, bus, n, columns...}
+struct Tab : airb::Interactions {
+    void add8(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a, uint32_t b) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3, b, b + 1, b + 2, b + 3}); }
+    void add4(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3}); }
+    void add5(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t key, uint32_t a) { add(sign, mult, bus, {key, a, a + 1, a + 2, a + 3}); }
+};
+constexpr uint32_t SEND = 0, RECV = 1;
+// preprocessed traces are built canonical and turned into Montgomery form in one pass (monty_all)
+inline void monty_all(std::vector<uint32_t>& t) { for (uint32_t& v : t) v = to_monty(v); }
+inline Ext ext_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
+template <class S>
+int pub_row_index(const S& sh, int row) { for (size_t i = 0; i < sh.pub_rows.size(); i++) if (sh.pub_rows[i] == row) return (int)i; return -1; }
+// the transcript table's program over the shape's own columns (ts_cols); ts_main: its main width
+template <class S>
+std::vector<uint32_t> ts_program(const S& sh, uint32_t ts_main) {
+    const auto c = ts_cols(sh);
+    Builder k;
+    for (uint32_t j = 0; j < 8; j++) k.add(ALL, pmul(pv(c.CF + j), padd(pv(c.W + j), pneg(pv(c.CV + j)))));
+    const int npr = (int)sh.pub_rows.size();
+    for (int p = 0; p < sh.NP; p++)              // the outer proof's public values: those of proof 0, then those of proof 1, ...
+        for (int i = 0; i < sh.NPUB; i++) {
+            const int pos = sh.HL + 8 + i;
+            k.add(ALL, pmul(pv(c.IP + (uint32_t)(p * npr + pub_row_index(sh, pos / 8))), padd(pv(c.W + (uint32_t)(pos % 8)), pneg(ppub((uint32_t)(p * sh.NPUB + i))))));
+        }
+    // the trace root sits behind the header: words HL .. HL + 7 of the transcript = the rest of row HL / 8 and the start of the next one
+    const uint32_t o = (uint32_t)(sh.HL % 8);
+    for (uint32_t j = 0; j < 8 - o; j++) k.add(ALL, pmul(pv(c.IND0), padd(pv(c.W + o + j), pneg(pv(c.TR + j)))));
+    for (uint32_t j = 0; j < o; j++) k.add(TRANSITION, pmul(pv(c.IND0), padd(pv(c.W + j, true), pneg(pv(c.TR + 8 - o + j)))));
+    return k.finish(c.pre + ts_main, sh.npub_total());
+}
+// the fold chip's table in its `rec` form.  inj (the machine verifier): the column where a lower height's reduced opening is injected into the chain, sent on BUS_Q
+// with the flag and the query's index behind it
+inline std::vector<uint32_t> fold_table(int R, uint32_t inj = 0) {
+    using namespace frichip;
+    Tab t;
+    t.add(SEND, ACTIVE, BUS_E0, {LNX, K2, E0, E0 + 1, E0 + 2, E0 + 3}); t.add(SEND, ACTIVE, BUS_E1, {LNX, K2, E1, E1 + 1, E1 + 2, E1 + 3});
+    t.add(SEND, L_REC, BUS_Q, {frichip::PT, IDX, XS, OWN, OWN + 1, OWN + 2, OWN + 3});
+    if (inj) t.add(SEND, inj + 4, BUS_Q, {LNX, inj + 5, IDX, XS, inj, inj + 1, inj + 2, inj + 3});
+    t.add5(RECV, ACTIVE, BUS_BETA, LNX, BETA);
+    t.add5(SEND, L_REC + (uint32_t)R - 1u, BUS_FIN, frichip::PT, FOLD);
+    return t.w;
+}
+// the SAMPLES chip's fixed columns for several proofs: proof p's rows behind proof p - 1's; its sponge rows are numbered from ITS tags, its queries from p Q
+template <class S>
+void samples_pre_all(const S& sh, int log_rows, std::vector<uint32_t>& t) {
+    t.assign((size_t)frichip::S_PRE << log_rows, 0u);
+    std::vector<uint32_t> one;
+    for (int p = 0; p < sh.NP; p++) {
+        frichip::samples_pre(sh.R, (size_t)sh.Q, lg((size_t)sh.NS), one, (int)sh.ttag(p, sh.TP));
+        for (int r = 0; r < sh.NS; r++) {
+            uint32_t* row = one.data() + (size_t)frichip::S_PRE * (size_t)r;
+            for (uint32_t j = 0; j < 8; j++) if (row[frichip::S_ACT + j]) row[frichip::S_KQ + j] = fadd(row[frichip::S_KQ + j], to_monty((uint32_t)(p * sh.Q)));
+        }
+        std::memcpy(t.data() + (size_t)frichip::S_PRE * (size_t)p * (size_t)sh.NS, one.data(), (size_t)frichip::S_PRE * (size_t)sh.NS * 4);
+    }
+}
+// every chip's preprocessed trace by chip number: PRE[c] builds chip c's (null: the chip has none), for the chips the machine has
+template <class S, class PreFn>
+void all_pre(const S& sh, const keyed::KeyedMachine& m, const PreFn* PRE, std::vector<uint32_t>* pre) {
+    for (int c = 0; c < m.n; c++) if (PRE[c]) PRE[c](sh, m.height[c], pre[c]);
+}
+// ... staged on the device, all of them in ONE block of S_REC_A in machine order (staging: the key keeps its own copies); d_pre: by chip number, null where there is none
+inline int stage_pre(zkhip_ctx* ctx, const keyed::KeyedMachine& m, const std::vector<uint32_t>* pre, const uint32_t** d_pre) {
+    size_t total = 0, at = 0;
+    for (int c = 0; c < m.n; c++) total += pre[c].size();
+    void* d;
+    ZK_TRY(ctx_reserve(ctx, S_REC_A, total * 4, &d));
+    for (int i = 0; i < m.n; i++) {
+        const int c = m.order[i];
+        d_pre[c] = nullptr;
+        if (pre[c].empty()) continue;
+        ZK_TRY(dev_h2d(ctx, (uint32_t*)d + at, pre[c].data(), pre[c].size() * 4));
+        d_pre[c] = (const uint32_t*)d + at;
+        at += pre[c].size();
+    }
+    return ZKHIP_OK;
+}
+// ZKHIP_REC_TIMING (the A/B build only): a prover's laps -- the time since the last one with the stream drained, to stderr
+#ifdef ZKHIP_AB_HOOKS
+inline bool rec_timing() { static const bool on = getenv("ZKHIP_REC_TIMING") != nullptr; return on; }
+#endif
+struct Lap {
+#ifdef ZKHIP_AB_HOOKS
+    zkhip_ctx* ctx; const char* who; int pad;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    Lap(zkhip_ctx* ctx_, const char* who_, int pad_) : ctx(ctx_), who(who_), pad(pad_) {}
+    void operator()(const char* what) {
+        if (!rec_timing()) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "  [%s] %-*s %8.2f ms\n", who, pad, what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    }
+#else
+    Lap(zkhip_ctx*, const char*, int) {}
+    void operator()(const char*) {}
+#endif
+};
 
 // ---- the shape of an inner proof: everything the machine's structure depends on
 struct Shape {
@@ -226,8 +276,8 @@ constexpr uint32_t PP_SS = 0, PP_SPG = 1, PP_CH = 2, PP_END = 3, PP_K = 4, PP_RI
 std::vector<uint32_t> p2r_program(const Shape& sh) {
     using namespace p2chip;
     const uint32_t M0 = P2_PRE, IN_ = M0 + IN, OUT = M0 + oute(7), D_ = M0 + D, BIT_ = M0 + BIT, KP_ = M0 + R_KP;
-    Cons c;
-    c.b.body = permutation_body(M0, &c.b.count);
+    Builder c;
+    c.body = permutation_body(M0, &c.count);
     for (uint32_t j = 0; j < 8; j++) c.add(ALL, padd(padd(pv(D_ + j), pneg(pv(IN_ + j))), padd(pmul(pv(BIT_), pv(IN_ + j)), pneg(pmul(pv(BIT_), pv(IN_ + 8 + j))))));
     c.add(ALL, padd(pmul(pv(BIT_), pv(BIT_)), pneg(pv(BIT_))));
     c.add(ALL, pmul(padd(pv(PP_SS), pv(PP_SPG)), pv(BIT_)));
@@ -237,15 +287,8 @@ std::vector<uint32_t> p2r_program(const Shape& sh) {
     for (uint32_t j = 0; j < 8; j++) c.add(TRANSITION, pmul(pv(PP_K + j, true), padd(pv(IN_ + j, true), pneg(pv(OUT + j)))));
     c.add(TRANSITION, pmul(pv(PP_CH, true), padd(padd(pv(KP_), pscale(pv(KP_, true), P - 2)), pneg(pv(BIT_)))));
     c.add(ALL, pmul(pv(PP_END), padd(pv(KP_), pneg(pv(BIT_)))));
-    return c.program(P2_PRE + P2_MAIN, sh.npub_total());
+    return c.finish(P2_PRE + P2_MAIN, sh.npub_total());
 }
-// interaction tables: {sign, multiplicity column, bus, n, columns...}
-struct Tab : airb::Interactions {
-    void add8(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a, uint32_t b) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3, b, b + 1, b + 2, b + 3}); }
-    void add4(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t a) { add(sign, mult, bus, {a, a + 1, a + 2, a + 3}); }
-    void add5(uint32_t sign, uint32_t mult, uint32_t bus, uint32_t key, uint32_t a) { add(sign, mult, bus, {key, a, a + 1, a + 2, a + 3}); }
-};
-constexpr uint32_t SEND = 0, RECV = 1;
 std::vector<uint32_t> p2r_table() {
     using namespace p2chip;
     const uint32_t M0 = P2_PRE, o = M0 + oute(7), IN_ = M0 + IN, KP_ = M0 + R_KP;
@@ -258,8 +301,6 @@ std::vector<uint32_t> p2r_table() {
     t.add(RECV, PP_QIDX, BUS_QI, {PP_QN, KP_});
     return t.w;
 }
-// preprocessed traces are built canonical and turned into Montgomery form in one pass (monty_all)
-void monty_all(std::vector<uint32_t>& t) { for (uint32_t& v : t) v = to_monty(v); }
 void p2r_pre(const Shape& sh, int log_rows, std::vector<uint32_t>& t) {
     t.assign((size_t)P2_PRE << log_rows, 0u);
     for (int p = 0; p < sh.NP; p++) {
@@ -320,23 +361,6 @@ TsCols ts_cols(const Shape& sh) {
     c.W = c.pre; c.TR = c.pre + 8; c.CH = c.pre + 16;
     return c;
 }
-int pub_row_index(const Shape& sh, int row) { for (size_t i = 0; i < sh.pub_rows.size(); i++) if (sh.pub_rows[i] == row) return (int)i; return -1; }
-std::vector<uint32_t> ts_program(const Shape& sh) {
-    const TsCols c = ts_cols(sh);
-    Cons k;
-    for (uint32_t j = 0; j < 8; j++) k.add(ALL, pmul(pv(c.CF + j), padd(pv(c.W + j), pneg(pv(c.CV + j)))));
-    const int npr = (int)sh.pub_rows.size();
-    for (int p = 0; p < sh.NP; p++)              // the outer proof's public values: those of proof 0, then those of proof 1, ...
-        for (int i = 0; i < sh.NPUB; i++) {
-            const int pos = sh.HL + 8 + i;
-            k.add(ALL, pmul(pv(c.IP + (uint32_t)(p * npr + pub_row_index(sh, pos / 8))), padd(pv(c.W + (uint32_t)(pos % 8)), pneg(ppub((uint32_t)(p * sh.NPUB + i))))));
-        }
-    // the trace root sits behind the header: words HL .. HL + 7 of the transcript = the rest of row HL / 8 and the start of the next one
-    const uint32_t o = (uint32_t)(sh.HL % 8);
-    for (uint32_t j = 0; j < 8 - o; j++) k.add(ALL, pmul(pv(c.IND0), padd(pv(c.W + o + j), pneg(pv(c.TR + j)))));
-    for (uint32_t j = 0; j < o; j++) k.add(TRANSITION, pmul(pv(c.IND0), padd(pv(c.W + j, true), pneg(pv(c.TR + 8 - o + j)))));
-    return k.program(c.pre + TS_MAIN, sh.npub_total());
-}
 std::vector<uint32_t> ts_table(const Shape& sh) {
     const TsCols c = ts_cols(sh);
     Tab t;
@@ -383,18 +407,18 @@ constexpr uint32_t RS_PRE = 12, RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST
 constexpr uint32_t RS_V = 0, RS_ACCIN = 8, RS_T = 12, RS_FA = 44, RS_MAIN = 48;
 std::vector<uint32_t> rowsum_program(const Shape& sh) {
     const uint32_t M0 = RS_PRE;
-    Cons c;
+    Builder c;
     const EE fa = ev(M0 + RS_FA);
-    c.ext(TRANSITION, egate(pv(RP_NFC, true), esub(ev(M0 + RS_FA, true), fa)));
+    add_ext(c, TRANSITION, egate(pv(RP_NFC, true), esub(ev(M0 + RS_FA, true), fa)));
     EE prev = ev(M0 + RS_ACCIN);
     for (int s = 7; s >= 0; s--) {
         const EE cur = ev(M0 + RS_T + 4u * (uint32_t)s);
-        c.ext(ALL, esub(cur, eadd(emul(prev, fa), eb(pv(M0 + RS_V + (uint32_t)s)))));
+        add_ext(c, ALL, esub(cur, eadd(emul(prev, fa), eb(pv(M0 + RS_V + (uint32_t)s)))));
         prev = cur;
     }
-    c.ext(TRANSITION, egate(pv(RP_NOTFIRST, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
-    c.ext(ALL, egate(padd(pv(RP_ACT), pneg(pv(RP_NOTFIRST))), ev(M0 + RS_ACCIN)));
-    return c.program(RS_PRE + RS_MAIN, sh.npub_total());
+    add_ext(c, TRANSITION, egate(pv(RP_NOTFIRST, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
+    add_ext(c, ALL, egate(padd(pv(RP_ACT), pneg(pv(RP_NOTFIRST))), ev(M0 + RS_ACCIN)));
+    return c.finish(RS_PRE + RS_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> rowsum_table() {
     const uint32_t M0 = RS_PRE, v = M0 + RS_V, t0 = M0 + RS_T, fa = M0 + RS_FA;
@@ -444,20 +468,20 @@ constexpr QCols qcols() {
 constexpr uint32_t Q_MAIN = ((qcols().end - Q_PRE) + 3u) & ~3u;
 std::vector<uint32_t> query_program(const Shape& sh) {
     constexpr QCols m = qcols();
-    Cons c;
+    Builder c;
     const uint32_t consts[7] = {m.ZETA, m.ZNX, m.YL, m.YN, m.YQ, m.OFFN, m.OFFQ};
-    for (uint32_t col : consts) c.ext(TRANSITION, egate(pv(QP_NFC, true), esub(ev(col, true), ev(col))));
+    for (uint32_t col : consts) add_ext(c, TRANSITION, egate(pv(QP_NFC, true), esub(ev(col, true), ev(col))));
     const EE x = eb(pscale(pv(m.XQ), GEN));
-    const Poly act = pv(QP_ACT);
-    c.ext(ALL, egate(act, esub(emul(esub(x, ev(m.ZETA)), ev(m.I1)), ec(1))));
-    c.ext(ALL, egate(act, esub(emul(esub(x, ev(m.ZNX)), ev(m.I2)), ec(1))));
-    c.ext(ALL, esub(ev(m.P1), emul(esub(ev(m.AT), ev(m.YL)), ev(m.I1))));
-    c.ext(ALL, esub(ev(m.P2), emul(esub(ev(m.AT), ev(m.YN)), ev(m.I2))));
-    c.ext(ALL, esub(ev(m.P2O), emul(ev(m.OFFN), ev(m.P2))));
-    c.ext(ALL, esub(ev(m.P3), emul(esub(ev(m.AQ), ev(m.YQ)), ev(m.I1))));
-    c.ext(ALL, esub(ev(m.P3O), emul(ev(m.OFFQ), ev(m.P3))));
-    c.ext(ALL, esub(ev(m.RO), eadd(ev(m.P1), ev(m.P2O), ev(m.P3O))));
-    return c.program(Q_PRE + Q_MAIN, sh.npub_total());
+    const Terms act = pv(QP_ACT);
+    add_ext(c, ALL, egate(act, esub(emul(esub(x, ev(m.ZETA)), ev(m.I1)), ec(1))));
+    add_ext(c, ALL, egate(act, esub(emul(esub(x, ev(m.ZNX)), ev(m.I2)), ec(1))));
+    add_ext(c, ALL, esub(ev(m.P1), emul(esub(ev(m.AT), ev(m.YL)), ev(m.I1))));
+    add_ext(c, ALL, esub(ev(m.P2), emul(esub(ev(m.AT), ev(m.YN)), ev(m.I2))));
+    add_ext(c, ALL, esub(ev(m.P2O), emul(ev(m.OFFN), ev(m.P2))));
+    add_ext(c, ALL, esub(ev(m.P3), emul(esub(ev(m.AQ), ev(m.YQ)), ev(m.I1))));
+    add_ext(c, ALL, esub(ev(m.P3O), emul(ev(m.OFFQ), ev(m.P3))));
+    add_ext(c, ALL, esub(ev(m.RO), eadd(ev(m.P1), ev(m.P2O), ev(m.P3O))));
+    return c.finish(Q_PRE + Q_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> query_table() {
     constexpr QCols m = qcols();
@@ -491,38 +515,38 @@ constexpr uint32_t OP_MAIN = 4u * O_COUNT;
 constexpr uint32_t OP_PRE_AIR = 28, OP_KEY0 = 12, OP_MUL0 = 20;
 inline uint32_t op_pre(const Shape& sh) { return sh.air ? OP_PRE_AIR : OP_PRE; }
 std::vector<uint32_t> opened_program(const Shape& sh) {
-    Cons c;
+    Builder c;
     const uint32_t B0 = op_pre(sh);
     auto e = [&](uint32_t name, bool nxt = false) { return ev(B0 + 4u * name, nxt); };
     const uint32_t consts[5] = {O_FA, O_FA4, O_ALPHA, O_SELT, O_SELF};
-    const Poly first = pv(OP_FIRST), nf = pv(OP_NOTFIRST, true);
-    for (uint32_t nm : consts) c.ext(TRANSITION, egate(nf, esub(e(nm, true), e(nm))));
-    c.ext(ALL, egate(first, esub(e(O_PW), ec(1))));
-    c.ext(ALL, esub(e(O_PWN), emul(e(O_PW), e(O_FA4))));
-    c.ext(TRANSITION, egate(nf, esub(e(O_PW, true), e(O_PWN))));
+    const Terms first = pv(OP_FIRST), nf = pv(OP_NOTFIRST, true);
+    for (uint32_t nm : consts) add_ext(c, TRANSITION, egate(nf, esub(e(nm, true), e(nm))));
+    add_ext(c, ALL, egate(first, esub(e(O_PW), ec(1))));
+    add_ext(c, ALL, esub(e(O_PWN), emul(e(O_PW), e(O_FA4))));
+    add_ext(c, TRANSITION, egate(nf, esub(e(O_PW, true), e(O_PWN))));
     const EE fa = e(O_FA);
     const uint32_t sets[2][7] = {{O_H2, O_H1, O_IL, O_A, O_B, O_C, O_D}, {O_G2, O_G1, O_INX, O_AN, O_BN, O_CN, O_DN}};
     for (const auto& s : sets) {
-        c.ext(ALL, esub(e(s[0]), eadd(e(s[5]), emul(fa, e(s[6])))));
-        c.ext(ALL, esub(e(s[1]), eadd(e(s[4]), emul(fa, e(s[0])))));
-        c.ext(ALL, esub(e(s[2]), eadd(e(s[3]), emul(fa, e(s[1])))));
+        add_ext(c, ALL, esub(e(s[0]), eadd(e(s[5]), emul(fa, e(s[6])))));
+        add_ext(c, ALL, esub(e(s[1]), eadd(e(s[4]), emul(fa, e(s[0])))));
+        add_ext(c, ALL, esub(e(s[2]), eadd(e(s[3]), emul(fa, e(s[1])))));
     }
     const uint32_t ys[2][3] = {{O_YLIN, O_YLO, O_IL}, {O_YNIN, O_YNO, O_INX}};
     for (const auto& y : ys) {
-        c.ext(ALL, egate(first, e(y[0])));
-        c.ext(ALL, esub(e(y[1]), eadd(e(y[0]), emul(e(O_PW), e(y[2])))));
-        c.ext(TRANSITION, egate(nf, esub(e(y[0], true), e(y[1]))));
+        add_ext(c, ALL, egate(first, e(y[0])));
+        add_ext(c, ALL, esub(e(y[1]), eadd(e(y[0]), emul(e(O_PW), e(y[2])))));
+        add_ext(c, TRANSITION, egate(nf, esub(e(y[0], true), e(y[1]))));
     }
-    if (sh.air) return c.program(B0 + OP_MAIN, sh.npub_total());       // (the AIR's fold is the EVAL chip's: the columns behind O_YNO stay zero)
-    c.ext(ALL, esub(e(O_A2), emul(e(O_A), e(O_A))));
-    c.ext(ALL, esub(e(O_AB), emul(e(O_A), e(O_B))));
+    if (sh.air) return c.finish(B0 + OP_MAIN, sh.npub_total());       // (the AIR's fold is the EVAL chip's: the columns behind O_YNO stay zero)
+    add_ext(c, ALL, esub(e(O_A2), emul(e(O_A), e(O_A))));
+    add_ext(c, ALL, esub(e(O_AB), emul(e(O_A), e(O_B))));
     const EE al = e(O_ALPHA);
-    c.ext(ALL, egate(first, e(O_ACCIN)));
-    c.ext(ALL, esub(e(O_U1), eadd(emul(e(O_ACCIN), al), esub(esub(e(O_C), emul(e(O_A2), e(O_B))), eb(pv(OP_K1))))));
-    c.ext(ALL, esub(e(O_U2), eadd(emul(e(O_U1), al), emul(e(O_SELT), esub(esub(esub(e(O_DN), e(O_AB)), e(O_C)), eb(pv(OP_K2)))))));
-    c.ext(ALL, esub(e(O_ACCO), eadd(emul(e(O_U2), al), emul(e(O_SELF), esub(e(O_D), eb(pv(OP_K3)))))));
-    c.ext(TRANSITION, egate(nf, esub(e(O_ACCIN, true), e(O_ACCO))));
-    return c.program(OP_PRE + OP_MAIN, sh.npub_total());
+    add_ext(c, ALL, egate(first, e(O_ACCIN)));
+    add_ext(c, ALL, esub(e(O_U1), eadd(emul(e(O_ACCIN), al), esub(esub(e(O_C), emul(e(O_A2), e(O_B))), eb(pv(OP_K1))))));
+    add_ext(c, ALL, esub(e(O_U2), eadd(emul(e(O_U1), al), emul(e(O_SELT), esub(esub(esub(e(O_DN), e(O_AB)), e(O_C)), eb(pv(OP_K2)))))));
+    add_ext(c, ALL, esub(e(O_ACCO), eadd(emul(e(O_U2), al), emul(e(O_SELF), esub(e(O_D), eb(pv(OP_K3)))))));
+    add_ext(c, TRANSITION, egate(nf, esub(e(O_ACCIN, true), e(O_ACCO))));
+    return c.finish(OP_PRE + OP_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> opened_table(const Shape& sh) {
     Tab t;
@@ -608,23 +632,23 @@ void zps_consts(const Shape& sh, uint32_t a[2], uint32_t b[2]) {
 }
 std::vector<uint32_t> scalars_program(const Shape& sh) {
     const ScCols m = sc_cols(sh);
-    Cons c;
+    Builder c;
     EE prev = ev(m.ZETA);
-    for (int i = 1; i <= sh.n; i++) { c.ext(ALL, esub(ev(m.zp(i)), emul(prev, prev))); prev = ev(m.zp(i)); }
+    for (int i = 1; i <= sh.n; i++) { add_ext(c, ALL, esub(ev(m.zp(i)), emul(prev, prev))); prev = ev(m.zp(i)); }
     const EE znn = prev;
     const uint32_t wn = from_monty(two_adic_generator(sh.n)), wni = from_monty(finv(two_adic_generator(sh.n)));
-    c.ext(ALL, esub(emul(esub(ev(m.ZETA), ec(1)), ev(m.INVF)), ec(1)));
-    c.ext(ALL, esub(ev(m.SELF), emul(esub(znn, ec(1)), ev(m.INVF))));
-    c.ext(ALL, esub(ev(m.SELT), esub(ev(m.ZETA), ec(wni))));
-    c.ext(ALL, esub(ev(m.ZNX), escale(ev(m.ZETA), wn)));
+    add_ext(c, ALL, esub(emul(esub(ev(m.ZETA), ec(1)), ev(m.INVF)), ec(1)));
+    add_ext(c, ALL, esub(ev(m.SELF), emul(esub(znn, ec(1)), ev(m.INVF))));
+    add_ext(c, ALL, esub(ev(m.SELT), esub(ev(m.ZETA), ec(wni))));
+    add_ext(c, ALL, esub(ev(m.ZNX), escale(ev(m.ZETA), wn)));
     prev = ev(m.FA);
-    for (int i = 1; i <= m.mb; i++) { c.ext(ALL, esub(ev(m.fp(i)), emul(prev, prev))); prev = ev(m.fp(i)); }
+    for (int i = 1; i <= m.mb; i++) { add_ext(c, ALL, esub(ev(m.fp(i)), emul(prev, prev))); prev = ev(m.fp(i)); }
     EE acc = ev(m.fp(m.bits[0]));
-    for (int k = 1; k < m.nbits; k++) { c.ext(ALL, esub(ev(m.pr(k)), emul(acc, ev(m.fp(m.bits[k]))))); acc = ev(m.pr(k)); }
-    c.ext(ALL, esub(ev(m.OFFN), acc));
-    c.ext(ALL, esub(ev(m.OFFQ), emul(ev(m.OFFN), ev(m.OFFN))));
+    for (int k = 1; k < m.nbits; k++) { add_ext(c, ALL, esub(ev(m.pr(k)), emul(acc, ev(m.fp(m.bits[k]))))); acc = ev(m.pr(k)); }
+    add_ext(c, ALL, esub(ev(m.OFFN), acc));
+    add_ext(c, ALL, esub(ev(m.OFFQ), emul(ev(m.OFFN), ev(m.OFFN))));
     prev = ev(m.qz(7));
-    for (int j = 6; j >= 0; j--) { c.ext(ALL, esub(ev(m.hq(j)), eadd(ev(m.qz(j)), emul(ev(m.FA), prev)))); prev = ev(m.hq(j)); }
+    for (int j = 6; j >= 0; j--) { add_ext(c, ALL, esub(ev(m.hq(j)), eadd(ev(m.qz(j)), emul(ev(m.FA), prev)))); prev = ev(m.hq(j)); }
     for (int k = 0; k < 2; k++) {
         EE q = ec(0);
         for (int t = 0; t < 4; t++) {
@@ -632,18 +656,18 @@ std::vector<uint32_t> scalars_program(const Shape& sh) {
             basis[t] = 1;
             q = eadd(q, emul(ec(basis[0], basis[1], basis[2], basis[3]), ev(m.qz(4 * k + t))));
         }
-        c.ext(ALL, esub(ev(k ? m.QK1 : m.QK0), q));
+        add_ext(c, ALL, esub(ev(k ? m.QK1 : m.QK0), q));
     }
     uint32_t za[2], zb[2];
     zps_consts(sh, za, zb);
     const EE z0 = eadd(escale(znn, za[0]), ec(zb[0])), z1 = eadd(escale(znn, za[1]), ec(zb[1]));
-    c.ext(ALL, esub(ev(m.QUO), eadd(emul(z0, ev(m.QK0)), emul(z1, ev(m.QK1)))));
-    c.ext(ALL, esub(ev(m.ACC), emul(ev(m.QUO), esub(znn, ec(1)))));
+    add_ext(c, ALL, esub(ev(m.QUO), eadd(emul(z0, ev(m.QK0)), emul(z1, ev(m.QK1)))));
+    add_ext(c, ALL, esub(ev(m.ACC), emul(ev(m.QUO), esub(znn, ec(1)))));
     if (sh.air) {
-        c.ext(ALL, esub(emul(ev(m.SELT), ev(m.INVT)), ec(1)));
-        c.ext(ALL, esub(ev(m.SELL), emul(esub(znn, ec(1)), ev(m.INVT))));
+        add_ext(c, ALL, esub(emul(ev(m.SELT), ev(m.INVT)), ec(1)));
+        add_ext(c, ALL, esub(ev(m.SELL), emul(esub(znn, ec(1)), ev(m.INVT))));
     }
-    return c.program(sc_pre(sh) + rup4(m.end - sc_pre(sh)), sh.npub_total());
+    return c.finish(sc_pre(sh) + rup4(m.end - sc_pre(sh)), sh.npub_total());
 }
 std::vector<uint32_t> scalars_table(const Shape& sh) {
     const ScCols m = sc_cols(sh);
@@ -689,16 +713,16 @@ constexpr uint32_t EV_PRE = 12, EP_COEF = 0, EP_K0 = 1, EP_FIRSTC = 4, EP_ACT = 
 constexpr uint32_t EV_F0 = 0, EV_M = 12, EV_TV = 16, EV_ACCIN = 20, EV_ACCO = 24, EV_ALPHA = 28, EV_MAIN = 32;
 std::vector<uint32_t> eval_program(const Shape& sh) {
     const uint32_t M0 = EV_PRE;
-    Cons c;
+    Builder c;
     const EE f0 = ev(M0 + EV_F0), f1 = ev(M0 + EV_F0 + 4), f2 = ev(M0 + EV_F0 + 8), mm = ev(M0 + EV_M), tv = ev(M0 + EV_TV), ai = ev(M0 + EV_ACCIN), ao = ev(M0 + EV_ACCO), al = ev(M0 + EV_ALPHA);
-    c.ext(ALL, esub(mm, emul(f0, f1)));
-    c.ext(ALL, esub(tv, egate(pv(EP_COEF), emul(mm, f2))));
+    add_ext(c, ALL, esub(mm, emul(f0, f1)));
+    add_ext(c, ALL, esub(tv, egate(pv(EP_COEF), emul(mm, f2))));
     // ACCO = ACCIN (1 + FIRSTC (alpha - 1)) + TV
-    c.ext(ALL, esub(ao, eadd(ai, egate(pv(EP_FIRSTC), esub(emul(ai, al), ai)), tv)));
-    c.ext(TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ACCIN, true), ao)));
-    c.ext(ALL, egate(pv(EP_PFIRST), ai));
-    c.ext(TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ALPHA, true), al)));
-    return c.program(EV_PRE + EV_MAIN, sh.npub_total());
+    add_ext(c, ALL, esub(ao, eadd(ai, egate(pv(EP_FIRSTC), esub(emul(ai, al), ai)), tv)));
+    add_ext(c, TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ACCIN, true), ao)));
+    add_ext(c, ALL, egate(pv(EP_PFIRST), ai));
+    add_ext(c, TRANSITION, egate(pv(EP_NFC, true), esub(ev(M0 + EV_ALPHA, true), al)));
+    return c.finish(EV_PRE + EV_MAIN, sh.npub_total());
 }
 std::vector<uint32_t> eval_table() {
     const uint32_t M0 = EV_PRE;
@@ -725,26 +749,7 @@ void eval_pre(const Shape& sh, int log_rows, std::vector<uint32_t>& t) {
 
 // ============================================================================================================ the machine
 enum Chip : int { C_P2R, C_ROWSUM, C_FOLD, C_TS, C_QUERY, C_OPENED, C_SAMPLES, C_SCALARS, C_EVAL, N_CHIPS };      // (C_EVAL: air mode only)
-struct Machine {
-    Shape sh;
-    int n = N_CHIPS - 1;                        // chips of this machine: eight, nine in air mode
-    int order[N_CHIPS];                         // position -> chip, tallest first (equal heights in the order of the enum)
-    int32_t log_ns[N_CHIPS]; uint32_t widths[N_CHIPS], pre_widths[N_CHIPS];
-    std::vector<uint32_t> prog[N_CHIPS], tab[N_CHIPS];     // by position
-    const uint32_t* progs[N_CHIPS]; size_t prog_words[N_CHIPS]; const uint32_t* tabs[N_CHIPS]; size_t tab_words[N_CHIPS];
-    int height[N_CHIPS];                        // by chip
-    int pos_of(int chip) const { for (int i = 0; i < n; i++) if (order[i] == chip) return i; return -1; }
-};
-std::vector<uint32_t> samples_table_words() { return frichip::samples_interactions(); }
-std::vector<uint32_t> fold_table(const Shape& sh) {
-    using namespace frichip;
-    Tab t;
-    t.add(SEND, ACTIVE, BUS_E0, {LNX, K2, E0, E0 + 1, E0 + 2, E0 + 3}); t.add(SEND, ACTIVE, BUS_E1, {LNX, K2, E1, E1 + 1, E1 + 2, E1 + 3});
-    t.add(SEND, L_REC, BUS_Q, {frichip::PT, IDX, XS, OWN, OWN + 1, OWN + 2, OWN + 3});
-    t.add5(RECV, ACTIVE, BUS_BETA, LNX, BETA);
-    t.add5(SEND, L_REC + (uint32_t)sh.R - 1u, BUS_FIN, frichip::PT, FOLD);
-    return t.w;
-}
+struct Machine { Shape sh; keyed::KeyedMachine km; };       // (eight chips, nine in air mode: km.n)
 // the machine of a shape: programs, tables, heights.  Built once per (shape, Poseidon2 tables) and kept.
 std::shared_ptr<const Machine> machine_of(const Shape& sh) {
     static std::mutex mu;
@@ -757,56 +762,33 @@ std::shared_ptr<const Machine> machine_of(const Shape& sh) {
     auto m = std::make_shared<Machine>();
     m->sh = sh;
     const size_t np = (size_t)sh.NP;
-    m->n = sh.air ? N_CHIPS : N_CHIPS - 1;
     const int h[N_CHIPS] = {lg(np * sh.p2_rows), lg(np * (size_t)sh.Q * (size_t)(sh.WB + 1)), lg(np * (size_t)sh.Q * (size_t)sh.R), lg(np * (size_t)sh.NTS), lg(np * (size_t)sh.Q),
                             lg(np * (size_t)sh.G), lg(np * (size_t)sh.NS), lg(np), lg(np * (sh.air ? sh.terms.size() : (size_t)1))};
-    for (int c = 0; c < N_CHIPS; c++) { m->height[c] = h[c]; m->order[c] = c; }
-    std::stable_sort(m->order, m->order + m->n, [&](int a, int b) { return h[a] > h[b]; });
     const ScCols scc = sc_cols(sh);
     const TsCols tsc = ts_cols(sh);
     const uint32_t w_main[N_CHIPS] = {P2_MAIN, RS_MAIN, frichip::width_of(sh.R, true, true), TS_MAIN, Q_MAIN, OP_MAIN, frichip::S_MAIN, rup4(scc.end - sc_pre(sh)), EV_MAIN};
     const uint32_t w_pre[N_CHIPS] = {P2_PRE, RS_PRE, 0u, tsc.pre, Q_PRE, op_pre(sh), frichip::S_PRE, sc_pre(sh), EV_PRE};
-    for (int i = 0; i < m->n; i++) {
-        const int c = m->order[i];
+    keyed::build(m->km, sh.air ? N_CHIPS : N_CHIPS - 1, h, w_main, w_pre, [&](int c, std::vector<uint32_t>& prog, std::vector<uint32_t>& tab) {
         switch (c) {
-            case C_P2R: m->prog[i] = p2r_program(sh); m->tab[i] = p2r_table(); break;
-            case C_ROWSUM: m->prog[i] = rowsum_program(sh); m->tab[i] = rowsum_table(); break;
-            case C_FOLD: m->prog[i] = *frichip::program(sh.R, true, true, (int)sh.npub_total()); m->tab[i] = fold_table(sh); break;
-            case C_TS: m->prog[i] = ts_program(sh); m->tab[i] = ts_table(sh); break;
-            case C_QUERY: m->prog[i] = query_program(sh); m->tab[i] = query_table(); break;
-            case C_OPENED: m->prog[i] = opened_program(sh); m->tab[i] = opened_table(sh); break;
-            case C_EVAL: m->prog[i] = eval_program(sh); m->tab[i] = eval_table(); break;
-            case C_SAMPLES: m->prog[i] = *frichip::samples_program(sh.R, sh.PB, sh.npub_total()); m->tab[i] = samples_table_words(); break;
-            default: m->prog[i] = scalars_program(sh); m->tab[i] = scalars_table(sh); break;
+            case C_P2R: prog = p2r_program(sh); tab = p2r_table(); break;
+            case C_ROWSUM: prog = rowsum_program(sh); tab = rowsum_table(); break;
+            case C_FOLD: prog = *frichip::program(sh.R, true, true, (int)sh.npub_total()); tab = fold_table(sh.R); break;
+            case C_TS: prog = ts_program(sh, TS_MAIN); tab = ts_table(sh); break;
+            case C_QUERY: prog = query_program(sh); tab = query_table(); break;
+            case C_OPENED: prog = opened_program(sh); tab = opened_table(sh); break;
+            case C_EVAL: prog = eval_program(sh); tab = eval_table(); break;
+            case C_SAMPLES: prog = *frichip::samples_program(sh.R, sh.PB, sh.npub_total()); tab = frichip::samples_interactions(); break;
+            default: prog = scalars_program(sh); tab = scalars_table(sh); break;
         }
-        m->log_ns[i] = h[c]; m->widths[i] = w_main[c]; m->pre_widths[i] = w_pre[c];
-    }
-    for (int i = 0; i < m->n; i++) { m->progs[i] = m->prog[i].data(); m->prog_words[i] = m->prog[i].size(); m->tabs[i] = m->tab[i].data(); m->tab_words[i] = m->tab[i].size(); }
+    });
     if (cache.size() > 16) cache.clear();
     cache.emplace(key, m);
     return m;
 }
 
-// the SAMPLES chip's fixed columns for several proofs: proof p's rows behind proof p - 1's; its sponge rows are numbered from ITS tags, its queries from p Q
-void samples_pre_all(const Shape& sh, int log_rows, std::vector<uint32_t>& t) {
-    t.assign((size_t)frichip::S_PRE << log_rows, 0u);
-    std::vector<uint32_t> one;
-    for (int p = 0; p < sh.NP; p++) {
-        frichip::samples_pre(sh.R, (size_t)sh.Q, lg((size_t)sh.NS), one, (int)sh.ttag(p, sh.TP));
-        for (int r = 0; r < sh.NS; r++) {
-            uint32_t* row = one.data() + (size_t)frichip::S_PRE * (size_t)r;
-            for (uint32_t j = 0; j < 8; j++) if (row[frichip::S_ACT + j]) row[frichip::S_KQ + j] = fadd(row[frichip::S_KQ + j], to_monty((uint32_t)(p * sh.Q)));
-        }
-        std::memcpy(t.data() + (size_t)frichip::S_PRE * (size_t)p * (size_t)sh.NS, one.data(), (size_t)frichip::S_PRE * (size_t)sh.NS * 4);
-    }
-}
-// every chip's preprocessed trace, by chip
-void all_pre(const Shape& sh, const Machine& m, std::vector<uint32_t> pre[N_CHIPS]) {
-    p2r_pre(sh, m.height[C_P2R], pre[C_P2R]); rowsum_pre(sh, m.height[C_ROWSUM], pre[C_ROWSUM]); ts_pre(sh, m.height[C_TS], pre[C_TS]);
-    query_pre(sh, m.height[C_QUERY], pre[C_QUERY]); opened_pre(sh, m.height[C_OPENED], pre[C_OPENED]); scalars_pre(sh, m.height[C_SCALARS], pre[C_SCALARS]);
-    samples_pre_all(sh, m.height[C_SAMPLES], pre[C_SAMPLES]);
-    if (sh.air) eval_pre(sh, m.height[C_EVAL], pre[C_EVAL]);
-}
+// every chip's preprocessed-trace builder, by chip (the fold chip has no preprocessed columns)
+typedef void (*PreFn)(const Shape&, int, std::vector<uint32_t>&);
+const PreFn PRE[N_CHIPS] = {p2r_pre, rowsum_pre, nullptr, ts_pre, query_pre, opened_pre, samples_pre_all<Shape>, scalars_pre, eval_pre};
 // ---- the witness: everything the main columns hold, read off the inner proof (which the host verifier has accepted)
 struct Witness {
     const uint32_t* w = nullptr;                // the proof's words (canonical)
@@ -815,7 +797,6 @@ struct Witness {
     uint32_t fin[4], tr[10];
     size_t q_trow(int q) const { return o_queries + (size_t)q * per_query; }
 };
-inline Ext ext_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
 inline void put_ext(uint32_t* row, uint32_t col, const Ext& e) { for (int i = 0; i < 4; i++) row[col + i] = e.c[i]; }
 
 }  // namespace
@@ -1083,7 +1064,7 @@ int fill_one(const Shape& sh, const Machine& m, int p, const uint8_t* inner, siz
     scput(scc.QUO, quo);
     sec("scalars");
     // (d) OPENED: the opened values, their fa-weighted sums, the AIR folded with alpha.  The rows behind the last proof carry ITS constants.
-    const size_t op_rows = (size_t)1 << m.height[C_OPENED];
+    const size_t op_rows = (size_t)1 << m.km.height[C_OPENED];
     const size_t op_lo = (size_t)p * (size_t)sh.G, op_hi = p + 1 == sh.NP ? op_rows : op_lo + (size_t)sh.G;
     Ext yl = ext_zero(), yn = ext_zero(), acc = ext_zero(), pwr = ext_one(), res_yl = yl, res_yn = yn, res_acc = acc;
     for (size_t row = op_lo; row < op_hi; row++) {
@@ -1161,7 +1142,7 @@ int fill_one(const Shape& sh, const Machine& m, int p, const uint8_t* inner, siz
     // (e) ROWSUM
     std::vector<Ext> at((size_t)Q), aq((size_t)Q);
     if (!on_device) {
-        const size_t rs_rows = (size_t)1 << m.height[C_ROWSUM], per = (size_t)Q * (size_t)(sh.WB + 1);
+        const size_t rs_rows = (size_t)1 << m.km.height[C_ROWSUM], per = (size_t)Q * (size_t)(sh.WB + 1);
         const size_t lo = (size_t)p * per, hi = p + 1 == sh.NP ? rs_rows : lo + per;
         Ext a = ext_zero();
         for (size_t r = lo; r < hi; r++) {
@@ -1186,7 +1167,7 @@ int fill_one(const Shape& sh, const Machine& m, int p, const uint8_t* inner, siz
     // (f) QUERY
     if (!on_device) {
         constexpr QCols qc = qcols();
-        const size_t q_rows = (size_t)1 << m.height[C_QUERY], lo = (size_t)p * (size_t)Q, hi = p + 1 == sh.NP ? q_rows : lo + (size_t)Q;
+        const size_t q_rows = (size_t)1 << m.km.height[C_QUERY], lo = (size_t)p * (size_t)Q, hi = p + 1 == sh.NP ? q_rows : lo + (size_t)Q;
         for (size_t rr = lo; rr < hi; rr++) {
             uint32_t* row = ht.q.data() + (size_t)Q_MAIN * rr;
             auto put = [&](uint32_t col, const Ext& e) { put_ext(row, col - Q_PRE, e); };
@@ -1436,19 +1417,7 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
     if (inner_prm->log_blowup != 1 || inner_prm->logup_pairs != 0 || inner_prm->log_fold > 1 || inner_prm->log_final != 0 || (inner_prm->hash_width != 0 && inner_prm->hash_width != 16) ||
         inner_prm->code_width != 0)
         return fail(ZKHIP_ERR_INVALID, "prove_shard_verifier: version-1 shard proofs (SP1 shape: blowup 2, fold by 2, constant final value, no lookups)");
-#ifdef ZKHIP_AB_HOOKS
-    static const bool timing = getenv("ZKHIP_REC_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "  [shard verifier] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-#else
-    auto lap = [](const char*) {};
-#endif
+    Lap lap(ctx, "shard verifier", 28);
     Shape sh;
     ZK_TRY(make_shape(log_n, width, (size_t)inner_prm->num_queries, inner_prm->pow_bits, n_public, n_proofs, sh, program, program_words));
     ZK_TRY(check_outer(sh, outer));
@@ -1457,16 +1426,16 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
     const int R = sh.R, Q = sh.Q, NP = sh.NP;
     const ScCols scc = sc_cols(sh);
     const uint32_t sc_w = rup4(scc.end - sc_pre(sh));
-    const uint32_t w_main[N_CHIPS] = {P2_MAIN, RS_MAIN, frichip::width_of(R, true, true), TS_MAIN, Q_MAIN, OP_MAIN, frichip::S_MAIN, sc_w, EV_MAIN};
+    const uint32_t* const w_main = m.km.w_main;
     lap("shape + machine");
     // round 6: ROWSUM, QUERY, the fold chains and the layers' pairs are the device's (sv_rowsum_query_kernel, sv_pairs_kernel); ZKHIP_REC_HOST=1 (and a call
     // from inside a lock-step batch, whose launches are merged) keeps the host's walk
     const bool host_forced = witnesses_on_host();
     const bool on_device = !host_forced && !t_batcher;
     HostTables ht;
-    if (!ht.sc.reset((size_t)sc_w << m.height[C_SCALARS]) || !ht.op.reset((size_t)OP_MAIN << m.height[C_OPENED]) || (!on_device && !ht.rs.reset((size_t)RS_MAIN << m.height[C_ROWSUM])) ||
-        (!on_device && !ht.q.reset((size_t)Q_MAIN << m.height[C_QUERY])) || !ht.ts.reset((size_t)TS_MAIN << m.height[C_TS]) || !ht.sm.reset((size_t)frichip::S_MAIN << m.height[C_SAMPLES]) ||
-        (sh.air && !ht.evl.reset((size_t)EV_MAIN << m.height[C_EVAL])))
+    if (!ht.sc.reset((size_t)sc_w << m.km.height[C_SCALARS]) || !ht.op.reset((size_t)OP_MAIN << m.km.height[C_OPENED]) || (!on_device && !ht.rs.reset((size_t)RS_MAIN << m.km.height[C_ROWSUM])) ||
+        (!on_device && !ht.q.reset((size_t)Q_MAIN << m.km.height[C_QUERY])) || !ht.ts.reset((size_t)TS_MAIN << m.km.height[C_TS]) || !ht.sm.reset((size_t)frichip::S_MAIN << m.km.height[C_SAMPLES]) ||
+        (sh.air && !ht.evl.reset((size_t)EV_MAIN << m.km.height[C_EVAL])))
         return fail(ZKHIP_ERR_NOMEM, "prove_shard_verifier: no host memory for the machine's tables");
     std::vector<Witness> wts((size_t)NP);
     std::vector<std::vector<uint32_t>> words((size_t)NP);
@@ -1526,11 +1495,11 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
         for (int p = 0; p < NP; p++) if (rcs[(size_t)p] != ZKHIP_OK) { set_error("proof " + std::to_string(p) + ": " + msgs[(size_t)p]); return rcs[(size_t)p]; }
     }
     lap("host: witnesses + tables");
-    for (size_t r = (size_t)NP; r < ((size_t)1 << m.height[C_SCALARS]); r++) std::memcpy(ht.sc.data() + sc_w * r, ht.sc.data(), sc_w * 4);     // rows behind the proofs repeat row 0
+    for (size_t r = (size_t)NP; r < ((size_t)1 << m.km.height[C_SCALARS]); r++) std::memcpy(ht.sc.data() + sc_w * r, ht.sc.data(), sc_w * 4);     // rows behind the proofs repeat row 0
     // device: the fold rows proof by proof (the last call fills the padding), then ONE launch for every Poseidon2 row
-    void* dev[N_CHIPS] = {nullptr};
+    uint32_t* dev[N_CHIPS] = {nullptr};      // the main traces on the device, by chip
     const int slots[N_CHIPS] = {S_REC_A, S_REC_C, S_REC_B, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_H, S_REC_I};
-    for (int c = 0; c < m.n; c++) ZK_TRY(ctx_reserve(ctx, slots[c], ((size_t)w_main[c] << m.height[c]) * 4, &dev[c]));
+    for (int c = 0; c < m.km.n; c++) ZK_TRY(ctx_reserve(ctx, slots[c], ((size_t)w_main[c] << m.km.height[c]) * 4, (void**)&dev[c]));
     if (on_device) {
         // ---- lists, words and values up in ONE DMA; the per-query rows, the fold rows, the pairs and every Poseidon2 row on the device
         const size_t nq = (size_t)NP * (size_t)Q, vw = sv_vals_words(sh), n_chains = ht.desc.size() / 6;
@@ -1541,26 +1510,26 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
         ZK_TRY(ctx_reserve(ctx, S_WIT_B, (n_fb + n_fi + n_fv + n_fs + n_fv) * 4, &scratch));
         uint32_t* d = (uint32_t*)stage;
         ZK_HIP(hipMemcpyAsync(d, ht.desc.data(), up_words * 4, hipMemcpyHostToDevice, ctx->stream));       // desc | data | chain_in | trows | vals: one pinned block
-        ZK_HIP(hipMemsetAsync(dev[C_ROWSUM], 0, ((size_t)RS_MAIN << m.height[C_ROWSUM]) * 4, ctx->stream));
-        ZK_HIP(hipMemsetAsync(dev[C_QUERY], 0, ((size_t)Q_MAIN << m.height[C_QUERY]) * 4, ctx->stream));
+        ZK_HIP(hipMemsetAsync(dev[C_ROWSUM], 0, ((size_t)RS_MAIN << m.km.height[C_ROWSUM]) * 4, ctx->stream));
+        ZK_HIP(hipMemsetAsync(dev[C_QUERY], 0, ((size_t)Q_MAIN << m.km.height[C_QUERY]) * 4, ctx->stream));
         SvWitArgs a{};
         a.data = d + ht.desc.size(); a.seg = ht.data.size() / (size_t)NP; a.words_off = (uint32_t)(8 * (size_t)Q * (size_t)R);
         a.vals = d + ht.desc.size() + ht.data.size() + ht.chain_in.size() + ht.trows.size(); a.vstride = (uint32_t)vw;
         a.NP = (uint32_t)NP; a.Q = (uint32_t)Q; a.R = (uint32_t)R; a.H = (uint32_t)sh.H; a.W = (uint32_t)sh.W; a.WB = (uint32_t)sh.WB;
         a.o_queries = (uint32_t)wts[0].o_queries; a.per_query = (uint32_t)wts[0].per_query;
-        a.rs = (uint32_t*)dev[C_ROWSUM]; a.rs_rows = (uint64_t)1 << m.height[C_ROWSUM]; a.qt = (uint32_t*)dev[C_QUERY]; a.q_rows = (uint64_t)1 << m.height[C_QUERY];
+        a.rs = (uint32_t*)dev[C_ROWSUM]; a.rs_rows = (uint64_t)1 << m.km.height[C_ROWSUM]; a.qt = (uint32_t*)dev[C_QUERY]; a.q_rows = (uint64_t)1 << m.km.height[C_QUERY];
         uint32_t* sc = (uint32_t*)scratch;
         a.f_betas = sc; a.f_indices = sc + n_fb; a.f_values = a.f_indices + n_fi; a.f_siblings = a.f_values + n_fv;
         uint32_t* d_finals = a.f_siblings + n_fs;
         hipLaunchKernelGGL(sv_rowsum_query_kernel, dim3((unsigned)((nq + 4096 + 63) / 64)), dim3(64), 0, ctx->stream, a);
         ZK_HIP(hipGetLastError());
-        ZK_TRY(fri_gen_trace_dev(ctx, R, nq, a.f_betas, a.f_indices, a.f_values, a.f_siblings, m.height[C_FOLD], (uint32_t*)dev[C_FOLD], w_main[C_FOLD], d_finals, (size_t)NP, (uint32_t)sh.TREES));
+        ZK_TRY(fri_gen_trace_dev(ctx, R, nq, a.f_betas, a.f_indices, a.f_values, a.f_siblings, m.km.height[C_FOLD], (uint32_t*)dev[C_FOLD], w_main[C_FOLD], d_finals, (size_t)NP, (uint32_t)sh.TREES));
         hipLaunchKernelGGL(sv_pairs_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, ctx->stream, a);
         ZK_HIP(hipGetLastError());
         lap("device: ROWSUM, QUERY, fold rows, pairs");
         p2chip::P2RArgs pa{};
         pa.desc = d; pa.data = a.data; pa.chain_inputs = pa.data + ht.data.size(); pa.trows = pa.chain_inputs + ht.chain_in.size();
-        pa.n_chains = (uint32_t)n_chains; pa.n_transcript = (uint32_t)ht.trows.size(); pa.rows = (uint64_t)1 << m.height[C_P2R]; pa.used_rows = (uint64_t)NP * sh.p2_rows;
+        pa.n_chains = (uint32_t)n_chains; pa.n_transcript = (uint32_t)ht.trows.size(); pa.rows = (uint64_t)1 << m.km.height[C_P2R]; pa.used_rows = (uint64_t)NP * sh.p2_rows;
         pa.trace = (uint32_t*)dev[C_P2R]; pa.ld = P2_MAIN; pa.roots = d + up_words;
         ZK_HIP(launch_p2r_rows(pa, ctx->stream));
         std::vector<uint32_t> down(down_words), finals(n_fv);
@@ -1583,7 +1552,7 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
             betas.insert(betas.end(), wt.betas.begin(), wt.betas.end()); indices.insert(indices.end(), wt.indices.begin(), wt.indices.end());
             values.insert(values.end(), wt.values.begin(), wt.values.end()); siblings.insert(siblings.end(), wt.siblings.begin(), wt.siblings.end());
         }
-        ZK_TRY(fri_gen_trace(ctx, R, nq, betas.data(), indices.data(), values.data(), siblings.data(), m.height[C_FOLD], (uint32_t*)dev[C_FOLD], w_main[C_FOLD], finals.data(),
+        ZK_TRY(fri_gen_trace(ctx, R, nq, betas.data(), indices.data(), values.data(), siblings.data(), m.km.height[C_FOLD], (uint32_t*)dev[C_FOLD], w_main[C_FOLD], finals.data(),
                              true, true, 0u, 0, -1, (size_t)NP, (uint32_t)sh.TREES));
         for (int p = 0; p < NP; p++)
             for (int q = 0; q < Q; q++)
@@ -1601,7 +1570,7 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
         lap("upload: P2R work lists");
         p2chip::P2RArgs a{};
         a.desc = d; a.data = d + ht.desc.size(); a.chain_inputs = a.data + ht.data.size(); a.trows = a.chain_inputs + ht.chain_in.size();
-        a.n_chains = (uint32_t)n_chains; a.n_transcript = (uint32_t)ht.trows.size(); a.rows = (uint64_t)1 << m.height[C_P2R]; a.used_rows = (uint64_t)NP * sh.p2_rows;
+        a.n_chains = (uint32_t)n_chains; a.n_transcript = (uint32_t)ht.trows.size(); a.rows = (uint64_t)1 << m.km.height[C_P2R]; a.used_rows = (uint64_t)NP * sh.p2_rows;
         a.trace = (uint32_t*)dev[C_P2R]; a.ld = P2_MAIN; a.roots = d + up_words;
         ZK_HIP(launch_p2r_rows(a, ctx->stream));
         std::vector<uint32_t> down(down_words);
@@ -1614,16 +1583,11 @@ static int shard_verifier_prove_impl(zkhip_ctx* ctx, const zkhip_machine_key* ke
     }   // (host mode)
     // the host tables up, then the machine's proof
     const ZeroedWords* host[N_CHIPS] = {nullptr, &ht.rs, nullptr, &ht.ts, &ht.q, &ht.op, &ht.sm, &ht.sc, &ht.evl};
-    for (int c = 0; c < m.n; c++) if (host[c] && host[c]->size()) ZK_TRY(dev_h2d(ctx, dev[c], host[c]->data(), host[c]->size() * 4));
-    zkhip_chip chips[N_CHIPS]{};
-    for (int i = 0; i < m.n; i++) {
-        const int c = m.order[i];
-        chips[i].d_trace = (const uint32_t*)dev[c]; chips[i].ld = w_main[c]; chips[i].log_n = m.height[c]; chips[i].width = w_main[c]; chips[i].partner = -1;
-    }
+    for (int c = 0; c < m.km.n; c++) if (host[c] && host[c]->size()) ZK_TRY(dev_h2d(ctx, dev[c], host[c]->data(), host[c]->size() * 4));
     std::vector<uint32_t> pv((size_t)NP * n_public);
     for (size_t i = 0; i < pv.size(); i++) pv[i] = public_values[i] % P;
     lap("upload: host tables");
-    const int rc = zkhip_prove_machine_keyed(ctx, key, chips, m.progs, m.prog_words, m.tabs, m.tab_words, m.n, pv.data(), pv.size(), outer, proof, cap, len);
+    const int rc = keyed::prove(ctx, key, m.km, dev, pv.data(), pv.size(), outer, proof, cap, len);
     lap("the machine's proof");
     recycle_later({ht.sc.release(), ht.op.release(), ht.rs.release(), ht.q.release(), ht.ts.release(), ht.sm.release(), ht.evl.release()});
     return rc;
@@ -1642,22 +1606,10 @@ static int sv_setup(zkhip_ctx* ctx, const uint32_t* program, size_t program_word
     const auto mp = machine_of(sh);
     const Machine& m = *mp;
     std::vector<uint32_t> pre[N_CHIPS];
-    all_pre(sh, m, pre);
-    size_t total = 0;
-    for (int c = 0; c < N_CHIPS; c++) total += pre[c].size();
-    void* d;
-    ZK_TRY(ctx_reserve(ctx, S_REC_A, total * 4, &d));       // (staging: the key keeps its own copies)
-    zkhip_chip chips[N_CHIPS]{};
-    size_t at = 0;
-    for (int i = 0; i < m.n; i++) {
-        const int c = m.order[i];
-        chips[i].log_n = m.height[c]; chips[i].width = m.pre_widths[i]; chips[i].ld = m.pre_widths[i]; chips[i].partner = -1;
-        if (pre[c].empty()) continue;
-        ZK_TRY(dev_h2d(ctx, (uint32_t*)d + at, pre[c].data(), pre[c].size() * 4));
-        chips[i].d_trace = (const uint32_t*)d + at;
-        at += pre[c].size();
-    }
-    return zkhip_machine_setup(ctx, chips, m.n, outer, key, vk);
+    all_pre(sh, m.km, PRE, pre);
+    const uint32_t* d_pre[N_CHIPS];
+    ZK_TRY(stage_pre(ctx, m.km, pre, d_pre));
+    return keyed::key_setup(ctx, m.km, d_pre, outer, key, vk);
 }
 // The same key WITHOUT a device (round 5; host_key.cpp): the preprocessed traces are host tables anyway -- their low-degree extensions and the
 // mixed-height Poseidon2 commitment are computed on the host's cores, so that a verifier that owns no GPU derives the key of the shape it
@@ -1671,17 +1623,9 @@ static int sv_key_host(const uint32_t* program, size_t program_words, int log_n,
         ZK_TRY(make_shape(log_n, width, n_queries, inner_pow_bits, n_public, n_proofs, sh, program, program_words));
         ZK_TRY(check_outer(sh, outer));
         const auto mp = machine_of(sh);
-        const Machine& m = *mp;
         std::vector<uint32_t> pre[N_CHIPS];
-        all_pre(sh, m, pre);
-        const uint32_t* traces[N_CHIPS]; int32_t lns[N_CHIPS]; uint32_t pws[N_CHIPS];
-        for (int i = 0; i < m.n; i++) {
-            const int c = m.order[i];
-            lns[i] = m.height[c]; pws[i] = m.pre_widths[i];
-            traces[i] = pre[c].empty() ? nullptr : pre[c].data();
-            if (pre[c].empty()) pws[i] = 0;
-        }
-        return zkhip_machine_key_host(traces, lns, pws, m.n, outer, vk);
+        all_pre(sh, mp->km, PRE, pre);
+        return keyed::key_host(mp->km, pre, outer, vk);
     } catch (const std::bad_alloc&) {
         return fail(ZKHIP_ERR_NOMEM, "shard_verifier_key_host: out of host memory");
     }
@@ -1702,8 +1646,7 @@ static size_t sv_proof_size(const uint32_t* program, size_t program_words, int l
     using namespace zk::rec;
     Shape sh;
     if (!outer || make_shape(log_n, width, n_queries, inner_pow_bits, n_public, n_proofs, sh, program, program_words) != ZKHIP_OK || check_outer(sh, outer) != ZKHIP_OK) return 0;
-    const auto m = machine_of(sh);
-    return zkhip_machine_proof_size_keyed(m->log_ns, m->widths, m->pre_widths, m->progs, m->prog_words, m->tabs, m->tab_words, m->n, outer, n_proofs * n_public);
+    return keyed::proof_size(machine_of(sh)->km, outer, n_proofs * n_public);
 }
 static int sv_verify(const uint32_t* program, size_t program_words, const uint8_t* proof, size_t len, int log_n, uint32_t width, size_t n_queries, int inner_pow_bits,
                      const uint32_t* public_values, size_t n_public, size_t n_proofs, const uint32_t vk[8], const zkhip_params* outer, int* reason) {
@@ -1713,41 +1656,16 @@ static int sv_verify(const uint32_t* program, size_t program_words, const uint8_
         if (reason) *reason = 1;
         return fail(ZKHIP_ERR_VERIFY, "verify_shard_recursive: bad arguments");
     }
-    const auto m = machine_of(sh);
     std::vector<uint32_t> pv(n_proofs * n_public);
     for (size_t i = 0; i < pv.size(); i++) pv[i] = public_values[i];
-    return zkhip_verify_machine_keyed(proof, len, m->log_ns, m->widths, m->pre_widths, vk, m->progs, m->prog_words, m->tabs, m->tab_words, m->n, pv.data(), pv.size(), outer, reason);
+    return keyed::verify(machine_of(sh)->km, proof, len, vk, pv.data(), pv.size(), outer, reason);
 }
 static size_t sv_describe(const uint32_t* program, size_t program_words, int log_n, uint32_t width, size_t n_queries, int inner_pow_bits, size_t n_public, size_t n_proofs, int which,
                           int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width) {
     using namespace zk::rec;
     Shape sh;
     if (which < 0 || kind < 0 || kind > 2 || make_shape(log_n, width, n_queries, inner_pow_bits, n_public, n_proofs, sh, program, program_words) != ZKHIP_OK) return 0;
-    const auto m = machine_of(sh);
-    if (which >= m->n) return 0;
-    if (log_rows) *log_rows = m->log_ns[which];
-    if (main_width) *main_width = m->widths[which];
-    if (pre_width) *pre_width = m->pre_widths[which];
-    std::vector<uint32_t> pre;
-    const std::vector<uint32_t>* src = kind == 0 ? &m->prog[which] : &m->tab[which];
-    if (kind == 2) {
-        const int c = m->order[which], h = m->height[c];
-        switch (c) {
-            case C_P2R: p2r_pre(sh, h, pre); break;
-            case C_ROWSUM: rowsum_pre(sh, h, pre); break;
-            case C_TS: ts_pre(sh, h, pre); break;
-            case C_QUERY: query_pre(sh, h, pre); break;
-            case C_OPENED: opened_pre(sh, h, pre); break;
-            case C_SAMPLES: samples_pre_all(sh, h, pre); break;
-            case C_SCALARS: scalars_pre(sh, h, pre); break;
-            case C_EVAL: eval_pre(sh, h, pre); break;
-            default: break;
-        }
-        for (uint32_t& v : pre) v = from_monty(v);
-        src = &pre;
-    }
-    if (out && cap_words >= src->size()) std::memcpy(out, src->data(), src->size() * 4);
-    return src->size();
+    return keyed::describe(machine_of(sh)->km, which, kind, [&](int c, int h, std::vector<uint32_t>& pre) { if (PRE[c]) PRE[c](sh, h, pre); }, out, cap_words, log_rows, main_width, pre_width);
 }
 
 extern "C" {
