@@ -8,6 +8,8 @@
  *     the inner proof; the whole-verifier machines are zkhip.h's zkhip_prove_shard_verifier / zkhip_prove_machine_verifier).  Round 6 removed the
  *     three earlier FRI-only generations (zkhip_prove_fri_queries / _layers / _transcript with their keys, sizes, trace generators and verifiers):
  *     their chips live on as the FOLD, SAMPLES and Poseidon2 chips of the shard verifier machines, their programs and views below;
+ *   - the fold-by-16 line (RISC Zero-shape inner proofs), one machine per verifier step: zkhip_prove_fri16, _paths, _indices, _openings, _rowpaths and _head
+ *     (the head of the transcript: the machine whose public values are the inner proof's own);
  *   - diagnostics and self-tests.
  * Each entry names the upstream structure it stands in for (sp1-core-machine / sp1-recursion chips, reference Cargo.lock:5822, 6047, 6172).
  */
@@ -381,6 +383,47 @@ int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                size_t cap, size_t* len);
 int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason);
+
+/* ---- the fold-16 HEAD machine: the row-paths machine with the head of the transcript inside ----
+ * Statement: everything the row-paths machine states, and: the sponge chain starts from the all-zero state, absorbs the ten header words of a version-3 proof
+ * (log_n, W, log_blowup, Q, inner_pow_bits, NP, 0, 4, F, 24), the trace root listed in ROOTS and the NP public values of THIS proof, draws alpha, absorbs the
+ * quotient root listed in ROOTS, draws zeta, absorbs the 2 W + 8 opened extension values, draws fa, and the commit phase continues from that very state; the
+ * eight constants of the reduced opening are fa, zeta, zeta g_N and the sums and powers of fa over those opened values.  The machine's public values are the
+ * inner proof's own public values (n_inner_public of them, 1 .. 30) and nothing else.  alpha is drawn and used by nothing in this step: the AIR identity at zeta
+ * is the step that consumes it.  Eleven tables, the row-paths machine's numbering with OPENED16 at 10 (tests/fri16_head_air.py writes all of it again).
+ * zkhip_fri16_view_head hands out what the prover needs beside the row-paths view: the opened values [2 W + 8][4] in the order they are observed (values at
+ * zeta, at zeta g, quotient values; canonical) and alpha; it fails like zkhip_fri16_view_shard and refuses, each with its message, proofs with lookup pairs, with
+ * a program (version 7), with a code group and with the width-16 hash.  zkhip_fri16_head_describe / _key_host (no GPU) / _key / _proof_size: as the _rowpaths_
+ * entries with n_inner_public behind trace_width.  zkhip_fri16_head_gen_traces: P2TH, SAMPLES and OPENED16 on the device (dense, [2^lr][352], [2^lr][288],
+ * [2^lr][36]) from the inner public values, the two roots, the opened values, the layer roots, the final coefficients and the witness alone; it hands back the
+ * eight derived constants [8][4] and the capacity the commit phase finds.  zkhip_prove_fri16_head takes the row-paths prover's arguments, the inner public
+ * values and the opened values; constants and capacity are what the view says, compared with what the head derives.  Refused before anything is proven: all
+ * zkhip_prove_fri16_rowpaths refuses, a derived constant that is not the view's (named: fa, zeta, zeta g_N, YL, YN, YQ, OFFN, OFFQ), a derived capacity that is
+ * not the view's, opened or public values that are not canonical, n_inner_public = 0 or > 30.  zkhip_verify_fri16_head is host only.
+ * STILL OUTSIDE: the AIR identity at zeta, lookups, version-7 and version-8 inner proofs, roots leaving the key, the wiring into shard_verifier.inl. */
+int zkhip_fri16_view_head(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                          uint32_t* opened, uint32_t alpha[4]);
+size_t zkhip_fri16_head_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                 uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_head_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                              uint32_t vk[8]);
+int zkhip_fri16_head_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                         uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
+                         const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_head_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm);
+int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                const uint32_t* inner_public, const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* opened, const uint32_t* roots,
+                                const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2th, uint32_t* d_samples, uint32_t* d_opened, uint32_t constants[32],
+                                uint32_t capacity[8]);
+int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                           uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16_head(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                            uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */

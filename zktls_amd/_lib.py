@@ -59,6 +59,8 @@ EXPORTS = [
     "zkhip_fri16_openings_gen_traces", "zkhip_prove_fri16_openings", "zkhip_verify_fri16_openings",
     "zkhip_fri16_view_row_paths", "zkhip_fri16_rowpaths_describe", "zkhip_fri16_rowpaths_key_host", "zkhip_fri16_rowpaths_key", "zkhip_fri16_rowpaths_proof_size",
     "zkhip_fri16_rowpaths_gen_trace", "zkhip_prove_fri16_rowpaths", "zkhip_verify_fri16_rowpaths",
+    "zkhip_fri16_view_head", "zkhip_fri16_head_describe", "zkhip_fri16_head_key_host", "zkhip_fri16_head_key", "zkhip_fri16_head_proof_size",
+    "zkhip_fri16_head_gen_traces", "zkhip_prove_fri16_head", "zkhip_verify_fri16_head",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -406,6 +408,23 @@ def load():
     L.zkhip_prove_fri16_rowpaths.argtypes = [C.c_void_p, C.c_void_p] + fri16_oshape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
                                                                                         u32p, u32p, u32p, u32p, C.POINTER(Params), u8p, C.c_size_t, szp]
     L.zkhip_verify_fri16_rowpaths.argtypes = L.zkhip_verify_fri16_openings.argtypes
+    # the fold-16 head machine: the row-paths machine's entries with n_inner_public behind trace_width
+    fri16_hshape = fri16_oshape + [C.c_uint32]
+    L.zkhip_fri16_view_head.argtypes = [u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), u32p, u32p]
+    L.zkhip_fri16_head_describe.restype = C.c_size_t
+    L.zkhip_fri16_head_describe.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    L.zkhip_fri16_head_key_host.argtypes = fri16_hshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), u32p]      # final_poly, layer roots, trace root, quotient root
+    L.zkhip_fri16_head_key.argtypes = [C.c_void_p] + fri16_hshape + [u32p, u32p, u32p, u32p, C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_head_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_head_proof_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(Params)]
+    L.zkhip_fri16_head_gen_traces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, u32p, u32p]
+    L.zkhip_prove_fri16_head.argtypes = [C.c_void_p, C.c_void_p] + fri16_hshape + [u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
+                                                                                    u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(Params), u8p, C.c_size_t,
+                                                                                    C.POINTER(C.c_size_t)]
+    L.zkhip_verify_fri16_head.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(Params),
+                                          C.POINTER(C.c_int)]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -24,7 +24,7 @@
 //   3 QUERIES  preprocessed: distinct (index, reduced opening) with multiplicity.       4 COEFFS  preprocessed: (j, c_j, queries).
 // NOT in this machine: the Merkle paths of the layer rows, the transcript (challenges, query indices), the reduced openings.  tests/fri16_air.py writes
 // the programs, tables and traces independently; the words must be equal.
-// FIVE machines are kept here as ONE description read at five kinds (enum Kind), each kind the one before it with a step more of the inner verifier inside:
+// SIX machines are kept here as ONE description read at six kinds (enum Kind), each kind the one before it with a step more of the inner verifier inside:
 //   LAYERS   (zkhip_prove_fri16)           the five tables above
 //   PATHS    (zkhip_prove_fri16_paths)     P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands, and a preprocessed ROOTS table: the layer rows' Merkle
 //                                          paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py)
@@ -37,6 +37,11 @@
 //   ROWPATHS (zkhip_prove_fri16_rowpaths)  the Merkle paths of the opened trace row and quotient row proven: P24R, a second layer-paths-style variant of the width-24 chip,
 //                                          stands where the preprocessed ROWS table stood; the key holds roots and final coefficients only, no opened word
 //                                          (tests/fri16_rowpaths_air.py)
+//   HEAD     (zkhip_prove_fri16_head)      the head of the transcript inside: P2TH walks the duplex challenger from the all-zero state -- the header, the trace root, the inner
+//                                          proof's public values, alpha, the quotient root, zeta, the opened values, fa -- into the commit phase; OPENED16 sums the opened
+//                                          values in fa; the eight constants reach ROWSUM16H and QUERY16H over buses.  The public values are the INNER PROOF'S public values
+//                                          and nothing else.  alpha is drawn and used by nothing here: the AIR identity at zeta is the step that consumes it
+//                                          (tests/fri16_head_air.py)
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
 // table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
 // to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
@@ -86,17 +91,19 @@ constexpr uint32_t CFC = FIN_PRE + FC, CFACC = FIN_PRE + FACC, CFAX = FIN_PRE + 
 constexpr uint32_t LAY_PRE = 84, LAY_LN = 0, LAY_KEY = 1, LAY_M = 17, LAY_E = 20, Q_PRE = 8, C_PRE = 8, TAB_MAIN = 4;
 // ONE numbering of the tables for the five kinds: a later kind appends tables (5; 6, 7; 8, 9) or puts a chip where a key table stood (2, 3, 9)
 enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_P24L = 2, T_QUERIES = 3, T_QUERY16 = 3, T_COEFFS = 4, T_ROOTS = 5, T_P2T = 6, T_SAMPLES = 7, T_ROWSUM16 = 8, T_ROWS = 9,
-              T_P24R = 9, MAX_TABLES = 10 };
+              T_P24R = 9, T_OPENED16 = 10, MAX_TABLES = 11 };
 inline uint32_t canon_nibble_factor(uint32_t first_bit, uint32_t nbits, uint32_t j) { return from_monty(nibble_factor(first_bit, nbits, j)); }
 
 // The five machines are ONE description read at five kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
 // (pow_bits, C S NT from INDICES on; W from OPENINGS on) stays zero below it.  shape_of, program_of, interactions_of and machine_of are further down, behind the chips.
-enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS };
+enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS, HEAD };
 struct Shape {
     Kind kind = LAYERS;
     int R = 0, F = 0, b = 0, lf = 0, H = 0, pow_bits = 0, n_tables = 0;
     size_t Q = 0, C = 0, S = 0, NT = 0;      // C, S, NT: coefficient rows, rows that hand words out, rows of the transcript's chain
     uint32_t W = 0;                          // the inner proof's trace width
+    uint32_t NP = 0;                         // HEAD: the inner proof's public values; A sponge rows up to alpha, HD rows in front of the commit phase's
+    size_t A = 0, HD = 0;
     int log_rows[MAX_TABLES];                // by table number
     uint32_t main_w[MAX_TABLES], pre_w[MAX_TABLES];
 };
@@ -433,11 +440,11 @@ std::vector<uint32_t> build_p2t_program(uint32_t n_public) {
 }
 // ROOTS' program: the harmless identity of a key table, and FOLDROWS (1 - LISTED) = 0 -- the multiplicity of the send (layer, beta) to FOLD16B is a MAIN column, and a
 // padding row's preprocessed cells are zero (layer 0, nothing received from the transcript): without this a padding row could hand layer 0 a challenge of the prover's choice
-std::vector<uint32_t> build_roots_program(uint32_t n_public) {
+std::vector<uint32_t> build_roots_program(uint32_t n_public, uint32_t pre_w = ROOTS_PRE16) {      // (the head machine's ROOTS has eight more preprocessed columns)
     Builder b;
-    b.add(FIRST, Terms{{1u, {var(ROOTS_PRE16 + ROOTS_MAIN_I - 1u)}}});
-    b.add(ALL, Terms{{1u, {var(ROOTS_PRE16 + 5u)}}, {P - 1, {var(ROOTS_PRE16 + 5u), var(10u)}}});
-    return b.finish(ROOTS_PRE16 + ROOTS_MAIN_I, n_public);
+    b.add(FIRST, Terms{{1u, {var(pre_w + ROOTS_MAIN_I - 1u)}}});
+    b.add(ALL, Terms{{1u, {var(pre_w + 5u)}}, {P - 1, {var(pre_w + 5u), var(10u)}}});
+    return b.finish(pre_w + ROOTS_MAIN_I, n_public);
 }
 // the key's tables by table number: FINAL's schedule, QUERIES by query number, COEFFS, ROOTS, and the schedules of P2T and SAMPLES -- no index and no challenge
 int build_indices_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[], const char* who) {
@@ -525,8 +532,8 @@ constexpr uint32_t BUS_ROW16 = 81, BUS_AT16 = 82, BUS_AQ16 = 83, N_PUBLIC_O = 40
 constexpr uint32_t RP_TAG = 0, RP_ACT = 1, RP_NOTFIRST = 2, RP_LAST0 = 3, RP_LAST1 = 4, RP_QN = 5, RP_K0 = 6, RP_K1 = 7;
 constexpr uint32_t PUB_FA = 8, PUB_ZETA = 12;       // public values: FA, then ZETA ZNX YL YN YQ OFFN OFFQ in QUERY16's column order
 
-std::vector<uint32_t> build_fold16c_program(int R, int lf) {
-    const std::vector<uint32_t> p = build_fold16_program(R, lf, true, N_PUBLIC_O);
+std::vector<uint32_t> build_fold16c_program(int R, int lf, uint32_t n_public = N_PUBLIC_O) {
+    const std::vector<uint32_t> p = build_fold16_program(R, lf, true, n_public);
     const uint32_t XQ = fold16_width((uint32_t)lf);
     Builder b;
     b.body.assign(p.begin() + 6, p.end());
@@ -534,15 +541,13 @@ std::vector<uint32_t> build_fold16c_program(int R, int lf) {
     Terms t{{1u, {var(XQ)}}};
     for (uint32_t j = 0; j < 16; j++) t.push_back(Term{neg(from_monty(fpow(two_adic_generator(4), reverse_bits(j, 4)))), {var(X), var(OF + j)}});
     b.add(ALL, t);
-    return b.finish(XQ + 4u, N_PUBLIC_O);
+    return b.finish(XQ + 4u, n_public);
 }
 // QUERY16's columns in the combined row: the shard verifier's QUERY chip's
 constexpr uint32_t QC_IDX = Q16_PRE + QM_IDX, QC_XQ = Q16_PRE + QM_XQ, QC_RO = Q16_PRE + QM_RO, QC_AT = QC_RO + 4, QC_AQ = QC_RO + 8, QC_I1 = QC_RO + 12, QC_I2 = QC_RO + 16,
                    QC_P1 = QC_RO + 20, QC_P2 = QC_RO + 24, QC_P2O = QC_RO + 28, QC_P3 = QC_RO + 32, QC_P3O = QC_RO + 36, QC_ZETA = Q16_PRE + QM_ZETA, QC_ZNX = QC_ZETA + 4,
                    QC_YL = QC_ZETA + 8, QC_YN = QC_ZETA + 12, QC_YQ = QC_ZETA + 16, QC_OFFN = QC_ZETA + 20, QC_OFFQ = QC_ZETA + 24;
-std::vector<uint32_t> build_query16_program() {
-    Builder b;
-    for (uint32_t i = 0; i < 7; i++) add_ext(b, ALL, esub(ev(QC_ZETA + 4 * i), epub(PUB_ZETA + 4 * i)));
+void query16_products(Builder& b) {      // the eight product constraints with x = g XQ: what QUERY16 and QUERY16H share
     const EE x = eb(pscale(pv(QC_XQ), GEN));
     const Terms act = pv(QP_ACT);
     add_ext(b, ALL, egate(act, esub(emul(esub(x, ev(QC_ZETA)), ev(QC_I1)), eone())));
@@ -553,13 +558,19 @@ std::vector<uint32_t> build_query16_program() {
     add_ext(b, ALL, esub(ev(QC_P3), emul(esub(ev(QC_AQ), ev(QC_YQ)), ev(QC_I1))));
     add_ext(b, ALL, esub(ev(QC_P3O), emul(ev(QC_OFFQ), ev(QC_P3))));
     add_ext(b, ALL, esub(ev(QC_RO), eadd(eadd(ev(QC_P1), ev(QC_P2O)), ev(QC_P3O))));
+}
+std::vector<uint32_t> build_query16_program() {
+    Builder b;
+    for (uint32_t i = 0; i < 7; i++) add_ext(b, ALL, esub(ev(QC_ZETA + 4 * i), epub(PUB_ZETA + 4 * i)));
+    query16_products(b);
     return b.finish(Q16_PRE + Q16_MAIN, N_PUBLIC_O);
 }
-std::vector<uint32_t> build_rowsum16_program() {
-    const uint32_t M0 = RS16_PRE;
+// (head: ROWSUM16H -- twelve preprocessed columns, FA one constant down the table, received on the first row, in place of FA = its public value)
+std::vector<uint32_t> build_rowsum16_program(uint32_t M0 = RS16_PRE, bool head = false, uint32_t n_public = N_PUBLIC_O) {
     Builder b;
     const EE fa = ev(M0 + RS_FA);
-    add_ext(b, ALL, esub(fa, epub(PUB_FA)));
+    if (head) add_ext(b, TRANSITION, esub(ev(M0 + RS_FA, true), fa));
+    else add_ext(b, ALL, esub(fa, epub(PUB_FA)));
     EE prev = ev(M0 + RS_ACCIN);
     for (int s = 7; s >= 0; s--) {
         const EE cur = ev(M0 + RS_T + 4u * (uint32_t)s);
@@ -568,7 +579,7 @@ std::vector<uint32_t> build_rowsum16_program() {
     }
     add_ext(b, TRANSITION, egate(pv(RP_NOTFIRST, true), esub(ev(M0 + RS_ACCIN, true), ev(M0 + RS_T))));
     add_ext(b, ALL, egate(padd(pv(RP_ACT), pneg(pv(RP_NOTFIRST))), ev(M0 + RS_ACCIN)));
-    return b.finish(RS16_PRE + RS_MAIN16, N_PUBLIC_O);
+    return b.finish(M0 + RS_MAIN16, n_public);
 }
 // ROWSUM16's schedule: per query the trace blocks from the last to the first, then the quotient block
 void rowsum16_schedule(size_t Q, size_t W, int log_rows, std::vector<uint32_t>& t) {
@@ -662,23 +673,197 @@ int build_rowpaths_key_tables(const Shape& s, const uint32_t* final_poly, const 
     return ZKHIP_OK;
 }
 
+// ---------------------------------------------------------------- the HEAD machine: the row-paths machine with the head of the transcript inside
+// Eleven tables, numbered as in the row-paths machine with OPENED16 at 10.  The public values are the NP public values of the inner proof (1 .. 30) and nothing else: no
+// capacity word, no constant.  FOLD16C, FINAL, P24L, COEFFS, SAMPLES and P24R: the row-paths machine's programs and interaction tables word for word but the public-value
+// count in the header (and the first row number in SAMPLES' key table).  The sponge chain now starts from the ALL-ZERO state and walks, before the commit phase's rows:
+//   A = ceil((18 + NP) / 8) rows   the stream (log_n, W, log_blowup, Q, inner_pow_bits, NP, 0, 4, F, 24 | trace root | public values), eight words a row; the last one is
+//                                  partial unless 18 + NP is a multiple of 8: its remaining rate words keep the previous output (a sample with pending inputs permutes in
+//                                  overwrite mode).  alpha = (out[7], out[6], out[5], out[4]) of row A - 1 -- drawn, and USED BY NOTHING in this machine: the AIR identity at
+//                                  zeta is the step that consumes it
+//   1 row                          the quotient root; zeta is its output (a sample right after a full block costs no permutation)
+//   W + 4 rows                     the 2 W + 8 opened extension values (values at zeta, at zeta g, quotient values: the order the verifier observes them in), two a row;
+//                                  fa is the last row's output, and the commit phase continues from that very state
+// HD = A + 1 + W + 4 rows in front of the R + C + S rows P2T has in the kinds before.
+//   P2TH     P2T's 352 permutation columns and chain constraints; row 0's capacity is ZERO where it was public; preprocessed (64 columns): P2T's twenty, then per rate word
+//            a header flag and value (HF_j (IN_j - HV_j) = 0), six public-value indicators (PUBI_i (IN_j - public value 8 i + j - 18) = 0 where row i, word j holds one),
+//            per rate word a key and a multiplicity for the receive of a root word from ROOTS (key 8 tree + word; the trace root sits at stream words 10 .. 17: 6 + 2 over
+//            rows 1 and 2), a flag OPN for the receive of the row's eight rate words from OPENED16 keyed by the row number, and the multiplicities of the two sends of
+//            (out[7], out[6], out[5], out[4]): zeta from the quotient root's row (1: to QUERY16H), fa from the last opened-value row (2: to ROWSUM16H and OPENED16)
+//   ROOTS    rows R and R + 1 gain the sends (8 tree + j, root_j) under the preprocessed multiplicity HM, 1 on those two rows only; LISTED stays 0 there
+//   OPENED16 one row per opened-value row: V[8] FA FA2 PW T PT Y PWN (fri16_rows.cuh); FA2 = FA FA, T = V0 + FA V1, PT = PW T, PWN = PW FA2 on every row; PW = 1 and Y = PT on
+//            a segment's first row; PW' = PWN and Y' = Y + PT' inside a segment; FA' = FA on every transition.  Preprocessed ACT NOTFIRST ROW ENDL ENDN ENDQ FIRST.  Sends
+//            the two halves of V to P2TH, Y at the three segment ends as YL YN YQ, PWN at the end of the first as OFFN = fa^W; receives fa on its first row
+//   QUERY16H QUERY16 with every constant one value down the table (c' = c) and received on the first row (ZETA YL YN YQ OFFN), ZNX = g_N ZETA, OFFQ = OFFN OFFN
+//   ROWSUM16H ROWSUM16 with FA' = FA and fa received on the first row (twelve preprocessed columns: the first-row multiplicity needs one)
+// Every multiplicity of the head is preprocessed.  The key holds roots, final coefficients and header constants: no opened word, no constant, no challenge.  NP = 0 is
+// refused (a keyed machine without public values is not something any test here has carried), NP > 30 too (six indicator columns).
+// STILL OUTSIDE: the AIR identity at zeta (alpha unused), lookups, version-7 and version-8 inner proofs, roots leaving the key, the wiring into shard_verifier.inl.
+// tests/fri16_head_air.py writes it again.
+constexpr uint32_t BUS_HR = 85, BUS_OV0 = 86, BUS_OV1 = 87, BUS_ZETA = 88, BUS_FAH = 89, BUS_YL = 90, BUS_YN = 91, BUS_YQ = 92, BUS_OFFN = 93, MAX_NP = 30;
+constexpr uint32_t PTH_PRE = 64, PH_HF = 20, PH_HV = 28, PH_PUBI = 36, PH_RK = 42, PH_RM = 50, PH_OPN = 58, PH_ZM = 59, PH_FM = 60, HEAD_STREAM = 18;
+constexpr uint32_t ROOTS_PRE_H = 20, RT_HM = 11, RT_HK = 12, QP_FIRST = 6, RS16H_PRE = 12, RP_FIRST = 8;
+constexpr uint32_t OPN_PRE = 8, OQ_ACT = 0, OQ_NOTFIRST = 1, OQ_ROW = 2, OQ_ENDL = 3, OQ_ENDN = 4, OQ_ENDQ = 5, OQ_FIRST = 6;
+// the ten header words: transcript_init for a version-3 proof (sh.ext, no program, no code group, no lookup pairs)
+void head_header(const Shape& s, uint32_t h[10]) {
+    const uint32_t w[10] = {(uint32_t)(s.H - s.b), s.W, (uint32_t)s.b, (uint32_t)s.Q, (uint32_t)s.pow_bits, s.NP, 0u, 4u, (uint32_t)s.F, 24u};
+    std::memcpy(h, w, sizeof w);
+}
+std::vector<uint32_t> build_p2th_program(const Shape& s) {
+    using namespace p2chip;
+    const uint32_t M0 = PTH_PRE, OUT = M0 + oute(7);
+    Builder b;
+    b.body = permutation_body(M0, &b.count);
+    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(M0 + D + j)}}, {P - 1, {var(M0 + IN + j)}}});
+    b.add(ALL, Terms{{1u, {var(M0 + BIT)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(FIRST, Terms{{1u, {var(M0 + IN + 8 + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_SPG, true), var(M0 + IN + 8 + j, true)}}, {P - 1, {var(PT_SPG, true), var(OUT + 8 + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(TRANSITION, Terms{{1u, {var(PT_K + j, true), var(M0 + IN + j, true)}}, {P - 1, {var(PT_K + j, true), var(OUT + j)}}});
+    for (uint32_t j = 0; j < 8; j++) b.add(ALL, Terms{{1u, {var(PH_HF + j), var(M0 + IN + j)}}, {P - 1, {var(PH_HF + j), var(PH_HV + j)}}});
+    for (uint32_t i = 0; i < (uint32_t)s.A; i++)
+        for (uint32_t j = 0; j < 8; j++) {
+            const uint32_t pos = 8 * i + j;
+            if (pos < HEAD_STREAM || pos >= HEAD_STREAM + s.NP) continue;
+            b.add(ALL, Terms{{1u, {var(PH_PUBI + i), var(M0 + IN + j)}}, {P - 1, {var(PH_PUBI + i), pub(pos - HEAD_STREAM)}}});
+        }
+    return b.finish(PTH_PRE + T_WIDTH, s.NP);
+}
+std::vector<uint32_t> build_query16h_program(const Shape& s) {
+    Builder b;
+    for (uint32_t i = 0; i < 7; i++) add_ext(b, TRANSITION, esub(ev(QC_ZETA + 4 * i, true), ev(QC_ZETA + 4 * i)));
+    add_ext(b, ALL, esub(ev(QC_ZNX), escale(ev(QC_ZETA), from_monty(two_adic_generator(s.H - s.b)))));
+    add_ext(b, ALL, esub(ev(QC_OFFQ), emul(ev(QC_OFFN), ev(QC_OFFN))));
+    query16_products(b);
+    return b.finish(Q16_PRE + Q16_MAIN, s.NP);
+}
+std::vector<uint32_t> build_opened16_program(uint32_t n_public) {
+    const uint32_t M0 = OPN_PRE;
+    Builder b;
+    const EE fa = ev(M0 + OP_FA), fa2 = ev(M0 + OP_FA2), pw = ev(M0 + OP_PW), t = ev(M0 + OP_T), pt = ev(M0 + OP_PT), y = ev(M0 + OP_Y), pwn = ev(M0 + OP_PWN);
+    add_ext(b, ALL, esub(fa2, emul(fa, fa)));
+    add_ext(b, ALL, esub(t, eadd(ev(M0 + OP_V), emul(fa, ev(M0 + OP_V + 4)))));
+    add_ext(b, ALL, esub(pt, emul(pw, t)));
+    add_ext(b, ALL, esub(pwn, emul(pw, fa2)));
+    const Terms seg_first = padd(pv(OQ_ACT), pneg(pv(OQ_NOTFIRST)));
+    add_ext(b, ALL, egate(seg_first, esub(pw, eone())));
+    add_ext(b, ALL, egate(seg_first, esub(y, pt)));
+    add_ext(b, TRANSITION, egate(pv(OQ_NOTFIRST, true), esub(ev(M0 + OP_PW, true), pwn)));
+    add_ext(b, TRANSITION, egate(pv(OQ_NOTFIRST, true), esub(ev(M0 + OP_Y, true), eadd(y, ev(M0 + OP_PT, true)))));
+    add_ext(b, TRANSITION, esub(ev(M0 + OP_FA, true), fa));
+    return b.finish(OPN_PRE + OP_MAIN16, n_public);
+}
+int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s, uint32_t NP = 0);
+// the key's tables by table number: the row-paths machine's at the head machine's widths, the head's schedule in front of P2T's, OPENED16's schedule -- functions of the
+// shape and NP alone but for the roots and the final coefficients
+int build_head_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root, std::vector<uint32_t> pre[],
+                          const char* who) {
+    Shape so;                                                  // the kinds before, at their own widths (the openings shape: no shape of the head's is refused for its heights)
+    ZK_TRY(shape_of(OPENINGS, s.R, s.F, s.b, s.Q, s.pow_bits, s.W, so));
+    std::vector<uint32_t> t[MAX_TABLES];
+    ZK_TRY(build_rowpaths_key_tables(so, final_poly, roots, trace_root, quotient_root, t, who));
+    const size_t R = (size_t)s.R, W = s.W;
+    for (int i = 0; i < s.n_tables; i++) pre[i].assign((size_t)s.pre_w[i] << s.log_rows[i], 0u);
+    pre[T_FINAL] = t[T_FINAL]; pre[T_COEFFS] = t[T_COEFFS]; pre[T_QUERY16] = t[T_QUERY16];
+    pre[T_QUERY16][QP_FIRST] = MONTY_R1;
+    for (size_t r = 0; r < ((size_t)1 << s.log_rows[T_ROOTS]); r++) std::memcpy(pre[T_ROOTS].data() + ROOTS_PRE_H * r, t[T_ROOTS].data() + ROOTS_PRE16 * r, 4 * ROOTS_PRE16);
+    for (size_t tree = 0; tree < 2; tree++) {
+        uint32_t* w = pre[T_ROOTS].data() + ROOTS_PRE_H * (R + tree);
+        w[RT_HM] = MONTY_R1;
+        for (uint32_t j = 0; j < 8; j++) w[RT_HK + j] = to_monty((uint32_t)(8 * tree + j));
+    }
+    for (size_t r = 0; r < ((size_t)1 << s.log_rows[T_ROWSUM16]); r++) std::memcpy(pre[T_ROWSUM16].data() + RS16H_PRE * r, t[T_ROWSUM16].data() + RS16_PRE * r, 4 * RS16_PRE);
+    pre[T_ROWSUM16][RP_FIRST] = MONTY_R1;
+    uint32_t hdr[10];
+    head_header(s, hdr);
+    for (size_t r = 0; r < s.HD; r++) {
+        uint32_t* w = pre[T_P2T].data() + PTH_PRE * r;
+        if (r) w[PT_SPG] = MONTY_R1;
+        if (r < s.A) {
+            for (uint32_t j = 0; j < 8; j++) {
+                const size_t pos = 8 * r + j;
+                if (pos >= HEAD_STREAM + s.NP) w[PT_K + j] = MONTY_R1;
+                else if (pos < 10) { w[PH_HF + j] = MONTY_R1; w[PH_HV + j] = to_monty(hdr[pos]); }
+                else if (pos < HEAD_STREAM) { w[PH_RK + j] = to_monty((uint32_t)(pos - 10)); w[PH_RM + j] = MONTY_R1; }
+                else w[PH_PUBI + r] = MONTY_R1;
+            }
+        } else if (r == s.A) {
+            for (uint32_t j = 0; j < 8; j++) { w[PH_RK + j] = to_monty(8u + j); w[PH_RM + j] = MONTY_R1; }
+            w[PH_ZM] = MONTY_R1;
+        } else {
+            w[PH_OPN] = MONTY_R1; w[PT_ROW] = to_monty((uint32_t)r);
+            if (r + 1 == s.HD) w[PH_FM] = to_monty(2u);
+        }
+    }
+    for (size_t r = 0; r < s.NT; r++) {
+        uint32_t* w = pre[T_P2T].data() + PTH_PRE * (s.HD + r);
+        std::memcpy(w, t[T_P2T].data() + PT_PRE * r, 4 * PT_PRE);
+        w[PT_SPG] = MONTY_R1;
+        if (w[PT_SMP]) w[PT_ROW] = to_monty((uint32_t)(s.HD + r));
+    }
+    frichip::samples_chip_pre(s.Q, s.log_rows[T_SAMPLES], (int)(s.HD + R + s.C), pre[T_SAMPLES]);
+    for (size_t i = 0; i < W + 4; i++) {
+        uint32_t* w = pre[T_OPENED16].data() + OPN_PRE * i;
+        const size_t first = i < W / 2 ? 0 : (i < W ? W / 2 : W);
+        w[OQ_ACT] = MONTY_R1; w[OQ_NOTFIRST] = i != first ? MONTY_R1 : 0u; w[OQ_ROW] = to_monty((uint32_t)(s.A + 1 + i));
+        w[OQ_ENDL] = i + 1 == W / 2 ? MONTY_R1 : 0u; w[OQ_ENDN] = i + 1 == W ? MONTY_R1 : 0u; w[OQ_ENDQ] = i == W + 3 ? MONTY_R1 : 0u; w[OQ_FIRST] = i == 0 ? MONTY_R1 : 0u;
+    }
+    pre[T_P24R].clear();
+    return ZKHIP_OK;
+}
+// the head of the chain walked on the host (HD permutations): every row's input state, the three challenges and the capacity the commit phase finds -- canonical
+struct Head { std::vector<uint32_t> inputs; uint32_t alpha[4], zeta[4], fa[4], capacity[8]; };
+void walk_head(const Shape& s, const uint32_t* inner_public, const uint32_t* trace_root, const uint32_t* quotient_root, const uint32_t* opened, Head& h) {
+    std::vector<uint32_t> stream(HEAD_STREAM + s.NP);
+    head_header(s, stream.data());
+    std::memcpy(stream.data() + 10, trace_root, 32);
+    std::memcpy(stream.data() + HEAD_STREAM, inner_public, 4 * (size_t)s.NP);
+    h.inputs.assign(16 * s.HD, 0u);
+    uint32_t st[16] = {0};
+    size_t r = 0;
+    auto step = [&]() { for (int j = 0; j < 16; j++) h.inputs[16 * r + j] = from_monty(st[j]); r++; p2_permute(st); };
+    for (size_t i = 0; i < s.A; i++) {
+        for (size_t j = 0; j < 8 && 8 * i + j < stream.size(); j++) st[j] = to_monty(stream[8 * i + j]);
+        step();
+    }
+    for (int j = 0; j < 4; j++) h.alpha[j] = from_monty(st[7 - j]);
+    for (int j = 0; j < 8; j++) st[j] = to_monty(quotient_root[j]);
+    step();
+    for (int j = 0; j < 4; j++) h.zeta[j] = from_monty(st[7 - j]);
+    for (size_t i = 0; i < (size_t)s.W + 4; i++) {
+        for (int j = 0; j < 8; j++) st[j] = to_monty(opened[8 * i + j]);
+        step();
+    }
+    for (int j = 0; j < 4; j++) h.fa[j] = from_monty(st[7 - j]);
+    for (int j = 0; j < 8; j++) h.capacity[j] = from_monty(st[8 + j]);
+}
+// the eight constants from the head's challenges and the four sums the OPENED16 launch leaves (YL YN YQ OFFN, canonical): zeta g_N and OFFQ = OFFN^2 on the host
+void head_constants(const Shape& s, const Head& h, const uint32_t sums[16], uint32_t consts[32]) {
+    std::memcpy(consts, h.fa, 16); std::memcpy(consts + 4, h.zeta, 16);
+    const Ext znx = ext_mul_base(ext_from_canon(h.zeta), two_adic_generator(s.H - s.b)), offn = ext_from_canon(sums + 12), offq = ext_mul(offn, offn);
+    for (int i = 0; i < 4; i++) { consts[8 + i] = from_monty(znx.c[i]); consts[28 + i] = from_monty(offq.c[i]); }
+    std::memcpy(consts + 12, sums, 48); std::memcpy(consts + 24, sums + 12, 16);
+}
+
 // ---------------------------------------------------------------- the one description: shape, programs, interaction tables, machine, and what every entry does with them
-constexpr int N_TABLES[5] = {5, 6, 8, 10, 10};
-inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : N_PUBLIC_O; }
+constexpr int N_TABLES[6] = {5, 6, 8, 10, 10, 11};
+inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : s.kind == HEAD ? s.NP : N_PUBLIC_O; }
 
 // pow_bits is read from INDICES on, W from OPENINGS on.  ROWSUM16, ROWS and P24R have at least 2^6 rows: a keyed machine takes at most 8 tables of one height, and the
 // other eight can all have 2^5 rows; from 2^6 rows on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting where ROWS stands --
 // P24R can still meet eight others, and that shape is refused
-int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s) {
+int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s, uint32_t NP) {
     if (R < 1 || R > MAX_R || F < 0 || F > MAX_F || b < 1 || b > 3 || F + b > MAX_LF || Q < 1 || Q > MAX_Q || 4 * R + F + b > TWO_ADICITY)
         return fail(ZKHIP_ERR_INVALID, "fri16: 1..5 layers, log_final 0..8, log_blowup 1..3 (log_final + log_blowup <= 11), 1..1024 queries, and a domain of at most 2^27 points");
     if (kind >= INDICES && (pow_bits < 0 || pow_bits > 30)) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
     if (kind >= OPENINGS && (W < 8 || W > MAX_OPEN_W || W % 8))
         return fail(ZKHIP_ERR_INVALID, "fri16 openings: a trace width of 8 .. 1024 in multiples of 8 (inner proofs without lookup pairs and with a quotient row of 8 words)");
+    if (kind == HEAD && (NP < 1 || NP > MAX_NP))
+        return fail(ZKHIP_ERR_INVALID, "fri16 head: 1 .. 30 inner public values (the machine's public values are the inner proof's: none cannot be carried, and P2TH has six indicator columns)");
     s = Shape{};
     s.kind = kind; s.R = R; s.F = F; s.b = b; s.lf = F + b; s.H = 4 * R + s.lf; s.Q = Q; s.n_tables = N_TABLES[kind];
     if (kind >= INDICES) { s.pow_bits = pow_bits; s.C = F >= 1 ? (size_t)1 << (F - 1) : 0; s.S = frichip::samples_chip_rows(Q); s.NT = (size_t)R + s.C + s.S; }
     if (kind >= OPENINGS) s.W = W;
+    if (kind == HEAD) { s.NP = NP; s.A = (HEAD_STREAM + NP + 7) / 8; s.HD = s.A + 1 + (size_t)W + 4; }
     size_t layer_paths = 0;                                      // rows of P24L per query: every layer's leaf and path
     for (int l = 0; l < R; l++) layer_paths += (size_t)p24chip::LEAF_ROWS + (size_t)(s.H - 4 * (l + 1));
     const size_t row_paths = (size_t)(W + 15) / 16 + 1 + 2 * (size_t)s.H;      // rows of P24R per query: the two leaves and the two paths
@@ -690,15 +875,16 @@ int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W,
     if (kind < OPENINGS) table(T_QUERIES, lg(Q), TAB_MAIN, Q_PRE);
     else table(T_QUERY16, lg(Q), Q16_MAIN, Q16_PRE);
     table(T_COEFFS, lg((size_t)1 << F), TAB_MAIN, C_PRE);
-    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, ROOTS_PRE16);
-    table(T_P2T, lg(s.NT), p2chip::T_WIDTH, PT_PRE);
+    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, kind == HEAD ? ROOTS_PRE_H : ROOTS_PRE16);
+    table(T_P2T, lg(s.HD + s.NT), p2chip::T_WIDTH, kind == HEAD ? PTH_PRE : PT_PRE);
     table(T_SAMPLES, lg(s.S), frichip::S_MAIN, frichip::S_PRE);
-    table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, RS16_PRE);
+    table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, kind == HEAD ? RS16H_PRE : RS16_PRE);
     if (kind == OPENINGS) table(T_ROWS, std::max(6, lg(Q * (size_t)(W + QROW16) / 4)), TAB_MAIN, ROWS_PRE16);
     else table(T_P24R, std::max(6, lg(Q * row_paths)), p24chip::WIDTH_R, 0u);
-    for (int t = 0; kind == ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
+    table(T_OPENED16, std::max(6, lg((size_t)W + 4)), OP_MAIN16, OPN_PRE);
+    for (int t = 0; kind >= ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
         if (std::count(s.log_rows, s.log_rows + s.n_tables, s.log_rows[t]) > MAX_SAME_HEIGHT)
-            return fail(ZKHIP_ERR_INVALID, "fri16 rowpaths: nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
+            return fail(ZKHIP_ERR_INVALID, std::string(kind == HEAD ? "fri16 head" : "fri16 rowpaths") + ": nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
     return ZKHIP_OK;
 }
 
@@ -707,15 +893,16 @@ std::vector<uint32_t> program_of(const Shape& s, int t) {
     const Kind k = s.kind;
     const uint32_t np = n_public_of(s);
     switch (t) {
-    case T_FOLD16: return k >= OPENINGS ? build_fold16c_program(s.R, s.lf) : build_fold16_program(s.R, s.lf, k >= INDICES, np);
+    case T_FOLD16: return k >= OPENINGS ? build_fold16c_program(s.R, s.lf, np) : build_fold16_program(s.R, s.lf, k >= INDICES, np);
     case T_FINAL: return build_final_program(np);
     case T_P24L: if (k >= PATHS) return *p24chip::program_fri16_layers(np); break;                                 // (LAYERS: a key table)
-    case T_QUERY16: if (k >= OPENINGS) return build_query16_program(); break;                                     // (below: QUERIES, a key table)
-    case T_ROOTS: if (k >= INDICES) return build_roots_program(np); break;                                        // (PATHS: a key table)
-    case T_P2T: return build_p2t_program(np);
+    case T_QUERY16: if (k >= OPENINGS) return k == HEAD ? build_query16h_program(s) : build_query16_program(); break;                                     // (below: QUERIES, a key table)
+    case T_ROOTS: if (k >= INDICES) return build_roots_program(np, s.pre_w[T_ROOTS]); break;                                        // (PATHS: a key table)
+    case T_P2T: return k == HEAD ? build_p2th_program(s) : build_p2t_program(np);
     case T_SAMPLES: return *frichip::samples_chip_program(s.H, s.pow_bits, np);
-    case T_ROWSUM16: return build_rowsum16_program();
-    case T_P24R: if (k == ROWPATHS) return *p24chip::program_fri16_rows(np); break;                               // (OPENINGS: ROWS, a key table)
+    case T_ROWSUM16: return k == HEAD ? build_rowsum16_program(RS16H_PRE, true, np) : build_rowsum16_program();
+    case T_P24R: if (k >= ROWPATHS) return *p24chip::program_fri16_rows(np); break;                               // (OPENINGS: ROWS, a key table)
+    case T_OPENED16: return build_opened16_program(np);
     default: break;                                                                                                // COEFFS
     }
     return build_table_program(np, s.pre_w[t], s.main_w[t]);
@@ -725,8 +912,8 @@ std::vector<uint32_t> program_of(const Shape& s, int t) {
 std::vector<uint32_t> interactions_of(const Shape& s, int t) {
     if (t == T_SAMPLES) return frichip::samples_chip_interactions();
     const Kind k = s.kind;
-    const uint32_t R = (uint32_t)s.R, XQ = fold16_width((uint32_t)s.lf), RM = ROOTS_PRE16, in = PT_PRE + p2chip::IN, o = PT_PRE + p2chip::oute(7), rv = RS16_PRE + RS_V,
-                   rt = RS16_PRE + RS_T;
+    const uint32_t R = (uint32_t)s.R, XQ = fold16_width((uint32_t)s.lf), RM = s.pre_w[T_ROOTS], in = s.pre_w[T_P2T] + p2chip::IN, o = s.pre_w[T_P2T] + p2chip::oute(7),
+                   rv = s.pre_w[T_ROWSUM16] + RS_V, rt = s.pre_w[T_ROWSUM16] + RS_T, rfa = s.pre_w[T_ROWSUM16] + RS_FA;
     Interactions v;
     switch (t) {
     case T_FOLD16:
@@ -761,9 +948,13 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
             v.add(1u, QP_ACT, BUS_Q16, {QC_IDX, QC_XQ, QC_RO, QC_RO + 1, QC_RO + 2, QC_RO + 3});
             v.add(1u, QP_ACT, BUS_AT16, {QP_QN, QC_AT, QC_AT + 1, QC_AT + 2, QC_AT + 3});
             v.add(1u, QP_ACT, BUS_AQ16, {QP_QN, QC_AQ, QC_AQ + 1, QC_AQ + 2, QC_AQ + 3});
-            if (k == ROWPATHS) {                                                                                   // which tree a tag belongs to and at which index it is opened
+            if (k >= ROWPATHS) {                                                                                   // which tree a tag belongs to and at which index it is opened
                 v.add(0u, QP_ACT, BUS_TAG16, {QP_TG0, QP_LN0, QC_IDX});
                 v.add(0u, QP_ACT, BUS_TAG16, {QP_TG1, QP_LN1, QC_IDX});
+            }
+            if (k == HEAD) {                                                                                       // QUERY16H: the constants arrive on the first row
+                const uint32_t bus[5] = {BUS_ZETA, BUS_YL, BUS_YN, BUS_YQ, BUS_OFFN}, col[5] = {QC_ZETA, QC_YL, QC_YN, QC_YQ, QC_OFFN};
+                for (int i = 0; i < 5; i++) v.add(1u, QP_FIRST, bus[i], {col[i], col[i] + 1, col[i] + 2, col[i] + 3});
             }
         }
         break;
@@ -780,6 +971,7 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
             v.add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
             v.add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
         }
+        if (k == HEAD) for (uint32_t j = 0; j < 8; j++) v.add(0u, RT_HM, BUS_HR, {RT_HK + j, RT_ROOT + j});            // the trace root and the quotient root, word by word, to P2TH
         break;
     case T_P2T:
         v.add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
@@ -789,13 +981,32 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
         v.add(0u, PT_ROOT, BUS_TB, {PT_LN, o + 7, o + 6, o + 5, o + 4});
         v.add(0u, PT_SMP, frichip::BUS_S0, {PT_ROW, o + 7, o + 6, o + 5, o + 4});
         v.add(0u, PT_SMP, frichip::BUS_S1, {PT_ROW, o + 3, o + 2, o + 1, o});
+        if (k == HEAD) {                                                                                           // P2TH: roots in, opened values in, zeta and fa out
+            for (uint32_t j = 0; j < 8; j++) v.add(1u, PH_RM + j, BUS_HR, {PH_RK + j, in + j});
+            v.add(1u, PH_OPN, BUS_OV0, {PT_ROW, in, in + 1, in + 2, in + 3});
+            v.add(1u, PH_OPN, BUS_OV1, {PT_ROW, in + 4, in + 5, in + 6, in + 7});
+            v.add(0u, PH_ZM, BUS_ZETA, {o + 7, o + 6, o + 5, o + 4});
+            v.add(0u, PH_FM, BUS_FAH, {o + 7, o + 6, o + 5, o + 4});
+        }
         break;
     case T_ROWSUM16:
         v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
         v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K1, rv + 4, rv + 5, rv + 6, rv + 7});
         v.add(0u, RP_LAST0, BUS_AT16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
         v.add(0u, RP_LAST1, BUS_AQ16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
+        if (k == HEAD) v.add(1u, RP_FIRST, BUS_FAH, {rfa, rfa + 1, rfa + 2, rfa + 3});                                 // ROWSUM16H: fa arrives on the first row
         break;
+    case T_OPENED16: {
+        const uint32_t m = OPN_PRE, y = m + OP_Y, pwn = m + OP_PWN, fa = m + OP_FA;
+        v.add(0u, OQ_ACT, BUS_OV0, {OQ_ROW, m + OP_V, m + OP_V + 1, m + OP_V + 2, m + OP_V + 3});
+        v.add(0u, OQ_ACT, BUS_OV1, {OQ_ROW, m + OP_V + 4, m + OP_V + 5, m + OP_V + 6, m + OP_V + 7});
+        v.add(0u, OQ_ENDL, BUS_YL, {y, y + 1, y + 2, y + 3});
+        v.add(0u, OQ_ENDN, BUS_YN, {y, y + 1, y + 2, y + 3});
+        v.add(0u, OQ_ENDQ, BUS_YQ, {y, y + 1, y + 2, y + 3});
+        v.add(0u, OQ_ENDL, BUS_OFFN, {pwn, pwn + 1, pwn + 2, pwn + 3});
+        v.add(1u, OQ_FIRST, BUS_FAH, {fa, fa + 1, fa + 2, fa + 3});
+        break;
+    }
     default:
         if (k == OPENINGS) v.add(1u, 6u, BUS_ROW16, {0u, 1u, 2u, 3u, 4u, 5u});                                     // ROWS
         else {                                                                                                     // P24R
@@ -816,12 +1027,12 @@ struct Machine { Shape s; keyed::KeyedMachine km; };
 // (P24L's, P24R's and P2T's programs follow the Poseidon2 tables in effect: the cache is dropped when they change)
 std::shared_ptr<const Machine> machine_of(const Shape& s) {
     static std::mutex mu;
-    static std::map<std::array<uint64_t, 7>, std::shared_ptr<const Machine>> cache;
+    static std::map<std::array<uint64_t, 8>, std::shared_ptr<const Machine>> cache;
     static uint64_t cached_gen = ~0ull;
     std::lock_guard<std::mutex> lk(mu);
     const uint64_t gen = g_p2_generation.load();
     if (cached_gen != gen || cache.size() > 64) { cache.clear(); cached_gen = gen; }
-    const std::array<uint64_t, 7> key{(uint64_t)s.kind, (uint64_t)s.R, (uint64_t)s.F, (uint64_t)s.b, (uint64_t)s.Q, (uint64_t)s.pow_bits, (uint64_t)s.W};
+    const std::array<uint64_t, 8> key{(uint64_t)s.kind, (uint64_t)s.R, (uint64_t)s.F, (uint64_t)s.b, (uint64_t)s.Q, (uint64_t)s.pow_bits, (uint64_t)s.W, (uint64_t)s.NP};
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     auto m = std::make_shared<Machine>();
@@ -833,9 +1044,9 @@ std::shared_ptr<const Machine> machine_of(const Shape& s) {
 
 // what the entries of every kind do with a shape
 size_t describe(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, int which, int what, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
-                uint32_t* pre_width, int* table) {
+                uint32_t* pre_width, int* table, uint32_t NP = 0) {
     Shape s;
-    if (which < 0 || which >= N_TABLES[kind] || what < 0 || what > 1 || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
+    if (which < 0 || which >= N_TABLES[kind] || what < 0 || what > 1 || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) return 0;
     const auto m = machine_of(s);
     if (table) *table = m->km.order[which];
     return keyed::describe(m->km, which, what, [](int, int, std::vector<uint32_t>&) {}, out, cap_words, log_rows, main_width, pre_width);
@@ -854,15 +1065,15 @@ int key_upload(zkhip_ctx* ctx, const Shape& s, const std::vector<uint32_t>* pre,
     }
     return keyed::key_setup(ctx, m->km, d_pre, prm, key, vk);
 }
-size_t proof_size(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const zkhip_params* prm) {
+size_t proof_size(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const zkhip_params* prm, uint32_t NP = 0) {
     Shape s;
-    if (!prm || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) return 0;
+    if (!prm || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) return 0;
     return keyed::proof_size(machine_of(s)->km, prm, n_public_of(s));
 }
 int verify(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const uint8_t* proof, size_t len, const uint32_t* public_values, const uint32_t vk[8],
-           const zkhip_params* prm, int* reason, const char* who) {
+           const zkhip_params* prm, int* reason, const char* who, uint32_t NP = 0) {
     Shape s;
-    if (!proof || !public_values || !vk || !prm || shape_of(kind, R, F, b, Q, pow_bits, W, s) != ZKHIP_OK) {
+    if (!proof || !public_values || !vk || !prm || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) {
         if (reason) *reason = 1;
         return fail(ZKHIP_ERR_VERIFY, std::string(who) + ": bad arguments");
     }
@@ -878,6 +1089,8 @@ __global__ void __launch_bounds__(64) fri16_openings_rows_kernel_batch(const ope
 __global__ void __launch_bounds__(64) fri16_openings_rows_tall_kernel_batch(const openings_rows_bargs* __restrict__ zk_arr) { fri16_openings_rows_body<true>(zk_arr[blockIdx.z].a); }
 struct xq_cols_bargs { XqColsArgs a; static xq_cols_bargs make(XqColsArgs a) { return xq_cols_bargs{a}; } };
 __global__ void __launch_bounds__(64) fri16_xq_cols_kernel_batch(const xq_cols_bargs* __restrict__ zk_arr) { fri16_xq_cols_body(zk_arr[blockIdx.z].a); }
+struct opened_rows_bargs { OpenedRowsArgs a; static opened_rows_bargs make(OpenedRowsArgs a) { return opened_rows_bargs{a}; } };
+__global__ void __launch_bounds__(OPENED_LANES) fri16_opened_rows_kernel_batch(const opened_rows_bargs* __restrict__ zk_arr) { fri16_opened_rows_body(zk_arr[blockIdx.z].a); }
 
 }  // namespace
 }  // namespace fri16
@@ -967,7 +1180,7 @@ static int fri16_paths_check_view(const fri16::Shape& s, int inner_hash_width, c
 static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::Chain& c, const uint32_t* view_betas, const uint32_t* view_indices, const uint32_t* counts,
                                  uint32_t* d_p2t, uint32_t* d_samples, uint32_t* d_qmain, uint32_t* d_rmain, uint32_t* status) {
     const size_t R = (size_t)s.R, Q = s.Q, ni = (Q + 3) & ~(size_t)3, nr = (R + 3) & ~(size_t)3;
-    const size_t o_words = 16 * s.NT, o_betas = o_words + 8 * s.S, o_vbetas = o_betas + 4 * R, o_vidx = o_vbetas + 4 * R, o_counts = o_vidx + ni, o_status = o_counts + nr, up_words = o_status + 4;
+    const size_t o_words = c.inputs.size(), o_betas = o_words + 8 * s.S, o_vbetas = o_betas + 4 * R, o_vidx = o_vbetas + 4 * R, o_counts = o_vidx + ni, o_status = o_counts + nr, up_words = o_status + 4;
     void* stage;
     ZK_TRY(ctx_reserve(ctx, S_REC_E, up_words * 4, &stage));
     uint32_t* d = (uint32_t*)stage;
@@ -984,7 +1197,7 @@ static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fr
     p2chip::Fri16TranscriptArgs a{};
     a.chain_inputs = d; a.words = d + o_words; a.drawn_betas = d + o_betas; a.view_betas = view_betas ? d + o_vbetas : nullptr; a.view_indices = view_indices ? d + o_vidx : nullptr;
     a.counts = counts ? d + o_counts : nullptr;
-    a.n_chain = (uint32_t)s.NT; a.n_sample_rows = (uint32_t)s.S; a.R = (uint32_t)R; a.Q = (uint32_t)Q; a.index_bits = (uint32_t)s.H;
+    a.n_chain = (uint32_t)(c.inputs.size() / 16); a.n_sample_rows = (uint32_t)s.S; a.R = (uint32_t)R; a.Q = (uint32_t)Q; a.index_bits = (uint32_t)s.H;
     a.p2t_rows = d_p2t ? (uint64_t)1 << s.log_rows[fri16::T_P2T] : 0; a.samples_rows = (uint64_t)1 << s.log_rows[fri16::T_SAMPLES];
     a.queries_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERIES]; a.roots_rows = (uint64_t)1 << s.log_rows[fri16::T_ROOTS];
     a.p2t = d_p2t; a.samples = d_samples; a.queries_main = d_qmain; a.roots_main = d_rmain; a.status = d + o_status;
@@ -1097,6 +1310,33 @@ static int fri16_rowpaths_check_paths(const fri16::Shape& s, const uint32_t* tpa
     return ZKHIP_OK;
 }
 
+// OPENED16 in one launch from one staging block (the opened values, fa); sums: YL YN YQ OFFN (canonical), where the lanes at the segment ends leave them -- one copy back
+static int fri16_head_opened_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* opened, const uint32_t fa[4], uint32_t* d_opened, uint32_t sums[16]) {
+    const size_t nv = 8 * ((size_t)s.W + 4), words = nv + 4 + 16;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, words * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(words, 0u);
+        std::memcpy(up.data(), opened, nv * 4);
+        std::memcpy(up.data() + nv, fa, 16);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), words * 4));
+    }
+    fri16::OpenedRowsArgs a{};
+    a.opened = d; a.fa = d + nv; a.W = s.W; a.rows = (uint64_t)1 << s.log_rows[fri16::T_OPENED16]; a.trace = d_opened; a.sums = d + nv + 4;
+    ZK_LAUNCH(fri16::fri16_opened_rows_kernel, fri16::fri16_opened_rows_kernel_batch, fri16::opened_rows_bargs, dim3(1), dim3(fri16::OPENED_LANES), 0, ctx->stream, a);
+    ZK_HIP(hipGetLastError());
+    return dev_d2h(ctx, sums, a.sums, 64);
+}
+static int fri16_head_check_inputs(const fri16::Shape& s, const uint32_t* inner_public, const uint32_t* trace_root, const uint32_t* quotient_root, const uint32_t* opened,
+                                   const char* who) {
+    if (!inner_public || !trace_root || !quotient_root || !opened) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(inner_public, s.NP)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner public values must be canonical");
+    if (!fri16::canonical(opened, 8 * ((size_t)s.W + 4))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the opened values must be canonical");
+    if (!fri16::canonical(trace_root, 8) || !fri16::canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+    return ZKHIP_OK;
+}
+
 // ---------------------------------------------------------------- the provers' stages.  Each reserves what it makes, launches, and refuses in the caller's name (who).
 // FOLD16's and FINAL's traces (S_REC_A, S_REC_B): what every prover starts with
 static int fri16_reserve_fold_final(zkhip_ctx* ctx, const fri16::Shape& s, uint32_t** d_fold, uint32_t** d_final) {
@@ -1128,12 +1368,13 @@ static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std
 // draw, a witness that fails the proof of work
 static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness,
                                   const uint32_t* betas, const uint32_t* indices, const fri16::PathPlan& pl, uint32_t* d_qmain, uint32_t* d_rmain, const uint32_t** d_p2t,
-                                  const uint32_t** d_samples, const char* who) {
+                                  const uint32_t** d_samples, const char* who, const std::vector<uint32_t>* head_inputs = nullptr) {      // head_inputs: the HD rows in front (HEAD)
     void *t_p2t, *t_smp;
     ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
     ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
     fri16::Chain c;
     fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
+    if (head_inputs) c.inputs.insert(c.inputs.begin(), head_inputs->begin(), head_inputs->end());
     uint32_t status = 0;
     ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status));
     if (status & 1u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges are not the ones the transcript draws from these roots and this capacity");
@@ -1653,6 +1894,132 @@ int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int
 int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
     return fri16::verify(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, public_values, vk, prm, reason, "verify_fri16_rowpaths");
+}
+
+// ---------------------------------------------------------------- HEAD
+size_t zkhip_fri16_head_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                 uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
+    return fri16::describe(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+}
+
+int zkhip_fri16_head_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                              uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_head_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_head_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_head_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_head_key_host"));
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+}
+
+// (the row-paths key's slots, and one of its own for OPENED16's schedule)
+static const int FRI16_HEAD_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B, S_REC_H};
+
+int zkhip_fri16_head_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                         uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
+                         const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_head_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_head_key: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_head_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_head_key"));
+    return fri16::key_upload(ctx, s, pre, FRI16_HEAD_KEY_SLOTS, prm, key, vk);
+}
+
+size_t zkhip_fri16_head_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
+    return fri16::proof_size(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+}
+
+int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                const uint32_t* inner_public, const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* opened, const uint32_t* roots,
+                                const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2th, uint32_t* d_samples, uint32_t* d_opened, uint32_t constants[32],
+                                uint32_t capacity[8]) {
+    CHECK_CTX(ctx);
+    const char* who = "fri16_head_gen_traces";
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16_head_check_inputs(s, inner_public, trace_root, quotient_root, opened, who));
+    if (!d_p2th || !d_samples || !d_opened || !constants || !capacity || ((uintptr_t)d_p2th | (uintptr_t)d_samples | (uintptr_t)d_opened) % 16)
+        return fail(ZKHIP_ERR_INVALID, "fri16_head_gen_traces: 16-byte aligned dense traces (352, 288 and 36 columns), constants and capacity");
+    fri16::Head h;
+    fri16::walk_head(s, inner_public, trace_root, quotient_root, opened, h);
+    ZK_TRY(fri16_indices_check_inputs(s, h.capacity, roots, final_poly, witness, who));
+    uint32_t sums[16];
+    ZK_TRY(fri16_head_opened_impl(ctx, s, opened, h.fa, d_opened, sums));
+    fri16::head_constants(s, h, sums, constants);
+    std::memcpy(capacity, h.capacity, 32);
+    fri16::Chain c;
+    fri16::walk_chain(s, h.capacity, roots, final_poly, witness, c);
+    c.inputs.insert(c.inputs.begin(), h.inputs.begin(), h.inputs.end());
+    uint32_t status = 0;
+    return fri16_transcript_impl(ctx, s, c, nullptr, nullptr, nullptr, d_p2th, d_samples, nullptr, nullptr, &status);
+}
+
+int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                           uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    using namespace fri16;
+    const char* who = "prove_fri16_head";
+    Shape s;
+    if (n_inner_public > MAX_NP) return fail(ZKHIP_ERR_INVALID, "prove_fri16_head: more than 30 inner public values");
+    ZK_TRY(shape_of(HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_head: null argument");
+    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
+    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
+    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
+    ZK_TRY(check_openings_constants(s, constants, who));
+    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, who));
+    ZK_TRY(fri16_head_check_inputs(s, inner_public, trace_root, quotient_root, opened, who));
+    const size_t Q = s.Q;
+    uint32_t *t_fold, *t_final;
+    void* t_p24r;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
+    Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block; OPENED16
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16}, z));
+    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
+    // the head first: the chain from the all-zero state, OPENED16, the eight constants and the capacity DERIVED -- refused here, before anything is proven: a derived
+    // constant or capacity that is not the view's; then all zkhip_prove_fri16_rowpaths refuses, on the derived values
+    Head h;
+    walk_head(s, inner_public, trace_root, quotient_root, opened, h);
+    uint32_t sums[16], derived[32];
+    ZK_TRY(fri16_head_opened_impl(ctx, s, opened, h.fa, z.at(T_OPENED16), sums));
+    head_constants(s, h, sums, derived);
+    static const char* const names[8] = {"fa", "zeta", "zeta g_N", "YL", "YN", "YQ", "OFFN", "OFFQ"};
+    for (int k = 0; k < 8; k++)
+        if (std::memcmp(derived + 4 * k, constants + 4 * k, 16) != 0)
+            return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constant " + names[k] + " derived from the head of the transcript is not the view's");
+    if (std::memcmp(h.capacity, capacity, 32) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the capacity the head of the transcript leaves is not the view's");
+    PathPlan pl;
+    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr;
+    ZK_TRY(plan_paths(s, indices, paths, pl));
+    ZK_TRY(fri16_transcript_stage(ctx, s, h.capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who, &h.inputs));
+    {
+        const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
+        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, z.at(T_ROOTS) + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
+    }
+    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, derived, t_fold, t_final, &t_rs, &t_q, &d_rows, who));
+    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
+    std::vector<uint32_t> ends;
+    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
+    for (size_t p = 0; p < 2 * Q; p++)
+        if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
+            return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") + " tree: the opened row's path does not end in the root");
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r, z.at(T_OPENED16)};
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, inner_public, n_public_of(s), prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_head(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                            uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    return fri16::verify(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_head", n_inner_public);
 }
 
 }  // extern "C"

@@ -76,6 +76,16 @@ struct XqColsArgs {
     const uint32_t* indices; uint32_t Q, R, H;
     uint64_t rows; uint32_t* trace; uint64_t ld; uint32_t col;
 };
+// the head machine: OPENED16 (V[8] FA[4] FA2[4] PW[4] T[4] PT[4] Y[4] PWN[4]), dense.  One row per 8 opened words (two extension values) in transcript order:
+// W / 2 rows of values at zeta, W / 2 of values at zeta g, 4 of quotient values -- three segments, each summed in fa from its own first row
+constexpr uint32_t OP_V = 0, OP_FA = 8, OP_FA2 = 12, OP_PW = 16, OP_T = 20, OP_PT = 24, OP_Y = 28, OP_PWN = 32, OP_MAIN16 = 36, OPENED_LANES = 256;
+struct OpenedRowsArgs {
+    const uint32_t* opened;             // canonical words on the device, 16-byte aligned: [W + 4][8]
+    const uint32_t* fa;                 // canonical [4]
+    uint32_t W; uint64_t rows;          // the table's height, >= W + 4
+    uint32_t* trace;                    // Montgomery, dense, 16-byte aligned
+    uint32_t* sums;                     // [4][4] CANONICAL: YL, YN, YQ, OFFN = fa^W, written by the lanes at the segment ends
+};
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ Ext ld_ext(const uint32_t* p) {
@@ -378,6 +388,107 @@ __device__ __forceinline__ void fri16_xq_cols_body(const XqColsArgs& a) {
     st4(a.trace + r * a.ld + a.col, xq, 0u, 0u, 0u);
 }
 __global__ void __launch_bounds__(64) fri16_xq_cols_kernel(XqColsArgs a) { fri16_xq_cols_body(a); }
+
+// ---- the head machine's OPENED16 rows.  Row r holds two opened extension values V0, V1; with p its position in its segment (values at zeta, values at zeta g,
+// quotient values): PW = fa^(2 p), T = V0 + fa V1, PT = PW T, Y = the segment's sum of PT up to this row, PWN = PW fa^2.  Y at a segment's end is the sum of
+// fa^j value_j over the segment; PWN at the end of the first one is fa^W.
+__device__ __forceinline__ Ext ext_pow_dev(Ext a, uint32_t e) {
+    Ext r = Ext{{MONTY_R1, 0u, 0u, 0u}};
+#pragma unroll 1
+    while (e) { if (e & 1u) r = ext_mul_dev(r, a); a = ext_mul_dev(a, a); e >>= 1; }
+    return r;
+}
+__device__ __forceinline__ void opened_load(const OpenedRowsArgs& a, uint32_t r, uint32_t v[8]) {
+    const uint4 lo = *reinterpret_cast<const uint4*>(a.opened + 8u * (size_t)r), hi = *reinterpret_cast<const uint4*>(a.opened + 8u * (size_t)r + 4);
+    v[0] = dmul(lo.x, MONTY_R2); v[1] = dmul(lo.y, MONTY_R2); v[2] = dmul(lo.z, MONTY_R2); v[3] = dmul(lo.w, MONTY_R2);
+    v[4] = dmul(hi.x, MONTY_R2); v[5] = dmul(hi.y, MONTY_R2); v[6] = dmul(hi.z, MONTY_R2); v[7] = dmul(hi.w, MONTY_R2);
+}
+__device__ __forceinline__ void opened_store(const OpenedRowsArgs& a, uint32_t r, const uint32_t v[8], const Ext& fa, const Ext& fa2, const Ext& pw, const Ext& t, const Ext& pt,
+                                             const Ext& y, const Ext& pwn) {
+    uint32_t* row = a.trace + (uint64_t)r * OP_MAIN16;
+    st4(row + OP_V, v[0], v[1], v[2], v[3]); st4(row + OP_V + 4, v[4], v[5], v[6], v[7]);
+    st_ext(row + OP_FA, fa); st_ext(row + OP_FA2, fa2); st_ext(row + OP_PW, pw); st_ext(row + OP_T, t); st_ext(row + OP_PT, pt); st_ext(row + OP_Y, y); st_ext(row + OP_PWN, pwn);
+    const uint32_t half = a.W >> 1;
+    auto canon4 = [&](uint32_t* dst, const Ext& e) { st4(dst, canon_dev(e.c[0]), canon_dev(e.c[1]), canon_dev(e.c[2]), canon_dev(e.c[3])); };
+    if (r + 1u == half) { canon4(a.sums, y); canon4(a.sums + 12, pwn); }
+    if (r + 1u == a.W) canon4(a.sums + 4, y);
+    if (r == a.W + 3u) canon4(a.sums + 8, y);
+}
+// the padding rows, shared among `lanes` lanes: FA and FA2 in their columns (FA' = FA holds on every transition), zero elsewhere
+__device__ __forceinline__ void opened_padding_rows(const OpenedRowsArgs& a, uint32_t g, uint32_t lanes, const Ext& fa, const Ext& fa2) {
+    for (uint64_t r = (uint64_t)a.W + 4u + g; r < a.rows; r += lanes) {
+        uint32_t* row = a.trace + r * OP_MAIN16;
+        st4(row + OP_V, 0u, 0u, 0u, 0u); st4(row + OP_V + 4, 0u, 0u, 0u, 0u);
+        st_ext(row + OP_FA, fa); st_ext(row + OP_FA2, fa2);
+#pragma unroll
+        for (uint32_t c = OP_PW; c < OP_MAIN16; c += 4) st4(row + c, 0u, 0u, 0u, 0u);
+    }
+}
+// The scan form, ONE workgroup of OPENED_LANES lanes: a lane per row computes T and fa^(2 p) from its position (square-and-multiply, at most 9 steps), the lanes of a
+// wave take an inclusive segmented sum of PW T with a cross-lane scan (a lane takes from lane - d only while both its position in its segment and its lane number
+// are >= d), the waves' last values go through LDS and every lane adds what reaches its wave from the waves before; with more than OPENED_LANES rows (W > 504) the
+// workgroup takes rounds, the running value carried in a register every lane computes alike.  No second workgroup, nothing to wait for.
+__device__ __forceinline__ void fri16_opened_rows_body(const OpenedRowsArgs& a) {
+    constexpr uint32_t WAVES = OPENED_LANES / 64u;
+    __shared__ uint32_t tot[WAVES][4];
+    __shared__ uint32_t reaches_back[WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, half = a.W >> 1, active = a.W + 4u;
+    const Ext fa = ld_ext(a.fa), fa2 = ext_mul_dev(fa, fa);
+    Ext run = ext_zero();                                              // the sum that reaches the round's first row from the rounds before
+#pragma unroll 1
+    for (uint32_t base = 0; base < active; base += OPENED_LANES) {
+        const uint32_t r = base + tid;
+        const bool act = r < active;
+        const uint32_t first = r < half ? 0u : (r < a.W ? half : a.W), p = act ? r - first : 0u, reach = p < lane ? p : lane;
+        uint32_t v[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) v[s] = 0u;
+        if (act) opened_load(a, r, v);
+        const Ext t = ext_add_dev(Ext{{v[0], v[1], v[2], v[3]}}, ext_mul_dev(fa, Ext{{v[4], v[5], v[6], v[7]}}));
+        const Ext pw = ext_pow_dev(fa2, p), pt = act ? ext_mul_dev(pw, t) : ext_zero();
+        Ext y = pt;
+#pragma unroll 1
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const Ext o = shfl_up_ext(y, d, 64);
+            if (reach >= d) y = ext_add_dev(y, o);
+        }
+        if (lane == 63u) { tot[wave][0] = y.c[0]; tot[wave][1] = y.c[1]; tot[wave][2] = y.c[2]; tot[wave][3] = y.c[3]; reaches_back[wave] = p > 63u ? 1u : 0u; }
+        __syncthreads();
+        Ext c = run, mine = ext_zero();
+#pragma unroll
+        for (uint32_t w = 0; w < WAVES; w++) {
+            if (w == wave) mine = c;
+            Ext full = Ext{{tot[w][0], tot[w][1], tot[w][2], tot[w][3]}};
+            if (reaches_back[w]) full = ext_add_dev(full, c);
+            c = full;
+        }
+        run = c;
+        if (p > lane) y = ext_add_dev(y, mine);
+        __syncthreads();                                               // (the next round writes tot again)
+        if (act) opened_store(a, r, v, fa, fa2, pw, t, pt, y, ext_mul_dev(pw, fa2));
+    }
+    opened_padding_rows(a, tid, OPENED_LANES, fa, fa2);
+}
+// The plain form: one lane walks all rows, the others wait for the padding rows (tools/fri16_head_forms.hip checks the scan form against it and times both)
+__device__ __forceinline__ void fri16_opened_rows_plain_body(const OpenedRowsArgs& a) {
+    const uint32_t tid = threadIdx.x, half = a.W >> 1, active = a.W + 4u;
+    const Ext fa = ld_ext(a.fa), fa2 = ext_mul_dev(fa, fa);
+    if (tid == 0u) {
+        Ext pw = ext_zero(), y = ext_zero();
+#pragma unroll 1
+        for (uint32_t r = 0; r < active; r++) {
+            if (r == 0u || r == half || r == a.W) { pw = Ext{{MONTY_R1, 0u, 0u, 0u}}; y = ext_zero(); }
+            uint32_t v[8];
+            opened_load(a, r, v);
+            const Ext t = ext_add_dev(Ext{{v[0], v[1], v[2], v[3]}}, ext_mul_dev(fa, Ext{{v[4], v[5], v[6], v[7]}})), pt = ext_mul_dev(pw, t), pwn = ext_mul_dev(pw, fa2);
+            y = ext_add_dev(y, pt);
+            opened_store(a, r, v, fa, fa2, pw, t, pt, y, pwn);
+            pw = pwn;
+        }
+    }
+    opened_padding_rows(a, tid, blockDim.x, fa, fa2);
+}
+__global__ void __launch_bounds__(OPENED_LANES) fri16_opened_rows_kernel(OpenedRowsArgs a) { fri16_opened_rows_body(a); }
 #endif
 
 }  // namespace fri16

@@ -179,6 +179,8 @@ struct FriViewSink {
     uint32_t *trace_rows = nullptr, *quotient_rows = nullptr, *constants = nullptr;
     // row paths (zkhip_fri16_view_row_paths): per query the trace row's and the quotient row's Merkle path ([Q][H][8] each) as the proof holds them, and the two roots
     uint32_t *trace_paths = nullptr, *quotient_paths = nullptr, *trace_root = nullptr, *quotient_root = nullptr;
+    // head (zkhip_fri16_view_head): the opened extension values in the order they are observed -- values at zeta, at zeta g, quotient values, [2 width + 8][4] -- and alpha
+    uint32_t *opened = nullptr, *alpha = nullptr;
 };
 
 static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
@@ -256,6 +258,13 @@ static int verify_shard_impl(const uint8_t* proof, size_t len, int log_n, uint32
     for (size_t j = 0; j < wp; j++) ch.observe_ext(opl[j]);
     for (size_t j = 0; j < wp; j++) ch.observe_ext(opn[j]);
     for (size_t j = 0; j < QW; j++) ch.observe_ext(opq[j]);
+    if (sink && sink->opened) {
+        const Ext* segs[3] = {loc.data(), nxt.data(), opq};
+        const size_t lens[3] = {width, width, QW};
+        size_t o = 0;
+        for (int g = 0; g < 3; g++) for (size_t j = 0; j < lens[g]; j++) for (int i = 0; i < 4; i++) sink->opened[o++] = from_monty(segs[g][j].c[i]);
+        for (int i = 0; i < 4; i++) sink->alpha[i] = from_monty(alpha.c[i]);
+    }
 
     // (a) the AIR identity at zeta: folded constraints / Z_H == sum_k zps_k * q_k
     {
@@ -623,6 +632,29 @@ int zkhip_fri16_view_row_paths(const uint8_t* proof, size_t len, int log_n, uint
     sink.fold16 = true;
     sink.final_poly = final_poly.data();
     sink.trace_paths = trace_paths; sink.quotient_paths = quotient_paths; sink.trace_root = trace_root; sink.quotient_root = quotient_root;
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
+}
+
+// ... and the head of the transcript (the head machine of fri16_chip.hip): the opened extension values [2 width + 8][4] in the order the verifier observes them (values at
+// zeta, values at zeta g, quotient values) and alpha.  Refused, each with its message: lookup pairs, a program (version 7), a code group (CW != 0), the width-16 hash.
+int zkhip_fri16_view_head(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
+                          uint32_t* opened, uint32_t alpha[4]) {
+    if (!prm || !opened || !alpha) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: null argument");
+    Shape sh;
+    if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    if (prm->logup_pairs) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with lookup pairs are not taken (logup_pairs = 0 only)");
+    if (proof && len >= 8 && ((const uint32_t*)proof)[1] == 7u) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a program (version 7) are not taken (their header has the program's digest)");
+    if (sh.cw) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a code group (CW != 0) are not taken (their header and their first root differ)");
+    if (sh.hw != 24) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with the width-16 hash are not taken (the head machine's header names the width-24 hash)");
+    const size_t Q = (size_t)prm->num_queries;
+    std::vector<uint32_t> betas(4 * (size_t)sh.R), final_poly((size_t)4 << sh.F), indices(Q), values(4 * Q), siblings(60 * Q * (size_t)sh.R);
+    FriViewSink sink{betas.data(), nullptr, indices.data(), values.data(), siblings.data(), sh.R, nullptr, nullptr, nullptr};
+    sink.fold16 = true;
+    sink.final_poly = final_poly.data();
+    sink.opened = opened; sink.alpha = alpha;
     int why = 0;
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }

@@ -898,6 +898,56 @@ class Context:
                                                   buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 HEAD machine (the head of the transcript in-circuit: P2TH, OPENED16, the constants over buses)
+    def fri16_head_key(self, view, params=None):
+        """zkhip_fri16_head_key: the key of the fold-16 head machine, committed on the device -- from the shape, the inner proof's grinding bits, trace width and
+        number of public values, the final coefficients, the layer roots, the trace root and the quotient root: no opened word, no constant, no challenge -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+        _, _, troot, qroot = _fri16_rowpaths_arrays(view)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_head_key(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
+                                            *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_head_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, pubs, troot, qroot, opened, roots, final_poly, witness):
+        """zkhip_fri16_head_gen_traces: the P2TH, SAMPLES and OPENED16 main traces from the inner public values, the two roots, the opened values [2 W + 8][4], the layer
+        roots, the final coefficients and the witness alone -> (P2TH [2^lr][352], SAMPLES [2^lr][288], OPENED16 [2^lr][36] (canonical words, downloaded), the eight
+        derived constants [8][4], the capacity the commit phase finds [8])"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        NP = len(pubs)
+        lns = {d[4]: d[1] for d in (fri16_head_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, 0) for which in range(11))}
+        pv, tr, qr, op, rt, fp = u(pubs), u(troot), u(qroot), u(opened), u(roots), u(final_poly)
+        assert tr.size == qr.size == 8 and op.size == 8 * (W + 4) and rt.size == 8 * R and fp.size == 4 << F
+        p2th, smp, opn = self.alloc(352 << lns[6]), self.alloc(288 << lns[7]), self.alloc(36 << lns[10])
+        consts, cap = np.zeros(32, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_head_gen_traces(self.handle, R, F, log_blowup, n_queries, pow_bits, W, NP, *[a.ctypes.data_as(u32p) for a in (pv, tr, qr, op, rt, fp)],
+                                                   int(witness), C.c_void_p(p2th.ptr), C.c_void_p(smp.ptr), C.c_void_p(opn.ptr), consts.ctypes.data_as(u32p),
+                                                   cap.ctypes.data_as(u32p)))
+        return p2th.download().reshape(-1, 352), smp.download().reshape(-1, 288), opn.download().reshape(-1, 36), consts.reshape(8, 4), cap
+
+    def prove_fri16_head(self, key, view, params=None):
+        """zkhip_prove_fri16_head: everything prove_fri16_rowpaths states, and "the transcript starts from the all-zero state, absorbs the header, the trace root, THESE
+        public values, the quotient root and the opened values, and the eight constants and the commit phase's capacity are what it gives".  view: a row-paths view with
+        "pubs" (the inner proof's public values) and "opened" [2 W + 8][4].  The proof's public values are view["pubs"].  Refused before anything is proven: all
+        prove_fri16_rowpaths refuses, a derived constant or capacity that is not the view's, values that are not canonical, more than 30 public values or none"""
+        params = params or Params(1, 100, 16)
+        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
+        W, trows, qrows, consts = _fri16_openings_arrays(view)
+        tpaths, qpaths, troot, qroot = _fri16_rowpaths_arrays(view)
+        pubs, opened = _fri16_head_arrays(view)
+        pb = int(view["pow_bits"])
+        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
+        assert cap.size == 8
+        size = self.lib.zkhip_fri16_head_proof_size(*shape, pb, W, pubs.size, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_head(self.handle, key.handle, *shape, hw, pb, W, pubs.size, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+                                              paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]),
+                                              *[a.ctypes.data_as(u32p) for a in (trows, qrows, consts, tpaths, qpaths, troot, qroot, pubs, opened)], C.byref(params),
+                                              buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1806,6 +1856,50 @@ def verify_fri16_rowpaths(proof, public_values, R, F, log_blowup, n_queries, pow
     """zkhip_verify_fri16_rowpaths: the shape, the inner proof's grinding bits and trace width, the 40 public values (capacity, then the eight constants), the key
     -> (rc, reason).  Host only."""
     return _verify("verify_fri16_rowpaths", proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk=vk, params=params, n_public=40)
+
+
+def _fri16_head_arrays(view):
+    """a head view -> (the inner proof's public values flat, the opened values [2 W + 8][4] flat)"""
+    u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+    pubs, opened = u(view["pubs"]), u(view["opened"])
+    assert opened.size == 8 * (int(view["W"]) + 4)
+    return pubs, opened
+
+
+def fri16_view_head(proof, log_n, width, public_values=(), params=None):
+    """zkhip_fri16_view_head: the head of a fold-by-16 proof's transcript -> {"opened": [2 W + 8][4] in the order the verifier observes them, "alpha": [4],
+    "pubs": the public values}, or raises if the proof is rejected, has lookup pairs, a program, a code group or the width-16 hash.  Host only."""
+    params = params or _lib.segment_params()
+    lib = _lib.load()
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+    opened, alpha = np.zeros(4 * (2 * width + 8), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    check(lib.zkhip_fri16_view_head(pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size, C.byref(params), opened.ctypes.data_as(u32p),
+                                    alpha.ctypes.data_as(u32p)))
+    return {"opened": opened.reshape(-1, 4).tolist(), "alpha": alpha.tolist(), "pubs": [int(x) for x in pv]}
+
+
+def fri16_head_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kind):
+    """zkhip_fri16_head_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..10) of the fold-16 head machine
+    -> (words, log rows, main width, preprocessed width, table number: the row-paths machine's with 10 OPENED16); raises with the library's message for a shape it refuses"""
+    return _describe("fri16_head_describe", R, F, log_blowup, n_queries, pow_bits, W, NP, which=which, kind=kind)
+
+
+def fri16_head_key_host(view, params=None):
+    """zkhip_fri16_head_key_host: the fold-16 head machine's key of a view (with "pow_bits", "W", "troot", "qroot", "pubs"), without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
+    _, _, troot, qroot = _fri16_rowpaths_arrays(view)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_head_key_host(*shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
+                                                *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_head(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
+    """zkhip_verify_fri16_head: the shape, the inner proof's grinding bits and trace width, the inner proof's public values (the machine's own), the key
+    -> (rc, reason).  Host only."""
+    return _verify("verify_fri16_head", proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, len(inner_public), vk=vk, params=params)
 
 
 def fri_view_transcript(proof, log_n, width, public_values=(), params=None):
