@@ -100,13 +100,54 @@ __device__ __forceinline__ void hash_rows_vec_body(const uint32_t* __restrict__ 
     d[0] = make_uint4(s[0], s[1], s[2], s[3]);
     d[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
-__device__ __forceinline__ void hash_rows_vec_kernel_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_body<true>(mat, ld, width, height, digests); }
+// The same rows through the permutation's sponge forms (p2_permute_mx_form), which leave out what the next block overwrites: every
+// permutation but the last is an ABSORB (an ABSORB_RATE before a last half block, which keeps s[4..7]), the last one a SQUEEZE, and the
+// capacity starts as cap0, the zero words in the form those pass on.  The tail rule is hash_rows_vec_body<true>'s.
+__device__ __forceinline__ void hash_rows_sponge_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) {
+    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row - __lane_id() >= height) return;
+    const uint4* rp = reinterpret_cast<const uint4*>(mat + (row < height ? row : height - 1) * ld);
+    uint32_t s[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { s[i] = 0u; s[8 + i] = (uint32_t)P2T.mx16.cap0[i]; }
+    const uint32_t nb = width / 8, half = width & 4u;
+    uint32_t q = 0;
+    for (; q + 1 < nb; q++) {
+        const uint4 v0 = rp[2 * q], v1 = rp[2 * q + 1];
+        s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
+        s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+        p2_permute_mx_form<P2MxForm::ABSORB>(s);
+    }
+    if (half && nb) {
+        const uint4 v0 = rp[2 * q], v1 = rp[2 * q + 1];
+        s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
+        s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+        p2_permute_mx_form<P2MxForm::ABSORB_RATE>(s);
+        q++;
+    }
+    if (width) {
+        const uint4 v0 = rp[2 * q];
+        s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
+        if (!half) {                        // (a last half block keeps the other four rate words: overwrite mode)
+            const uint4 v1 = rp[2 * q + 1];
+            s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+        }
+        p2_permute_mx_form<P2MxForm::SQUEEZE>(s);
+    }
+    if (row >= height) return;
+    uint4* d = reinterpret_cast<uint4*>(digests + row * 8);
+    d[0] = make_uint4(s[0], s[1], s[2], s[3]);
+    d[1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
+__device__ __forceinline__ void hash_rows_vec_kernel_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_sponge_body(mat, ld, width, height, digests); }
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) hash_rows_vec_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_kernel_body(mat, ld, width, height, digests); }
 struct hash_rows_vec_kernel_bargs { const uint32_t* mat; uint64_t ld; uint32_t width; uint64_t height; uint32_t* digests; static hash_rows_vec_kernel_bargs make(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* digests) { return hash_rows_vec_kernel_bargs{mat, ld, width, height, digests}; } };
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) hash_rows_vec_kernel_batch(const hash_rows_vec_kernel_bargs* __restrict__ zk_arr) { const hash_rows_vec_kernel_bargs& zk_b = zk_arr[blockIdx.z]; hash_rows_vec_kernel_body(zk_b.mat, zk_b.ld, zk_b.width, zk_b.height, zk_b.digests); }
 #ifdef ZKHIP_AB_HOOKS
 // the all-VALU permutation in the same kernel, for A/B timing (ZKHIP_HASH_VEC_VALU set)
 __global__ void __launch_bounds__(256) hash_rows_vec_valu_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_body<false>(mat, ld, width, height, digests); }
+// the closed matrix-core permutation per block where the sponge forms stand, for A/B timing (ZKHIP_HASH_VEC_CLOSED set)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) hash_rows_vec_closed_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t height, uint32_t* __restrict__ digests) { hash_rows_vec_body<true>(mat, ld, width, height, digests); }
 #endif
 
 // Several matrices of one height whose widths and pitches are multiples of 4 words (16-byte aligned rows): the sponge absorbs the
@@ -207,6 +248,11 @@ hipError_t launch_hash_rows(const LeafArgs& a, hipStream_t s) {
     static const bool valu = getenv("ZKHIP_HASH_VEC_VALU") != nullptr;
     if (vec && valu) {
         hash_rows_vec_valu_kernel<<<grid, block, 0, s>>>(m0.ptr, m0.ld, m0.width, a.height, a.digests);
+        return hipGetLastError();
+    }
+    static const bool closed = getenv("ZKHIP_HASH_VEC_CLOSED") != nullptr;
+    if (vec && closed) {
+        hash_rows_vec_closed_kernel<<<grid, block, 0, s>>>(m0.ptr, m0.ld, m0.width, a.height, a.digests);
         return hipGetLastError();
     }
 #endif
