@@ -425,6 +425,38 @@ int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, 
 int zkhip_verify_fri16_head(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
+/* ---- the fold-16 IDENTITY machine: the head machine with the AIR identity at zeta inside ----
+ * Statement: everything the head machine states, and the synthetic AIR's identity at zeta (verify_shard_impl's step (a) for a version-3 proof without lookup
+ * pairs): the constraints of the W / 4 groups of four trace columns, folded with the alpha the transcript chain draws and the selectors zeta - 1 / g_N and
+ * (zeta^N - 1) / (zeta - 1), equal the quotient put together from the eight opened quotient values times zeta^N - 1.  Thirteen tables: the head machine's eleven,
+ * AIR16 at 11 (one row per group) and SCALARS16 at 12 (one row, repeated); tests/fri16_identity_air.py writes all of it again.  The inner proofs are the head
+ * machine's (version 3, no lookup pairs, no program, no code group, width-24 hash, W a multiple of 8, 1 .. 30 public values) and the public values are the
+ * inner proof's own.  zkhip_fri16_identity_describe / _key_host (no GPU) / _key / _proof_size: the _head_ entries' arguments.
+ * zkhip_fri16_identity_gen_traces: AIR16 and SCALARS16 on the device (dense, [2^lr][56] and [2^7][4 (17 + log_n)]) from the shape, alpha, zeta and the opened
+ * values [2 W + 8][4] alone; it hands back (canonical) ACCO of the last group and QUO (zeta^N - 1), which an inner proof that holds makes equal.
+ * zkhip_prove_fri16_identity takes the head prover's arguments (zkhip_fri16_view_head hands all of them out).  Refused before anything is proven: all
+ * zkhip_prove_fri16_head refuses, zeta = 1, and "the inner proof's AIR identity at zeta does not hold".  zkhip_verify_fri16_identity is host only.
+ * STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, roots leaving the key, the wiring into shard_verifier.inl. */
+size_t zkhip_fri16_identity_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                     uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_identity_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                  const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                                  uint32_t vk[8]);
+int zkhip_fri16_identity_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
+                             const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_identity_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm);
+int zkhip_fri16_identity_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                    const uint32_t alpha[4], const uint32_t zeta[4], const uint32_t* opened, uint32_t* d_air, uint32_t* d_scalars, uint32_t accumulators[8]);
+int zkhip_prove_fri16_identity(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                               const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                               const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                               uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
+
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */
 int zkhip_air_synthetic(uint32_t width, size_t n_public, uint32_t* out, size_t cap, size_t* words);

@@ -61,6 +61,8 @@ EXPORTS = [
     "zkhip_fri16_rowpaths_gen_trace", "zkhip_prove_fri16_rowpaths", "zkhip_verify_fri16_rowpaths",
     "zkhip_fri16_view_head", "zkhip_fri16_head_describe", "zkhip_fri16_head_key_host", "zkhip_fri16_head_key", "zkhip_fri16_head_proof_size",
     "zkhip_fri16_head_gen_traces", "zkhip_prove_fri16_head", "zkhip_verify_fri16_head",
+    "zkhip_fri16_identity_describe", "zkhip_fri16_identity_key_host", "zkhip_fri16_identity_key", "zkhip_fri16_identity_proof_size", "zkhip_fri16_identity_gen_traces",
+    "zkhip_prove_fri16_identity", "zkhip_verify_fri16_identity",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -425,6 +427,13 @@ def load():
                                                                                     C.POINTER(C.c_size_t)]
     L.zkhip_verify_fri16_head.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(Params),
                                           C.POINTER(C.c_int)]
+    # the fold-16 identity machine: the head machine's entries' arguments
+    for name in ("describe", "key_host", "key", "proof_size"):
+        getattr(L, "zkhip_fri16_identity_" + name).restype = getattr(L, "zkhip_fri16_head_" + name).restype
+        getattr(L, "zkhip_fri16_identity_" + name).argtypes = getattr(L, "zkhip_fri16_head_" + name).argtypes
+    L.zkhip_fri16_identity_gen_traces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, u32p, C.c_void_p, C.c_void_p, u32p]
+    L.zkhip_prove_fri16_identity.argtypes = L.zkhip_prove_fri16_head.argtypes
+    L.zkhip_verify_fri16_identity.argtypes = L.zkhip_verify_fri16_head.argtypes
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

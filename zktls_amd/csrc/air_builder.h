@@ -86,6 +86,22 @@ inline EE emul(const EE& a, const EE& b) {
 inline EE egate(const Terms& f, const EE& e) { return EE{pmul(f, e[0]), pmul(f, e[1]), pmul(f, e[2]), pmul(f, e[3])}; }
 inline void add_ext(Builder& b, uint32_t sel, const EE& e) { for (int i = 0; i < 4; i++) b.add(sel, e[i]); }
 
+// zps_k(zeta) = a_k zeta^N + b_k, N = 2^n, for the two quotient chunks over the cosets g w_{2N}^k <w_N> (canonical): what the SCALARS chip of the shard verifier
+// (shard_verifier.inl) and SCALARS16 of the fold-16 identity machine (fri16_chip.hip) put the quotient together with
+inline void zps_consts(int n, uint32_t a[2], uint32_t b[2]) {
+    const uint64_t N = (uint64_t)1 << n;
+    const uint32_t wq = two_adic_generator(n + 1);
+    uint32_t sN[2];
+    for (int k = 0; k < 2; k++) sN[k] = fpow(fmul(MONTY_GEN, fpow(wq, (uint64_t)k)), N);
+    for (int k = 0; k < 2; k++) {
+        const int j = 1 - k;
+        const uint32_t sj_inv = finv(sN[j]);
+        const uint32_t den_inv = finv(fsub(fmul(sN[k], sj_inv), MONTY_R1));
+        a[k] = from_monty(fmul(sj_inv, den_inv));
+        b[k] = from_monty(fneg(den_inv));
+    }
+}
+
 struct Interactions {
     std::vector<uint32_t> w{LOOKUP_MAGIC, 0u, 0u};
     void add(uint32_t sign, uint32_t mult, uint32_t bus, std::initializer_list<uint32_t> cols) {

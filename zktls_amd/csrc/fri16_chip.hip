@@ -24,7 +24,7 @@
 //   3 QUERIES  preprocessed: distinct (index, reduced opening) with multiplicity.       4 COEFFS  preprocessed: (j, c_j, queries).
 // NOT in this machine: the Merkle paths of the layer rows, the transcript (challenges, query indices), the reduced openings.  tests/fri16_air.py writes
 // the programs, tables and traces independently; the words must be equal.
-// SIX machines are kept here as ONE description read at six kinds (enum Kind), each kind the one before it with a step more of the inner verifier inside:
+// SEVEN machines are kept here as ONE description read at seven kinds (enum Kind), each kind the one before it with a step more of the inner verifier inside:
 //   LAYERS   (zkhip_prove_fri16)           the five tables above
 //   PATHS    (zkhip_prove_fri16_paths)     P24L, the width-24 Poseidon2 chip's layer-paths variant, where LAYERS stands, and a preprocessed ROOTS table: the layer rows' Merkle
 //                                          paths ARE proven and the key holds the layer roots and no layer value (tests/fri16_paths_air.py)
@@ -42,6 +42,10 @@
 //                                          values in fa; the eight constants reach ROWSUM16H and QUERY16H over buses.  The public values are the INNER PROOF'S public values
 //                                          and nothing else.  alpha is drawn and used by nothing here: the AIR identity at zeta is the step that consumes it
 //                                          (tests/fri16_head_air.py)
+//   IDENTITY (zkhip_prove_fri16_identity)  the AIR identity at zeta inside: AIR16 folds the synthetic AIR's constraints over the opened values (which OPENED16 sends on
+//                                          two more buses) with the alpha P2TH now sends; SCALARS16 squares zeta up to zeta^N, derives the two selectors, puts the quotient
+//                                          together from the eight opened quotient values and ties the two: acc = quot (zeta^N - 1).  With it the proof says that the inner
+//                                          statement holds, not only that its columns were opened consistently (tests/fri16_identity_air.py)
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
 // table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
 // to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
@@ -89,14 +93,14 @@ constexpr uint32_t BUS_L16 = 70, BUS_Q16 = 71, BUS_FIN16 = 72, BUS_COEF = 73;
 constexpr uint32_t FJ = 0, FFIRST = 1, FLAST = 2, FACT = 3, FNL = 4;                                  // FINAL's schedule; its main columns in the combined row:
 constexpr uint32_t CFC = FIN_PRE + FC, CFACC = FIN_PRE + FACC, CFAX = FIN_PRE + FAX, CFX = FIN_PRE + FX;
 constexpr uint32_t LAY_PRE = 84, LAY_LN = 0, LAY_KEY = 1, LAY_M = 17, LAY_E = 20, Q_PRE = 8, C_PRE = 8, TAB_MAIN = 4;
-// ONE numbering of the tables for the five kinds: a later kind appends tables (5; 6, 7; 8, 9) or puts a chip where a key table stood (2, 3, 9)
+// ONE numbering of the tables for all kinds: a later kind appends tables (5; 6, 7; 8, 9; 10; 11, 12) or puts a chip where a key table stood (2, 3, 9)
 enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_P24L = 2, T_QUERIES = 3, T_QUERY16 = 3, T_COEFFS = 4, T_ROOTS = 5, T_P2T = 6, T_SAMPLES = 7, T_ROWSUM16 = 8, T_ROWS = 9,
-              T_P24R = 9, T_OPENED16 = 10, MAX_TABLES = 11 };
+              T_P24R = 9, T_OPENED16 = 10, T_AIR16 = 11, T_SCALARS16 = 12, MAX_TABLES = 13 };
 inline uint32_t canon_nibble_factor(uint32_t first_bit, uint32_t nbits, uint32_t j) { return from_monty(nibble_factor(first_bit, nbits, j)); }
 
-// The five machines are ONE description read at five kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
+// The machines are ONE description read at seven kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
 // (pow_bits, C S NT from INDICES on; W from OPENINGS on) stays zero below it.  shape_of, program_of, interactions_of and machine_of are further down, behind the chips.
-enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS, HEAD };
+enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS, HEAD, IDENTITY };
 struct Shape {
     Kind kind = LAYERS;
     int R = 0, F = 0, b = 0, lf = 0, H = 0, pow_bits = 0, n_tables = 0;
@@ -736,8 +740,7 @@ std::vector<uint32_t> build_query16h_program(const Shape& s) {
     query16_products(b);
     return b.finish(Q16_PRE + Q16_MAIN, s.NP);
 }
-std::vector<uint32_t> build_opened16_program(uint32_t n_public) {
-    const uint32_t M0 = OPN_PRE;
+std::vector<uint32_t> build_opened16_program(uint32_t n_public, uint32_t M0 = OPN_PRE) {      // (the identity machine's OPENED16 has four more preprocessed columns)
     Builder b;
     const EE fa = ev(M0 + OP_FA), fa2 = ev(M0 + OP_FA2), pw = ev(M0 + OP_PW), t = ev(M0 + OP_T), pt = ev(M0 + OP_PT), y = ev(M0 + OP_Y), pwn = ev(M0 + OP_PWN);
     add_ext(b, ALL, esub(fa2, emul(fa, fa)));
@@ -750,7 +753,7 @@ std::vector<uint32_t> build_opened16_program(uint32_t n_public) {
     add_ext(b, TRANSITION, egate(pv(OQ_NOTFIRST, true), esub(ev(M0 + OP_PW, true), pwn)));
     add_ext(b, TRANSITION, egate(pv(OQ_NOTFIRST, true), esub(ev(M0 + OP_Y, true), eadd(y, ev(M0 + OP_PT, true)))));
     add_ext(b, TRANSITION, esub(ev(M0 + OP_FA, true), fa));
-    return b.finish(OPN_PRE + OP_MAIN16, n_public);
+    return b.finish(M0 + OP_MAIN16, n_public);
 }
 int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s, uint32_t NP = 0);
 // the key's tables by table number: the row-paths machine's at the head machine's widths, the head's schedule in front of P2T's, OPENED16's schedule -- functions of the
@@ -802,7 +805,7 @@ int build_head_key_tables(const Shape& s, const uint32_t* final_poly, const uint
     }
     frichip::samples_chip_pre(s.Q, s.log_rows[T_SAMPLES], (int)(s.HD + R + s.C), pre[T_SAMPLES]);
     for (size_t i = 0; i < W + 4; i++) {
-        uint32_t* w = pre[T_OPENED16].data() + OPN_PRE * i;
+        uint32_t* w = pre[T_OPENED16].data() + (size_t)s.pre_w[T_OPENED16] * i;
         const size_t first = i < W / 2 ? 0 : (i < W ? W / 2 : W);
         w[OQ_ACT] = MONTY_R1; w[OQ_NOTFIRST] = i != first ? MONTY_R1 : 0u; w[OQ_ROW] = to_monty((uint32_t)(s.A + 1 + i));
         w[OQ_ENDL] = i + 1 == W / 2 ? MONTY_R1 : 0u; w[OQ_ENDN] = i + 1 == W ? MONTY_R1 : 0u; w[OQ_ENDQ] = i == W + 3 ? MONTY_R1 : 0u; w[OQ_FIRST] = i == 0 ? MONTY_R1 : 0u;
@@ -844,9 +847,99 @@ void head_constants(const Shape& s, const Head& h, const uint32_t sums[16], uint
     std::memcpy(consts + 12, sums, 48); std::memcpy(consts + 24, sums + 12, 16);
 }
 
+// ---------------------------------------------------------------- the IDENTITY machine: the head machine with the AIR identity at zeta inside
+// Thirteen tables: the head machine's eleven, AIR16 at 11, SCALARS16 at 12.  The public values stay the inner proof's.  What it states beside the head machine's
+// statement is (a) of verify_shard_impl (verifier.cpp) for air == nullptr, LQ == 0, lqd = 1: with G = W / 4 groups a, b, c, d = loc[4 g .. 4 g + 3], dn = nxt[4 g + 3],
+//     c1 = c - a^2 b - (g + 1),  c2 = sel_trans (dn - a b - c - (2 g + 3)),  c3 = sel_first (d - (5 g + 7)),  acc <- ((acc alpha + c1) alpha + c2) alpha + c3 from 0,
+//     sel_trans = zeta - 1 / g_N,  sel_first = (zeta^N - 1) / (zeta - 1),  quot = sum_{k < 2} (a_k zeta^N + b_k) sum_e X^e opq[4 k + e]  (airb::zps_consts),
+//     acc = quot (zeta^N - 1)
+// with alpha, zeta and the opened values the ones the transcript chain itself draws and absorbs.
+//   AIR16     one row per group, max(6, lg G) log-rows.  Preprocessed (12): ACT FIRST NOTFIRST LAST, K1 = g + 1, K2 = 2 g + 3, K3 = 5 g + 7, the three OPENED16 row keys
+//             it reads (A + 1 + 2 g, A + 1 + 2 g + 1, A + 1 + W / 2 + 2 g + 1), two unused.  Main A B C D DN ALPHA SELT SELF A2 AB ACCIN U1 U2 ACCO (fri16_rows.cuh); the
+//             constraints are the non-air tail of the shard verifier's OPENED chip (shard_verifier.inl: opened_program).  Receives A, C on the first-half bus and B, D, DN
+//             on the second-half bus under their row keys, ALPHA SELT SELF on its first row; sends ACCO on its LAST row.  An all-zero row satisfies it and moves nothing
+//   SCALARS16 2^7 rows, ONE row repeated (c' = c for every column: (zeta - 1) INVF = 1 has no all-zero row).  Preprocessed (8): FIRST, the four quotient rows' keys.
+//             Main ALPHA ZETA ZP_1 .. ZP_n INVF SELF SELT QZ_0 .. QZ_7 QK0 QK1 QUO ACC; the matching lines of the shard verifier's SCALARS chip (scalars_program).
+//             On its first row: receives alpha and zeta from P2TH, the eight quotient values from OPENED16, ACC from AIR16; sends ALPHA SELT SELF to AIR16.
+//             The program depends on n = H - b
+//   P2TH      one more send, alpha = (out[7 .. 4]) of row A - 1, multiplicity in preprocessed column 61; zeta's multiplicity is 2 in this key (QUERY16H and SCALARS16)
+//   OPENED16  twelve preprocessed columns: H0 (column 8; 1 on loc and quotient rows) and H1 (column 9; those and the odd nxt rows) are the multiplicities of two more
+//             sends, (ROW, V[0 .. 3]) and (ROW, V[4 .. 7])
+// STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, roots leaving the key, the wiring into shard_verifier.inl.  tests/fri16_identity_air.py writes it again.
+constexpr uint32_t BUS_OH0 = 94, BUS_OH1 = 95, BUS_ALPHA = 96, BUS_KA16 = 97, BUS_KSELT = 98, BUS_KSELF = 99, BUS_ACC16 = 100;
+constexpr uint32_t PH_AM = 61, OPN_PRE_I = 12, OQ_H0 = 8, OQ_H1 = 9;
+constexpr uint32_t AIR16_PRE = 12, AP_ACT = 0, AP_FIRST = 1, AP_NOTFIRST = 2, AP_LAST = 3, AP_K1 = 4, AP_K2 = 5, AP_K3 = 6, AP_KL0 = 7, AP_KL1 = 8, AP_KN1 = 9;
+constexpr uint32_t SC16_PRE = 8, SP_FIRST = 0, SP_KQ = 1;
+std::vector<uint32_t> build_air16_program(uint32_t n_public) {
+    const uint32_t M0 = AIR16_PRE;
+    Builder b;
+    auto e = [&](uint32_t col, bool nxt = false) { return ev(M0 + col, nxt); };
+    const Terms first = pv(AP_FIRST), nf = pv(AP_NOTFIRST, true);
+    for (uint32_t c : {AI_ALPHA, AI_SELT, AI_SELF}) add_ext(b, TRANSITION, egate(nf, esub(e(c, true), e(c))));
+    add_ext(b, ALL, esub(e(AI_A2), emul(e(AI_A), e(AI_A))));
+    add_ext(b, ALL, esub(e(AI_AB), emul(e(AI_A), e(AI_B))));
+    const EE al = e(AI_ALPHA);
+    add_ext(b, ALL, egate(first, e(AI_ACCIN)));
+    add_ext(b, ALL, esub(e(AI_U1), eadd(emul(e(AI_ACCIN), al), esub(esub(e(AI_C), emul(e(AI_A2), e(AI_B))), eb(pv(AP_K1))))));
+    add_ext(b, ALL, esub(e(AI_U2), eadd(emul(e(AI_U1), al), emul(e(AI_SELT), esub(esub(esub(e(AI_DN), e(AI_AB)), e(AI_C)), eb(pv(AP_K2)))))));
+    add_ext(b, ALL, esub(e(AI_ACCO), eadd(emul(e(AI_U2), al), emul(e(AI_SELF), esub(e(AI_D), eb(pv(AP_K3)))))));
+    add_ext(b, TRANSITION, egate(nf, esub(e(AI_ACCIN, true), e(AI_ACCO))));
+    return b.finish(AIR16_PRE + AIR_MAIN16, n_public);
+}
+std::vector<uint32_t> build_scalars16_program(const Shape& s) {
+    const uint32_t M0 = SC16_PRE, n = (uint32_t)(s.H - s.b), c = M0 + sc16_invf(n), INVF = c, SELF = c + 4, SELT = c + 8, QZ = c + 12, QK0 = c + 44, QK1 = c + 48, QUO = c + 52, ACC = c + 56;
+    Builder b;
+    const EE zeta = ev(M0 + SC_ZETA);
+    EE prev = zeta;
+    for (uint32_t i = 0; i < n; i++) { add_ext(b, ALL, esub(ev(M0 + SC_ZP + 4 * i), emul(prev, prev))); prev = ev(M0 + SC_ZP + 4 * i); }
+    const EE znn = prev;
+    add_ext(b, ALL, esub(emul(esub(zeta, ec(1)), ev(INVF)), ec(1)));
+    add_ext(b, ALL, esub(ev(SELF), emul(esub(znn, ec(1)), ev(INVF))));
+    add_ext(b, ALL, esub(ev(SELT), esub(zeta, ec(from_monty(finv(two_adic_generator((int)n)))))));
+    for (int k = 0; k < 2; k++) {
+        EE q = ec(0);
+        for (int t = 0; t < 4; t++) {
+            uint64_t basis[4] = {0, 0, 0, 0};
+            basis[t] = 1;
+            q = eadd(q, emul(ec(basis[0], basis[1], basis[2], basis[3]), ev(QZ + 4u * (uint32_t)(4 * k + t))));
+        }
+        add_ext(b, ALL, esub(ev(k ? QK1 : QK0), q));
+    }
+    uint32_t za[2], zb[2];
+    zps_consts((int)n, za, zb);
+    const EE z0 = eadd(escale(znn, za[0]), ec(zb[0])), z1 = eadd(escale(znn, za[1]), ec(zb[1]));
+    add_ext(b, ALL, esub(ev(QUO), eadd(emul(z0, ev(QK0)), emul(z1, ev(QK1)))));
+    add_ext(b, ALL, esub(ev(ACC), emul(ev(QUO), esub(znn, ec(1)))));
+    for (uint32_t col = M0; col < M0 + sc16_width(n); col += 4) add_ext(b, TRANSITION, esub(ev(col, true), ev(col)));      // every row behind row 0 repeats row 0
+    return b.finish(M0 + sc16_width(n), s.NP);
+}
+// the key's tables by table number: the head machine's (alpha's multiplicity, zeta's second receiver, OPENED16's two half-row multiplicities) and the schedules of AIR16
+// and SCALARS16 -- functions of the shape and NP alone but for the roots and the final coefficients
+int build_identity_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root, std::vector<uint32_t> pre[],
+                              const char* who) {
+    ZK_TRY(build_head_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, who));
+    const size_t W = s.W, G = W / 4, row0 = s.A + 1;
+    pre[T_P2T][PTH_PRE * (s.A - 1) + PH_AM] = MONTY_R1;
+    pre[T_P2T][PTH_PRE * s.A + PH_ZM] = to_monty(2u);
+    for (size_t i = 0; i < W + 4; i++) {
+        uint32_t* w = pre[T_OPENED16].data() + OPN_PRE_I * i;
+        const bool whole = i < W / 2 || i >= W;                                    // loc and quotient rows
+        w[OQ_H0] = whole ? MONTY_R1 : 0u; w[OQ_H1] = whole || ((i - W / 2) & 1) ? MONTY_R1 : 0u;
+    }
+    for (size_t g = 0; g < G; g++) {
+        uint32_t* w = pre[T_AIR16].data() + AIR16_PRE * g;
+        w[AP_ACT] = MONTY_R1; w[AP_FIRST] = g == 0 ? MONTY_R1 : 0u; w[AP_NOTFIRST] = g ? MONTY_R1 : 0u; w[AP_LAST] = g + 1 == G ? MONTY_R1 : 0u;
+        w[AP_K1] = to_monty((uint32_t)g + 1u); w[AP_K2] = to_monty(2u * (uint32_t)g + 3u); w[AP_K3] = to_monty(5u * (uint32_t)g + 7u);
+        w[AP_KL0] = to_monty((uint32_t)(row0 + 2 * g)); w[AP_KL1] = to_monty((uint32_t)(row0 + 2 * g + 1)); w[AP_KN1] = to_monty((uint32_t)(row0 + W / 2 + 2 * g + 1));
+    }
+    pre[T_SCALARS16][SP_FIRST] = MONTY_R1;
+    for (uint32_t i = 0; i < 4; i++) pre[T_SCALARS16][SP_KQ + i] = to_monty((uint32_t)(row0 + W) + i);
+    return ZKHIP_OK;
+}
+
 // ---------------------------------------------------------------- the one description: shape, programs, interaction tables, machine, and what every entry does with them
-constexpr int N_TABLES[6] = {5, 6, 8, 10, 10, 11};
-inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : s.kind == HEAD ? s.NP : N_PUBLIC_O; }
+constexpr int N_TABLES[7] = {5, 6, 8, 10, 10, 11, 13};
+inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : s.kind >= HEAD ? s.NP : N_PUBLIC_O; }
 
 // pow_bits is read from INDICES on, W from OPENINGS on.  ROWSUM16, ROWS and P24R have at least 2^6 rows: a keyed machine takes at most 8 tables of one height, and the
 // other eight can all have 2^5 rows; from 2^6 rows on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting where ROWS stands --
@@ -857,13 +950,13 @@ int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W,
     if (kind >= INDICES && (pow_bits < 0 || pow_bits > 30)) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
     if (kind >= OPENINGS && (W < 8 || W > MAX_OPEN_W || W % 8))
         return fail(ZKHIP_ERR_INVALID, "fri16 openings: a trace width of 8 .. 1024 in multiples of 8 (inner proofs without lookup pairs and with a quotient row of 8 words)");
-    if (kind == HEAD && (NP < 1 || NP > MAX_NP))
+    if (kind >= HEAD && (NP < 1 || NP > MAX_NP))
         return fail(ZKHIP_ERR_INVALID, "fri16 head: 1 .. 30 inner public values (the machine's public values are the inner proof's: none cannot be carried, and P2TH has six indicator columns)");
     s = Shape{};
     s.kind = kind; s.R = R; s.F = F; s.b = b; s.lf = F + b; s.H = 4 * R + s.lf; s.Q = Q; s.n_tables = N_TABLES[kind];
     if (kind >= INDICES) { s.pow_bits = pow_bits; s.C = F >= 1 ? (size_t)1 << (F - 1) : 0; s.S = frichip::samples_chip_rows(Q); s.NT = (size_t)R + s.C + s.S; }
     if (kind >= OPENINGS) s.W = W;
-    if (kind == HEAD) { s.NP = NP; s.A = (HEAD_STREAM + NP + 7) / 8; s.HD = s.A + 1 + (size_t)W + 4; }
+    if (kind >= HEAD) { s.NP = NP; s.A = (HEAD_STREAM + NP + 7) / 8; s.HD = s.A + 1 + (size_t)W + 4; }
     size_t layer_paths = 0;                                      // rows of P24L per query: every layer's leaf and path
     for (int l = 0; l < R; l++) layer_paths += (size_t)p24chip::LEAF_ROWS + (size_t)(s.H - 4 * (l + 1));
     const size_t row_paths = (size_t)(W + 15) / 16 + 1 + 2 * (size_t)s.H;      // rows of P24R per query: the two leaves and the two paths
@@ -875,16 +968,19 @@ int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W,
     if (kind < OPENINGS) table(T_QUERIES, lg(Q), TAB_MAIN, Q_PRE);
     else table(T_QUERY16, lg(Q), Q16_MAIN, Q16_PRE);
     table(T_COEFFS, lg((size_t)1 << F), TAB_MAIN, C_PRE);
-    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, kind == HEAD ? ROOTS_PRE_H : ROOTS_PRE16);
-    table(T_P2T, lg(s.HD + s.NT), p2chip::T_WIDTH, kind == HEAD ? PTH_PRE : PT_PRE);
+    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, kind >= HEAD ? ROOTS_PRE_H : ROOTS_PRE16);
+    table(T_P2T, lg(s.HD + s.NT), p2chip::T_WIDTH, kind >= HEAD ? PTH_PRE : PT_PRE);
     table(T_SAMPLES, lg(s.S), frichip::S_MAIN, frichip::S_PRE);
-    table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, kind == HEAD ? RS16H_PRE : RS16_PRE);
+    table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, kind >= HEAD ? RS16H_PRE : RS16_PRE);
     if (kind == OPENINGS) table(T_ROWS, std::max(6, lg(Q * (size_t)(W + QROW16) / 4)), TAB_MAIN, ROWS_PRE16);
     else table(T_P24R, std::max(6, lg(Q * row_paths)), p24chip::WIDTH_R, 0u);
-    table(T_OPENED16, std::max(6, lg((size_t)W + 4)), OP_MAIN16, OPN_PRE);
+    table(T_OPENED16, std::max(6, lg((size_t)W + 4)), OP_MAIN16, kind == IDENTITY ? OPN_PRE_I : OPN_PRE);
+    // (IDENTITY: the floors 2^6 and 2^7 keep AIR16 and SCALARS16 from making nine tables of one height where the head machine has eight of 2^5)
+    table(T_AIR16, std::max(6, lg((size_t)W / 4)), AIR_MAIN16, AIR16_PRE);
+    table(T_SCALARS16, (int)SC16_LOG_ROWS, sc16_width((uint32_t)(s.H - s.b)), SC16_PRE);
     for (int t = 0; kind >= ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
         if (std::count(s.log_rows, s.log_rows + s.n_tables, s.log_rows[t]) > MAX_SAME_HEIGHT)
-            return fail(ZKHIP_ERR_INVALID, std::string(kind == HEAD ? "fri16 head" : "fri16 rowpaths") + ": nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
+            return fail(ZKHIP_ERR_INVALID, std::string(kind == IDENTITY ? "fri16 identity" : kind == HEAD ? "fri16 head" : "fri16 rowpaths") + ": nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
     return ZKHIP_OK;
 }
 
@@ -896,13 +992,15 @@ std::vector<uint32_t> program_of(const Shape& s, int t) {
     case T_FOLD16: return k >= OPENINGS ? build_fold16c_program(s.R, s.lf, np) : build_fold16_program(s.R, s.lf, k >= INDICES, np);
     case T_FINAL: return build_final_program(np);
     case T_P24L: if (k >= PATHS) return *p24chip::program_fri16_layers(np); break;                                 // (LAYERS: a key table)
-    case T_QUERY16: if (k >= OPENINGS) return k == HEAD ? build_query16h_program(s) : build_query16_program(); break;                                     // (below: QUERIES, a key table)
+    case T_QUERY16: if (k >= OPENINGS) return k >= HEAD ? build_query16h_program(s) : build_query16_program(); break;                                     // (below: QUERIES, a key table)
     case T_ROOTS: if (k >= INDICES) return build_roots_program(np, s.pre_w[T_ROOTS]); break;                                        // (PATHS: a key table)
-    case T_P2T: return k == HEAD ? build_p2th_program(s) : build_p2t_program(np);
+    case T_P2T: return k >= HEAD ? build_p2th_program(s) : build_p2t_program(np);
     case T_SAMPLES: return *frichip::samples_chip_program(s.H, s.pow_bits, np);
-    case T_ROWSUM16: return k == HEAD ? build_rowsum16_program(RS16H_PRE, true, np) : build_rowsum16_program();
+    case T_ROWSUM16: return k >= HEAD ? build_rowsum16_program(RS16H_PRE, true, np) : build_rowsum16_program();
     case T_P24R: if (k >= ROWPATHS) return *p24chip::program_fri16_rows(np); break;                               // (OPENINGS: ROWS, a key table)
-    case T_OPENED16: return build_opened16_program(np);
+    case T_OPENED16: return build_opened16_program(np, s.pre_w[T_OPENED16]);
+    case T_AIR16: return build_air16_program(np);
+    case T_SCALARS16: return build_scalars16_program(s);
     default: break;                                                                                                // COEFFS
     }
     return build_table_program(np, s.pre_w[t], s.main_w[t]);
@@ -952,7 +1050,7 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
                 v.add(0u, QP_ACT, BUS_TAG16, {QP_TG0, QP_LN0, QC_IDX});
                 v.add(0u, QP_ACT, BUS_TAG16, {QP_TG1, QP_LN1, QC_IDX});
             }
-            if (k == HEAD) {                                                                                       // QUERY16H: the constants arrive on the first row
+            if (k >= HEAD) {                                                                                       // QUERY16H: the constants arrive on the first row
                 const uint32_t bus[5] = {BUS_ZETA, BUS_YL, BUS_YN, BUS_YQ, BUS_OFFN}, col[5] = {QC_ZETA, QC_YL, QC_YN, QC_YQ, QC_OFFN};
                 for (int i = 0; i < 5; i++) v.add(1u, QP_FIRST, bus[i], {col[i], col[i] + 1, col[i] + 2, col[i] + 3});
             }
@@ -971,7 +1069,7 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
             v.add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
             v.add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
         }
-        if (k == HEAD) for (uint32_t j = 0; j < 8; j++) v.add(0u, RT_HM, BUS_HR, {RT_HK + j, RT_ROOT + j});            // the trace root and the quotient root, word by word, to P2TH
+        if (k >= HEAD) for (uint32_t j = 0; j < 8; j++) v.add(0u, RT_HM, BUS_HR, {RT_HK + j, RT_ROOT + j});            // the trace root and the quotient root, word by word, to P2TH
         break;
     case T_P2T:
         v.add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
@@ -981,23 +1079,24 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
         v.add(0u, PT_ROOT, BUS_TB, {PT_LN, o + 7, o + 6, o + 5, o + 4});
         v.add(0u, PT_SMP, frichip::BUS_S0, {PT_ROW, o + 7, o + 6, o + 5, o + 4});
         v.add(0u, PT_SMP, frichip::BUS_S1, {PT_ROW, o + 3, o + 2, o + 1, o});
-        if (k == HEAD) {                                                                                           // P2TH: roots in, opened values in, zeta and fa out
+        if (k >= HEAD) {                                                                                           // P2TH: roots in, opened values in, zeta and fa out
             for (uint32_t j = 0; j < 8; j++) v.add(1u, PH_RM + j, BUS_HR, {PH_RK + j, in + j});
             v.add(1u, PH_OPN, BUS_OV0, {PT_ROW, in, in + 1, in + 2, in + 3});
             v.add(1u, PH_OPN, BUS_OV1, {PT_ROW, in + 4, in + 5, in + 6, in + 7});
             v.add(0u, PH_ZM, BUS_ZETA, {o + 7, o + 6, o + 5, o + 4});
             v.add(0u, PH_FM, BUS_FAH, {o + 7, o + 6, o + 5, o + 4});
         }
+        if (k == IDENTITY) v.add(0u, PH_AM, BUS_ALPHA, {o + 7, o + 6, o + 5, o + 4});                                   // alpha, from row A - 1, to SCALARS16
         break;
     case T_ROWSUM16:
         v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
         v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K1, rv + 4, rv + 5, rv + 6, rv + 7});
         v.add(0u, RP_LAST0, BUS_AT16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
         v.add(0u, RP_LAST1, BUS_AQ16, {RP_QN, rt, rt + 1, rt + 2, rt + 3});
-        if (k == HEAD) v.add(1u, RP_FIRST, BUS_FAH, {rfa, rfa + 1, rfa + 2, rfa + 3});                                 // ROWSUM16H: fa arrives on the first row
+        if (k >= HEAD) v.add(1u, RP_FIRST, BUS_FAH, {rfa, rfa + 1, rfa + 2, rfa + 3});                                 // ROWSUM16H: fa arrives on the first row
         break;
     case T_OPENED16: {
-        const uint32_t m = OPN_PRE, y = m + OP_Y, pwn = m + OP_PWN, fa = m + OP_FA;
+        const uint32_t m = s.pre_w[T_OPENED16], y = m + OP_Y, pwn = m + OP_PWN, fa = m + OP_FA;
         v.add(0u, OQ_ACT, BUS_OV0, {OQ_ROW, m + OP_V, m + OP_V + 1, m + OP_V + 2, m + OP_V + 3});
         v.add(0u, OQ_ACT, BUS_OV1, {OQ_ROW, m + OP_V + 4, m + OP_V + 5, m + OP_V + 6, m + OP_V + 7});
         v.add(0u, OQ_ENDL, BUS_YL, {y, y + 1, y + 2, y + 3});
@@ -1005,6 +1104,31 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
         v.add(0u, OQ_ENDQ, BUS_YQ, {y, y + 1, y + 2, y + 3});
         v.add(0u, OQ_ENDL, BUS_OFFN, {pwn, pwn + 1, pwn + 2, pwn + 3});
         v.add(1u, OQ_FIRST, BUS_FAH, {fa, fa + 1, fa + 2, fa + 3});
+        if (k == IDENTITY) {                                                                                       // the row's two halves under its row number, to AIR16 and SCALARS16
+            v.add(0u, OQ_H0, BUS_OH0, {OQ_ROW, m + OP_V, m + OP_V + 1, m + OP_V + 2, m + OP_V + 3});
+            v.add(0u, OQ_H1, BUS_OH1, {OQ_ROW, m + OP_V + 4, m + OP_V + 5, m + OP_V + 6, m + OP_V + 7});
+        }
+        break;
+    }
+    case T_AIR16: {
+        const uint32_t m = AIR16_PRE, half[5] = {BUS_OH0, BUS_OH1, BUS_OH0, BUS_OH1, BUS_OH1}, key[5] = {AP_KL0, AP_KL0, AP_KL1, AP_KL1, AP_KN1}, col[5] = {AI_A, AI_B, AI_C, AI_D, AI_DN};
+        for (int i = 0; i < 5; i++) v.add(1u, AP_ACT, half[i], {key[i], m + col[i], m + col[i] + 1, m + col[i] + 2, m + col[i] + 3});
+        const uint32_t bus[3] = {BUS_KA16, BUS_KSELT, BUS_KSELF}, cst[3] = {AI_ALPHA, AI_SELT, AI_SELF};
+        for (int i = 0; i < 3; i++) v.add(1u, AP_FIRST, bus[i], {m + cst[i], m + cst[i] + 1, m + cst[i] + 2, m + cst[i] + 3});
+        v.add(0u, AP_LAST, BUS_ACC16, {m + AI_ACCO, m + AI_ACCO + 1, m + AI_ACCO + 2, m + AI_ACCO + 3});
+        break;
+    }
+    case T_SCALARS16: {
+        const uint32_t m = SC16_PRE, c = m + sc16_invf((uint32_t)(s.H - s.b)), qz = c + 12u, acc = c + 56u;
+        v.add(1u, SP_FIRST, BUS_ALPHA, {m + SC_ALPHA, m + SC_ALPHA + 1, m + SC_ALPHA + 2, m + SC_ALPHA + 3});
+        v.add(1u, SP_FIRST, BUS_ZETA, {m + SC_ZETA, m + SC_ZETA + 1, m + SC_ZETA + 2, m + SC_ZETA + 3});
+        for (uint32_t i = 0; i < 4; i++) {
+            v.add(1u, SP_FIRST, BUS_OH0, {SP_KQ + i, qz + 8 * i, qz + 8 * i + 1, qz + 8 * i + 2, qz + 8 * i + 3});
+            v.add(1u, SP_FIRST, BUS_OH1, {SP_KQ + i, qz + 8 * i + 4, qz + 8 * i + 5, qz + 8 * i + 6, qz + 8 * i + 7});
+        }
+        v.add(1u, SP_FIRST, BUS_ACC16, {acc, acc + 1, acc + 2, acc + 3});
+        const uint32_t bus[3] = {BUS_KA16, BUS_KSELT, BUS_KSELF}, cst[3] = {m + SC_ALPHA, c + 8u, c + 4u};
+        for (int i = 0; i < 3; i++) v.add(0u, SP_FIRST, bus[i], {cst[i], cst[i] + 1, cst[i] + 2, cst[i] + 3});
         break;
     }
     default:
@@ -1091,6 +1215,8 @@ struct xq_cols_bargs { XqColsArgs a; static xq_cols_bargs make(XqColsArgs a) { r
 __global__ void __launch_bounds__(64) fri16_xq_cols_kernel_batch(const xq_cols_bargs* __restrict__ zk_arr) { fri16_xq_cols_body(zk_arr[blockIdx.z].a); }
 struct opened_rows_bargs { OpenedRowsArgs a; static opened_rows_bargs make(OpenedRowsArgs a) { return opened_rows_bargs{a}; } };
 __global__ void __launch_bounds__(OPENED_LANES) fri16_opened_rows_kernel_batch(const opened_rows_bargs* __restrict__ zk_arr) { fri16_opened_rows_body(zk_arr[blockIdx.z].a); }
+struct identity_rows_bargs { IdentityRowsArgs a; static identity_rows_bargs make(IdentityRowsArgs a) { return identity_rows_bargs{a}; } };
+__global__ void __launch_bounds__(IDENTITY_LANES) fri16_identity_rows_kernel_batch(const identity_rows_bargs* __restrict__ zk_arr) { fri16_identity_rows_body(zk_arr[blockIdx.z].a); }
 
 }  // namespace
 }  // namespace fri16
@@ -1334,6 +1460,36 @@ static int fri16_head_check_inputs(const fri16::Shape& s, const uint32_t* inner_
     if (!fri16::canonical(inner_public, s.NP)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner public values must be canonical");
     if (!fri16::canonical(opened, 8 * ((size_t)s.W + 4))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the opened values must be canonical");
     if (!fri16::canonical(trace_root, 8) || !fri16::canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+    return ZKHIP_OK;
+}
+
+// AIR16 and SCALARS16 in one launch from one staging block (the opened values, alpha, zeta); accs: ACCO of the last group, then QUO (zeta^N - 1), canonical -- one copy back
+static int fri16_identity_rows_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* opened, const uint32_t alpha[4], const uint32_t zeta[4], uint32_t* d_air,
+                                    uint32_t* d_scalars, uint32_t accs[8]) {
+    const size_t nv = 8 * ((size_t)s.W + 4), words = nv + 8 + 8;
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, words * 4, &stage));
+    uint32_t* d = (uint32_t*)stage;
+    {
+        std::vector<uint32_t> up(words, 0u);
+        std::memcpy(up.data(), opened, nv * 4);
+        std::memcpy(up.data() + nv, alpha, 16);
+        std::memcpy(up.data() + nv + 4, zeta, 16);
+        ZK_TRY(dev_h2d(ctx, d, up.data(), words * 4));
+    }
+    const int n = s.H - s.b;
+    uint32_t za[2], zb[2];
+    airb::zps_consts(n, za, zb);
+    fri16::IdentityRowsArgs a{};
+    a.opened = d; a.alpha = d + nv; a.zeta = d + nv + 4; a.W = s.W; a.n = (uint32_t)n; a.gn_inv = finv(two_adic_generator(n));
+    for (int k = 0; k < 2; k++) { a.za[k] = to_monty(za[k]); a.zb[k] = to_monty(zb[k]); }
+    a.air_rows = (uint64_t)1 << s.log_rows[fri16::T_AIR16]; a.air = d_air; a.scalars = d_scalars; a.accs = d + nv + 8;
+    ZK_LAUNCH(fri16::fri16_identity_rows_kernel, fri16::fri16_identity_rows_kernel_batch, fri16::identity_rows_bargs, dim3(1), dim3(fri16::IDENTITY_LANES), 0, ctx->stream, a);
+    ZK_HIP(hipGetLastError());
+    return dev_d2h(ctx, accs, a.accs, 32);
+}
+static int fri16_identity_check_zeta(const uint32_t zeta[4], const char* who) {
+    if (zeta[0] == 1u && !(zeta[1] | zeta[2] | zeta[3])) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": zeta is 1: the first-row selector has no value there");
     return ZKHIP_OK;
 }
 
@@ -1959,19 +2115,19 @@ int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, si
     return fri16_transcript_impl(ctx, s, c, nullptr, nullptr, nullptr, d_p2th, d_samples, nullptr, nullptr, &status);
 }
 
-int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
-                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
-                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
-                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
-                           uint8_t* proof, size_t cap, size_t* len) {
+// the prover of the head machine and of the identity machine (kind; who: the entry's name in the refusals): the identity machine is the head machine plus one stage
+static int fri16_prove_head_kind(fri16::Kind kind, const char* who, zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries,
+                                 int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly,
+                                 const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8],
+                                 uint32_t witness, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths,
+                                 const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened,
+                                 const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
     CHECK_CTX(ctx);
     using namespace fri16;
-    const char* who = "prove_fri16_head";
     Shape s;
-    if (n_inner_public > MAX_NP) return fail(ZKHIP_ERR_INVALID, "prove_fri16_head: more than 30 inner public values");
-    ZK_TRY(shape_of(HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_head: null argument");
+    if (n_inner_public > MAX_NP) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": more than 30 inner public values");
+    ZK_TRY(shape_of(kind, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
     ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
     ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
@@ -1984,7 +2140,8 @@ int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, 
     ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
     ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
     Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block; OPENED16
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16}, z));
+    if (kind == IDENTITY) ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16, T_AIR16, T_SCALARS16}, z));
+    else ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16}, z));
     ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
     // the head first: the chain from the all-zero state, OPENED16, the eight constants and the capacity DERIVED -- refused here, before anything is proven: a derived
     // constant or capacity that is not the view's; then all zkhip_prove_fri16_rowpaths refuses, on the derived values
@@ -2014,12 +2171,98 @@ int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, 
         if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
             return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") + " tree: the opened row's path does not end in the root");
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r, z.at(T_OPENED16)};
+    if (kind == IDENTITY) {      // AIR16 and SCALARS16 from alpha, zeta and the opened values; refused here, still before anything is proven: zeta = 1, an identity that does not hold
+        uint32_t accs[8];
+        ZK_TRY(fri16_identity_check_zeta(h.zeta, who));
+        ZK_TRY(fri16_identity_rows_impl(ctx, s, opened, h.alpha, h.zeta, z.at(T_AIR16), z.at(T_SCALARS16), accs));
+        if (std::memcmp(accs, accs + 4, 16) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner proof's AIR identity at zeta does not hold");
+        traces[T_AIR16] = z.at(T_AIR16); traces[T_SCALARS16] = z.at(T_SCALARS16);
+    }
     return keyed::prove(ctx, key, machine_of(s)->km, traces, inner_public, n_public_of(s), prm, proof, cap, len);
+}
+
+int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                           uint8_t* proof, size_t cap, size_t* len) {
+    return fri16_prove_head_kind(fri16::HEAD, "prove_fri16_head", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas, final_poly,
+                                 indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root, quotient_root,
+                                 inner_public, opened, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_head(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
     return fri16::verify(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_head", n_inner_public);
+}
+
+// ---------------------------------------------------------------- IDENTITY
+size_t zkhip_fri16_identity_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                     uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
+    return fri16::describe(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+}
+
+int zkhip_fri16_identity_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                  const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
+                                  uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_identity_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_identity_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_identity_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_identity_key_host"));
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+}
+
+// (the head key's slots, and two more for the schedules of AIR16 and SCALARS16)
+static const int FRI16_IDENTITY_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B, S_REC_H, S_REC_I, S_STAGE};
+
+int zkhip_fri16_identity_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                             uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
+                             const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_identity_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_identity_key: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_identity_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_identity_key"));
+    return fri16::key_upload(ctx, s, pre, FRI16_IDENTITY_KEY_SLOTS, prm, key, vk);
+}
+
+size_t zkhip_fri16_identity_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
+    return fri16::proof_size(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+}
+
+int zkhip_fri16_identity_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                    const uint32_t alpha[4], const uint32_t zeta[4], const uint32_t* opened, uint32_t* d_air, uint32_t* d_scalars, uint32_t accumulators[8]) {
+    CHECK_CTX(ctx);
+    const char* who = "fri16_identity_gen_traces";
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    if (!alpha || !zeta || !opened || !d_air || !d_scalars || !accumulators || ((uintptr_t)d_air | (uintptr_t)d_scalars) % 16)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": alpha, zeta, the opened values, 16-byte aligned dense traces (56 and 4 (17 + log_n) columns) and the accumulators");
+    if (!fri16::canonical(alpha, 4) || !fri16::canonical(zeta, 4)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges must be canonical");
+    if (!fri16::canonical(opened, 8 * ((size_t)s.W + 4))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the opened values must be canonical");
+    ZK_TRY(fri16_identity_check_zeta(zeta, who));
+    return fri16_identity_rows_impl(ctx, s, opened, alpha, zeta, d_air, d_scalars, accumulators);
+}
+
+int zkhip_prove_fri16_identity(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                               uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                               const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                               const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                               const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                               uint8_t* proof, size_t cap, size_t* len) {
+    return fri16_prove_head_kind(fri16::IDENTITY, "prove_fri16_identity", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas,
+                                 final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root,
+                                 quotient_root, inner_public, opened, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                                uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    return fri16::verify(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_identity", n_inner_public);
 }
 
 }  // extern "C"

@@ -86,6 +86,22 @@ struct OpenedRowsArgs {
     uint32_t* trace;                    // Montgomery, dense, 16-byte aligned
     uint32_t* sums;                     // [4][4] CANONICAL: YL, YN, YQ, OFFN = fa^W, written by the lanes at the segment ends
 };
+// the identity machine: AIR16 (A B C D DN ALPHA SELT SELF A2 AB ACCIN U1 U2 ACCO, four words each, one row per group of four trace columns) and SCALARS16
+// (ALPHA ZETA ZP_1 .. ZP_n INVF SELF SELT QZ_0 .. QZ_7 QK0 QK1 QUO ACC, four words each, ONE row repeated down the table), both dense
+constexpr uint32_t AI_A = 0, AI_B = 4, AI_C = 8, AI_D = 12, AI_DN = 16, AI_ALPHA = 20, AI_SELT = 24, AI_SELF = 28, AI_A2 = 32, AI_AB = 36, AI_ACCIN = 40, AI_U1 = 44, AI_U2 = 48,
+                   AI_ACCO = 52, AIR_MAIN16 = 56, IDENTITY_LANES = 256;
+constexpr uint32_t SC_ALPHA = 0, SC_ZETA = 4, SC_ZP = 8, SC16_LOG_ROWS = 7, SC16_MAX_N = 26;
+ZK_HD constexpr uint32_t sc16_invf(uint32_t n) { return SC_ZP + 4u * n; }          // then SELF SELT QZ[8] QK0 QK1 QUO ACC
+ZK_HD constexpr uint32_t sc16_width(uint32_t n) { return sc16_invf(n) + 4u * 15u; }
+struct IdentityRowsArgs {
+    const uint32_t* opened;             // canonical words on the device, 16-byte aligned: [2 W + 8][4], loc, nxt, quotient values
+    const uint32_t *alpha, *zeta;       // canonical [4] each
+    uint32_t W, n;                      // the trace width (G = W / 4 <= 256 groups); zeta^N takes n squarings
+    uint32_t gn_inv, za[2], zb[2];      // Montgomery: 1 / g_N; zps_k = za_k zeta^N + zb_k
+    uint64_t air_rows;                  // AIR16's height, G <= air_rows <= 256
+    uint32_t *air, *scalars;            // Montgomery, dense, 16-byte aligned; SCALARS16 has 2^7 rows of sc16_width(n) words
+    uint32_t* accs;                     // [2][4] CANONICAL: ACCO of the last group, QUO (zeta^N - 1)
+};
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ Ext ld_ext(const uint32_t* p) {
@@ -489,6 +505,141 @@ __device__ __forceinline__ void fri16_opened_rows_plain_body(const OpenedRowsArg
     opened_padding_rows(a, tid, blockDim.x, fa, fa2);
 }
 __global__ void __launch_bounds__(OPENED_LANES) fri16_opened_rows_kernel(OpenedRowsArgs a) { fri16_opened_rows_body(a); }
+
+// ---- the identity machine's AIR16 and SCALARS16 rows.  Group g holds a, b, c, d = loc[4 g .. 4 g + 3] and dn = nxt[4 g + 3]; with c1 = c - a^2 b - (g + 1),
+// c2 = SELT (dn - a b - c - (2 g + 3)), c3 = SELF (d - (5 g + 7)):  U1 = ACCIN alpha + c1, U2 = U1 alpha + c2, ACCO = U2 alpha + c3, ACCIN = the ACCO of the group before.
+struct IdentityScalars { Ext alpha, zeta, znn, invf, self, selt; };
+__device__ __forceinline__ Ext ext_sub_base_dev(const Ext& e, uint32_t x) { return Ext{{dsub(e.c[0], x), e.c[1], e.c[2], e.c[3]}}; }
+__device__ __forceinline__ void identity_scalars(const IdentityRowsArgs& a, IdentityScalars& k) {      // every lane alike: n squarings, one inversion
+    k.alpha = ld_ext(a.alpha); k.zeta = ld_ext(a.zeta);
+    k.znn = k.zeta;
+#pragma unroll 1
+    for (uint32_t i = 0; i < a.n; i++) k.znn = ext_mul_dev(k.znn, k.znn);
+    k.invf = ext_inv_dev(ext_sub_base_dev(k.zeta, MONTY_R1));
+    k.self = ext_mul_dev(ext_sub_base_dev(k.znn, MONTY_R1), k.invf);
+    k.selt = ext_sub_base_dev(k.zeta, a.gn_inv);
+}
+// SCALARS16's one row into `row` (LDS, sc16_width(n) words) and QUO (zeta^N - 1), canonical, where the host reads it: one lane
+__device__ __forceinline__ void identity_scalars_row(const IdentityRowsArgs& a, const IdentityScalars& k, uint32_t* row) {
+    auto put = [&](uint32_t col, const Ext& e) { row[col] = e.c[0]; row[col + 1] = e.c[1]; row[col + 2] = e.c[2]; row[col + 3] = e.c[3]; };
+    put(SC_ALPHA, k.alpha); put(SC_ZETA, k.zeta);
+    Ext z = k.zeta;
+#pragma unroll 1
+    for (uint32_t i = 0; i < a.n; i++) { z = ext_mul_dev(z, z); put(SC_ZP + 4u * i, z); }
+    const uint32_t c = sc16_invf(a.n);
+    put(c, k.invf); put(c + 4, k.self); put(c + 8, k.selt);
+    Ext qk[2];
+#pragma unroll
+    for (uint32_t h = 0; h < 2; h++) {
+        qk[h] = ext_zero();
+#pragma unroll
+        for (uint32_t t = 0; t < 4; t++) {
+            const Ext q = ld_ext(a.opened + 4u * (2u * (size_t)a.W + 4u * h + t));
+            put(c + 12 + 4u * (4u * h + t), q);
+            Ext basis = ext_zero();
+            basis.c[t] = MONTY_R1;
+            qk[h] = ext_add_dev(qk[h], ext_mul_dev(basis, q));
+        }
+        put(c + 44 + 4u * h, qk[h]);
+    }
+    Ext z0 = ext_mul_base_dev(k.znn, a.za[0]), z1 = ext_mul_base_dev(k.znn, a.za[1]);
+    z0.c[0] = dadd(z0.c[0], a.zb[0]); z1.c[0] = dadd(z1.c[0], a.zb[1]);
+    const Ext quo = ext_add_dev(ext_mul_dev(z0, qk[0]), ext_mul_dev(z1, qk[1])), acc = ext_mul_dev(quo, ext_sub_base_dev(k.znn, MONTY_R1));
+    put(c + 52, quo); put(c + 56, acc);
+    st4(a.accs + 4, canon_dev(acc.c[0]), canon_dev(acc.c[1]), canon_dev(acc.c[2]), canon_dev(acc.c[3]));
+}
+// the row repeated down SCALARS16, all lanes, adjacent lanes writing adjacent 16 bytes
+__device__ __forceinline__ void identity_scalars_rows(const IdentityRowsArgs& a, const uint32_t* row, uint32_t tid, uint32_t lanes) {
+    const uint32_t w4 = sc16_width(a.n) >> 2, total = w4 << SC16_LOG_ROWS;
+    for (uint32_t i = tid; i < total; i += lanes) {
+        const uint32_t c = 4u * (i % w4);
+        st4(a.scalars + 4u * (size_t)i, row[c], row[c + 1], row[c + 2], row[c + 3]);
+    }
+}
+struct IdentityGroup { Ext a, b, c, d, dn, a2, ab, c1, c2, c3; };
+__device__ __forceinline__ void identity_group(const IdentityRowsArgs& a, const IdentityScalars& k, uint32_t g, IdentityGroup& r) {
+    const uint32_t* loc = a.opened + 16u * (size_t)g;
+    r.a = ld_ext(loc); r.b = ld_ext(loc + 4); r.c = ld_ext(loc + 8); r.d = ld_ext(loc + 12);
+    r.dn = ld_ext(a.opened + 4u * ((size_t)a.W + 4u * g + 3u));
+    r.a2 = ext_mul_dev(r.a, r.a); r.ab = ext_mul_dev(r.a, r.b);
+    r.c1 = ext_sub_base_dev(ext_sub_dev(r.c, ext_mul_dev(r.a2, r.b)), dmul(g + 1u, MONTY_R2));
+    r.c2 = ext_mul_dev(k.selt, ext_sub_base_dev(ext_sub_dev(ext_sub_dev(r.dn, r.ab), r.c), dmul(2u * g + 3u, MONTY_R2)));
+    r.c3 = ext_mul_dev(k.self, ext_sub_base_dev(r.d, dmul(5u * g + 7u, MONTY_R2)));
+}
+// one AIR16 row from the ACCIN that reaches it; returns its ACCO
+__device__ __forceinline__ Ext identity_store(const IdentityRowsArgs& a, const IdentityScalars& k, uint32_t g, const IdentityGroup& r, const Ext& accin) {
+    const Ext u1 = ext_add_dev(ext_mul_dev(accin, k.alpha), r.c1), u2 = ext_add_dev(ext_mul_dev(u1, k.alpha), r.c2), acco = ext_add_dev(ext_mul_dev(u2, k.alpha), r.c3);
+    uint32_t* t = a.air + (uint64_t)g * AIR_MAIN16;
+    st_ext(t + AI_A, r.a); st_ext(t + AI_B, r.b); st_ext(t + AI_C, r.c); st_ext(t + AI_D, r.d); st_ext(t + AI_DN, r.dn);
+    st_ext(t + AI_ALPHA, k.alpha); st_ext(t + AI_SELT, k.selt); st_ext(t + AI_SELF, k.self); st_ext(t + AI_A2, r.a2); st_ext(t + AI_AB, r.ab);
+    st_ext(t + AI_ACCIN, accin); st_ext(t + AI_U1, u1); st_ext(t + AI_U2, u2); st_ext(t + AI_ACCO, acco);
+    if (g + 1u == (a.W >> 2)) st4(a.accs, canon_dev(acco.c[0]), canon_dev(acco.c[1]), canon_dev(acco.c[2]), canon_dev(acco.c[3]));
+    return acco;
+}
+__device__ __forceinline__ void identity_zero_row(const IdentityRowsArgs& a, uint32_t g) {
+    uint32_t* t = a.air + (uint64_t)g * AIR_MAIN16;
+#pragma unroll
+    for (uint32_t c = 0; c < AIR_MAIN16; c += 4) st4(t + c, 0u, 0u, 0u, 0u);
+}
+// The scan form, ONE workgroup of IDENTITY_LANES lanes, a lane per AIR16 row (G <= 256: one round).  ACCO_g = alpha^3 ACCO_(g-1) + t_g with t_g = c1 alpha^2 + c2 alpha
+// + c3 is an affine recurrence with one multiplier: an inclusive cross-lane scan in which step d adds alpha^(3 d) times lane - d's value (the power squared per step,
+// the same in every lane), the waves' last values joined through LDS as fri16_opened_rows_body does -- wave w starts from c_w = tot_(w-1) + alpha^(3 64) c_(w-1), lane l
+// adds alpha^(3 (l + 1)) c_w.  Each lane then redoes its three steps from the ACCIN that reaches it and writes its row.  Lane 0 computes SCALARS16's row into LDS; all
+// lanes write it down the table.  No second workgroup, nothing to wait for.
+__device__ __forceinline__ void fri16_identity_rows_body(const IdentityRowsArgs& a) {
+    __shared__ uint32_t sc_row[sc16_width(SC16_MAX_N)];
+    __shared__ uint32_t tot[IDENTITY_LANES / 64u][4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, G = a.W >> 2;
+    IdentityScalars k;
+    identity_scalars(a, k);
+    if (tid == 0u) identity_scalars_row(a, k, sc_row);
+    const bool act = tid < G;
+    IdentityGroup r;
+    Ext p = ext_zero();
+    const Ext al2 = ext_mul_dev(k.alpha, k.alpha), al3 = ext_mul_dev(al2, k.alpha);
+    if (act) {
+        identity_group(a, k, tid, r);
+        p = ext_add_dev(ext_add_dev(ext_mul_dev(r.c1, al2), ext_mul_dev(r.c2, k.alpha)), r.c3);
+    }
+    Ext m = al3;
+#pragma unroll 1
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const Ext o = shfl_up_ext(p, d, 64);
+        if (lane >= d) p = ext_add_dev(p, ext_mul_dev(o, m));
+        m = ext_mul_dev(m, m);
+    }
+    if (lane == 63u) { tot[wave][0] = p.c[0]; tot[wave][1] = p.c[1]; tot[wave][2] = p.c[2]; tot[wave][3] = p.c[3]; }
+    __syncthreads();
+    Ext cin = ext_zero();                                              // ACCO of the last lane of the wave before
+#pragma unroll 1
+    for (uint32_t w = 0; w < wave; w++) cin = ext_add_dev(Ext{{tot[w][0], tot[w][1], tot[w][2], tot[w][3]}}, ext_mul_dev(m, cin));
+    p = ext_add_dev(p, ext_mul_dev(ext_pow_dev(al3, lane + 1u), cin));
+    Ext accin = shfl_up_ext(p, 1u, 64);
+    if (lane == 0u) accin = cin;
+    if (act) identity_store(a, k, tid, r, accin);
+    else if (tid < a.air_rows) identity_zero_row(a, tid);
+    identity_scalars_rows(a, sc_row, tid, IDENTITY_LANES);
+}
+// The plain form: one lane walks all groups, the others zero the padding rows (tools/fri16_identity_forms.hip checks the scan form against it and times both)
+__device__ __forceinline__ void fri16_identity_rows_plain_body(const IdentityRowsArgs& a) {
+    __shared__ uint32_t sc_row[sc16_width(SC16_MAX_N)];
+    const uint32_t tid = threadIdx.x, G = a.W >> 2;
+    IdentityScalars k;
+    identity_scalars(a, k);
+    if (tid == 0u) {
+        identity_scalars_row(a, k, sc_row);
+        Ext acc = ext_zero();
+#pragma unroll 1
+        for (uint32_t g = 0; g < G; g++) {
+            IdentityGroup r;
+            identity_group(a, k, g, r);
+            acc = identity_store(a, k, g, r, acc);
+        }
+    } else if (tid >= G && tid < a.air_rows) identity_zero_row(a, tid);
+    __syncthreads();
+    identity_scalars_rows(a, sc_row, tid, blockDim.x);
+}
+__global__ void __launch_bounds__(IDENTITY_LANES) fri16_identity_rows_kernel(IdentityRowsArgs a) { fri16_identity_rows_body(a); }
 #endif
 
 }  // namespace fri16

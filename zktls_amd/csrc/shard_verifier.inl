@@ -616,20 +616,7 @@ ScCols sc_cols(const Shape& sh) {
     c.end = n;
     return c;
 }
-// zps_k(zeta) = a_k zeta^N + b_k for the two quotient chunks (canonical)
-void zps_consts(const Shape& sh, uint32_t a[2], uint32_t b[2]) {
-    const uint64_t N = (uint64_t)1 << sh.n;
-    const uint32_t wq = two_adic_generator(sh.n + 1);
-    uint32_t sN[2];
-    for (int k = 0; k < 2; k++) sN[k] = fpow(fmul(MONTY_GEN, fpow(wq, (uint64_t)k)), N);
-    for (int k = 0; k < 2; k++) {
-        const int j = 1 - k;
-        const uint32_t sj_inv = finv(sN[j]);
-        const uint32_t den_inv = finv(fsub(fmul(sN[k], sj_inv), MONTY_R1));
-        a[k] = from_monty(fmul(sj_inv, den_inv));
-        b[k] = from_monty(fneg(den_inv));
-    }
-}
+// (zps_k(zeta) = a_k zeta^N + b_k for the two quotient chunks: airb::zps_consts, air_builder.h)
 std::vector<uint32_t> scalars_program(const Shape& sh) {
     const ScCols m = sc_cols(sh);
     Builder c;
@@ -659,7 +646,7 @@ std::vector<uint32_t> scalars_program(const Shape& sh) {
         add_ext(c, ALL, esub(ev(k ? m.QK1 : m.QK0), q));
     }
     uint32_t za[2], zb[2];
-    zps_consts(sh, za, zb);
+    zps_consts(sh.n, za, zb);
     const EE z0 = eadd(escale(znn, za[0]), ec(zb[0])), z1 = eadd(escale(znn, za[1]), ec(zb[1]));
     add_ext(c, ALL, esub(ev(m.QUO), eadd(emul(z0, ev(m.QK0)), emul(z1, ev(m.QK1)))));
     add_ext(c, ALL, esub(ev(m.ACC), emul(ev(m.QUO), esub(znn, ec(1)))));
@@ -1059,7 +1046,7 @@ int fill_one(const Shape& sh, const Machine& m, int p, const uint8_t* inner, siz
         scput(k ? scc.QK1 : scc.QK0, q);
     }
     uint32_t za[2], zb[2];
-    zps_consts(sh, za, zb);
+    zps_consts(sh.n, za, zb);
     const Ext quo = ext_add(ext_mul(ext_add_base(ext_mul_base(znn, to_monty(za[0])), to_monty(zb[0])), qk[0]), ext_mul(ext_add_base(ext_mul_base(znn, to_monty(za[1])), to_monty(zb[1])), qk[1]));
     scput(scc.QUO, quo);
     sec("scalars");

@@ -902,11 +902,14 @@ class Context:
     def fri16_head_key(self, view, params=None):
         """zkhip_fri16_head_key: the key of the fold-16 head machine, committed on the device -- from the shape, the inner proof's grinding bits, trace width and
         number of public values, the final coefficients, the layer roots, the trace root and the quotient root: no opened word, no constant, no challenge -> MachineKey"""
+        return self._fri16_head_kind_key("head", view, params)
+
+    def _fri16_head_kind_key(self, kind, view, params):
         params = params or Params(1, 100, 16)
         shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
         _, _, troot, qroot = _fri16_rowpaths_arrays(view)
         handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_head_key(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
+        check(getattr(self.lib, "zkhip_fri16_%s_key" % kind)(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
                                             *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
         return MachineKey(self, handle, root, None)
 
@@ -931,6 +934,9 @@ class Context:
         public values, the quotient root and the opened values, and the eight constants and the commit phase's capacity are what it gives".  view: a row-paths view with
         "pubs" (the inner proof's public values) and "opened" [2 W + 8][4].  The proof's public values are view["pubs"].  Refused before anything is proven: all
         prove_fri16_rowpaths refuses, a derived constant or capacity that is not the view's, values that are not canonical, more than 30 public values or none"""
+        return self._prove_fri16_head_kind("head", key, view, params)
+
+    def _prove_fri16_head_kind(self, kind, key, view, params):
         params = params or Params(1, 100, 16)
         shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
         W, trows, qrows, consts = _fri16_openings_arrays(view)
@@ -939,14 +945,38 @@ class Context:
         pb = int(view["pow_bits"])
         cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
         assert cap.size == 8
-        size = self.lib.zkhip_fri16_head_proof_size(*shape, pb, W, pubs.size, C.byref(params))
+        size = getattr(self.lib, "zkhip_fri16_%s_proof_size" % kind)(*shape, pb, W, pubs.size, C.byref(params))
         buf = np.empty(max(size, 1), dtype=np.uint8)
         got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16_head(self.handle, key.handle, *shape, hw, pb, W, pubs.size, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
+        check(getattr(self.lib, "zkhip_prove_fri16_%s" % kind)(self.handle, key.handle, *shape, hw, pb, W, pubs.size, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
                                               paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]),
                                               *[a.ctypes.data_as(u32p) for a in (trows, qrows, consts, tpaths, qpaths, troot, qroot, pubs, opened)], C.byref(params),
                                               buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
+
+    # ---- the fold-by-16 IDENTITY machine (the AIR identity at zeta in-circuit: AIR16, SCALARS16)
+    def fri16_identity_key(self, view, params=None):
+        """zkhip_fri16_identity_key: the key of the fold-16 identity machine, committed on the device -- fri16_head_key's arguments -> MachineKey"""
+        return self._fri16_head_kind_key("identity", view, params)
+
+    def fri16_identity_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, NP, alpha, zeta, opened):
+        """zkhip_fri16_identity_gen_traces: the AIR16 and SCALARS16 main traces from the shape, alpha, zeta and the opened values [2 W + 8][4] alone -> (AIR16 [2^lr][56],
+        SCALARS16 [2^7][4 (17 + log_n)] (canonical words, downloaded), the two accumulators [2][4] (canonical): ACCO of the last group, QUO (zeta^N - 1))"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        dims = {d[4]: (d[1], d[2]) for d in (fri16_identity_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, 0) for which in range(13))}
+        al, ze, op = u(alpha), u(zeta), u(opened)
+        assert al.size == ze.size == 4 and op.size == 8 * (W + 4)
+        air, sc = self.alloc(dims[11][1] << dims[11][0]), self.alloc(dims[12][1] << dims[12][0])
+        accs = np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_identity_gen_traces(self.handle, R, F, log_blowup, n_queries, pow_bits, W, NP, *[a.ctypes.data_as(u32p) for a in (al, ze, op)],
+                                                       C.c_void_p(air.ptr), C.c_void_p(sc.ptr), accs.ctypes.data_as(u32p)))
+        return air.download().reshape(-1, dims[11][1]), sc.download().reshape(-1, dims[12][1]), accs.reshape(2, 4)
+
+    def prove_fri16_identity(self, key, view, params=None):
+        """zkhip_prove_fri16_identity: everything prove_fri16_head states, and "the synthetic AIR's constraints at zeta, folded with the alpha the transcript draws, equal
+        the quotient the opened quotient values give times zeta^N - 1".  view: a head view.  Refused before anything is proven: all prove_fri16_head refuses, zeta = 1, an
+        inner proof whose AIR identity at zeta does not hold"""
+        return self._prove_fri16_head_kind("identity", key, view, params)
 
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
@@ -1885,15 +1915,31 @@ def fri16_head_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kin
     return _describe("fri16_head_describe", R, F, log_blowup, n_queries, pow_bits, W, NP, which=which, kind=kind)
 
 
-def fri16_head_key_host(view, params=None):
+def fri16_head_key_host(view, params=None, _entry="zkhip_fri16_head_key_host"):
     """zkhip_fri16_head_key_host: the fold-16 head machine's key of a view (with "pow_bits", "W", "troot", "qroot", "pubs"), without a GPU -> 8 canonical words"""
     params = params or Params(1, 100, 16)
     shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
     _, _, troot, qroot = _fri16_rowpaths_arrays(view)
     vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_head_key_host(*shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
-                                                *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), vk.ctypes.data_as(u32p)))
+    check(getattr(_lib.load(), _entry)(*shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
+                                       *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), vk.ctypes.data_as(u32p)))
     return vk
+
+
+def fri16_identity_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kind):
+    """zkhip_fri16_identity_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..12) of the fold-16 identity machine
+    -> (words, log_rows, main_width, pre_width, table number)"""
+    return _describe("fri16_identity_describe", R, F, log_blowup, n_queries, pow_bits, W, NP, which=which, kind=kind)
+
+
+def fri16_identity_key_host(view, params=None):
+    """zkhip_fri16_identity_key_host: the fold-16 identity machine's key of a head view, without a GPU -> 8 canonical words"""
+    return fri16_head_key_host(view, params, _entry="zkhip_fri16_identity_key_host")
+
+
+def verify_fri16_identity(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
+    """zkhip_verify_fri16_identity: verify_fri16_head's arguments -> (rc, reason); host only"""
+    return _verify("verify_fri16_identity", proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, len(inner_public), vk=vk, params=params)
 
 
 def verify_fri16_head(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
