@@ -254,8 +254,119 @@ template <int NG>
 #endif
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QWPE, QWPE))) quotient_kernel_batch(const quotient_kernel_bargs* __restrict__ zk_arr) { const quotient_kernel_bargs& zk_b = zk_arr[blockIdx.z]; quotient_kernel_body<NG>(zk_b.a); }
 
+// ------------------------------------------------------------------ lane-per-row forms (quotient here, row sums below)
+// The chain kernel above and rowdot_regs_kernel spread a row over 16 lanes and keep the per-column weights, which never change from row
+// to row, in vector registers (64 of 126 / 172 VGPRs: two waves per SIMD), and every lane-row pays four dacc_finish, four DPP sums and
+// (quotient) the row's scalars.  Here a LANE owns a whole row: a wavefront stages its 64 rows through LDS in slices of 32 columns -- one
+// 128-byte line per row and slice, eight adjacent lanes per line, the access pattern of the LDE pass kernels -- and reads its own row
+// back 16 bytes at a time.  The weights of a slice are wave-uniform (scalar loads), the four running sums stay in the lane over all
+// slices, one dacc_finish per limb and row, no cross-lane sum.  The next slice is in flight in registers while the current one is
+// consumed, so one LDS buffer per wavefront serves; the pitch of 36 words puts the sixteen lanes of a ds_read_b128 group on sixteen
+// distinct 16-byte slots.  The tile is private to its wavefront and LDS operations of one wavefront execute in order: no barrier, only
+// fences that keep the compiler from moving LDS accesses across the hand-over.  Read the ISA after touching these kernels: the weights
+// must stay s_load (a volatile asm in the body turned them into vector loads, whose waits also wait for the slice in flight), and no
+// s_waitcnt vmcnt may stand between a slice's LDS writes and the next slice's.
+constexpr int SLICE_COLS = 32;
+constexpr int SLICE_PITCH = SLICE_COLS + 4;                      // words
+constexpr uint64_t STREAM_MIN_ROWS = 2048;                       // eight workgroups of 256 rows; below, the 16-lane forms have more wavefronts to offer
+ZK_D void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+#ifdef ZKHIP_AB_HOOKS
+// A/B builds: ZKHIP_STREAM_OLD=1 sends every shape to the 16-lane forms (read per launch, so that one process can compare both)
+static bool stream_forms_off() { const char* e = getenv("ZKHIP_STREAM_OLD"); return e && atoi(e) != 0; }
+#endif
+
+// A wavefront takes 64 consecutive rows j of one chunk (e = 2 j + parity: four of the chains of quotient_kernel, each chain's 17th row
+// being the next chain's first) plus the successor of the last: 65 staged rows for 64 points.  A lane reads its own row from the tile
+// and the d word of row e + 2 from its successor's copy; xs, the selectors and the LogUp addend are read once per row.
+__device__ __forceinline__ void quotient_stream_kernel_body(const QuotientArgs& a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[4][65 * SLICE_PITCH];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int H = a.log_n + 1;
+    const uint32_t m = 1u << H;
+    const uint32_t wpp = m >> 7;                                  // wavefronts per chunk
+    const uint32_t gw = blockIdx.x * 4u + wave;
+    if (gw >= 2u * wpp) return;
+    const uint32_t parity = gw / wpp, j0 = (gw % wpp) * 64u;
+    uint32_t* t = tile[wave];
+    // staging: load k of a slice is the 16 bytes (lane % 8) of local row 8 k + lane / 8; lanes 0..7 also load row 64
+    const uint32_t part = lane & 7u, sub = lane >> 3;
+    const uint32_t* src[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const uint32_t j = j0 + 8u * k + (k < 8 ? sub : 0u);
+        const uint32_t pr = __brev((2u * j + parity) & (m - 1)) >> (32 - H);       // row 64 of the last wavefront wraps to e = parity
+        src[k] = a.lde + (uint64_t)pr * a.ld + 4u * part;
+    }
+    const bool tail = lane < 8u;
+    uint4 pf[9];
+#pragma unroll
+    for (int k = 0; k < 8; k++) pf[k] = ld_stream(src[k]);
+    pf[8] = tail ? ld_stream(src[8]) : make_uint4(0, 0, 0, 0);
+
+    const uint32_t j = j0 + lane;
+    const uint32_t p = __brev(2u * j + parity) >> (32 - H);
+    uint32_t sel_first = a.sel_first[p];
+    const uint32_t sel_trans = dsub(a.xs[p], a.wn_inv);
+    asm("" : "+v"(sel_first));                                    // in its register before the loop: a wait for this load inside it would also wait for the slice in flight
+    const uint32_t nsl = a.width / SLICE_COLS;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    for (uint32_t s = 0; s < nsl; s++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) *reinterpret_cast<uint4*>(t + (8u * k + sub) * SLICE_PITCH + 4u * part) = pf[k];
+        if (tail) *reinterpret_cast<uint4*>(t + 64u * SLICE_PITCH + 4u * part) = pf[8];
+        if (s + 1 < nsl) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) pf[k] = ld_stream(src[k] + SLICE_COLS * (s + 1));
+            if (tail) pf[8] = ld_stream(src[8] + SLICE_COLS * (s + 1));
+        }
+        wave_lds_handover();
+        const uint4* wp = reinterpret_cast<const uint4*>(a.alpha_pow + 16u * (SLICE_COLS / 4) * s);      // wave-uniform
+#pragma unroll
+        for (int g = 0; g < SLICE_COLS / 4; g++) {
+            const uint4 v = *reinterpret_cast<const uint4*>(t + lane * SLICE_PITCH + 4 * g);
+            const uint32_t dn = t[(lane + 1u) * SLICE_PITCH + 4 * g + 3];
+            const uint4 w0 = wp[4 * g], w1 = wp[4 * g + 1], w2 = wp[4 * g + 2], kk = wp[4 * g + 3];
+            // the constraints of quotient_kernel, word for word
+            const uint32_t aab = dmul(dmont_lazy(v.x, v.x), v.y);
+            const uint32_t c1 = dsub(dsub(v.z, aab), kk.x);
+            const uint32_t ab = dmul(v.x, v.y);
+            const uint32_t c2 = dmul(dsub_lazy(dsub(dsub(dn, ab), v.z), kk.y), sel_trans);
+            const uint32_t c3 = dmul(dsub_lazy(v.w, kk.z), sel_first);
+            dacc2(acc[0], w0.x, c1, w1.x, c2); dacc1(acc[0], w2.x, c3);
+            dacc2(acc[1], w0.y, c1, w1.y, c2); dacc1(acc[1], w2.y, c3);
+            dacc2(acc[2], w0.z, c1, w1.z, c2); dacc1(acc[2], w2.z, c3);
+            dacc2(acc[3], w0.w, c1, w1.w, c2); dacc1(acc[3], w2.w, c3);
+        }
+        wave_lds_handover();
+    }
+    Ext r = Ext{{dacc_finish(acc[0]), dacc_finish(acc[1]), dacc_finish(acc[2]), dacc_finish(acc[3])}};
+    if (a.addend) r = ext_add(r, ld_ext(a.addend + 4 * (uint64_t)p));
+    r = ext_mul_base_dev(r, parity ? a.inv_zh_odd : a.inv_zh_even);
+    st_ext(a.out + ((uint64_t)parity * (m >> 1) + j) * 4, r);
+    if (a.lde_out) st_ext(a.lde_out + (uint64_t)p * a.lde_ld + 4u * parity, r);
+}
+__global__ void __launch_bounds__(256) quotient_stream_kernel(QuotientArgs a) { quotient_stream_kernel_body(a); }
+struct quotient_stream_kernel_bargs { QuotientArgs a; static quotient_stream_kernel_bargs make(QuotientArgs a) { return quotient_stream_kernel_bargs{a}; } };
+__global__ void __launch_bounds__(256) quotient_stream_kernel_batch(const quotient_stream_kernel_bargs* __restrict__ zk_arr) { const quotient_stream_kernel_bargs& zk_b = zk_arr[blockIdx.z]; quotient_stream_kernel_body(zk_b.a); }
+
+// shapes the lane-per-row form takes: whole slices, whole workgroups of one chunk (rows are 16-byte aligned for either form)
+static bool quotient_stream_form(const QuotientArgs& a) {
+#ifdef ZKHIP_AB_HOOKS
+    if (stream_forms_off()) return false;
+#endif
+    return a.width % SLICE_COLS == 0 && (2ull << a.log_n) >= STREAM_MIN_ROWS;
+}
+
 hipError_t launch_quotient(const QuotientArgs& a, hipStream_t s) {
     const uint64_t m = 2ull << a.log_n;
+    if (quotient_stream_form(a)) {
+        ZK_LAUNCH(quotient_stream_kernel, quotient_stream_kernel_batch, quotient_stream_kernel_bargs, dim3((unsigned)(m / 256)), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
     const uint64_t threads = (m / QCHAIN) * a.lanes_per_row;
     const uint32_t G = a.width / 4;
     const int ng = (int)((G + a.lanes_per_row - 1) / a.lanes_per_row);
@@ -1146,6 +1257,48 @@ struct rowdot_regs_kernel_bargs { const uint32_t* mat; uint64_t ld; uint32_t wid
 template <int NK>
 __global__ void __launch_bounds__(256) rowdot_regs_kernel_batch(const rowdot_regs_kernel_bargs* __restrict__ zk_arr) { const rowdot_regs_kernel_bargs& zk_b = zk_arr[blockIdx.z]; rowdot_regs_kernel_body<NK>(zk_b.mat, zk_b.ld, zk_b.width, zk_b.rows, zk_b.L, zk_b.alpha_pow, zk_b.out_at); }
 
+// The lane-per-row form (see quotient_stream_kernel): a wavefront takes 64 consecutive rows, stages them through its LDS tile in
+// slices of 32 columns and each lane sums its own row; the powers of a slice's eight column quads are scalar loads.  Same exact field sum
+// as the forms above in another order, one dacc_finish per limb and row.
+__device__ __forceinline__ void rowdot_stream_kernel_body(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* __restrict__ alpha_pow, uint32_t* __restrict__ out_at) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[4][64 * SLICE_PITCH];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + wave) * 64u;
+    if (r0 >= rows) return;                                       // rows is a multiple of 64: whole waves leave together
+    uint32_t* t = tile[wave];
+    const uint32_t part = lane & 7u, sub = lane >> 3;
+    const uint32_t* src = mat + (r0 + sub) * ld + 4u * part;      // load k of a slice: the 16 bytes `part` of local row 8 k + sub
+    uint4 pf[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) pf[k] = ld_stream(src + 8u * k * ld);
+    const uint32_t nsl = width / SLICE_COLS;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    for (uint32_t s = 0; s < nsl; s++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) *reinterpret_cast<uint4*>(t + (8u * k + sub) * SLICE_PITCH + 4u * part) = pf[k];
+        if (s + 1 < nsl) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) pf[k] = ld_stream(src + 8u * k * ld + SLICE_COLS * (s + 1));
+        }
+        wave_lds_handover();
+        const uint4* ap = reinterpret_cast<const uint4*>(alpha_pow + 16u * (SLICE_COLS / 4) * s);       // wave-uniform
+#pragma unroll
+        for (int q = 0; q < SLICE_COLS / 4; q++) {
+            const uint4 v = *reinterpret_cast<const uint4*>(t + lane * SLICE_PITCH + 4 * q);
+            const uint4 a0 = ap[4 * q], a1 = ap[4 * q + 1], a2 = ap[4 * q + 2], a3 = ap[4 * q + 3];
+            dacc2(acc[0], a0.x, v.x, a1.x, v.y); dacc2(acc[0], a2.x, v.z, a3.x, v.w);
+            dacc2(acc[1], a0.y, v.x, a1.y, v.y); dacc2(acc[1], a2.y, v.z, a3.y, v.w);
+            dacc2(acc[2], a0.z, v.x, a1.z, v.y); dacc2(acc[2], a2.z, v.z, a3.z, v.w);
+            dacc2(acc[3], a0.w, v.x, a1.w, v.y); dacc2(acc[3], a2.w, v.z, a3.w, v.w);
+        }
+        wave_lds_handover();
+    }
+    st_ext(out_at + 4 * (r0 + lane), Ext{{dacc_finish(acc[0]), dacc_finish(acc[1]), dacc_finish(acc[2]), dacc_finish(acc[3])}});
+}
+__global__ void __launch_bounds__(256) rowdot_stream_kernel(const uint32_t* __restrict__ mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* __restrict__ alpha_pow, uint32_t* __restrict__ out_at) { rowdot_stream_kernel_body(mat, ld, width, rows, alpha_pow, out_at); }
+struct rowdot_stream_kernel_bargs { const uint32_t* mat; uint64_t ld; uint32_t width; uint64_t rows; const uint32_t* alpha_pow; uint32_t* out_at; static rowdot_stream_kernel_bargs make(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* alpha_pow, uint32_t* out_at) { return rowdot_stream_kernel_bargs{mat, ld, width, rows, alpha_pow, out_at}; } };
+__global__ void __launch_bounds__(256) rowdot_stream_kernel_batch(const rowdot_stream_kernel_bargs* __restrict__ zk_arr) { const rowdot_stream_kernel_bargs& zk_b = zk_arr[blockIdx.z]; rowdot_stream_kernel_body(zk_b.mat, zk_b.ld, zk_b.width, zk_b.rows, zk_b.alpha_pow, zk_b.out_at); }
+
 static hipError_t launch_rowdot(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* alpha_pow, uint32_t* out_at, hipStream_t s);
 __device__ __forceinline__ void reduced_combine_kernel_body(const ReducedArgs& a, const uint32_t* __restrict__ at_in, const uint32_t* __restrict__ ap_in) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1188,6 +1341,15 @@ int rowdot_form(uint32_t width, uint64_t rows) {
 static hipError_t launch_rowdot(const uint32_t* mat, uint64_t ld, uint32_t width, uint64_t rows, const uint32_t* alpha_pow, uint32_t* out_at, hipStream_t s) {
     const int L = lanes_for(width);
     const int form = rowdot_form(width, rows);
+    // inside the register forms (so rowdot_form and what zkhip_reduced_opening reports stay what they were): whole slices, whole wavefronts
+    bool stream = form && width % SLICE_COLS == 0 && rows % 64 == 0 && rows >= STREAM_MIN_ROWS;
+#ifdef ZKHIP_AB_HOOKS
+    if (stream_forms_off()) stream = false;
+#endif
+    if (stream) {
+        ZK_LAUNCH(rowdot_stream_kernel, rowdot_stream_kernel_batch, rowdot_stream_kernel_bargs, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, mat, ld, width, rows, alpha_pow, out_at);
+        return hipGetLastError();
+    }
     if (form) {
         const uint64_t rows_per_wg = (uint64_t)(256 / L) * ROWDOT_TRIPS;
         const dim3 grid((unsigned)((rows + rows_per_wg - 1) / rows_per_wg)), block(256);
