@@ -457,6 +457,43 @@ int zkhip_prove_fri16_identity(zkhip_ctx* ctx, const zkhip_machine_key* key, int
 int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
 
+/* ---- the fold-16 LIFT machine: the identity machine whose key depends on the SHAPE alone ----
+ * Statement: "some valid segment proof of this shape with THESE public values exists" -- everything the identity machine states, with the layer roots, the trace
+ * root, the quotient root and the final coefficients no longer in the key: they are MAIN columns of ROOTS (8 .. 15) and COEFFS (4 .. 7), pinned by Fiat-Shamir alone
+ * (the transcript chain starts from the all-zero state and absorbs every one of them over a bus).  ROOTS' preprocessed column 2 is ACT (1 on rows 0 .. R + 1) and
+ * ENDS (1 - ACT) = 0 keeps a padding row from receiving a path end; every other multiplicity that gates a moved word is preprocessed.  The same thirteen tables,
+ * heights, inner proofs and public values as the identity machine; tests/fri16_lift_air.py writes the changed parts again.  One key per shape: two segments of one
+ * execution share it, and whoever verifies needs no one who saw the inner proof.
+ * zkhip_fri16_lift_describe / _proof_size: the _identity_ entries' arguments.  zkhip_fri16_lift_key_host (no GPU) / _key: the _identity_ entries' WITHOUT final_poly,
+ * roots, trace_root and quotient_root.  zkhip_fri16_lift_gen_tables: the main columns of ROOTS (dense [2^5][16]; its first eight columns, which the transcript
+ * launch makes, come out zero) and COEFFS (dense [max(2^5, 2^F)][8]) on the device from the canonical roots and coefficients -- one launch, Montgomery form made in
+ * the kernel, rows past the active ones zero.  zkhip_prove_fri16_lift takes the identity prover's arguments and refuses what it refuses, with the same messages
+ * (root or coefficient words >= P among them).  zkhip_verify_fri16_lift is host only.
+ * zkhip_prove_fri16_lift_segment: segment proof in, lift proof out -- ONE pass of the host verifier over `proof` (log_n, width, public_values, inner_prm) with every
+ * fold-16 view attached, then the lift prover under outer_prm.  It fails with the host verifier's code and message when the inner proof does not verify, and with
+ * zkhip_fri16_view_head's message on a form that view does not take.
+ * STILL OUTSIDE: the join of several lift proofs and the r0 host mirror's compress path (Risc0HipGuestProver::with_compress(), the Rust twin), lookups, version-7
+ * and version-8 inner proofs, the wiring into shard_verifier.inl, a batch entry over the lock-step lanes. */
+size_t zkhip_fri16_lift_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                 uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
+int zkhip_fri16_lift_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const zkhip_params* prm, uint32_t vk[8]);
+int zkhip_fri16_lift_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                         uint32_t n_inner_public, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_lift_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm);
+int zkhip_fri16_lift_gen_tables(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* roots, const uint32_t trace_root[8],
+                                const uint32_t quotient_root[8], const uint32_t* final_poly, uint32_t* d_roots_main, uint32_t* d_coeffs_main);
+int zkhip_prove_fri16_lift(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                           uint8_t* proof, size_t cap, size_t* len);
+int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                            uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
+int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
+                                   size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len);
+
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */
 int zkhip_air_synthetic(uint32_t width, size_t n_public, uint32_t* out, size_t cap, size_t* words);

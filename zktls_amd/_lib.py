@@ -63,6 +63,8 @@ EXPORTS = [
     "zkhip_fri16_head_gen_traces", "zkhip_prove_fri16_head", "zkhip_verify_fri16_head",
     "zkhip_fri16_identity_describe", "zkhip_fri16_identity_key_host", "zkhip_fri16_identity_key", "zkhip_fri16_identity_proof_size", "zkhip_fri16_identity_gen_traces",
     "zkhip_prove_fri16_identity", "zkhip_verify_fri16_identity",
+    "zkhip_fri16_lift_describe", "zkhip_fri16_lift_key_host", "zkhip_fri16_lift_key", "zkhip_fri16_lift_proof_size", "zkhip_fri16_lift_gen_tables",
+    "zkhip_prove_fri16_lift", "zkhip_verify_fri16_lift", "zkhip_prove_fri16_lift_segment",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -434,6 +436,17 @@ def load():
     L.zkhip_fri16_identity_gen_traces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, u32p, C.c_void_p, C.c_void_p, u32p]
     L.zkhip_prove_fri16_identity.argtypes = L.zkhip_prove_fri16_head.argtypes
     L.zkhip_verify_fri16_identity.argtypes = L.zkhip_verify_fri16_head.argtypes
+    # the fold-16 lift machine: the identity machine's entries, the key's WITHOUT the proof-dependent arrays; the launch of its two tables; segment proof in, lift proof out
+    for name in ("describe", "proof_size"):
+        getattr(L, "zkhip_fri16_lift_" + name).restype = C.c_size_t
+        getattr(L, "zkhip_fri16_lift_" + name).argtypes = getattr(L, "zkhip_fri16_head_" + name).argtypes
+    L.zkhip_fri16_lift_key_host.argtypes = fri16_hshape + [C.POINTER(Params), u32p]
+    L.zkhip_fri16_lift_key.argtypes = [C.c_void_p] + fri16_hshape + [C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_lift_gen_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, u32p, u32p, u32p, u32p, C.c_void_p, C.c_void_p]
+    L.zkhip_prove_fri16_lift.argtypes = L.zkhip_prove_fri16_head.argtypes
+    L.zkhip_verify_fri16_lift.argtypes = L.zkhip_verify_fri16_head.argtypes
+    L.zkhip_prove_fri16_lift_segment.argtypes = [C.c_void_p, C.c_void_p, u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(Params), u8p,
+                                                 C.c_size_t, C.POINTER(C.c_size_t)]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

@@ -160,6 +160,13 @@ extern thread_local int t_query_threads_cap;
 int fri_view_all_unhashed(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
                           uint32_t* betas, uint32_t final_value[4], uint32_t* indices, uint32_t* values, uint32_t* siblings, uint32_t* roots, uint32_t* paths,
                           uint32_t transcript[10], const uint32_t* program = nullptr, size_t program_words = 0);      // (program: a version-7 proof of that constraint program)  -- above: the context's pinned host block, grown to `bytes`; contents undefined
+// verifier.cpp: every fold-16 view of a version-3 shard proof (canonical words, the layouts of the zkhip_fri16_view_* entries) from one pass of the verifier
+struct Fri16FullView {
+    int R = 0, F = 0, hash_width = 0;
+    std::vector<uint32_t> betas, final_poly, indices, values, siblings, roots, paths, trace_rows, quotient_rows, trace_paths, quotient_paths, opened;
+    uint32_t transcript[10] = {0}, constants[32] = {0}, trace_root[8] = {0}, quotient_root[8] = {0}, alpha[4] = {0};
+};
+int fri16_view_all(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm, Fri16FullView& v);
 int get_plan(zkhip_ctx* ctx, int log_n, int kind, uint32_t shift_monty, const NttPlan** out);
 // internal op entry points shared by capi.cpp and prover.cpp (device pointers, ctx stream)
 int op_coset_lde(zkhip_ctx* ctx, const uint32_t* d_in, size_t in_ld, uint32_t* d_out, size_t out_ld,

@@ -46,6 +46,10 @@
 //                                          two more buses) with the alpha P2TH now sends; SCALARS16 squares zeta up to zeta^N, derives the two selectors, puts the quotient
 //                                          together from the eight opened quotient values and ties the two: acc = quot (zeta^N - 1).  With it the proof says that the inner
 //                                          statement holds, not only that its columns were opened consistently (tests/fri16_identity_air.py)
+//   LIFT     (zkhip_prove_fri16_lift)      the roots and the final coefficients OUT of the key: they are main columns of ROOTS and COEFFS, made on the device
+//                                          (fri16_lift_tables_kernel) and pinned by the transcript chain alone.  The key is a function of the shape and the public-value
+//                                          count: ONE key per shape states "some valid segment proof of this shape with these public values exists" -- RISC Zero's lift.
+//                                          zkhip_prove_fri16_lift_segment is the call from segment proof to lift proof (tests/fri16_lift_air.py)
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
 // table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
 // to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
@@ -98,9 +102,9 @@ enum : int { T_FOLD16 = 0, T_FINAL = 1, T_LAYERS = 2, T_P24L = 2, T_QUERIES = 3,
               T_P24R = 9, T_OPENED16 = 10, T_AIR16 = 11, T_SCALARS16 = 12, MAX_TABLES = 13 };
 inline uint32_t canon_nibble_factor(uint32_t first_bit, uint32_t nbits, uint32_t j) { return from_monty(nibble_factor(first_bit, nbits, j)); }
 
-// The machines are ONE description read at seven kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
+// The machines are ONE description read at eight kinds, each kind the one before it with a step more of the inner verifier inside.  What a kind adds to the shape
 // (pow_bits, C S NT from INDICES on; W from OPENINGS on) stays zero below it.  shape_of, program_of, interactions_of and machine_of are further down, behind the chips.
-enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS, HEAD, IDENTITY };
+enum Kind : int { LAYERS = 0, PATHS, INDICES, OPENINGS, ROWPATHS, HEAD, IDENTITY, LIFT };
 struct Shape {
     Kind kind = LAYERS;
     int R = 0, F = 0, b = 0, lf = 0, H = 0, pow_bits = 0, n_tables = 0;
@@ -252,8 +256,9 @@ std::vector<uint32_t> build_final_program(uint32_t n_public) {
         b.add(TRANSITION, Terms{{1u, {var(FNL), var(CFACC + c, true)}}, {P - 1, {var(FNL), var(CFAX + c)}}, {P - 1, {var(FNL), var(CFC + c, true)}}});
     return b.finish(FIN_PRE + FIN_MAIN, n_public);
 }
-std::vector<uint32_t> build_table_program(uint32_t n_public, uint32_t pre_width, uint32_t main_width = TAB_MAIN) {          // the contents are fixed by the KEY: one harmless identity
-    return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + main_width, 1u, n_public, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + main_width - 1u)};
+// (pinned: the main column the identity names, by default the last; the lift machine's COEFFS holds c_j in its last four and names the last UNUSED one)
+std::vector<uint32_t> build_table_program(uint32_t n_public, uint32_t pre_width, uint32_t main_width = TAB_MAIN, uint32_t pinned = ~0u) {          // the contents are fixed by the KEY: one harmless identity
+    return std::vector<uint32_t>{AIR_MAGIC, 1u, pre_width + main_width, 1u, n_public, 6u + 5u, FIRST, 1u, 1u, 1u, var(pre_width + (pinned == ~0u ? main_width - 1u : pinned))};
 }
 
 inline Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
@@ -444,11 +449,14 @@ std::vector<uint32_t> build_p2t_program(uint32_t n_public) {
 }
 // ROOTS' program: the harmless identity of a key table, and FOLDROWS (1 - LISTED) = 0 -- the multiplicity of the send (layer, beta) to FOLD16B is a MAIN column, and a
 // padding row's preprocessed cells are zero (layer 0, nothing received from the transcript): without this a padding row could hand layer 0 a challenge of the prover's choice
-std::vector<uint32_t> build_roots_program(uint32_t n_public, uint32_t pre_w = ROOTS_PRE16) {      // (the head machine's ROOTS has eight more preprocessed columns)
+// (lift: the root words are eight more MAIN columns behind these, so the first-row identity keeps naming the spare column 7, not the last one; and the receive
+// multiplicity ENDS is gated by the preprocessed ACT as FOLDROWS is by LISTED -- a padding row's digest is free there, so it must receive nothing)
+std::vector<uint32_t> build_roots_program(uint32_t n_public, uint32_t pre_w = ROOTS_PRE16, bool lift = false) {      // (the head machine's ROOTS has eight more preprocessed columns)
     Builder b;
     b.add(FIRST, Terms{{1u, {var(pre_w + ROOTS_MAIN_I - 1u)}}});
     b.add(ALL, Terms{{1u, {var(pre_w + 5u)}}, {P - 1, {var(pre_w + 5u), var(10u)}}});
-    return b.finish(pre_w + ROOTS_MAIN_I, n_public);
+    if (lift) b.add(ALL, Terms{{1u, {var(pre_w)}}, {P - 1, {var(pre_w), var(RT_ROOT)}}});                              // ENDS (1 - ACT) = 0; ACT sits where root word 0 stood
+    return b.finish(pre_w + (lift ? ROOTS_MAIN_L : ROOTS_MAIN_I), n_public);
 }
 // the key's tables by table number: FINAL's schedule, QUERIES by query number, COEFFS, ROOTS, and the schedules of P2T and SAMPLES -- no index and no challenge
 int build_indices_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* values, const uint32_t* roots, std::vector<uint32_t> pre[], const char* who) {
@@ -937,8 +945,27 @@ int build_identity_key_tables(const Shape& s, const uint32_t* final_poly, const 
     return ZKHIP_OK;
 }
 
+// ---------------------------------------------------------------- the LIFT machine: the identity machine with the roots and the final coefficients OUT of the key
+// The identity machine's thirteen tables, heights, inner proofs and public values.  What changes: ROOTS' eight root words are MAIN columns 8 .. 15 (ENDS BETA[4] FOLDROWS
+// and the two spare columns stay in front of them), on the R layer rows and on the two tree rows; the tuples of BUS_RT0 / RT1, BUS_TR0 / TR1 and BUS_HR read them there.
+// LN, DEP, LISTED, HM and the HK keys stay preprocessed; preprocessed column 2, where root word 0 stood, is ACT (1 on rows 0 .. R + 1) and columns 3 .. 9 are zero;
+// ENDS (1 - ACT) = 0 keeps a padding row, whose digest is now free, from receiving a path end.  COEFFS' c_j are MAIN columns 4 .. 7 behind its four unused ones; j, the
+// multiplicity Q of the send to FINAL and the multiplicity 1 of the send to P2T stay preprocessed, columns 1 .. 4 are zero.  Both first-row identities name a spare
+// column, not a moved word.  Every multiplicity that gates a tuple with a moved word is preprocessed or constrained (DESIGN.md 3c has the table), and Fiat-Shamir pins
+// the values: the chain starts from zero and absorbs every root and coefficient over a bus.  So the key is a function of the SHAPE and NP alone: it states "some valid
+// segment proof of this shape with THESE public values exists".
+// STILL OUTSIDE: the join of several lift proofs and the r0 host mirror's compress path, lookups, version-7 and version-8 inner proofs, the wiring into
+// shard_verifier.inl, a batch entry.  tests/fri16_lift_air.py writes it again.
+int build_lift_key_tables(const Shape& s, std::vector<uint32_t> pre[], const char* who) {
+    const std::vector<uint32_t> no_coeffs((size_t)4 << s.F, 0u), no_roots(8 * (size_t)s.R, 0u);
+    const uint32_t no_root[8] = {0};
+    ZK_TRY(build_identity_key_tables(s, no_coeffs.data(), no_roots.data(), no_root, no_root, pre, who));
+    for (size_t r = 0; r < (size_t)s.R + 2; r++) pre[T_ROOTS][ROOTS_PRE_H * r + RT_ROOT] = MONTY_R1;      // ACT
+    return ZKHIP_OK;
+}
+
 // ---------------------------------------------------------------- the one description: shape, programs, interaction tables, machine, and what every entry does with them
-constexpr int N_TABLES[7] = {5, 6, 8, 10, 10, 11, 13};
+constexpr int N_TABLES[8] = {5, 6, 8, 10, 10, 11, 13, 13};
 inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uint32_t)s.R : s.kind == INDICES ? N_PUBLIC_I : s.kind >= HEAD ? s.NP : N_PUBLIC_O; }
 
 // pow_bits is read from INDICES on, W from OPENINGS on.  ROWSUM16, ROWS and P24R have at least 2^6 rows: a keyed machine takes at most 8 tables of one height, and the
@@ -967,20 +994,20 @@ int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W,
     else table(T_P24L, lg(Q * layer_paths), p24chip::WIDTH_L, 0u);
     if (kind < OPENINGS) table(T_QUERIES, lg(Q), TAB_MAIN, Q_PRE);
     else table(T_QUERY16, lg(Q), Q16_MAIN, Q16_PRE);
-    table(T_COEFFS, lg((size_t)1 << F), TAB_MAIN, C_PRE);
-    table(T_ROOTS, lg((size_t)R), kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, kind >= HEAD ? ROOTS_PRE_H : ROOTS_PRE16);
+    table(T_COEFFS, lg((size_t)1 << F), kind == LIFT ? COEFFS_MAIN_L : TAB_MAIN, C_PRE);
+    table(T_ROOTS, lg((size_t)R), kind == LIFT ? ROOTS_MAIN_L : kind >= INDICES ? ROOTS_MAIN_I : TAB_MAIN, kind >= HEAD ? ROOTS_PRE_H : ROOTS_PRE16);
     table(T_P2T, lg(s.HD + s.NT), p2chip::T_WIDTH, kind >= HEAD ? PTH_PRE : PT_PRE);
     table(T_SAMPLES, lg(s.S), frichip::S_MAIN, frichip::S_PRE);
     table(T_ROWSUM16, std::max(6, lg(Q * (size_t)(W / 8 + 1))), RS_MAIN16, kind >= HEAD ? RS16H_PRE : RS16_PRE);
     if (kind == OPENINGS) table(T_ROWS, std::max(6, lg(Q * (size_t)(W + QROW16) / 4)), TAB_MAIN, ROWS_PRE16);
     else table(T_P24R, std::max(6, lg(Q * row_paths)), p24chip::WIDTH_R, 0u);
-    table(T_OPENED16, std::max(6, lg((size_t)W + 4)), OP_MAIN16, kind == IDENTITY ? OPN_PRE_I : OPN_PRE);
+    table(T_OPENED16, std::max(6, lg((size_t)W + 4)), OP_MAIN16, kind >= IDENTITY ? OPN_PRE_I : OPN_PRE);
     // (IDENTITY: the floors 2^6 and 2^7 keep AIR16 and SCALARS16 from making nine tables of one height where the head machine has eight of 2^5)
     table(T_AIR16, std::max(6, lg((size_t)W / 4)), AIR_MAIN16, AIR16_PRE);
     table(T_SCALARS16, (int)SC16_LOG_ROWS, sc16_width((uint32_t)(s.H - s.b)), SC16_PRE);
     for (int t = 0; kind >= ROWPATHS && t < s.n_tables; t++)          // (below ROWPATHS the floors above keep nine tables from meeting)
         if (std::count(s.log_rows, s.log_rows + s.n_tables, s.log_rows[t]) > MAX_SAME_HEIGHT)
-            return fail(ZKHIP_ERR_INVALID, std::string(kind == IDENTITY ? "fri16 identity" : kind == HEAD ? "fri16 head" : "fri16 rowpaths") + ": nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
+            return fail(ZKHIP_ERR_INVALID, std::string(kind == LIFT ? "fri16 lift" : kind == IDENTITY ? "fri16 identity" : kind == HEAD ? "fri16 head" : "fri16 rowpaths") + ": nine tables of this shape have 2^" + std::to_string(s.log_rows[t]) + " rows; a keyed machine takes at most 8 tables of one height");
     return ZKHIP_OK;
 }
 
@@ -993,7 +1020,7 @@ std::vector<uint32_t> program_of(const Shape& s, int t) {
     case T_FINAL: return build_final_program(np);
     case T_P24L: if (k >= PATHS) return *p24chip::program_fri16_layers(np); break;                                 // (LAYERS: a key table)
     case T_QUERY16: if (k >= OPENINGS) return k >= HEAD ? build_query16h_program(s) : build_query16_program(); break;                                     // (below: QUERIES, a key table)
-    case T_ROOTS: if (k >= INDICES) return build_roots_program(np, s.pre_w[T_ROOTS]); break;                                        // (PATHS: a key table)
+    case T_ROOTS: if (k >= INDICES) return build_roots_program(np, s.pre_w[T_ROOTS], k == LIFT); break;                                        // (PATHS: a key table)
     case T_P2T: return k >= HEAD ? build_p2th_program(s) : build_p2t_program(np);
     case T_SAMPLES: return *frichip::samples_chip_program(s.H, s.pow_bits, np);
     case T_ROWSUM16: return k >= HEAD ? build_rowsum16_program(RS16H_PRE, true, np) : build_rowsum16_program();
@@ -1001,7 +1028,8 @@ std::vector<uint32_t> program_of(const Shape& s, int t) {
     case T_OPENED16: return build_opened16_program(np, s.pre_w[T_OPENED16]);
     case T_AIR16: return build_air16_program(np);
     case T_SCALARS16: return build_scalars16_program(s);
-    default: break;                                                                                                // COEFFS
+    case T_COEFFS: if (k == LIFT) return build_table_program(np, C_PRE, COEFFS_MAIN_L, CL_C - 1u); break;          // (below: the last of four unused columns is the last column)
+    default: break;
     }
     return build_table_program(np, s.pre_w[t], s.main_w[t]);
 }
@@ -1056,21 +1084,25 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
             }
         }
         break;
-    case T_COEFFS:
-        v.add(0u, 5u, BUS_COEF, {0u, 1u, 2u, 3u, 4u});
-        if (k >= INDICES) v.add(0u, 6u, BUS_CT, {0u, 1u, 2u, 3u, 4u});                                             // one more send, to P2T
+    case T_COEFFS: {
+        const uint32_t c = k == LIFT ? C_PRE + CL_C : 1u;                                                          // (lift: c_j is a main column)
+        v.add(0u, 5u, BUS_COEF, {0u, c, c + 1, c + 2, c + 3});
+        if (k >= INDICES) v.add(0u, 6u, BUS_CT, {0u, c, c + 1, c + 2, c + 3});                                     // one more send, to P2T
         break;
-    case T_ROOTS:
-        v.add(1u, RM, BUS_RT0, {RT_LN, RT_DEP, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
-        v.add(1u, RM, BUS_RT1, {RT_LN, RT_DEP, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+    }
+    case T_ROOTS: {
+        const uint32_t rt = k == LIFT ? RM + RL_ROOT : RT_ROOT;                                                    // (lift: the root words are main columns)
+        v.add(1u, RM, BUS_RT0, {RT_LN, RT_DEP, rt, rt + 1, rt + 2, rt + 3});
+        v.add(1u, RM, BUS_RT1, {RT_LN, RT_DEP, rt + 4, rt + 5, rt + 6, rt + 7});
         if (k >= INDICES) {                                                                                        // root and beta from the layer's root row, beta on to the fold rows
-            v.add(1u, 10u, BUS_TR0, {RT_LN, RT_ROOT, RT_ROOT + 1, RT_ROOT + 2, RT_ROOT + 3});
-            v.add(1u, 10u, BUS_TR1, {RT_LN, RT_ROOT + 4, RT_ROOT + 5, RT_ROOT + 6, RT_ROOT + 7});
+            v.add(1u, 10u, BUS_TR0, {RT_LN, rt, rt + 1, rt + 2, rt + 3});
+            v.add(1u, 10u, BUS_TR1, {RT_LN, rt + 4, rt + 5, rt + 6, rt + 7});
             v.add(1u, 10u, BUS_TB, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
             v.add(0u, RM + 5, BUS_BF16, {RT_LN, RM + 1, RM + 2, RM + 3, RM + 4});
         }
-        if (k >= HEAD) for (uint32_t j = 0; j < 8; j++) v.add(0u, RT_HM, BUS_HR, {RT_HK + j, RT_ROOT + j});            // the trace root and the quotient root, word by word, to P2TH
+        if (k >= HEAD) for (uint32_t j = 0; j < 8; j++) v.add(0u, RT_HM, BUS_HR, {RT_HK + j, rt + j});                 // the trace root and the quotient root, word by word, to P2TH
         break;
+    }
     case T_P2T:
         v.add(1u, PT_C0, BUS_CT, {PT_KEY0, in, in + 1, in + 2, in + 3});
         v.add(1u, PT_C1, BUS_CT, {PT_KEY1, in + 4, in + 5, in + 6, in + 7});
@@ -1086,7 +1118,7 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
             v.add(0u, PH_ZM, BUS_ZETA, {o + 7, o + 6, o + 5, o + 4});
             v.add(0u, PH_FM, BUS_FAH, {o + 7, o + 6, o + 5, o + 4});
         }
-        if (k == IDENTITY) v.add(0u, PH_AM, BUS_ALPHA, {o + 7, o + 6, o + 5, o + 4});                                   // alpha, from row A - 1, to SCALARS16
+        if (k >= IDENTITY) v.add(0u, PH_AM, BUS_ALPHA, {o + 7, o + 6, o + 5, o + 4});                                   // alpha, from row A - 1, to SCALARS16
         break;
     case T_ROWSUM16:
         v.add(0u, RP_ACT, BUS_ROW16, {RP_TAG, RP_K0, rv, rv + 1, rv + 2, rv + 3});
@@ -1104,7 +1136,7 @@ std::vector<uint32_t> interactions_of(const Shape& s, int t) {
         v.add(0u, OQ_ENDQ, BUS_YQ, {y, y + 1, y + 2, y + 3});
         v.add(0u, OQ_ENDL, BUS_OFFN, {pwn, pwn + 1, pwn + 2, pwn + 3});
         v.add(1u, OQ_FIRST, BUS_FAH, {fa, fa + 1, fa + 2, fa + 3});
-        if (k == IDENTITY) {                                                                                       // the row's two halves under its row number, to AIR16 and SCALARS16
+        if (k >= IDENTITY) {                                                                                       // the row's two halves under its row number, to AIR16 and SCALARS16
             v.add(0u, OQ_H0, BUS_OH0, {OQ_ROW, m + OP_V, m + OP_V + 1, m + OP_V + 2, m + OP_V + 3});
             v.add(0u, OQ_H1, BUS_OH1, {OQ_ROW, m + OP_V + 4, m + OP_V + 5, m + OP_V + 6, m + OP_V + 7});
         }
@@ -1217,6 +1249,8 @@ struct opened_rows_bargs { OpenedRowsArgs a; static opened_rows_bargs make(Opene
 __global__ void __launch_bounds__(OPENED_LANES) fri16_opened_rows_kernel_batch(const opened_rows_bargs* __restrict__ zk_arr) { fri16_opened_rows_body(zk_arr[blockIdx.z].a); }
 struct identity_rows_bargs { IdentityRowsArgs a; static identity_rows_bargs make(IdentityRowsArgs a) { return identity_rows_bargs{a}; } };
 __global__ void __launch_bounds__(IDENTITY_LANES) fri16_identity_rows_kernel_batch(const identity_rows_bargs* __restrict__ zk_arr) { fri16_identity_rows_body(zk_arr[blockIdx.z].a); }
+struct lift_tables_bargs { LiftTablesArgs a; static lift_tables_bargs make(LiftTablesArgs a) { return lift_tables_bargs{a}; } };
+__global__ void __launch_bounds__(64) fri16_lift_tables_kernel_batch(const lift_tables_bargs* __restrict__ zk_arr) { fri16_lift_tables_body(zk_arr[blockIdx.z].a); }
 
 }  // namespace
 }  // namespace fri16
@@ -1304,7 +1338,7 @@ static int fri16_paths_check_view(const fri16::Shape& s, int inner_hash_width, c
 
 // P2T, SAMPLES and (non-null) the main columns of QUERIES and ROOTS in one launch from one staging block; status: what the kernel found different from the view
 static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::Chain& c, const uint32_t* view_betas, const uint32_t* view_indices, const uint32_t* counts,
-                                 uint32_t* d_p2t, uint32_t* d_samples, uint32_t* d_qmain, uint32_t* d_rmain, uint32_t* status) {
+                                 uint32_t* d_p2t, uint32_t* d_samples, uint32_t* d_qmain, uint32_t* d_rmain, uint32_t* status, const uint32_t** d_chain = nullptr) {
     const size_t R = (size_t)s.R, Q = s.Q, ni = (Q + 3) & ~(size_t)3, nr = (R + 3) & ~(size_t)3;
     const size_t o_words = c.inputs.size(), o_betas = o_words + 8 * s.S, o_vbetas = o_betas + 4 * R, o_vidx = o_vbetas + 4 * R, o_counts = o_vidx + ni, o_status = o_counts + nr, up_words = o_status + 4;
     void* stage;
@@ -1328,6 +1362,7 @@ static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fr
     a.queries_rows = (uint64_t)1 << s.log_rows[fri16::T_QUERIES]; a.roots_rows = (uint64_t)1 << s.log_rows[fri16::T_ROOTS];
     a.p2t = d_p2t; a.samples = d_samples; a.queries_main = d_qmain; a.roots_main = d_rmain; a.status = d + o_status;
     ZK_HIP(launch_fri16_transcript(a, ctx->stream));
+    if (d_chain) *d_chain = d;                                   // (the chain's input states stay where they were uploaded: the lift machine's tables are read off them)
     return dev_d2h(ctx, status, a.status, 4);
 }
 static int fri16_indices_check_inputs(const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, const char* who) {
@@ -1493,6 +1528,20 @@ static int fri16_identity_check_zeta(const uint32_t zeta[4], const char* who) {
     return ZKHIP_OK;
 }
 
+// ROOTS' and COEFFS' main columns of the lift machine in one launch, from the chain's input states where the transcript stage uploaded them (d_chain; row_quotient and
+// row_layers: the rows of the quotient root and of layer root 0) and ROOTS' first eight columns as the transcript launch wrote them (d_base, or null: zero)
+static int fri16_lift_tables_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* d_chain, uint32_t row_quotient, uint32_t row_layers, const uint32_t* d_base,
+                                  uint32_t* d_roots_main, uint32_t* d_coeffs_main) {
+    fri16::LiftTablesArgs a{};
+    a.chain = d_chain; a.roots_base = d_base; a.R = (uint32_t)s.R; a.F = (uint32_t)s.F; a.row_quotient = row_quotient; a.row_layers = row_layers;
+    a.roots_rows = (uint64_t)1 << s.log_rows[fri16::T_ROOTS]; a.coeffs_rows = (uint64_t)1 << s.log_rows[fri16::T_COEFFS];
+    a.roots_main = d_roots_main; a.coeffs_main = d_coeffs_main;
+    const uint64_t lanes = 4 * a.roots_rows + 2 * a.coeffs_rows;
+    ZK_LAUNCH(fri16::fri16_lift_tables_kernel, fri16::fri16_lift_tables_kernel_batch, fri16::lift_tables_bargs, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, ctx->stream, a);
+    ZK_HIP(hipGetLastError());
+    return ZKHIP_OK;
+}
+
 // ---------------------------------------------------------------- the provers' stages.  Each reserves what it makes, launches, and refuses in the caller's name (who).
 // FOLD16's and FINAL's traces (S_REC_A, S_REC_B): what every prover starts with
 static int fri16_reserve_fold_final(zkhip_ctx* ctx, const fri16::Shape& s, uint32_t** d_fold, uint32_t** d_final) {
@@ -1506,15 +1555,18 @@ static int fri16_reserve_fold_final(zkhip_ctx* ctx, const fri16::Shape& s, uint3
 // a scratch block of the plain table's width, which the transcript kernel fills with the indices
 struct Fri16SmallTables {
     uint32_t* d = nullptr;
-    size_t off[fri16::MAX_TABLES] = {0}, words[fri16::MAX_TABLES] = {0}, total = 0;
+    size_t off[fri16::MAX_TABLES] = {0}, words[fri16::MAX_TABLES] = {0}, total = 0, off_scratch = 0;
     uint32_t* at(int t) const { return d + off[t]; }
+    uint32_t* scratch() const { return d + off_scratch; }        // (the lift machine: ROOTS' first eight main columns as the transcript launch writes them, dense)
 };
-static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std::initializer_list<int> tables, Fri16SmallTables& z) {
+static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std::initializer_list<int> tables, Fri16SmallTables& z, size_t scratch_words = 0) {
     for (int t : tables) {
         z.off[t] = z.total;
         z.words[t] = (size_t)(t == fri16::T_QUERIES && s.kind >= fri16::OPENINGS ? fri16::TAB_MAIN : s.main_w[t]) << s.log_rows[t];
         z.total += z.words[t];
     }
+    z.off_scratch = z.total;
+    z.total += scratch_words;
     void* p;
     ZK_TRY(ctx_reserve(ctx, S_CHIP, z.total * 4, &p));
     z.d = (uint32_t*)p;
@@ -1524,7 +1576,8 @@ static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std
 // draw, a witness that fails the proof of work
 static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness,
                                   const uint32_t* betas, const uint32_t* indices, const fri16::PathPlan& pl, uint32_t* d_qmain, uint32_t* d_rmain, const uint32_t** d_p2t,
-                                  const uint32_t** d_samples, const char* who, const std::vector<uint32_t>* head_inputs = nullptr) {      // head_inputs: the HD rows in front (HEAD)
+                                  const uint32_t** d_samples, const char* who, const std::vector<uint32_t>* head_inputs = nullptr,      // head_inputs: the HD rows in front (HEAD)
+                                  const uint32_t** d_chain = nullptr) {                                                                 // d_chain: where the chain's input states lie on the device
     void *t_p2t, *t_smp;
     ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
     ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
@@ -1532,7 +1585,7 @@ static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const u
     fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
     if (head_inputs) c.inputs.insert(c.inputs.begin(), head_inputs->begin(), head_inputs->end());
     uint32_t status = 0;
-    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status));
+    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status, d_chain));
     if (status & 1u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges are not the ones the transcript draws from these roots and this capacity");
     if (s.pow_bits && (c.words[0] & ((1u << s.pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the witness does not satisfy the proof of work");
     if (status & 2u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the query indices are not the ones the transcript draws");
@@ -2140,9 +2193,13 @@ static int fri16_prove_head_kind(fri16::Kind kind, const char* who, zkhip_ctx* c
     ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
     ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
     Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block; OPENED16
-    if (kind == IDENTITY) ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16, T_AIR16, T_SCALARS16}, z));
+    // (LIFT: the transcript launch writes ROOTS' first eight columns into a dense scratch block; the lift launch makes both tables whole from it and the chain's inputs)
+    const bool lift = kind == LIFT;
+    const size_t roots_ld = lift ? ROOTS_MAIN_I : s.main_w[T_ROOTS];
+    if (kind >= IDENTITY) ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16, T_AIR16, T_SCALARS16}, z, lift ? (size_t)ROOTS_MAIN_I << s.log_rows[T_ROOTS] : 0));
     else ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16}, z));
-    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
+    uint32_t* const d_rmain = lift ? z.scratch() : z.at(T_ROOTS);
+    if (!lift) ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
     // the head first: the chain from the all-zero state, OPENED16, the eight constants and the capacity DERIVED -- refused here, before anything is proven: a derived
     // constant or capacity that is not the view's; then all zkhip_prove_fri16_rowpaths refuses, on the derived values
     Head h;
@@ -2156,13 +2213,15 @@ static int fri16_prove_head_kind(fri16::Kind kind, const char* who, zkhip_ctx* c
             return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constant " + names[k] + " derived from the head of the transcript is not the view's");
     if (std::memcmp(h.capacity, capacity, 32) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the capacity the head of the transcript leaves is not the view's");
     PathPlan pl;
-    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr;
+    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr, *d_chain = nullptr;
     ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_transcript_stage(ctx, s, h.capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who, &h.inputs));
+    ZK_TRY(fri16_transcript_stage(ctx, s, h.capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), d_rmain, &t_p2t, &t_smp, who, &h.inputs, &d_chain));
     {
         const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
-        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, z.at(T_ROOTS) + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
+        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, d_rmain + roots_ld * ((size_t)R + tree), &ends_of_tree, 4));
     }
+    // (the staging block the chain's inputs lie in is not reserved again before this launch has read them: the next stage's d2h waits for the stream)
+    if (lift) ZK_TRY(fri16_lift_tables_impl(ctx, s, d_chain, (uint32_t)s.A, (uint32_t)s.HD, d_rmain, z.at(T_ROOTS), z.at(T_COEFFS)));
     ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, derived, t_fold, t_final, &t_rs, &t_q, &d_rows, who));
     ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
     std::vector<uint32_t> ends;
@@ -2171,7 +2230,7 @@ static int fri16_prove_head_kind(fri16::Kind kind, const char* who, zkhip_ctx* c
         if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
             return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") + " tree: the opened row's path does not end in the root");
     const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r, z.at(T_OPENED16)};
-    if (kind == IDENTITY) {      // AIR16 and SCALARS16 from alpha, zeta and the opened values; refused here, still before anything is proven: zeta = 1, an identity that does not hold
+    if (kind >= IDENTITY) {      // AIR16 and SCALARS16 from alpha, zeta and the opened values; refused here, still before anything is proven: zeta = 1, an identity that does not hold
         uint32_t accs[8];
         ZK_TRY(fri16_identity_check_zeta(h.zeta, who));
         ZK_TRY(fri16_identity_rows_impl(ctx, s, opened, h.alpha, h.zeta, z.at(T_AIR16), z.at(T_SCALARS16), accs));
@@ -2263,6 +2322,100 @@ int zkhip_prove_fri16_identity(zkhip_ctx* ctx, const zkhip_machine_key* key, int
 int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
     return fri16::verify(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_identity", n_inner_public);
+}
+
+// ---------------------------------------------------------------- LIFT
+size_t zkhip_fri16_lift_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
+                                 uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
+    return fri16::describe(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+}
+
+int zkhip_fri16_lift_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const zkhip_params* prm, uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_lift_key_host"));
+    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_lift_key_host: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_lift_key_tables(s, pre, "fri16_lift_key_host"));
+    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+}
+
+int zkhip_fri16_lift_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                         uint32_t n_inner_public, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_lift_key"));
+    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_lift_key: null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16::build_lift_key_tables(s, pre, "fri16_lift_key"));
+    return fri16::key_upload(ctx, s, pre, FRI16_IDENTITY_KEY_SLOTS, prm, key, vk);      // (the identity key's slots: the same tables at the same preprocessed widths)
+}
+
+size_t zkhip_fri16_lift_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
+    return fri16::proof_size(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+}
+
+// the lift launch alone, for the table tests: the words are staged as the transcript stage leaves them (a chain of input states: three stream rows with the trace root
+// at stream words 10 .. 17, the quotient root's row, the R root rows, the coefficient rows) and ROOTS' first eight columns come out zero
+int zkhip_fri16_lift_gen_tables(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* roots, const uint32_t trace_root[8],
+                                const uint32_t quotient_root[8], const uint32_t* final_poly, uint32_t* d_roots_main, uint32_t* d_coeffs_main) {
+    CHECK_CTX(ctx);
+    const char* who = "fri16_lift_gen_tables";
+    // ROOTS and COEFFS depend on R and F alone, so every pair of 1..5 layers and log_final 0..8 is taken here, also those whose domain no whole machine has
+    if (R < 1 || R > fri16::MAX_R || F < 0 || F > fri16::MAX_F || log_blowup < 1 || log_blowup > 3 || n_queries < 1 || n_queries > fri16::MAX_Q)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": 1..5 layers, log_final 0..8, log_blowup 1..3, 1..1024 queries");
+    fri16::Shape s{};
+    s.kind = fri16::LIFT; s.R = R; s.F = F; s.C = F >= 1 ? (size_t)1 << (F - 1) : 0;
+    s.log_rows[fri16::T_ROOTS] = fri16::lg((size_t)R); s.log_rows[fri16::T_COEFFS] = fri16::lg((size_t)1 << F);
+    if (!roots || !trace_root || !quotient_root || !final_poly || !d_roots_main || !d_coeffs_main || ((uintptr_t)d_roots_main | (uintptr_t)d_coeffs_main) % 16)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots, the final coefficients and 16-byte aligned dense traces (16 and 8 columns)");
+    if (!fri16::canonical(roots, 8 * (size_t)s.R) || !fri16::canonical(final_poly, (size_t)4 << s.F)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    if (!fri16::canonical(trace_root, 8) || !fri16::canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+    const size_t row_quotient = 3, row_layers = 4, rows = row_layers + (size_t)s.R + std::max<size_t>(s.C, 1);
+    std::vector<uint32_t> up(16 * rows, 0u);
+    for (size_t j = 0; j < 8; j++) { const size_t pos = fri16::LIFT_STREAM_ROOT + j; up[16 * (pos >> 3) + (pos & 7)] = trace_root[j]; }
+    std::memcpy(up.data() + 16 * row_quotient, quotient_root, 32);
+    for (size_t l = 0; l < (size_t)s.R; l++) std::memcpy(up.data() + 16 * (row_layers + l), roots + 8 * l, 32);
+    for (size_t j = 0; j < ((size_t)1 << s.F); j++) std::memcpy(up.data() + 16 * (row_layers + (size_t)s.R + (j >> 1)) + 4 * (j & 1), final_poly + 4 * j, 16);
+    void* stage;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, up.size() * 4, &stage));
+    ZK_TRY(dev_h2d(ctx, stage, up.data(), up.size() * 4));
+    ZK_TRY(fri16_lift_tables_impl(ctx, s, (const uint32_t*)stage, (uint32_t)row_quotient, (uint32_t)row_layers, nullptr, d_roots_main, d_coeffs_main));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    return ZKHIP_OK;
+}
+
+int zkhip_prove_fri16_lift(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
+                           const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
+                           const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
+                           const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
+                           uint8_t* proof, size_t cap, size_t* len) {
+    return fri16_prove_head_kind(fri16::LIFT, "prove_fri16_lift", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas,
+                                 final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root,
+                                 quotient_root, inner_public, opened, prm, proof, cap, len);
+}
+
+int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
+                            uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
+    return fri16::verify(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_lift", n_inner_public);
+}
+
+// segment proof in, lift proof out: ONE pass of the host verifier with every fold-16 view sink attached (verifier.cpp: fri16_view_all -- it fails with the verifier's
+// code and message when the inner proof does not verify, and with the views' messages on a form they do not take), then the lift prover on what it left
+int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
+                                   size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len) {
+    CHECK_CTX(ctx);
+    if (!key || !proof || !public_values || !inner_prm || !outer_prm || !out || !out_len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: null argument");
+    if (n_public > fri16::MAX_NP) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: more than 30 inner public values");
+    Fri16FullView v;
+    ZK_TRY(fri16_view_all(proof, len, log_n, width, public_values, n_public, inner_prm, v));
+    return zkhip_prove_fri16_lift(ctx, key, v.R, v.F, inner_prm->log_blowup, (size_t)inner_prm->num_queries, v.hash_width, inner_prm->pow_bits, width, (uint32_t)n_public,
+                                  v.betas.data(), v.final_poly.data(), v.indices.data(), v.values.data(), v.siblings.data(), v.roots.data(), v.paths.data(), v.transcript,
+                                  v.transcript[9], v.trace_rows.data(), v.quotient_rows.data(), v.constants, v.trace_paths.data(), v.quotient_paths.data(), v.trace_root,
+                                  v.quotient_root, public_values, v.opened.data(), outer_prm, out, cap, out_len);
 }
 
 }  // extern "C"

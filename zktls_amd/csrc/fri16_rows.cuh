@@ -102,6 +102,18 @@ struct IdentityRowsArgs {
     uint32_t *air, *scalars;            // Montgomery, dense, 16-byte aligned; SCALARS16 has 2^7 rows of sc16_width(n) words
     uint32_t* accs;                     // [2][4] CANONICAL: ACCO of the last group, QUO (zeta^N - 1)
 };
+// the lift machine: the main columns of ROOTS (ENDS BETA[4] FOLDROWS 0 0 ROOT[8]) and COEFFS (0 0 0 0 C[4]), both dense.  The root and coefficient words are read where
+// the transcript stage left them on the device: the chain's input states ([rows][16] canonical), in which row `row_layers` + l holds layer root l in its rate half, the
+// rows behind the R root rows the final coefficients two a row (F = 0: c_0 in the first four words of the witness row), row `row_quotient` the quotient root, and the
+// stream words 10 .. 17 of rows 1 and 2 the trace root
+constexpr uint32_t ROOTS_MAIN_L = 16, RL_ROOT = 8, COEFFS_MAIN_L = 8, CL_C = 4, LIFT_STREAM_ROOT = 10;
+struct LiftTablesArgs {
+    const uint32_t* chain;              // canonical words on the device, 16-byte aligned: [rows][16]
+    const uint32_t* roots_base;         // Montgomery [roots_rows][8]: ROOTS' first eight main columns as the transcript launch wrote them, or null: zero
+    uint32_t R, F, row_quotient, row_layers;
+    uint64_t roots_rows, coeffs_rows;   // the tables' heights: >= R + 2, >= 2^F
+    uint32_t *roots_main, *coeffs_main; // Montgomery, dense, 16-byte aligned: [roots_rows][16], [coeffs_rows][8]
+};
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ Ext ld_ext(const uint32_t* p) {
@@ -640,6 +652,41 @@ __device__ __forceinline__ void fri16_identity_rows_plain_body(const IdentityRow
     identity_scalars_rows(a, sc_row, tid, blockDim.x);
 }
 __global__ void __launch_bounds__(IDENTITY_LANES) fri16_identity_rows_kernel(IdentityRowsArgs a) { fri16_identity_rows_body(a); }
+
+// ROOTS' and COEFFS' main columns of the lift machine in one launch: a lane per 16-byte group of a row, adjacent lanes on adjacent addresses -- four groups per ROOTS
+// row (two copied from roots_base, two the root's halves), then two per COEFFS row (the unused columns, c_j).  Rows past the active ones are written as zero; the
+// words go to Montgomery form here.  Every store is a 16-byte vector store.
+__device__ __forceinline__ void fri16_lift_tables_body(const LiftTablesArgs& a) {
+    uint64_t g = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t root_groups = 4 * a.roots_rows;
+    if (g < root_groups) {
+        const uint64_t row = g >> 2;
+        const uint32_t grp = (uint32_t)g & 3u, h = grp & 1u;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (grp < 2u) { if (a.roots_base) v = *reinterpret_cast<const uint4*>(a.roots_base + 4 * g - 8 * row); }
+        else if (row < a.R) v = *reinterpret_cast<const uint4*>(a.chain + 16 * ((uint64_t)a.row_layers + row) + 4u * h);
+        else if (row == a.R) {                                         // the trace root: stream words 10 .. 17, which straddle two rows
+            uint32_t w[4];
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) { const uint32_t pos = LIFT_STREAM_ROOT + 4u * h + i; w[i] = a.chain[16u * (pos >> 3) + (pos & 7u)]; }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        } else if (row == (uint64_t)a.R + 1) v = *reinterpret_cast<const uint4*>(a.chain + 16 * (uint64_t)a.row_quotient + 4u * h);
+        if (grp >= 2u) v = make_uint4(dmul(v.x, MONTY_R2), dmul(v.y, MONTY_R2), dmul(v.z, MONTY_R2), dmul(v.w, MONTY_R2));
+        *reinterpret_cast<uint4*>(a.roots_main + 4 * g) = v;
+        return;
+    }
+    g -= root_groups;
+    if (g >= 2 * a.coeffs_rows) return;
+    const uint64_t j = g >> 1;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if ((g & 1u) && j < ((uint64_t)1 << a.F)) {
+        const uint64_t row = (uint64_t)a.row_layers + a.R + (a.F ? j >> 1 : 0);
+        v = *reinterpret_cast<const uint4*>(a.chain + 16 * row + (a.F ? 4u * ((uint32_t)j & 1u) : 0u));
+        v = make_uint4(dmul(v.x, MONTY_R2), dmul(v.y, MONTY_R2), dmul(v.z, MONTY_R2), dmul(v.w, MONTY_R2));
+    }
+    *reinterpret_cast<uint4*>(a.coeffs_main + 4 * g) = v;
+}
+__global__ void __launch_bounds__(64) fri16_lift_tables_kernel(LiftTablesArgs a) { fri16_lift_tables_body(a); }
 #endif
 
 }  // namespace fri16

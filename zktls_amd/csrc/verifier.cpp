@@ -638,17 +638,22 @@ int zkhip_fri16_view_row_paths(const uint8_t* proof, size_t len, int log_n, uint
 
 // ... and the head of the transcript (the head machine of fri16_chip.hip): the opened extension values [2 width + 8][4] in the order the verifier observes them (values at
 // zeta, values at zeta g, quotient values) and alpha.  Refused, each with its message: lookup pairs, a program (version 7), a code group (CW != 0), the width-16 hash.
+// the forms the head view takes, each refusal with its message (shared with fri16_view_all below)
+static int fri16_head_form(const Shape& sh, const zkhip_params* prm, const uint8_t* proof, size_t len) {
+    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
+    if (prm->logup_pairs) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with lookup pairs are not taken (logup_pairs = 0 only)");
+    if (proof && len >= 8 && ((const uint32_t*)proof)[1] == 7u) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a program (version 7) are not taken (their header has the program's digest)");
+    if (sh.cw) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a code group (CW != 0) are not taken (their header and their first root differ)");
+    if (sh.hw != 24) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with the width-16 hash are not taken (the head machine's header names the width-24 hash)");
+    return ZKHIP_OK;
+}
 int zkhip_fri16_view_head(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm,
                           uint32_t* opened, uint32_t alpha[4]) {
     if (!prm || !opened || !alpha) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: null argument");
     Shape sh;
     if (check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
     shape_of(log_n, prm, sh);
-    if (sh.K != 4 || sh.R < 1) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: fold-by-16 proofs (log_fold = 4) with at least one committed layer only");
-    if (prm->logup_pairs) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with lookup pairs are not taken (logup_pairs = 0 only)");
-    if (proof && len >= 8 && ((const uint32_t*)proof)[1] == 7u) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a program (version 7) are not taken (their header has the program's digest)");
-    if (sh.cw) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with a code group (CW != 0) are not taken (their header and their first root differ)");
-    if (sh.hw != 24) return fail(ZKHIP_ERR_INVALID, "fri16_view_head: proofs with the width-16 hash are not taken (the head machine's header names the width-24 hash)");
+    if (fri16_head_form(sh, prm, proof, len) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
     const size_t Q = (size_t)prm->num_queries;
     std::vector<uint32_t> betas(4 * (size_t)sh.R), final_poly((size_t)4 << sh.F), indices(Q), values(4 * Q), siblings(60 * Q * (size_t)sh.R);
     FriViewSink sink{betas.data(), nullptr, indices.data(), values.data(), siblings.data(), sh.R, nullptr, nullptr, nullptr};
@@ -676,6 +681,28 @@ int fri_view_all_unhashed(const uint8_t* proof, size_t len, int log_n, uint32_t 
     AirView av;
     if (program && !air_validate(program, program_words, width, n_public, &av)) return fail(ZKHIP_ERR_INVALID, "fri_view_all: malformed constraint program");
     return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, program ? &av : nullptr, &sink);
+}
+// every fold-16 view of a proof from ONE pass of the verifier (what zkhip_fri16_view_shard / _transcript / _openings / _row_paths / _head fill, each in a pass of its
+// own): the lift prover's arguments.  Fails with the verifier's code and message on a proof that does not verify, with the head view's on a form it does not take.
+int fri16_view_all(const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public, const zkhip_params* prm, Fri16FullView& v) {
+    Shape sh;
+    if (!prm || check_shape(log_n, width, prm) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    shape_of(log_n, prm, sh);
+    if (fri16_head_form(sh, prm, proof, len) != ZKHIP_OK) return ZKHIP_ERR_INVALID;
+    const size_t Q = (size_t)prm->num_queries, R = (size_t)sh.R, H = (size_t)log_n + (size_t)sh.b;
+    v.R = sh.R; v.F = sh.F; v.hash_width = sh.hw;
+    v.betas.assign(4 * R, 0u); v.final_poly.assign((size_t)4 << sh.F, 0u); v.indices.assign(Q, 0u); v.values.assign(4 * Q, 0u); v.siblings.assign(60 * Q * R, 0u);
+    v.roots.assign(8 * R, 0u); v.paths.assign(Q * zkhip_fri16_view_path_words(log_n, prm), 0u);
+    v.trace_rows.assign(Q * (size_t)width, 0u); v.quotient_rows.assign(8 * Q, 0u);
+    v.trace_paths.assign(8 * H * Q, 0u); v.quotient_paths.assign(8 * H * Q, 0u); v.opened.assign(4 * (2 * (size_t)width + 8), 0u);
+    FriViewSink sink{v.betas.data(), nullptr, v.indices.data(), v.values.data(), v.siblings.data(), sh.R, v.roots.data(), v.paths.data(), v.transcript};
+    sink.fold16 = true;
+    sink.final_poly = v.final_poly.data();
+    sink.trace_rows = v.trace_rows.data(); sink.quotient_rows = v.quotient_rows.data(); sink.constants = v.constants;
+    sink.trace_paths = v.trace_paths.data(); sink.quotient_paths = v.quotient_paths.data(); sink.trace_root = v.trace_root; sink.quotient_root = v.quotient_root;
+    sink.opened = v.opened.data(); sink.alpha = v.alpha;
+    int why = 0;
+    return verify_shard_impl(proof, len, log_n, width, public_values, n_public, prm, &why, nullptr, &sink);
 }
 }  // namespace zk
 }  // extern "C++"

@@ -978,6 +978,48 @@ class Context:
         inner proof whose AIR identity at zeta does not hold"""
         return self._prove_fri16_head_kind("identity", key, view, params)
 
+    # ---- the fold-by-16 LIFT machine (the identity machine with roots and final coefficients out of the key: one key per shape)
+    def fri16_lift_key(self, R, F, log_blowup, n_queries, pow_bits, W, NP, params=None, hash_width=24):
+        """zkhip_fri16_lift_key: the key of the fold-16 lift machine, committed on the device -- from the SHAPE alone (layers, log_final, log_blowup, queries, the inner
+        proof's grinding bits, trace width and number of public values): no root, no coefficient, no proof -> MachineKey"""
+        params = params or Params(1, 100, 16)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_lift_key(self.handle, R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def fri16_lift_gen_tables(self, R, F, log_blowup, n_queries, roots, troot, qroot, final_poly, buffers=False):
+        """zkhip_fri16_lift_gen_tables: the main columns of ROOTS and COEFFS of the lift machine from the canonical layer roots [R][8], the trace root, the quotient root
+        and the final coefficients [2^F][4] -> (ROOTS [2^5][16] (its first eight columns zero: the transcript launch makes those), COEFFS [max(2^5, 2^F)][8]), canonical
+        words, downloaded"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        rt, tr, qr, fp = u(roots), u(troot), u(qroot), u(final_poly)
+        assert rt.size == 8 * R and tr.size == qr.size == 8 and fp.size == 4 << F
+        rm, cm = self.alloc(16 << 5), self.alloc(8 << max(5, F))
+        check(self.lib.zkhip_fri16_lift_gen_tables(self.handle, R, F, log_blowup, n_queries, *[a.ctypes.data_as(u32p) for a in (rt, tr, qr, fp)], C.c_void_p(rm.ptr),
+                                                   C.c_void_p(cm.ptr)))
+        if buffers:                                          # (the device buffers themselves: their raw Montgomery words can be read)
+            return rm, cm
+        return rm.download().reshape(-1, 16), cm.download().reshape(-1, 8)
+
+    def prove_fri16_lift(self, key, view, params=None):
+        """zkhip_prove_fri16_lift: "some valid segment proof of this shape with THESE public values exists" -- everything prove_fri16_identity states, under a key that
+        holds no root and no coefficient.  view: a head view.  Refused before anything is proven: all prove_fri16_identity refuses"""
+        return self._prove_fri16_head_kind("lift", key, view, params)
+
+    def prove_fri16_lift_segment(self, key, proof, log_n, width, public_values, inner_params, params=None):
+        """zkhip_prove_fri16_lift_segment: segment proof in, lift proof out -- the host verifier once over `proof` with every fold-16 view attached, then prove_fri16_lift.
+        Raises with the host verifier's code and message when the inner proof does not verify or is of a form the views do not take"""
+        params = params or Params(1, 100, 16)
+        pr = np.ascontiguousarray(proof, dtype=np.uint8)
+        pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
+        sh = _fri16_segment_shape(log_n, inner_params)
+        size = self.lib.zkhip_fri16_lift_proof_size(*sh, int(inner_params.pow_bits), width, pv.size, C.byref(params)) if sh else 0
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(self.lib.zkhip_prove_fri16_lift_segment(self.handle, key.handle, pr.ctypes.data_as(u8p), pr.size, log_n, width, pv.ctypes.data_as(u32p), pv.size,
+                                                      C.byref(inner_params), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1940,6 +1982,33 @@ def fri16_identity_key_host(view, params=None):
 def verify_fri16_identity(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
     """zkhip_verify_fri16_identity: verify_fri16_head's arguments -> (rc, reason); host only"""
     return _verify("verify_fri16_identity", proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, len(inner_public), vk=vk, params=params)
+
+
+def _fri16_segment_shape(log_n, inner_params):
+    """(R, F, log_blowup, Q) of a fold-by-16 proof over 2^log_n rows, or None where the parameters are not a fold-by-16 shape with a committed layer"""
+    F, b = int(inner_params.log_final), int(inner_params.log_blowup)
+    if int(inner_params.log_fold) != 4 or log_n <= F or (log_n - F) % 4:
+        return None
+    return (log_n - F) // 4, F, b, int(inner_params.num_queries)
+
+
+def fri16_lift_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kind):
+    """zkhip_fri16_lift_describe: program (kind 0) or interaction table (kind 1) of the chip at machine position `which` (0..12) of the fold-16 lift machine
+    -> (words, log_rows, main_width, pre_width, table number)"""
+    return _describe("fri16_lift_describe", R, F, log_blowup, n_queries, pow_bits, W, NP, which=which, kind=kind)
+
+
+def fri16_lift_key_host(R, F, log_blowup, n_queries, pow_bits, W, NP, params=None, hash_width=24):
+    """zkhip_fri16_lift_key_host: the fold-16 lift machine's key of a SHAPE (no proof data), without a GPU -> 8 canonical words"""
+    params = params or Params(1, 100, 16)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_lift_key_host(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def verify_fri16_lift(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
+    """zkhip_verify_fri16_lift: verify_fri16_head's arguments, vk the SHAPE's key -> (rc, reason); host only"""
+    return _verify("verify_fri16_lift", proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, len(inner_public), vk=vk, params=params)
 
 
 def verify_fri16_head(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
