@@ -2,13 +2,20 @@
 (tests/fri16_air.py) word for word, the device key against the host key, proof bytes against the oracle's generic keyed-machine prover on the
 restatement's arrays, the views of segment proofs made on the GPU (their layer openings through the width-24 Poseidon2 chip), what the
 prover refuses before proving, and one full-size measurement."""
+import functools
 import time
+import types
 
 import numpy as np
 import pytest
 
 import fri16_air as A
-from test_fri16_chip_cpu import RANDOM_SHAPES, FOLD16_GOLDEN, golden_view, shape_of
+import fri16_head_air as HA
+import fri16_openings_air as OA
+import fri16_rowpaths_air as RPA
+import fri16_transcript_air as TA
+import zktls_amd.device as D
+from test_fri16_chip_cpu import RANDOM_SHAPES, FOLD16_GOLDEN, GOLDEN, golden_view, load, shape_of
 from zktls_amd._lib import Params, ZkHipError, segment_params
 from zktls_amd.device import fri16_key_host, fri16_view_shard, verify_fri16, verify_merkle_paths_p24
 
@@ -131,6 +138,40 @@ def test_prover_refuses_a_view_whose_chains_do_not_end_in_the_final_polynomial(c
             ctx.fri16_key(one_sibling, prm)
     finally:
         key.close()
+
+
+# ------------------------------------------------------------------ (i') every kind's entries refuse in their own name
+@functools.lru_cache(maxsize=None)
+def kind_view(kind):
+    """the golden view the kind's own tests prove"""
+    if kind in ("layers", "paths"):
+        return golden_view("v8_groups_r0_lookup_8x16")
+    if kind == "indices":
+        return TA.golden_view("v8_groups_r0_lookup_8x16", GOLDEN, load)
+    return {"openings": OA, "rowpaths": RPA}.get(kind, HA).golden_view("v3_r0_9x8", GOLDEN, load)
+
+
+@pytest.mark.parametrize("kind,infix", [("layers", ""), ("paths", "_paths"), ("indices", "_indices"), ("openings", "_openings"), ("rowpaths", "_rowpaths"), ("head", "_head"),
+                                        ("identity", "_identity"), ("lift", "_lift")])
+def test_every_kinds_entries_refuse_in_their_own_name(ctx, kind, infix):
+    """a null key is refused by the prove entry's argument checks (nothing is launched) with ZKHIP_ERR_INVALID and "<entry>: null argument"; from the paths machine on
+    the key entry and the host key entry refuse an inner hash width of 16, each naming itself"""
+    v, prm = kind_view(kind), Params(1, 8, 2)
+    with pytest.raises(ZkHipError, match=r"^zkhip error -1: prove_fri16%s: null argument$" % infix) as e:
+        getattr(ctx, "prove_fri16" + infix)(types.SimpleNamespace(handle=None), v, prm)
+    assert e.value.code == -1
+    if kind == "layers":
+        return
+    if kind == "lift":
+        shape = (len(v["roots"]), v["F"], v["b"], len(v["queries"]), v["pow_bits"], v["W"], len(v["pubs"]))
+        device, host = (lambda: ctx.fri16_lift_key(*shape, prm, hash_width=16)), (lambda: D.fri16_lift_key_host(*shape, prm, hash_width=16))
+    else:
+        w16 = dict(v, hash_width=16)
+        device, host = (lambda: getattr(ctx, "fri16%s_key" % infix)(w16, prm)), (lambda: getattr(D, "fri16%s_key_host" % infix)(w16, prm))
+    for call, name in ((device, "fri16%s_key: " % infix), (host, "fri16%s_key_host: " % infix)):
+        with pytest.raises(ZkHipError, match="^zkhip error -1: " + name) as e:
+            call()
+        assert e.value.code == -1
 
 
 # ------------------------------------------------------------------ (j) full size, measured and printed

@@ -115,6 +115,23 @@ struct Shape {
     int log_rows[MAX_TABLES];                // by table number
     uint32_t main_w[MAX_TABLES], pre_w[MAX_TABLES];
 };
+// what an entry is given of a shape: the kind and the words its signature has (the rest zero); shape_of reads what the kind takes
+struct ShapeArgs {
+    Kind kind = LAYERS;
+    int R = 0, F = 0, b = 0;
+    size_t Q = 0;
+    int pow_bits = 0;
+    uint32_t W = 0, NP = 0;
+};
+// every array and word a prover or key entry takes (host, canonical; not owned), null or zero where the kind has none, in the order the prove entries take them: a
+// prove entry fills its view by position.  Fri16FullView (context.h) owns one.
+struct View {
+    int hash_width = 0;
+    const uint32_t *betas = nullptr, *final_poly = nullptr, *indices = nullptr, *values = nullptr, *siblings = nullptr, *roots = nullptr, *paths = nullptr, *capacity = nullptr;
+    uint32_t witness = 0;
+    const uint32_t *trace_rows = nullptr, *quotient_rows = nullptr, *constants = nullptr, *trace_paths = nullptr, *quotient_paths = nullptr;
+    const uint32_t *trace_root = nullptr, *quotient_root = nullptr, *inner_public = nullptr, *opened = nullptr;
+};
 inline int lg(size_t n) { int l = 5; while (((size_t)1 << l) < n) l++; return l; }
 
 std::vector<uint32_t> build_fold16_program(int R, int lf, bool beta_bus = false, uint32_t n_public = 0) {      // beta_bus: FOLD16B, BETA is received, not public
@@ -263,11 +280,11 @@ std::vector<uint32_t> build_table_program(uint32_t n_public, uint32_t pre_width,
 
 inline Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
 bool canonical(const uint32_t* v, size_t n) { for (size_t i = 0; i < n; i++) if (v[i] >= P) return false; return true; }
-int check_view(const Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const char* who) {
-    if (!betas || !final_poly || !indices || !values || !siblings) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!canonical(betas, 4 * (size_t)s.R) || !canonical(final_poly, (size_t)4 << s.F) || !canonical(values, 4 * s.Q) || !canonical(siblings, 60 * s.Q * (size_t)s.R))
+int check_view(const Shape& s, const View& v, const char* who) {
+    if (!v.betas || !v.final_poly || !v.indices || !v.values || !v.siblings) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!canonical(v.betas, 4 * (size_t)s.R) || !canonical(v.final_poly, (size_t)4 << s.F) || !canonical(v.values, 4 * s.Q) || !canonical(v.siblings, 60 * s.Q * (size_t)s.R))
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
-    for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    for (size_t q = 0; q < s.Q; q++) if (v.indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
     return ZKHIP_OK;
 }
 // the fold of one row on the host (the kernels' arithmetic, portable forms)
@@ -763,13 +780,13 @@ std::vector<uint32_t> build_opened16_program(uint32_t n_public, uint32_t M0 = OP
     add_ext(b, TRANSITION, esub(ev(M0 + OP_FA, true), fa));
     return b.finish(M0 + OP_MAIN16, n_public);
 }
-int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s, uint32_t NP = 0);
+int shape_of(const ShapeArgs& a, Shape& s);
 // the key's tables by table number: the row-paths machine's at the head machine's widths, the head's schedule in front of P2T's, OPENED16's schedule -- functions of the
 // shape and NP alone but for the roots and the final coefficients
 int build_head_key_tables(const Shape& s, const uint32_t* final_poly, const uint32_t* roots, const uint32_t* trace_root, const uint32_t* quotient_root, std::vector<uint32_t> pre[],
                           const char* who) {
     Shape so;                                                  // the kinds before, at their own widths (the openings shape: no shape of the head's is refused for its heights)
-    ZK_TRY(shape_of(OPENINGS, s.R, s.F, s.b, s.Q, s.pow_bits, s.W, so));
+    ZK_TRY(shape_of({OPENINGS, s.R, s.F, s.b, s.Q, s.pow_bits, s.W}, so));
     std::vector<uint32_t> t[MAX_TABLES];
     ZK_TRY(build_rowpaths_key_tables(so, final_poly, roots, trace_root, quotient_root, t, who));
     const size_t R = (size_t)s.R, W = s.W;
@@ -971,7 +988,8 @@ inline uint32_t n_public_of(const Shape& s) { return s.kind <= PATHS ? 4u * (uin
 // pow_bits is read from INDICES on, W from OPENINGS on.  ROWSUM16, ROWS and P24R have at least 2^6 rows: a keyed machine takes at most 8 tables of one height, and the
 // other eight can all have 2^5 rows; from 2^6 rows on ROOTS (2^5 always) and SAMPLES (fewer rows than QUERY16 / 4) keep nine tables from meeting where ROWS stands --
 // P24R can still meet eight others, and that shape is refused
-int shape_of(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, Shape& s, uint32_t NP) {
+int shape_of(const ShapeArgs& a, Shape& s) {
+    const auto [kind, R, F, b, Q, pow_bits, W, NP] = a;
     if (R < 1 || R > MAX_R || F < 0 || F > MAX_F || b < 1 || b > 3 || F + b > MAX_LF || Q < 1 || Q > MAX_Q || 4 * R + F + b > TWO_ADICITY)
         return fail(ZKHIP_ERR_INVALID, "fri16: 1..5 layers, log_final 0..8, log_blowup 1..3 (log_final + log_blowup <= 11), 1..1024 queries, and a domain of at most 2^27 points");
     if (kind >= INDICES && (pow_bits < 0 || pow_bits > 30)) return fail(ZKHIP_ERR_INVALID, "fri16 indices: inner_pow_bits in [0, 30]");
@@ -1199,10 +1217,9 @@ std::shared_ptr<const Machine> machine_of(const Shape& s) {
 }
 
 // what the entries of every kind do with a shape
-size_t describe(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, int which, int what, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
-                uint32_t* pre_width, int* table, uint32_t NP = 0) {
+size_t describe(const ShapeArgs& a, int which, int what, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
     Shape s;
-    if (which < 0 || which >= N_TABLES[kind] || what < 0 || what > 1 || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) return 0;
+    if (which < 0 || which >= N_TABLES[a.kind] || what < 0 || what > 1 || shape_of(a, s) != ZKHIP_OK) return 0;
     const auto m = machine_of(s);
     if (table) *table = m->km.order[which];
     return keyed::describe(m->km, which, what, [](int, int, std::vector<uint32_t>&) {}, out, cap_words, log_rows, main_width, pre_width);
@@ -1221,15 +1238,14 @@ int key_upload(zkhip_ctx* ctx, const Shape& s, const std::vector<uint32_t>* pre,
     }
     return keyed::key_setup(ctx, m->km, d_pre, prm, key, vk);
 }
-size_t proof_size(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const zkhip_params* prm, uint32_t NP = 0) {
+size_t proof_size(const ShapeArgs& a, const zkhip_params* prm) {
     Shape s;
-    if (!prm || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) return 0;
+    if (!prm || shape_of(a, s) != ZKHIP_OK) return 0;
     return keyed::proof_size(machine_of(s)->km, prm, n_public_of(s));
 }
-int verify(Kind kind, int R, int F, int b, size_t Q, int pow_bits, uint32_t W, const uint8_t* proof, size_t len, const uint32_t* public_values, const uint32_t vk[8],
-           const zkhip_params* prm, int* reason, const char* who, uint32_t NP = 0) {
+int verify(const ShapeArgs& a, const uint8_t* proof, size_t len, const uint32_t* public_values, const uint32_t vk[8], const zkhip_params* prm, int* reason, const char* who) {
     Shape s;
-    if (!proof || !public_values || !vk || !prm || shape_of(kind, R, F, b, Q, pow_bits, W, s, NP) != ZKHIP_OK) {
+    if (!proof || !public_values || !vk || !prm || shape_of(a, s) != ZKHIP_OK) {
         if (reason) *reason = 1;
         return fail(ZKHIP_ERR_VERIFY, std::string(who) + ": bad arguments");
     }
@@ -1265,19 +1281,19 @@ using namespace zk;
     } while (0)
 
 // both main traces from the view's arrays, uploaded once; every chain's end (FOLD16's last row) against its block's end (FINAL's last row)
-static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                                 const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final, const uint32_t* d_values = nullptr) {
+static int fri16_gen_traces_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::View& view, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final,
+                                 const uint32_t* d_values = nullptr) {
     const size_t R = (size_t)s.R, Q = s.Q, nb = 4 * R, nf = (size_t)4 << s.F, ni = (Q + 3) & ~(size_t)3, nv = 4 * Q, ns = 60 * Q * R, up_words = nb + nf + ni + nv + ns;
     void* stage;
     ZK_TRY(ctx_reserve(ctx, S_STAGE, (up_words + 16 * Q) * 4, &stage));
     uint32_t* d = (uint32_t*)stage;
     {
         std::vector<uint32_t> up(up_words, 0u);
-        std::memcpy(up.data(), betas, nb * 4);
-        std::memcpy(up.data() + nb, final_poly, nf * 4);
-        std::memcpy(up.data() + nb + nf, indices, Q * 4);
-        std::memcpy(up.data() + nb + nf + ni, values, nv * 4);
-        std::memcpy(up.data() + nb + nf + ni + nv, siblings, ns * 4);
+        std::memcpy(up.data(), view.betas, nb * 4);
+        std::memcpy(up.data() + nb, view.final_poly, nf * 4);
+        std::memcpy(up.data() + nb + nf, view.indices, Q * 4);
+        std::memcpy(up.data() + nb + nf + ni, view.values, nv * 4);
+        std::memcpy(up.data() + nb + nf + ni + nv, view.siblings, ns * 4);
         ZK_TRY(dev_h2d(ctx, d, up.data(), up_words * 4));
     }
     // (d_values: the chains start from values already on the device -- the openings machine's, computed there from the opened rows)
@@ -1329,11 +1345,10 @@ static int fri16_paths_gen_p24l_impl(zkhip_ctx* ctx, const fri16::Shape& s, cons
     ends.resize(8 * pl.n);
     return ZKHIP_OK;
 }
-static int fri16_paths_check_view(const fri16::Shape& s, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                                  const uint32_t* siblings, const uint32_t* paths, const char* who) {
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, who));
-    if (!paths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    return fri16::check_view(s, betas, final_poly, indices, values, siblings, who);
+static int fri16_paths_check_view(const fri16::Shape& s, const fri16::View& v, const char* who) {
+    ZK_TRY(fri16::check_hash_width(v.hash_width, who));
+    if (!v.paths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    return fri16::check_view(s, v, who);
 }
 
 // P2T, SAMPLES and (non-null) the main columns of QUERIES and ROOTS in one launch from one staging block; status: what the kernel found different from the view
@@ -1365,9 +1380,9 @@ static int fri16_transcript_impl(zkhip_ctx* ctx, const fri16::Shape& s, const fr
     if (d_chain) *d_chain = d;                                   // (the chain's input states stay where they were uploaded: the lift machine's tables are read off them)
     return dev_d2h(ctx, status, a.status, 4);
 }
-static int fri16_indices_check_inputs(const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness, const char* who) {
-    if (!capacity || !roots || !final_poly) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!fri16::canonical(capacity, 8) || !fri16::canonical(roots, 8 * (size_t)s.R) || !fri16::canonical(final_poly, (size_t)4 << s.F) || witness >= P)
+static int fri16_indices_check_inputs(const fri16::Shape& s, const fri16::View& v, const char* who) {
+    if (!v.capacity || !v.roots || !v.final_poly) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(v.capacity, 8) || !fri16::canonical(v.roots, 8 * (size_t)s.R) || !fri16::canonical(v.final_poly, (size_t)4 << s.F) || v.witness >= P)
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
     return ZKHIP_OK;
 }
@@ -1413,11 +1428,11 @@ static int fri16_openings_rows_impl(zkhip_ctx* ctx, const fri16::Shape& s, const
     if (d_rows) *d_rows = d;
     return ZKHIP_OK;
 }
-static int fri16_openings_check_rows(const fri16::Shape& s, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, const uint32_t* indices, const char* who) {
-    if (!trows || !qrows || !consts || !indices) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!fri16::canonical(trows, s.Q * (size_t)s.W) || !fri16::canonical(qrows, s.Q * fri16::QROW16) || !fri16::canonical(consts, 32))
+static int fri16_openings_check_rows(const fri16::Shape& s, const fri16::View& v, const char* who) {
+    if (!v.trace_rows || !v.quotient_rows || !v.constants || !v.indices) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(v.trace_rows, s.Q * (size_t)s.W) || !fri16::canonical(v.quotient_rows, s.Q * fri16::QROW16) || !fri16::canonical(v.constants, 32))
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
-    for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
+    for (size_t q = 0; q < s.Q; q++) if (v.indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": a query index has more bits than the proof's domain");
     return ZKHIP_OK;
 }
 static int fri16_openings_no_inverse(const char* who, uint32_t q) {
@@ -1426,8 +1441,9 @@ static int fri16_openings_no_inverse(const char* who, uint32_t q) {
 
 // P24R in one launch: a path per (query, tree), tag order.  d_rows: the raw rows where fri16_openings_rows_impl left them on the device ([Q][W], then [Q][8]), or null:
 // they are uploaded here.  ends [2 Q][8]: where every path ends (canonical).
-static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* d_rows, const uint32_t* trows, const uint32_t* qrows, const uint32_t* indices,
-                                        const uint32_t* tpaths, const uint32_t* qpaths, uint32_t* d_trace, size_t ld, std::vector<uint32_t>& ends) {
+static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* d_rows, const fri16::View& v, uint32_t* d_trace, size_t ld,
+                                        std::vector<uint32_t>& ends) {
+    const uint32_t *trows = v.trace_rows, *qrows = v.quotient_rows, *indices = v.indices, *tpaths = v.trace_paths, *qpaths = v.quotient_paths;
     const size_t Q = s.Q, W = s.W, H = (size_t)s.H, n = 2 * Q, blocks = (W + 15) / 16, rows = (size_t)1 << s.log_rows[fri16::T_P24R];
     const size_t nd = 8 * n, ns = 8 * H * n, nr = d_rows ? 0 : Q * (W + fri16::QROW16), up_words = nd + ns + nr;
     void* stage;
@@ -1460,7 +1476,8 @@ static int fri16_rowpaths_gen_p24r_impl(zkhip_ctx* ctx, const fri16::Shape& s, c
     return dev_d2h(ctx, ends.data(), a.ends, ends.size() * 4);
 }
 // refused before anything is hashed: null or non-canonical path words, by query and tree
-static int fri16_rowpaths_check_paths(const fri16::Shape& s, const uint32_t* tpaths, const uint32_t* qpaths, const uint32_t* troot, const uint32_t* qroot, const char* who) {
+static int fri16_rowpaths_check_paths(const fri16::Shape& s, const fri16::View& v, const char* who) {      // (the roots: checked where the view has them)
+    const uint32_t *tpaths = v.trace_paths, *qpaths = v.quotient_paths, *troot = v.trace_root, *qroot = v.quotient_root;
     if (!tpaths || !qpaths) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
     if (troot && (!qroot || !fri16::canonical(troot, 8) || !fri16::canonical(qroot, 8))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
     const size_t per = 8 * (size_t)s.H;
@@ -1489,12 +1506,11 @@ static int fri16_head_opened_impl(zkhip_ctx* ctx, const fri16::Shape& s, const u
     ZK_HIP(hipGetLastError());
     return dev_d2h(ctx, sums, a.sums, 64);
 }
-static int fri16_head_check_inputs(const fri16::Shape& s, const uint32_t* inner_public, const uint32_t* trace_root, const uint32_t* quotient_root, const uint32_t* opened,
-                                   const char* who) {
-    if (!inner_public || !trace_root || !quotient_root || !opened) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    if (!fri16::canonical(inner_public, s.NP)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner public values must be canonical");
-    if (!fri16::canonical(opened, 8 * ((size_t)s.W + 4))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the opened values must be canonical");
-    if (!fri16::canonical(trace_root, 8) || !fri16::canonical(quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
+static int fri16_head_check_inputs(const fri16::Shape& s, const fri16::View& v, const char* who) {
+    if (!v.inner_public || !v.trace_root || !v.quotient_root || !v.opened) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (!fri16::canonical(v.inner_public, s.NP)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner public values must be canonical");
+    if (!fri16::canonical(v.opened, 8 * ((size_t)s.W + 4))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the opened values must be canonical");
+    if (!fri16::canonical(v.trace_root, 8) || !fri16::canonical(v.quotient_root, 8)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the roots must be canonical");
     return ZKHIP_OK;
 }
 
@@ -1559,7 +1575,7 @@ struct Fri16SmallTables {
     uint32_t* at(int t) const { return d + off[t]; }
     uint32_t* scratch() const { return d + off_scratch; }        // (the lift machine: ROOTS' first eight main columns as the transcript launch writes them, dense)
 };
-static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std::initializer_list<int> tables, Fri16SmallTables& z, size_t scratch_words = 0) {
+static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, const std::vector<int>& tables, Fri16SmallTables& z, size_t scratch_words = 0) {
     for (int t : tables) {
         z.off[t] = z.total;
         z.words[t] = (size_t)(t == fri16::T_QUERIES && s.kind >= fri16::OPENINGS ? fri16::TAB_MAIN : s.main_w[t]) << s.log_rows[t];
@@ -1574,18 +1590,17 @@ static int fri16_reserve_small_tables(zkhip_ctx* ctx, const fri16::Shape& s, std
 }
 // P2T and SAMPLES (S_REC_C, S_REC_D) and the main columns of QUERIES and ROOTS from the chain walked on the host.  Refused: challenges and indices the chain does not
 // draw, a witness that fails the proof of work
-static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* capacity, const uint32_t* roots, const uint32_t* final_poly, uint32_t witness,
-                                  const uint32_t* betas, const uint32_t* indices, const fri16::PathPlan& pl, uint32_t* d_qmain, uint32_t* d_rmain, const uint32_t** d_p2t,
-                                  const uint32_t** d_samples, const char* who, const std::vector<uint32_t>* head_inputs = nullptr,      // head_inputs: the HD rows in front (HEAD)
-                                  const uint32_t** d_chain = nullptr) {                                                                 // d_chain: where the chain's input states lie on the device
+static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::View& v, const fri16::PathPlan& pl, uint32_t* d_qmain, uint32_t* d_rmain,
+                                  const uint32_t** d_p2t, const uint32_t** d_samples, const char* who, const std::vector<uint32_t>* head_inputs,      // head_inputs: the HD rows in front (HEAD on), or null
+                                  const uint32_t** d_chain) {                                                                                         // d_chain: where the chain's input states lie on the device
     void *t_p2t, *t_smp;
     ZK_TRY(ctx_reserve(ctx, S_REC_C, ((size_t)p2chip::T_WIDTH << s.log_rows[fri16::T_P2T]) * 4, &t_p2t));
     ZK_TRY(ctx_reserve(ctx, S_REC_D, ((size_t)frichip::S_MAIN << s.log_rows[fri16::T_SAMPLES]) * 4, &t_smp));
     fri16::Chain c;
-    fri16::walk_chain(s, capacity, roots, final_poly, witness, c);
+    fri16::walk_chain(s, v.capacity, v.roots, v.final_poly, v.witness, c);
     if (head_inputs) c.inputs.insert(c.inputs.begin(), head_inputs->begin(), head_inputs->end());
     uint32_t status = 0;
-    ZK_TRY(fri16_transcript_impl(ctx, s, c, betas, indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status, d_chain));
+    ZK_TRY(fri16_transcript_impl(ctx, s, c, v.betas, v.indices, pl.counts.data(), (uint32_t*)t_p2t, (uint32_t*)t_smp, d_qmain, d_rmain, &status, d_chain));
     if (status & 1u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges are not the ones the transcript draws from these roots and this capacity");
     if (s.pow_bits && (c.words[0] & ((1u << s.pow_bits) - 1u))) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the witness does not satisfy the proof of work");
     if (status & 2u) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the query indices are not the ones the transcript draws");
@@ -1594,14 +1609,14 @@ static int fri16_transcript_stage(zkhip_ctx* ctx, const fri16::Shape& s, const u
 }
 // P24L (S_REC_H) from the plan of the view's paths and the FOLD16 trace.  Refused: queries that disagree about a shared row, paths that do not end in their layer's root.
 // (The plan is the caller's: from INDICES on the transcript stage, which comes first, takes the path counts from it.)
-static int fri16_layer_paths_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* paths, const uint32_t* roots, const uint32_t* d_fold, size_t ld_fold,
-                                   const fri16::PathPlan& pl, const uint32_t** d_p24) {
+static int fri16_layer_paths_stage(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::View& v, const uint32_t* d_fold, size_t ld_fold, const fri16::PathPlan& pl,
+                                   const uint32_t** d_p24) {
     void* t_p24;
     ZK_TRY(ctx_reserve(ctx, S_REC_H, ((size_t)p24chip::WIDTH_L << s.log_rows[fri16::T_P24L]) * 4, &t_p24));
     std::vector<uint32_t> ends;
-    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, paths, d_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
+    ZK_TRY(fri16_paths_gen_p24l_impl(ctx, s, v.paths, d_fold, ld_fold, (uint32_t*)t_p24, p24chip::WIDTH_L, pl, ends));
     for (size_t p = 0; p < pl.n; p++)
-        if (std::memcmp(ends.data() + 8 * p, roots + 8 * pl.layer_of[p], 32) != 0)
+        if (std::memcmp(ends.data() + 8 * p, v.roots + 8 * pl.layer_of[p], 32) != 0)
             return fail(ZKHIP_ERR_INVALID, "fri16 paths: query " + std::to_string(pl.first_query[p]) + " layer " + std::to_string(pl.layer_of[p]) +
                                                " does not open: its path does not end in the layer's root");
     *d_p24 = (const uint32_t*)t_p24;
@@ -1609,9 +1624,8 @@ static int fri16_layer_paths_stage(zkhip_ctx* ctx, const fri16::Shape& s, const 
 }
 // ROWSUM16 and QUERY16 (S_REC_F, S_REC_G), then FOLD16C and FINAL with the chains starting from the openings the device computed, XQ beside the fold kernel's columns.
 // Refused: points without an inverse, openings the rows do not give, chains that do not end in the final polynomial.  d_rows: where the raw rows stay on the device
-static int fri16_openings_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
-                                const uint32_t* siblings, const uint32_t* trows, const uint32_t* qrows, const uint32_t* consts, uint32_t* d_fold, uint32_t* d_final,
-                                const uint32_t** d_rowsum, const uint32_t** d_query, const uint32_t** d_rows, const char* who) {
+static int fri16_openings_stage(zkhip_ctx* ctx, const fri16::Shape& s, const fri16::View& v, uint32_t* d_fold, uint32_t* d_final, const uint32_t** d_rowsum,
+                                const uint32_t** d_query, const uint32_t** d_rows, const char* who) {
     using namespace fri16;
     const size_t ld_fold = s.main_w[T_FOLD16];
     void *t_rs, *t_q;
@@ -1619,11 +1633,11 @@ static int fri16_openings_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uin
     ZK_TRY(ctx_reserve(ctx, S_REC_G, ((size_t)Q16_MAIN << s.log_rows[T_QUERY16]) * 4, &t_q));
     uint32_t ost[2], *d_open = nullptr;
     const uint32_t* d_idx = nullptr;
-    ZK_TRY(fri16_openings_rows_impl(ctx, s, trows, qrows, consts, indices, values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx, d_rows));
+    ZK_TRY(fri16_openings_rows_impl(ctx, s, v.trace_rows, v.quotient_rows, v.constants, v.indices, v.values, (uint32_t*)t_rs, (uint32_t*)t_q, &d_open, ost, &d_idx, d_rows));
     if (ost[1] != 0xFFFFFFFFu) return fri16_openings_no_inverse(who, ost[1]);
     if (ost[0] != 0xFFFFFFFFu)
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the reduced opening of query " + std::to_string(ost[0]) + " computed from its rows and the constants is not the view's");
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, s.main_w[T_FINAL], d_open));
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, v, d_fold, ld_fold, d_final, s.main_w[T_FINAL], d_open));
     XqColsArgs xa{};
     xa.indices = d_idx; xa.Q = (uint32_t)s.Q; xa.R = (uint32_t)s.R; xa.H = (uint32_t)s.H;
     xa.rows = (uint64_t)1 << s.log_rows[T_FOLD16]; xa.trace = d_fold; xa.ld = ld_fold; xa.col = (uint32_t)ld_fold - 4u;
@@ -1632,10 +1646,166 @@ static int fri16_openings_stage(zkhip_ctx* ctx, const fri16::Shape& s, const uin
     *d_rowsum = (const uint32_t*)t_rs; *d_query = (const uint32_t*)t_q;
     return ZKHIP_OK;
 }
-// the 40 public values from OPENINGS on: the capacity, then the eight constants
-static void fri16_openings_public(const uint32_t capacity[8], const uint32_t constants[32], uint32_t pub[fri16::N_PUBLIC_O]) {
-    std::memcpy(pub, capacity, 32);
-    std::memcpy(pub + 8, constants, 128);
+
+// ---------------------------------------------------------------- the one key path and the one prover: a kind's key and prove entries below are wrappers around them
+// the key's tables by table number from what the kind's key takes of the view (the builders chain: each kind's calls the one before it)
+static int fri16_build_key_tables(const fri16::Shape& s, const fri16::View& v, std::vector<uint32_t> pre[], const char* who) {
+    using namespace fri16;
+    switch (s.kind) {
+    case LAYERS: ZK_TRY(check_view(s, v, who)); return build_tables(s, v.betas, v.final_poly, v.indices, v.values, v.siblings, pre);
+    case PATHS: return build_paths_key_tables(s, v.final_poly, v.indices, v.values, v.roots, pre, who);
+    case INDICES: return build_indices_key_tables(s, v.final_poly, v.values, v.roots, pre, who);
+    case OPENINGS: return build_openings_key_tables(s, v.final_poly, v.trace_rows, v.quotient_rows, v.roots, pre, who);
+    case ROWPATHS: return build_rowpaths_key_tables(s, v.final_poly, v.roots, v.trace_root, v.quotient_root, pre, who);
+    case HEAD: return build_head_key_tables(s, v.final_poly, v.roots, v.trace_root, v.quotient_root, pre, who);
+    case IDENTITY: return build_identity_key_tables(s, v.final_poly, v.roots, v.trace_root, v.quotient_root, pre, who);
+    case LIFT: return build_lift_key_tables(s, pre, who);
+    }
+    return fail(ZKHIP_ERR_INVALID, std::string(who) + ": no such machine");
+}
+// the key's scratch slots by table number.  LAYERS and PATHS give them out by machine position; from INDICES on one table serves every kind: those with preprocessed
+// columns, a later kind's (OPENED16's schedule; AIR16's and SCALARS16's) behind an earlier one's (P24R has no preprocessed columns: its slot is not read)
+static void fri16_key_slots(const fri16::Shape& s, int slots[fri16::MAX_TABLES]) {
+    static const int by_position[6] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
+    static const int by_table[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B, S_REC_H, S_REC_I, S_STAGE};
+    const auto m = fri16::machine_of(s);
+    for (int i = 0; i < s.n_tables; i++) {
+        const int t = m->km.order[i];
+        slots[t] = s.kind <= fri16::PATHS ? by_position[i] : by_table[t];
+    }
+}
+// the key of every kind (who: the entry's name in the refusals).  ctx null: the host key, vk alone
+static int fri16_key(const fri16::ShapeArgs& a, const char* who, zkhip_ctx* ctx, const fri16::View& v, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(a, s));
+    if (a.kind >= fri16::PATHS) ZK_TRY(fri16::check_hash_width(v.hash_width, who));
+    if (!prm || !vk || (ctx && !key)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    std::vector<uint32_t> pre[fri16::MAX_TABLES];
+    ZK_TRY(fri16_build_key_tables(s, v, pre, who));
+    if (!ctx) return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    int slots[fri16::MAX_TABLES];
+    fri16_key_slots(s, slots);
+    return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
+}
+
+// the prover of every kind (who: the entry's name in the refusals): a kind is the kind before it plus one stage, and every stage is gated on the kind.  Where two kinds
+// differ in the ORDER of their stages the gate keeps the difference: the context's slots are reused, and the first refusal of a bad view is part of the entry
+static int fri16_prove(const fri16::ShapeArgs& a, const char* who, zkhip_ctx* ctx, const zkhip_machine_key* key, const fri16::View& view, const zkhip_params* prm,
+                       uint8_t* proof, size_t cap, size_t* len) {
+    CHECK_CTX(ctx);
+    using namespace fri16;
+    const Kind kind = a.kind;
+    const bool lift = kind == LIFT;
+    Shape s;
+    if (kind >= HEAD && a.NP > MAX_NP) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": more than 30 inner public values");
+    ZK_TRY(shape_of(a, s));
+    if (!key || !prm || !proof || !len || (kind == PATHS && !view.roots) || (kind >= ROWPATHS && (!view.trace_root || !view.quotient_root)))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (kind == LAYERS) ZK_TRY(check_view(s, view, who));
+    else ZK_TRY(fri16_paths_check_view(s, view, who));
+    if (kind == PATHS && !canonical(view.roots, 8 * (size_t)s.R)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    if (kind >= INDICES) ZK_TRY(fri16_indices_check_inputs(s, view, who));
+    if (kind >= OPENINGS) {
+        ZK_TRY(fri16_openings_check_rows(s, view, who));
+        ZK_TRY(check_openings_constants(s, view.constants, who));
+    }
+    if (kind >= ROWPATHS) ZK_TRY(fri16_rowpaths_check_paths(s, view, who));
+    if (kind >= HEAD) ZK_TRY(fri16_head_check_inputs(s, view, who));
+    const size_t Q = s.Q, R = (size_t)s.R, ld_fold = s.main_w[T_FOLD16];
+    uint32_t *t_fold, *t_final;
+    void* t_p24r = nullptr;
+    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
+    if (kind >= ROWPATHS) ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
+    // the small tables' main columns.  The key's tables (LAYERS; QUERIES below OPENINGS; COEFFS below LIFT; ROWS) are unused, zero; QUERIES from INDICES on holds the
+    // indices (from OPENINGS on as a scratch block); ROOTS path ends, challenge and fold rows per layer; OPENED16, AIR16 and SCALARS16 their chips
+    // (LIFT: the transcript launch writes ROOTS' first eight columns into a dense scratch block; the lift launch makes both tables whole from it and the chain's inputs)
+    std::vector<int> small{T_QUERIES, T_COEFFS};
+    if (kind == LAYERS) small.insert(small.begin(), T_LAYERS);
+    if (kind >= PATHS) small.push_back(T_ROOTS);
+    if (kind == OPENINGS) small.push_back(T_ROWS);
+    if (kind >= HEAD) small.push_back(T_OPENED16);
+    if (kind >= IDENTITY) small.insert(small.end(), {T_AIR16, T_SCALARS16});
+    Fri16SmallTables z;
+    ZK_TRY(fri16_reserve_small_tables(ctx, s, small, z, lift ? (size_t)ROOTS_MAIN_I << s.log_rows[T_ROOTS] : 0));
+    uint32_t* const d_rmain = lift ? z.scratch() : z.at(T_ROOTS);
+    const size_t roots_ld = lift ? ROOTS_MAIN_I : s.main_w[T_ROOTS];
+    if (kind == LAYERS) ZK_TRY(dev_memset(ctx, z.d, 0, z.total * 4));      // (PATHS uploads the whole block below)
+    if (kind >= INDICES && !lift) ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
+    if (kind == OPENINGS) ZK_TRY(dev_memset(ctx, z.at(T_ROWS), 0, z.words[T_ROWS] * 4));
+    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final};
+    traces[T_COEFFS] = z.at(T_COEFFS);
+    if (kind == LAYERS) traces[T_LAYERS] = z.at(T_LAYERS);
+    if (kind < OPENINGS) traces[T_QUERIES] = z.at(T_QUERIES);
+    if (kind >= PATHS) traces[T_ROOTS] = z.at(T_ROOTS);
+    if (kind == OPENINGS) traces[T_ROWS] = z.at(T_ROWS);
+    // everything below is refused before anything is proven.  HEAD on, the head first: the chain from the all-zero state, OPENED16, the eight constants and the capacity
+    // DERIVED -- refused here: a derived constant or capacity that is not the view's; the later stages then read the derived values (v)
+    View v = view;
+    Head h;
+    uint32_t derived[32];
+    if (kind >= HEAD) {
+        walk_head(s, v.inner_public, v.trace_root, v.quotient_root, v.opened, h);
+        uint32_t sums[16];
+        ZK_TRY(fri16_head_opened_impl(ctx, s, v.opened, h.fa, z.at(T_OPENED16), sums));
+        head_constants(s, h, sums, derived);
+        static const char* const names[8] = {"fa", "zeta", "zeta g_N", "YL", "YN", "YQ", "OFFN", "OFFQ"};
+        for (int k = 0; k < 8; k++)
+            if (std::memcmp(derived + 4 * k, v.constants + 4 * k, 16) != 0)
+                return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constant " + names[k] + " derived from the head of the transcript is not the view's");
+        if (std::memcmp(h.capacity, v.capacity, 32) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the capacity the head of the transcript leaves is not the view's");
+        v.constants = derived; v.capacity = h.capacity;
+        traces[T_OPENED16] = z.at(T_OPENED16);
+    }
+    // INDICES on, the transcript before the chains (the plan first: the stage takes the path counts from it).  Refused: challenges and indices the chain does not draw,
+    // a witness that fails the proof of work
+    PathPlan pl;
+    const uint32_t *d_rows = nullptr, *d_chain = nullptr;
+    if (kind >= INDICES) {
+        ZK_TRY(plan_paths(s, v.indices, v.paths, pl));
+        ZK_TRY(fri16_transcript_stage(ctx, s, v, pl, z.at(T_QUERIES), d_rmain, &traces[T_P2T], &traces[T_SAMPLES], who, kind >= HEAD ? &h.inputs : nullptr, &d_chain));
+    }
+    if (kind >= ROWPATHS) {
+        const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
+        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, d_rmain + roots_ld * (R + tree), &ends_of_tree, 4));
+    }
+    // (the staging block the chain's inputs lie in is not reserved again before this launch has read them: the next stage's d2h waits for the stream)
+    if (lift) ZK_TRY(fri16_lift_tables_impl(ctx, s, d_chain, (uint32_t)s.A, (uint32_t)s.HD, d_rmain, z.at(T_ROOTS), z.at(T_COEFFS)));
+    // FOLD16 and FINAL; from OPENINGS on behind ROWSUM16 and QUERY16, the chains starting from the openings the device computed.  Refused: chains that do not end in the
+    // final polynomial; openings the rows do not give, points without an inverse
+    if (kind >= OPENINGS) ZK_TRY(fri16_openings_stage(ctx, s, v, t_fold, t_final, &traces[T_ROWSUM16], &traces[T_QUERY16], &d_rows, who));
+    else ZK_TRY(fri16_gen_traces_impl(ctx, s, v, t_fold, ld_fold, t_final, s.main_w[T_FINAL]));
+    // P24L.  Refused: queries that disagree, paths that do not end in their layer's root.  (PATHS plans here, and builds ROOTS' counts on the host.)
+    if (kind == PATHS) ZK_TRY(plan_paths(s, v.indices, v.paths, pl));
+    if (kind >= PATHS) ZK_TRY(fri16_layer_paths_stage(ctx, s, v, t_fold, ld_fold, pl, &traces[T_P24L]));
+    if (kind == PATHS) {
+        std::vector<uint32_t> tabs(z.total, 0u);
+        for (size_t l = 0; l < R; l++) tabs[z.off[T_ROOTS] + (size_t)TAB_MAIN * l] = to_monty(pl.counts[l]);
+        ZK_TRY(dev_h2d(ctx, z.d, tabs.data(), z.total * 4));
+    }
+    if (kind >= ROWPATHS) {
+        // P24R from the raw rows the openings launch left on the device (the staging block of S_REC_J is not reserved again before this)
+        std::vector<uint32_t> ends;
+        ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, v, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
+        for (size_t p = 0; p < 2 * Q; p++)
+            if (std::memcmp(ends.data() + 8 * p, p & 1 ? v.quotient_root : v.trace_root, 32) != 0)
+                return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") + " tree: the opened row's path does not end in the root");
+        traces[T_P24R] = (const uint32_t*)t_p24r;
+    }
+    if (kind >= IDENTITY) {      // AIR16 and SCALARS16 from alpha, zeta and the opened values; refused here, still before anything is proven: zeta = 1, an identity that does not hold
+        uint32_t accs[8];
+        ZK_TRY(fri16_identity_check_zeta(h.zeta, who));
+        ZK_TRY(fri16_identity_rows_impl(ctx, s, v.opened, h.alpha, h.zeta, z.at(T_AIR16), z.at(T_SCALARS16), accs));
+        if (std::memcmp(accs, accs + 4, 16) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner proof's AIR identity at zeta does not hold");
+        traces[T_AIR16] = z.at(T_AIR16); traces[T_SCALARS16] = z.at(T_SCALARS16);
+    }
+    // the public values: the challenges; the capacity; the capacity, then the eight constants; the inner proof's
+    uint32_t pub[N_PUBLIC_O];
+    if (kind == OPENINGS || kind == ROWPATHS) {
+        std::memcpy(pub, view.capacity, 32);
+        std::memcpy(pub + 8, view.constants, 128);
+    }
+    const uint32_t* public_values = kind <= PATHS ? view.betas : kind == INDICES ? view.capacity : kind >= HEAD ? view.inner_public : pub;
+    return keyed::prove(ctx, key, machine_of(s)->km, traces, public_values, n_public_of(s), prm, proof, cap, len);
 }
 
 extern "C" {
@@ -1643,106 +1813,71 @@ extern "C" {
 // ---------------------------------------------------------------- LAYERS: the first machine's entries
 size_t zkhip_fri16_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
                             uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+    return fri16::describe({fri16::LAYERS, R, F, log_blowup, n_queries}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_key_host(int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
                          const uint32_t* siblings, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key_host: null argument");
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key_host"));
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.betas = betas; v.final_poly = final_poly; v.indices = indices; v.values = values; v.siblings = siblings;
+    return fri16_key({fri16::LAYERS, R, F, log_blowup, n_queries}, "fri16_key_host", nullptr, v, prm, nullptr, vk);
 }
 
 int zkhip_fri16_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
                     const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_key: null argument");
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_key"));
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_tables(s, betas, final_poly, indices, values, siblings, pre));
-    const int by_position[5] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G};      // this machine and PATHS give the slots out by machine position
-    const auto m = fri16::machine_of(s);
-    int slots[fri16::MAX_TABLES];
-    for (int i = 0; i < s.n_tables; i++) slots[m->km.order[i]] = by_position[i];
-    return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
+    fri16::View v;
+    v.betas = betas; v.final_poly = final_poly; v.indices = indices; v.values = values; v.siblings = siblings;
+    return fri16_key({fri16::LAYERS, R, F, log_blowup, n_queries}, "fri16_key", ctx, v, prm, key, vk);
 }
 
 int zkhip_fri16_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices,
                            const uint32_t* values, const uint32_t* siblings, uint32_t* d_fold, size_t ld_fold, uint32_t* d_final, size_t ld_final) {
     CHECK_CTX(ctx);
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
-    ZK_TRY(fri16::check_view(s, betas, final_poly, indices, values, siblings, "fri16_gen_traces"));
+    ZK_TRY(fri16::shape_of({fri16::LAYERS, R, F, log_blowup, n_queries}, s));
+    fri16::View v;
+    v.betas = betas; v.final_poly = final_poly; v.indices = indices; v.values = values; v.siblings = siblings;
+    ZK_TRY(fri16::check_view(s, v, "fri16_gen_traces"));
     if (!d_fold || !d_final || ld_fold < s.main_w[0] || ld_final < fri16::FIN_MAIN || ld_fold % 4 || ld_final % 4 || ((uintptr_t)d_fold | (uintptr_t)d_final) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_gen_traces: 16-byte aligned traces, leading dimensions multiples of 4 that hold the tables' widths");
-    return fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, d_fold, ld_fold, d_final, ld_final);
+    return fri16_gen_traces_impl(ctx, s, v, d_fold, ld_fold, d_final, ld_final);
 }
 
 size_t zkhip_fri16_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, prm);
+    return fri16::proof_size({fri16::LAYERS, R, F, log_blowup, n_queries}, prm);
 }
 
 int zkhip_prove_fri16(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t* final_poly,
                       const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    Shape s;
-    ZK_TRY(shape_of(LAYERS, R, F, log_blowup, n_queries, 0, 0, s));
-    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16: null argument");
-    ZK_TRY(check_view(s, betas, final_poly, indices, values, siblings, "prove_fri16"));
-    uint32_t *t_fold, *t_final;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    Fri16SmallTables z;          // the three key tables' main columns: unused, zero
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_LAYERS, T_QUERIES, T_COEFFS}, z));
-    ZK_TRY(dev_memset(ctx, z.d, 0, z.total * 4));
-    // refused here, before anything is proven: a view whose chains do not end in the final polynomial
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, z.at(T_LAYERS), z.at(T_QUERIES), z.at(T_COEFFS)};
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, betas, n_public_of(s), prm, proof, cap, len);
+    const fri16::View v{0, betas, final_poly, indices, values, siblings};
+    return fri16_prove({fri16::LAYERS, R, F, log_blowup, n_queries}, "prove_fri16", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8], const zkhip_params* prm,
                        int* reason) {
-    return fri16::verify(fri16::LAYERS, R, F, log_blowup, n_queries, 0, 0, proof, len, betas, vk, prm, reason, "verify_fri16");
+    return fri16::verify({fri16::LAYERS, R, F, log_blowup, n_queries}, proof, len, betas, vk, prm, reason, "verify_fri16");
 }
 
 // ---------------------------------------------------------------- PATHS
 size_t zkhip_fri16_paths_describe(int R, int F, int log_blowup, size_t n_queries, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width,
                                   uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+    return fri16::describe({fri16::PATHS, R, F, log_blowup, n_queries}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_paths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
                                const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.indices = indices; v.values = values; v.roots = roots;
+    return fri16_key({fri16::PATHS, R, F, log_blowup, n_queries}, "fri16_paths_key_host", nullptr, v, prm, nullptr, vk);
 }
 
 int zkhip_fri16_paths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* final_poly, const uint32_t* indices,
                           const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_paths_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_paths_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_paths_key_tables(s, final_poly, indices, values, roots, pre, "fri16_paths_key"));
-    const int by_position[6] = {S_REC_C, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J};
-    const auto m = fri16::machine_of(s);
-    int slots[fri16::MAX_TABLES];
-    for (int i = 0; i < s.n_tables; i++) slots[m->km.order[i]] = by_position[i];
-    return fri16::key_upload(ctx, s, pre, slots, prm, key, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.indices = indices; v.values = values; v.roots = roots;
+    return fri16_key({fri16::PATHS, R, F, log_blowup, n_queries}, "fri16_paths_key", ctx, v, prm, key, vk);
 }
 
 int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas, const uint32_t* final_poly,
@@ -1750,13 +1885,15 @@ int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, si
                                 uint32_t* ends, size_t cap_paths, size_t* n_paths) {
     CHECK_CTX(ctx);
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, s));
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "fri16_paths_gen_trace"));
+    ZK_TRY(fri16::shape_of({fri16::PATHS, R, F, log_blowup, n_queries}, s));
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.betas = betas; v.final_poly = final_poly; v.indices = indices; v.values = values; v.siblings = siblings; v.paths = paths;
+    ZK_TRY(fri16_paths_check_view(s, v, "fri16_paths_gen_trace"));
     if (!d_trace || !ends || !n_paths || ld < p24chip::WIDTH_L || ld % 4 || (uintptr_t)d_trace % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_paths_gen_trace: a 16-byte aligned trace, a leading dimension that is a multiple of 4 and holds 552 columns, ends and n_paths");
     uint32_t *t_fold, *t_final;
     ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
+    ZK_TRY(fri16_gen_traces_impl(ctx, s, v, t_fold, s.main_w[0], t_final, s.main_w[1]));
     fri16::PathPlan pl;
     std::vector<uint32_t> e;
     ZK_TRY(fri16::plan_paths(s, indices, paths, pl));
@@ -1768,85 +1905,54 @@ int zkhip_fri16_paths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, si
 }
 
 size_t zkhip_fri16_paths_proof_size(int R, int F, int log_blowup, size_t n_queries, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, prm);
+    return fri16::proof_size({fri16::PATHS, R, F, log_blowup, n_queries}, prm);
 }
 
 int zkhip_prove_fri16_paths(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, const uint32_t* betas,
                             const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
                             const uint32_t* paths, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    Shape s;
-    ZK_TRY(shape_of(PATHS, R, F, log_blowup, n_queries, 0, 0, s));
-    if (!key || !prm || !proof || !len || !roots) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: null argument");
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, "prove_fri16_paths"));
-    if (!canonical(roots, 8 * (size_t)R)) return fail(ZKHIP_ERR_INVALID, "prove_fri16_paths: values must be canonical");
-    uint32_t *t_fold, *t_final;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    Fri16SmallTables z;          // the three tables' main columns: QUERIES and COEFFS unused, zero; ROOTS the number of path ends per layer
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
-    // refused here, before anything is proven: chains that do not end in the final polynomial, queries that disagree, paths that do not end in their layer's root
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
-    PathPlan pl;
-    const uint32_t* t_p24;
-    ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[0], pl, &t_p24));
-    {
-        std::vector<uint32_t> tabs(z.total, 0u);
-        for (int l = 0; l < R; l++) tabs[z.off[T_ROOTS] + (size_t)TAB_MAIN * l] = to_monty(pl.counts[l]);
-        ZK_TRY(dev_h2d(ctx, z.d, tabs.data(), z.total * 4));
-    }
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS)};
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, betas, n_public_of(s), prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths};
+    return fri16_prove({fri16::PATHS, R, F, log_blowup, n_queries}, "prove_fri16_paths", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_paths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, const uint32_t* betas, const uint32_t vk[8],
                              const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::PATHS, R, F, log_blowup, n_queries, 0, 0, proof, len, betas, vk, prm, reason, "verify_fri16_paths");
+    return fri16::verify({fri16::PATHS, R, F, log_blowup, n_queries}, proof, len, betas, vk, prm, reason, "verify_fri16_paths");
 }
 
 // ---------------------------------------------------------------- INDICES
 size_t zkhip_fri16_indices_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, int which, int kind, uint32_t* out, size_t cap_words, int* log_rows,
                                     uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+    return fri16::describe({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_indices_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly, const uint32_t* values,
                                  const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.values = values; v.roots = roots;
+    return fri16_key({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, "fri16_indices_key_host", nullptr, v, prm, nullptr, vk);
 }
-
-// (INDICES on: the key's slots by table number -- the tables with preprocessed columns)
-static const int FRI16_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B};
 
 int zkhip_fri16_indices_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, const uint32_t* final_poly,
                             const uint32_t* values, const uint32_t* roots, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_indices_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_indices_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_indices_key_tables(s, final_poly, values, roots, pre, "fri16_indices_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.values = values; v.roots = roots;
+    return fri16_key({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, "fri16_indices_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_indices_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, prm);
+    return fri16::proof_size({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, prm);
 }
 
 int zkhip_fri16_indices_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8], const uint32_t* roots,
                                    const uint32_t* final_poly, uint32_t witness, uint32_t* d_p2t, uint32_t* d_samples, uint32_t* betas, uint32_t* indices) {
     CHECK_CTX(ctx);
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, "fri16_indices_gen_traces"));
+    ZK_TRY(fri16::shape_of({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, s));
+    fri16::View v;
+    v.capacity = capacity; v.roots = roots; v.final_poly = final_poly; v.witness = witness;
+    ZK_TRY(fri16_indices_check_inputs(s, v, "fri16_indices_gen_traces"));
     if (!d_p2t || !d_samples || !betas || !indices || ((uintptr_t)d_p2t | (uintptr_t)d_samples) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_indices_gen_traces: 16-byte aligned dense traces (352 and 288 columns), betas and indices");
     fri16::Chain c;
@@ -1882,67 +1988,39 @@ int zkhip_fri16_samples_gen_trace(zkhip_ctx* ctx, int index_bits, size_t n_queri
 int zkhip_prove_fri16_indices(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
                               const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots,
                               const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    const char* who = "prove_fri16_indices";
-    Shape s;
-    ZK_TRY(shape_of(INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, s));
-    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_indices: null argument");
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
-    uint32_t *t_fold, *t_final;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    Fri16SmallTables z;          // the three tables' main columns: QUERIES the indices, COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
-    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
-    // refused here, before anything is proven: challenges and indices the chain does not draw, a witness that fails the proof of work; then all the paths machine refuses
-    PathPlan pl;
-    const uint32_t *t_p2t, *t_smp, *t_p24;
-    ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
-    ZK_TRY(fri16_gen_traces_impl(ctx, s, betas, final_poly, indices, values, siblings, t_fold, s.main_w[0], t_final, s.main_w[1]));
-    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[0], pl, &t_p24));
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, z.at(T_QUERIES), z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp};
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, capacity, n_public_of(s), prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness};
+    return fri16_prove({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, "prove_fri16_indices", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_indices(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, const uint32_t capacity[8],
                                const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits, 0, proof, len, capacity, vk, prm, reason, "verify_fri16_indices");
+    return fri16::verify({fri16::INDICES, R, F, log_blowup, n_queries, inner_pow_bits}, proof, len, capacity, vk, prm, reason, "verify_fri16_indices");
 }
 
 // ---------------------------------------------------------------- OPENINGS
 size_t zkhip_fri16_openings_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
                                      size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+    return fri16::describe({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_openings_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
                                   const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.trace_rows = trace_rows; v.quotient_rows = quotient_rows; v.roots = roots;
+    return fri16_key({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "fri16_openings_key_host", nullptr, v, prm, nullptr, vk);
 }
 
 int zkhip_fri16_openings_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                              const uint32_t* final_poly, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t* roots, const zkhip_params* prm,
                              zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_openings_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_openings_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_openings_key_tables(s, final_poly, trace_rows, quotient_rows, roots, pre, "fri16_openings_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.trace_rows = trace_rows; v.quotient_rows = quotient_rows; v.roots = roots;
+    return fri16_key({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "fri16_openings_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_openings_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm);
+    return fri16::proof_size({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, prm);
 }
 
 int zkhip_fri16_openings_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
@@ -1950,8 +2028,10 @@ int zkhip_fri16_openings_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup
                                     uint32_t* openings) {
     CHECK_CTX(ctx);
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, "fri16_openings_gen_traces"));
+    ZK_TRY(fri16::shape_of({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, s));
+    fri16::View v;
+    v.trace_rows = trace_rows; v.quotient_rows = quotient_rows; v.constants = constants; v.indices = indices;
+    ZK_TRY(fri16_openings_check_rows(s, v, "fri16_openings_gen_traces"));
     if (!d_rowsum || !d_query || !openings || ((uintptr_t)d_rowsum | (uintptr_t)d_query) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_openings_gen_traces: 16-byte aligned dense traces (48 and 72 columns) and the openings");
     uint32_t status[2], *d_open = nullptr;
@@ -1965,72 +2045,39 @@ int zkhip_prove_fri16_openings(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness,
                                const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const zkhip_params* prm, uint8_t* proof, size_t cap,
                                size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    const char* who = "prove_fri16_openings";
-    Shape s;
-    ZK_TRY(shape_of(OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    if (!key || !prm || !proof || !len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_openings: null argument");
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
-    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
-    ZK_TRY(check_openings_constants(s, constants, who));
-    uint32_t *t_fold, *t_final;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    Fri16SmallTables z;          // the small tables' main columns: COEFFS and ROWS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_ROWS}, z));
-    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
-    ZK_TRY(dev_memset(ctx, z.at(T_ROWS), 0, z.words[T_ROWS] * 4));
-    // refused here, before anything is proven: all zkhip_prove_fri16_indices refuses; then openings the rows do not give, points without an inverse
-    PathPlan pl;
-    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24;
-    ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
-    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, constants, t_fold, t_final, &t_rs, &t_q, nullptr, who));
-    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, z.at(T_ROWS)};
-    uint32_t pub[N_PUBLIC_O];
-    fri16_openings_public(capacity, constants, pub);
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, pub, n_public_of(s), prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants};
+    return fri16_prove({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "prove_fri16_openings", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_openings(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, public_values, vk, prm, reason, "verify_fri16_openings");
+    return fri16::verify({fri16::OPENINGS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, proof, len, public_values, vk, prm, reason, "verify_fri16_openings");
 }
 
 // ---------------------------------------------------------------- ROWPATHS
 size_t zkhip_fri16_rowpaths_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, int which, int kind, uint32_t* out,
                                      size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
+    return fri16::describe({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_rowpaths_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, const uint32_t* final_poly,
                                   const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "fri16_rowpaths_key_host", nullptr, v, prm, nullptr, vk);
 }
 
 int zkhip_fri16_rowpaths_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                              const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
                              zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_rowpaths_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_rowpaths_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_rowpaths_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_KEY_SLOTS, prm, key, vk);          // (P24R has no preprocessed columns: its slot is not read)
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "fri16_rowpaths_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_rowpaths_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm);
+    return fri16::proof_size({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, prm);
 }
 
 int zkhip_fri16_rowpaths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, const uint32_t* trace_rows,
@@ -2038,15 +2085,17 @@ int zkhip_fri16_rowpaths_gen_trace(zkhip_ctx* ctx, int R, int F, int log_blowup,
                                    uint32_t* ends) {
     CHECK_CTX(ctx);
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
+    ZK_TRY(fri16::shape_of({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, s));
     if (!trace_rows || !quotient_rows || !indices || !d_trace || !ends || (uintptr_t)d_trace % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: null argument, or a trace that is not 16-byte aligned (dense, 552 columns)");
     if (!fri16::canonical(trace_rows, s.Q * (size_t)s.W) || !fri16::canonical(quotient_rows, s.Q * fri16::QROW16))
         return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: values must be canonical");
     for (size_t q = 0; q < s.Q; q++) if (indices[q] >> s.H) return fail(ZKHIP_ERR_INVALID, "fri16_rowpaths_gen_trace: a query index has more bits than the proof's domain");
-    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, nullptr, nullptr, "fri16_rowpaths_gen_trace"));
+    fri16::View v;
+    v.trace_rows = trace_rows; v.quotient_rows = quotient_rows; v.indices = indices; v.trace_paths = trace_paths; v.quotient_paths = quotient_paths;
+    ZK_TRY(fri16_rowpaths_check_paths(s, v, "fri16_rowpaths_gen_trace"));
     std::vector<uint32_t> e;
-    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, nullptr, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, d_trace, p24chip::WIDTH_R, e));
+    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, nullptr, v, d_trace, p24chip::WIDTH_R, e));
     std::memcpy(ends, e.data(), e.size() * 4);
     return ZKHIP_OK;
 }
@@ -2057,90 +2106,41 @@ int zkhip_prove_fri16_rowpaths(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths,
                                const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm, uint8_t* proof,
                                size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    const char* who = "prove_fri16_rowpaths";
-    Shape s;
-    ZK_TRY(shape_of(ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s));
-    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: null argument");
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
-    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
-    ZK_TRY(check_openings_constants(s, constants, who));
-    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, who));
-    const size_t Q = s.Q;
-    uint32_t *t_fold, *t_final;
-    void* t_p24r;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
-    Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block
-    ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS}, z));
-    ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
-    // refused here, before anything is proven: all zkhip_prove_fri16_openings refuses; then row paths that do not end in their roots
-    PathPlan pl;
-    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr;
-    ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_transcript_stage(ctx, s, capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), z.at(T_ROOTS), &t_p2t, &t_smp, who));
-    {
-        const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
-        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, z.at(T_ROOTS) + (size_t)s.main_w[T_ROOTS] * ((size_t)R + tree), &ends_of_tree, 4));
-    }
-    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, constants, t_fold, t_final, &t_rs, &t_q, &d_rows, who));
-    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
-    // P24R from the raw rows the openings launch left on the device (the staging block of S_REC_J is not reserved again before this)
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
-    for (size_t p = 0; p < 2 * Q; p++)
-        if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, "prove_fri16_rowpaths: query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") +
-                                               " tree: the opened row's path does not end in the root");
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r};
-    uint32_t pub[N_PUBLIC_O];
-    fri16_openings_public(capacity, constants, pub);
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, pub, n_public_of(s), prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants,
+                        trace_paths, quotient_paths, trace_root, quotient_root};
+    return fri16_prove({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, "prove_fri16_rowpaths", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_rowpaths(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 const uint32_t public_values[40], const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, public_values, vk, prm, reason, "verify_fri16_rowpaths");
+    return fri16::verify({fri16::ROWPATHS, R, F, log_blowup, n_queries, inner_pow_bits, trace_width}, proof, len, public_values, vk, prm, reason, "verify_fri16_rowpaths");
 }
 
 // ---------------------------------------------------------------- HEAD
 size_t zkhip_fri16_head_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
                                  uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+    return fri16::describe({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_head_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
                               const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
                               uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_head_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_head_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_head_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_head_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_head_key_host", nullptr, v, prm, nullptr, vk);
 }
-
-// (the row-paths key's slots, and one of its own for OPENED16's schedule)
-static const int FRI16_HEAD_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B, S_REC_H};
 
 int zkhip_fri16_head_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                          uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
                          const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_head_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_head_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_head_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_head_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_HEAD_KEY_SLOTS, prm, key, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_head_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_head_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+    return fri16::proof_size({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, prm);
 }
 
 int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
@@ -2150,13 +2150,16 @@ int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, si
     CHECK_CTX(ctx);
     const char* who = "fri16_head_gen_traces";
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16_head_check_inputs(s, inner_public, trace_root, quotient_root, opened, who));
+    ZK_TRY(fri16::shape_of({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, s));
+    fri16::View v;
+    v.inner_public = inner_public; v.trace_root = trace_root; v.quotient_root = quotient_root; v.opened = opened; v.roots = roots; v.final_poly = final_poly; v.witness = witness;
+    ZK_TRY(fri16_head_check_inputs(s, v, who));
     if (!d_p2th || !d_samples || !d_opened || !constants || !capacity || ((uintptr_t)d_p2th | (uintptr_t)d_samples | (uintptr_t)d_opened) % 16)
         return fail(ZKHIP_ERR_INVALID, "fri16_head_gen_traces: 16-byte aligned dense traces (352, 288 and 36 columns), constants and capacity");
     fri16::Head h;
     fri16::walk_head(s, inner_public, trace_root, quotient_root, opened, h);
-    ZK_TRY(fri16_indices_check_inputs(s, h.capacity, roots, final_poly, witness, who));
+    v.capacity = h.capacity;
+    ZK_TRY(fri16_indices_check_inputs(s, v, who));
     uint32_t sums[16];
     ZK_TRY(fri16_head_opened_impl(ctx, s, opened, h.fa, d_opened, sums));
     fri16::head_constants(s, h, sums, constants);
@@ -2168,130 +2171,47 @@ int zkhip_fri16_head_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, si
     return fri16_transcript_impl(ctx, s, c, nullptr, nullptr, nullptr, d_p2th, d_samples, nullptr, nullptr, &status);
 }
 
-// the prover of the head machine and of the identity machine (kind; who: the entry's name in the refusals): the identity machine is the head machine plus one stage
-static int fri16_prove_head_kind(fri16::Kind kind, const char* who, zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries,
-                                 int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly,
-                                 const uint32_t* indices, const uint32_t* values, const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8],
-                                 uint32_t witness, const uint32_t* trace_rows, const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths,
-                                 const uint32_t* quotient_paths, const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened,
-                                 const zkhip_params* prm, uint8_t* proof, size_t cap, size_t* len) {
-    CHECK_CTX(ctx);
-    using namespace fri16;
-    Shape s;
-    if (n_inner_public > MAX_NP) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": more than 30 inner public values");
-    ZK_TRY(shape_of(kind, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    if (!key || !prm || !proof || !len || !trace_root || !quotient_root) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
-    ZK_TRY(fri16_paths_check_view(s, inner_hash_width, betas, final_poly, indices, values, siblings, paths, who));
-    ZK_TRY(fri16_indices_check_inputs(s, capacity, roots, final_poly, witness, who));
-    ZK_TRY(fri16_openings_check_rows(s, trace_rows, quotient_rows, constants, indices, who));
-    ZK_TRY(check_openings_constants(s, constants, who));
-    ZK_TRY(fri16_rowpaths_check_paths(s, trace_paths, quotient_paths, trace_root, quotient_root, who));
-    ZK_TRY(fri16_head_check_inputs(s, inner_public, trace_root, quotient_root, opened, who));
-    const size_t Q = s.Q;
-    uint32_t *t_fold, *t_final;
-    void* t_p24r;
-    ZK_TRY(fri16_reserve_fold_final(ctx, s, &t_fold, &t_final));
-    ZK_TRY(ctx_reserve(ctx, S_CHIP_B, ((size_t)p24chip::WIDTH_R << s.log_rows[T_P24R]) * 4, &t_p24r));
-    Fri16SmallTables z;          // the small tables' main columns: COEFFS unused (zero), ROOTS path ends, challenge and fold rows per layer; the scratch QUERIES block; OPENED16
-    // (LIFT: the transcript launch writes ROOTS' first eight columns into a dense scratch block; the lift launch makes both tables whole from it and the chain's inputs)
-    const bool lift = kind == LIFT;
-    const size_t roots_ld = lift ? ROOTS_MAIN_I : s.main_w[T_ROOTS];
-    if (kind >= IDENTITY) ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16, T_AIR16, T_SCALARS16}, z, lift ? (size_t)ROOTS_MAIN_I << s.log_rows[T_ROOTS] : 0));
-    else ZK_TRY(fri16_reserve_small_tables(ctx, s, {T_QUERIES, T_COEFFS, T_ROOTS, T_OPENED16}, z));
-    uint32_t* const d_rmain = lift ? z.scratch() : z.at(T_ROOTS);
-    if (!lift) ZK_TRY(dev_memset(ctx, z.at(T_COEFFS), 0, z.words[T_COEFFS] * 4));
-    // the head first: the chain from the all-zero state, OPENED16, the eight constants and the capacity DERIVED -- refused here, before anything is proven: a derived
-    // constant or capacity that is not the view's; then all zkhip_prove_fri16_rowpaths refuses, on the derived values
-    Head h;
-    walk_head(s, inner_public, trace_root, quotient_root, opened, h);
-    uint32_t sums[16], derived[32];
-    ZK_TRY(fri16_head_opened_impl(ctx, s, opened, h.fa, z.at(T_OPENED16), sums));
-    head_constants(s, h, sums, derived);
-    static const char* const names[8] = {"fa", "zeta", "zeta g_N", "YL", "YN", "YQ", "OFFN", "OFFQ"};
-    for (int k = 0; k < 8; k++)
-        if (std::memcmp(derived + 4 * k, constants + 4 * k, 16) != 0)
-            return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the constant " + names[k] + " derived from the head of the transcript is not the view's");
-    if (std::memcmp(h.capacity, capacity, 32) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the capacity the head of the transcript leaves is not the view's");
-    PathPlan pl;
-    const uint32_t *t_p2t, *t_smp, *t_rs, *t_q, *t_p24, *d_rows = nullptr, *d_chain = nullptr;
-    ZK_TRY(plan_paths(s, indices, paths, pl));
-    ZK_TRY(fri16_transcript_stage(ctx, s, h.capacity, roots, final_poly, witness, betas, indices, pl, z.at(T_QUERIES), d_rmain, &t_p2t, &t_smp, who, &h.inputs, &d_chain));
-    {
-        const uint32_t ends_of_tree = to_monty((uint32_t)Q);      // ROOTS' main column 0 on the two trees' rows: Q paths end in each
-        for (size_t tree = 0; tree < 2; tree++) ZK_TRY(dev_h2d(ctx, d_rmain + roots_ld * ((size_t)R + tree), &ends_of_tree, 4));
-    }
-    // (the staging block the chain's inputs lie in is not reserved again before this launch has read them: the next stage's d2h waits for the stream)
-    if (lift) ZK_TRY(fri16_lift_tables_impl(ctx, s, d_chain, (uint32_t)s.A, (uint32_t)s.HD, d_rmain, z.at(T_ROOTS), z.at(T_COEFFS)));
-    ZK_TRY(fri16_openings_stage(ctx, s, betas, final_poly, indices, values, siblings, trace_rows, quotient_rows, derived, t_fold, t_final, &t_rs, &t_q, &d_rows, who));
-    ZK_TRY(fri16_layer_paths_stage(ctx, s, paths, roots, t_fold, s.main_w[T_FOLD16], pl, &t_p24));
-    std::vector<uint32_t> ends;
-    ZK_TRY(fri16_rowpaths_gen_p24r_impl(ctx, s, d_rows, trace_rows, quotient_rows, indices, trace_paths, quotient_paths, (uint32_t*)t_p24r, p24chip::WIDTH_R, ends));
-    for (size_t p = 0; p < 2 * Q; p++)
-        if (std::memcmp(ends.data() + 8 * p, p & 1 ? quotient_root : trace_root, 32) != 0)
-            return fail(ZKHIP_ERR_INVALID, std::string(who) + ": query " + std::to_string(p / 2) + ", " + (p & 1 ? "quotient" : "trace") + " tree: the opened row's path does not end in the root");
-    const uint32_t* traces[MAX_TABLES] = {t_fold, t_final, t_p24, t_q, z.at(T_COEFFS), z.at(T_ROOTS), t_p2t, t_smp, t_rs, (const uint32_t*)t_p24r, z.at(T_OPENED16)};
-    if (kind >= IDENTITY) {      // AIR16 and SCALARS16 from alpha, zeta and the opened values; refused here, still before anything is proven: zeta = 1, an identity that does not hold
-        uint32_t accs[8];
-        ZK_TRY(fri16_identity_check_zeta(h.zeta, who));
-        ZK_TRY(fri16_identity_rows_impl(ctx, s, opened, h.alpha, h.zeta, z.at(T_AIR16), z.at(T_SCALARS16), accs));
-        if (std::memcmp(accs, accs + 4, 16) != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the inner proof's AIR identity at zeta does not hold");
-        traces[T_AIR16] = z.at(T_AIR16); traces[T_SCALARS16] = z.at(T_SCALARS16);
-    }
-    return keyed::prove(ctx, key, machine_of(s)->km, traces, inner_public, n_public_of(s), prm, proof, cap, len);
-}
-
 int zkhip_prove_fri16_head(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
                            uint32_t trace_width, uint32_t n_inner_public, const uint32_t* betas, const uint32_t* final_poly, const uint32_t* indices, const uint32_t* values,
                            const uint32_t* siblings, const uint32_t* roots, const uint32_t* paths, const uint32_t capacity[8], uint32_t witness, const uint32_t* trace_rows,
                            const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
                            const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
                            uint8_t* proof, size_t cap, size_t* len) {
-    return fri16_prove_head_kind(fri16::HEAD, "prove_fri16_head", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas, final_poly,
-                                 indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root, quotient_root,
-                                 inner_public, opened, prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants,
+                        trace_paths, quotient_paths, trace_root, quotient_root, inner_public, opened};
+    return fri16_prove({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "prove_fri16_head", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_head(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_head", n_inner_public);
+    return fri16::verify({fri16::HEAD, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, proof, len, inner_public, vk, prm, reason, "verify_fri16_head");
 }
 
 // ---------------------------------------------------------------- IDENTITY
 size_t zkhip_fri16_identity_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
                                      uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+    return fri16::describe({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_identity_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
                                   const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8], const zkhip_params* prm,
                                   uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_identity_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_identity_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_identity_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_identity_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_identity_key_host", nullptr, v, prm, nullptr, vk);
 }
-
-// (the head key's slots, and two more for the schedules of AIR16 and SCALARS16)
-static const int FRI16_IDENTITY_KEY_SLOTS[fri16::MAX_TABLES] = {-1, S_REC_C, -1, S_REC_D, S_REC_E, S_REC_F, S_REC_G, S_REC_J, S_REC_A, S_REC_B, S_REC_H, S_REC_I, S_STAGE};
 
 int zkhip_fri16_identity_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                              uint32_t n_inner_public, const uint32_t* final_poly, const uint32_t* roots, const uint32_t trace_root[8], const uint32_t quotient_root[8],
                              const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_identity_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_identity_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_identity_key_tables(s, final_poly, roots, trace_root, quotient_root, pre, "fri16_identity_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_IDENTITY_KEY_SLOTS, prm, key, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width; v.final_poly = final_poly; v.roots = roots; v.trace_root = trace_root; v.quotient_root = quotient_root;
+    return fri16_key({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_identity_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_identity_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+    return fri16::proof_size({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, prm);
 }
 
 int zkhip_fri16_identity_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
@@ -2299,7 +2219,7 @@ int zkhip_fri16_identity_gen_traces(zkhip_ctx* ctx, int R, int F, int log_blowup
     CHECK_CTX(ctx);
     const char* who = "fri16_identity_gen_traces";
     fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
+    ZK_TRY(fri16::shape_of({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, s));
     if (!alpha || !zeta || !opened || !d_air || !d_scalars || !accumulators || ((uintptr_t)d_air | (uintptr_t)d_scalars) % 16)
         return fail(ZKHIP_ERR_INVALID, std::string(who) + ": alpha, zeta, the opened values, 16-byte aligned dense traces (56 and 4 (17 + log_n) columns) and the accumulators");
     if (!fri16::canonical(alpha, 4) || !fri16::canonical(zeta, 4)) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the challenges must be canonical");
@@ -2314,47 +2234,39 @@ int zkhip_prove_fri16_identity(zkhip_ctx* ctx, const zkhip_machine_key* key, int
                                const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
                                const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
                                uint8_t* proof, size_t cap, size_t* len) {
-    return fri16_prove_head_kind(fri16::IDENTITY, "prove_fri16_identity", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas,
-                                 final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root,
-                                 quotient_root, inner_public, opened, prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants,
+                        trace_paths, quotient_paths, trace_root, quotient_root, inner_public, opened};
+    return fri16_prove({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "prove_fri16_identity", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                                 uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_identity", n_inner_public);
+    return fri16::verify({fri16::IDENTITY, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, proof, len, inner_public, vk, prm, reason, "verify_fri16_identity");
 }
 
 // ---------------------------------------------------------------- LIFT
 size_t zkhip_fri16_lift_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
                                  uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table) {
-    return fri16::describe(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, which, kind, out, cap_words, log_rows, main_width, pre_width, table, n_inner_public);
+    return fri16::describe({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, which, kind, out, cap_words, log_rows, main_width, pre_width, table);
 }
 
 int zkhip_fri16_lift_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
                               const zkhip_params* prm, uint32_t vk[8]) {
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_lift_key_host"));
-    if (!prm || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_lift_key_host: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_lift_key_tables(s, pre, "fri16_lift_key_host"));
-    return keyed::key_host(fri16::machine_of(s)->km, pre, prm, vk);
+    fri16::View v;
+    v.hash_width = inner_hash_width;
+    return fri16_key({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_lift_key_host", nullptr, v, prm, nullptr, vk);
 }
 
 int zkhip_fri16_lift_key(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
                          uint32_t n_inner_public, const zkhip_params* prm, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
-    fri16::Shape s;
-    ZK_TRY(fri16::shape_of(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, s, n_inner_public));
-    ZK_TRY(fri16::check_hash_width(inner_hash_width, "fri16_lift_key"));
-    if (!prm || !key || !vk) return fail(ZKHIP_ERR_INVALID, "fri16_lift_key: null argument");
-    std::vector<uint32_t> pre[fri16::MAX_TABLES];
-    ZK_TRY(fri16::build_lift_key_tables(s, pre, "fri16_lift_key"));
-    return fri16::key_upload(ctx, s, pre, FRI16_IDENTITY_KEY_SLOTS, prm, key, vk);      // (the identity key's slots: the same tables at the same preprocessed widths)
+    fri16::View v;
+    v.hash_width = inner_hash_width;
+    return fri16_key({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "fri16_lift_key", ctx, v, prm, key, vk);
 }
 
 size_t zkhip_fri16_lift_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* prm) {
-    return fri16::proof_size(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, prm, n_inner_public);
+    return fri16::proof_size({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, prm);
 }
 
 // the lift launch alone, for the table tests: the words are staged as the transcript stage leaves them (a chain of input states: three stream rows with the trace root
@@ -2393,14 +2305,14 @@ int zkhip_prove_fri16_lift(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, 
                            const uint32_t* quotient_rows, const uint32_t constants[32], const uint32_t* trace_paths, const uint32_t* quotient_paths,
                            const uint32_t trace_root[8], const uint32_t quotient_root[8], const uint32_t* inner_public, const uint32_t* opened, const zkhip_params* prm,
                            uint8_t* proof, size_t cap, size_t* len) {
-    return fri16_prove_head_kind(fri16::LIFT, "prove_fri16_lift", ctx, key, R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public, betas,
-                                 final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants, trace_paths, quotient_paths, trace_root,
-                                 quotient_root, inner_public, opened, prm, proof, cap, len);
+    const fri16::View v{inner_hash_width, betas, final_poly, indices, values, siblings, roots, paths, capacity, witness, trace_rows, quotient_rows, constants,
+                        trace_paths, quotient_paths, trace_root, quotient_root, inner_public, opened};
+    return fri16_prove({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, "prove_fri16_lift", ctx, key, v, prm, proof, cap, len);
 }
 
 int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width,
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason) {
-    return fri16::verify(fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, proof, len, inner_public, vk, prm, reason, "verify_fri16_lift", n_inner_public);
+    return fri16::verify({fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, proof, len, inner_public, vk, prm, reason, "verify_fri16_lift");
 }
 
 // segment proof in, lift proof out: ONE pass of the host verifier with every fold-16 view sink attached (verifier.cpp: fri16_view_all -- it fails with the verifier's
@@ -2410,12 +2322,13 @@ int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key,
     CHECK_CTX(ctx);
     if (!key || !proof || !public_values || !inner_prm || !outer_prm || !out || !out_len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: null argument");
     if (n_public > fri16::MAX_NP) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: more than 30 inner public values");
-    Fri16FullView v;
-    ZK_TRY(fri16_view_all(proof, len, log_n, width, public_values, n_public, inner_prm, v));
-    return zkhip_prove_fri16_lift(ctx, key, v.R, v.F, inner_prm->log_blowup, (size_t)inner_prm->num_queries, v.hash_width, inner_prm->pow_bits, width, (uint32_t)n_public,
-                                  v.betas.data(), v.final_poly.data(), v.indices.data(), v.values.data(), v.siblings.data(), v.roots.data(), v.paths.data(), v.transcript,
-                                  v.transcript[9], v.trace_rows.data(), v.quotient_rows.data(), v.constants, v.trace_paths.data(), v.quotient_paths.data(), v.trace_root,
-                                  v.quotient_root, public_values, v.opened.data(), outer_prm, out, cap, out_len);
+    Fri16FullView f;
+    ZK_TRY(fri16_view_all(proof, len, log_n, width, public_values, n_public, inner_prm, f));
+    const fri16::View v{f.hash_width, f.betas.data(), f.final_poly.data(), f.indices.data(), f.values.data(), f.siblings.data(), f.roots.data(), f.paths.data(), f.transcript,
+                        f.transcript[9], f.trace_rows.data(), f.quotient_rows.data(), f.constants, f.trace_paths.data(), f.quotient_paths.data(), f.trace_root, f.quotient_root,
+                        public_values, f.opened.data()};
+    return fri16_prove({fri16::LIFT, f.R, f.F, inner_prm->log_blowup, (size_t)inner_prm->num_queries, inner_prm->pow_bits, width, (uint32_t)n_public}, "prove_fri16_lift", ctx, key,
+                       v, outer_prm, out, cap, out_len);
 }
 
 }  // extern "C"

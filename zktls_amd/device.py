@@ -686,14 +686,29 @@ class Context:
                                                cap8.ctypes.data_as(u32p), int(witness), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the fold-by-16 machines: the key and the proof of every kind (_FRI16_KINDS below)
+    def _fri16_key(self, kind, view, params):
+        params = params or Params(1, 100, 16)
+        infix, _, fields, _ = _FRI16_KINDS[kind]
+        shape, hw, more, args = _fri16_gather(view, kind, fields)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(getattr(self.lib, "zkhip_fri16%s_key" % infix)(self.handle, *shape, *hw, *more, *args, C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def _prove_fri16(self, kind, key, view, params):
+        params = params or Params(1, 100, 16)
+        infix, _, _, n = _FRI16_KINDS[kind]
+        shape, hw, more, args = _fri16_gather(view, kind, _FRI16_VIEW[:n])
+        size = getattr(self.lib, "zkhip_fri16%s_proof_size" % infix)(*shape, *more, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        check(getattr(self.lib, "zkhip_prove_fri16%s" % infix)(self.handle, key.handle, *shape, *hw, *more, *args, C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
     # ---- the fold-by-16 FRI machine (FOLD16 + FINAL): key, traces, proof
     def fri16_key(self, view, params=None):
         """zkhip_fri16_key: the LAYERS / QUERIES / COEFFS tables and FINAL's schedule of a fold-16 view, committed on the device -> MachineKey"""
-        params = params or Params(1, 100, 16)
-        shape, arrs = _fri16_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_key(self.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("layers", view, params)
 
     def fri16_gen_traces(self, view, out=None):
         """zkhip_fri16_gen_traces: the two main traces of a fold-16 view -> (FOLD16 buffer, its log rows, its width, FINAL buffer, its log rows);
@@ -711,24 +726,13 @@ class Context:
     def prove_fri16(self, key, view, params=None):
         """zkhip_prove_fri16: "every listed query folds by 16 through the listed rows to the listed final polynomial at its last point"; a view whose
         chains do not end there is refused before anything is proven"""
-        params = params or Params(1, 100, 16)
-        shape, arrs = _fri16_arrays(view)
-        size = self.lib.zkhip_fri16_proof_size(*shape, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16(self.handle, key.handle, *shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("layers", key, view, params)
 
     # ---- the fold-by-16 PATHS machine (the layer rows' Merkle paths in-circuit: P24L + ROOTS where LAYERS stood)
     def fri16_paths_key(self, view, params=None):
         """zkhip_fri16_paths_key: QUERIES, COEFFS, ROOTS and FINAL's schedule of a fold-16 view, committed on the device -- from the final coefficients,
         the indices, the reduced openings and the layer roots alone -> MachineKey"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_paths_key(self.handle, *shape, hw, *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[2], arrs[3], roots)], C.byref(params), C.byref(handle),
-                                             root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("paths", view, params)
 
     def fri16_paths_gen_trace(self, view, out=None):
         """zkhip_fri16_paths_gen_trace: the P24L table of a fold-16 view -> (buffer, its log rows, path ends [n][8]); out: a buffer of an earlier call"""
@@ -745,24 +749,12 @@ class Context:
         """zkhip_prove_fri16_paths: "every listed query opens the listed layer commitments row by row and folds by 16 through these rows to the listed final
         polynomial at its last point"; refused before anything is proven: a path that does not end in its layer's root, queries that disagree about a
         shared row or its path, a chain that does not end in the final polynomial"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
-        size = self.lib.zkhip_fri16_paths_proof_size(*shape, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16_paths(self.handle, key.handle, *shape, hw, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
-                                               paths.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("paths", key, view, params)
 
     def fri16_indices_key(self, view, params=None):
         """zkhip_fri16_indices_key: the key of the fold-16 indices machine, committed on the device -- from the shape, the inner proof's grinding bits, the
         final coefficients, the reduced openings by query number and the layer roots: no index, no challenge -> MachineKey"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_indices_key(self.handle, *shape, hw, int(view["pow_bits"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[3], roots)], C.byref(params),
-                                               C.byref(handle), root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("indices", view, params)
 
     def fri16_indices_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, capacity, roots, final_poly, witness):
         """zkhip_fri16_indices_gen_traces: the P2T and SAMPLES main traces from the capacity, the layer roots, the final coefficients and the witness alone
@@ -794,30 +786,13 @@ class Context:
         proof-of-work word with its low bits zero and the query indices; every query, at the index drawn for it, opens the listed layer commitments and
         folds under the drawn challenges to the listed final polynomial".  view: a paths view with "capacity" [8], "witness" and "pow_bits".  Refused before
         anything is proven: challenges or indices the chain does not draw, a witness that fails the proof of work, and all prove_fri16_paths refuses"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
-        pb = int(view["pow_bits"])
-        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
-        assert cap.size == 8
-        size = self.lib.zkhip_fri16_indices_proof_size(*shape, pb, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16_indices(self.handle, key.handle, *shape, hw, pb, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
-                                                 paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]), C.byref(params), buf.ctypes.data_as(u8p), size,
-                                                 C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("indices", key, view, params)
 
     # ---- the fold-by-16 OPENINGS machine (the reduced openings in-circuit: ROWSUM16 and QUERY16)
     def fri16_openings_key(self, view, params=None):
         """zkhip_fri16_openings_key: the key of the fold-16 openings machine, committed on the device -- from the shape, the inner proof's grinding bits and trace
         width, the final coefficients, the opened trace and quotient rows by query number and the layer roots: no reduced opening, no index, no challenge -> MachineKey"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-        W, trows, qrows, _ = _fri16_openings_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_openings_key(self.handle, *shape, hw, int(view["pow_bits"]), W, *[a.ctypes.data_as(u32p) for a in (arrs[1], trows, qrows, roots)],
-                                                C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("openings", view, params)
 
     def fri16_openings_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, trows, qrows, consts, indices):
         """zkhip_fri16_openings_gen_traces: the ROWSUM16 and QUERY16 main traces from raw rows [Q][W] and [Q][8], the constants [8][4] and the indices alone
@@ -837,31 +812,13 @@ class Context:
         row and the quotient row listed for q, under the public constants, at the index drawn for q".  view: an indices view with "W", "trows" [Q][W], "qrows"
         [Q][8] and "consts" {FA, ZETA, ZNX, YL, YN, YQ, OFFN, OFFQ: [4]}.  Refused before anything is proven, each naming the query: all prove_fri16_indices
         refuses, a reduced opening the rows do not give, a point equal to zeta or zeta g, constants that do not match each other"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
-        W, trows, qrows, consts = _fri16_openings_arrays(view)
-        pb = int(view["pow_bits"])
-        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
-        assert cap.size == 8
-        size = self.lib.zkhip_fri16_openings_proof_size(*shape, pb, W, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16_openings(self.handle, key.handle, *shape, hw, pb, W, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
-                                                  paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]), trows.ctypes.data_as(u32p),
-                                                  qrows.ctypes.data_as(u32p), consts.ctypes.data_as(u32p), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("openings", key, view, params)
 
     # ---- the fold-by-16 ROW-PATHS machine (the opened rows' Merkle paths in-circuit: P24R where ROWS stood)
     def fri16_rowpaths_key(self, view, params=None):
         """zkhip_fri16_rowpaths_key: the key of the fold-16 row-paths machine, committed on the device -- from the shape, the inner proof's grinding bits and trace
         width, the final coefficients, the layer roots, the trace root and the quotient root: no row, no index, no value -> MachineKey"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-        _, _, troot, qroot = _fri16_rowpaths_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_fri16_rowpaths_key(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)],
-                                                C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("rowpaths", view, params)
 
     def fri16_rowpaths_gen_trace(self, R, F, log_blowup, n_queries, pow_bits, W, trows, qrows, indices, tpaths, qpaths):
         """zkhip_fri16_rowpaths_gen_trace: P24R's main trace from raw rows [Q][W] and [Q][8], the indices and the siblings [Q][H][8] of either tree alone, one launch
@@ -882,36 +839,13 @@ class Context:
         q of the trees whose roots the key lists as the trace root and the quotient root".  view: an openings view with "tpaths" / "qpaths" [Q][H][8] and "troot" /
         "qroot" [8].  Refused before anything is proven, each naming query and tree: all prove_fri16_openings refuses, a path that does not end in its root,
         path words that are not canonical"""
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
-        W, trows, qrows, consts = _fri16_openings_arrays(view)
-        tpaths, qpaths, troot, qroot = _fri16_rowpaths_arrays(view)
-        pb = int(view["pow_bits"])
-        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
-        assert cap.size == 8
-        size = self.lib.zkhip_fri16_rowpaths_proof_size(*shape, pb, W, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_fri16_rowpaths(self.handle, key.handle, *shape, hw, pb, W, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
-                                                  paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]),
-                                                  *[a.ctypes.data_as(u32p) for a in (trows, qrows, consts, tpaths, qpaths, troot, qroot)], C.byref(params),
-                                                  buf.ctypes.data_as(u8p), size, C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("rowpaths", key, view, params)
 
     # ---- the fold-by-16 HEAD machine (the head of the transcript in-circuit: P2TH, OPENED16, the constants over buses)
     def fri16_head_key(self, view, params=None):
         """zkhip_fri16_head_key: the key of the fold-16 head machine, committed on the device -- from the shape, the inner proof's grinding bits, trace width and
         number of public values, the final coefficients, the layer roots, the trace root and the quotient root: no opened word, no constant, no challenge -> MachineKey"""
-        return self._fri16_head_kind_key("head", view, params)
-
-    def _fri16_head_kind_key(self, kind, view, params):
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-        _, _, troot, qroot = _fri16_rowpaths_arrays(view)
-        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
-        check(getattr(self.lib, "zkhip_fri16_%s_key" % kind)(self.handle, *shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
-                                            *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
-        return MachineKey(self, handle, root, None)
+        return self._fri16_key("head", view, params)
 
     def fri16_head_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, pubs, troot, qroot, opened, roots, final_poly, witness):
         """zkhip_fri16_head_gen_traces: the P2TH, SAMPLES and OPENED16 main traces from the inner public values, the two roots, the opened values [2 W + 8][4], the layer
@@ -934,30 +868,12 @@ class Context:
         public values, the quotient root and the opened values, and the eight constants and the commit phase's capacity are what it gives".  view: a row-paths view with
         "pubs" (the inner proof's public values) and "opened" [2 W + 8][4].  The proof's public values are view["pubs"].  Refused before anything is proven: all
         prove_fri16_rowpaths refuses, a derived constant or capacity that is not the view's, values that are not canonical, more than 30 public values or none"""
-        return self._prove_fri16_head_kind("head", key, view, params)
-
-    def _prove_fri16_head_kind(self, kind, key, view, params):
-        params = params or Params(1, 100, 16)
-        shape, hw, arrs, roots, paths = _fri16_paths_arrays(view)
-        W, trows, qrows, consts = _fri16_openings_arrays(view)
-        tpaths, qpaths, troot, qroot = _fri16_rowpaths_arrays(view)
-        pubs, opened = _fri16_head_arrays(view)
-        pb = int(view["pow_bits"])
-        cap = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32))
-        assert cap.size == 8
-        size = getattr(self.lib, "zkhip_fri16_%s_proof_size" % kind)(*shape, pb, W, pubs.size, C.byref(params))
-        buf = np.empty(max(size, 1), dtype=np.uint8)
-        got = C.c_size_t(0)
-        check(getattr(self.lib, "zkhip_prove_fri16_%s" % kind)(self.handle, key.handle, *shape, hw, pb, W, pubs.size, *[a.ctypes.data_as(u32p) for a in arrs], roots.ctypes.data_as(u32p),
-                                              paths.ctypes.data_as(u32p), cap.ctypes.data_as(u32p), int(view["witness"]),
-                                              *[a.ctypes.data_as(u32p) for a in (trows, qrows, consts, tpaths, qpaths, troot, qroot, pubs, opened)], C.byref(params),
-                                              buf.ctypes.data_as(u8p), size, C.byref(got)))
-        return buf[: got.value]
+        return self._prove_fri16("head", key, view, params)
 
     # ---- the fold-by-16 IDENTITY machine (the AIR identity at zeta in-circuit: AIR16, SCALARS16)
     def fri16_identity_key(self, view, params=None):
         """zkhip_fri16_identity_key: the key of the fold-16 identity machine, committed on the device -- fri16_head_key's arguments -> MachineKey"""
-        return self._fri16_head_kind_key("identity", view, params)
+        return self._fri16_key("identity", view, params)
 
     def fri16_identity_gen_traces(self, R, F, log_blowup, n_queries, pow_bits, W, NP, alpha, zeta, opened):
         """zkhip_fri16_identity_gen_traces: the AIR16 and SCALARS16 main traces from the shape, alpha, zeta and the opened values [2 W + 8][4] alone -> (AIR16 [2^lr][56],
@@ -976,7 +892,7 @@ class Context:
         """zkhip_prove_fri16_identity: everything prove_fri16_head states, and "the synthetic AIR's constraints at zeta, folded with the alpha the transcript draws, equal
         the quotient the opened quotient values give times zeta^N - 1".  view: a head view.  Refused before anything is proven: all prove_fri16_head refuses, zeta = 1, an
         inner proof whose AIR identity at zeta does not hold"""
-        return self._prove_fri16_head_kind("identity", key, view, params)
+        return self._prove_fri16("identity", key, view, params)
 
     # ---- the fold-by-16 LIFT machine (the identity machine with roots and final coefficients out of the key: one key per shape)
     def fri16_lift_key(self, R, F, log_blowup, n_queries, pow_bits, W, NP, params=None, hash_width=24):
@@ -1004,7 +920,7 @@ class Context:
     def prove_fri16_lift(self, key, view, params=None):
         """zkhip_prove_fri16_lift: "some valid segment proof of this shape with THESE public values exists" -- everything prove_fri16_identity states, under a key that
         holds no root and no coefficient.  view: a head view.  Refused before anything is proven: all prove_fri16_identity refuses"""
-        return self._prove_fri16_head_kind("lift", key, view, params)
+        return self._prove_fri16("lift", key, view, params)
 
     def prove_fri16_lift_segment(self, key, proof, log_n, width, public_values, inner_params, params=None):
         """zkhip_prove_fri16_lift_segment: segment proof in, lift proof out -- the host verifier once over `proof` with every fold-16 view attached, then prove_fri16_lift.
@@ -1756,11 +1672,7 @@ def fri16_describe(R, F, log_blowup, n_queries, which, kind):
 
 def fri16_key_host(view, params=None):
     """zkhip_fri16_key_host: the fold-16 FRI machine's key of a view, without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, arrs = _fri16_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_key_host(*shape, *[a.ctypes.data_as(u32p) for a in arrs], C.byref(params), vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("layers", view, params)
 
 
 def verify_fri16(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
@@ -1787,11 +1699,7 @@ def fri16_paths_describe(R, F, log_blowup, n_queries, which, kind):
 
 def fri16_paths_key_host(view, params=None):
     """zkhip_fri16_paths_key_host: the fold-16 paths machine's key of a view, without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_paths_key_host(*shape, hw, *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[2], arrs[3], roots)], C.byref(params), vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("paths", view, params)
 
 
 def verify_fri16_paths(proof, betas, R, F, log_blowup, n_queries, vk, params=None):
@@ -1822,12 +1730,7 @@ def fri16_indices_describe(R, F, log_blowup, n_queries, pow_bits, which, kind):
 
 def fri16_indices_key_host(view, params=None):
     """zkhip_fri16_indices_key_host: the fold-16 indices machine's key of a view (with "pow_bits"), without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_indices_key_host(*shape, hw, int(view["pow_bits"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], arrs[3], roots)], C.byref(params),
-                                                   vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("indices", view, params)
 
 
 def verify_fri16_indices(proof, capacity, R, F, log_blowup, n_queries, pow_bits, vk, params=None):
@@ -1869,13 +1772,7 @@ def fri16_openings_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kin
 
 def fri16_openings_key_host(view, params=None):
     """zkhip_fri16_openings_key_host: the fold-16 openings machine's key of a view (with "pow_bits", "W", "trows", "qrows"), without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-    W, trows, qrows, _ = _fri16_openings_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_openings_key_host(*shape, hw, int(view["pow_bits"]), W, *[a.ctypes.data_as(u32p) for a in (arrs[1], trows, qrows, roots)], C.byref(params),
-                                                    vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("openings", view, params)
 
 
 def verify_fri16_openings(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
@@ -1915,13 +1812,7 @@ def fri16_rowpaths_describe(R, F, log_blowup, n_queries, pow_bits, W, which, kin
 
 def fri16_rowpaths_key_host(view, params=None):
     """zkhip_fri16_rowpaths_key_host: the fold-16 row-paths machine's key of a view (with "pow_bits", "W", "troot", "qroot"), without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-    _, _, troot, qroot = _fri16_rowpaths_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(_lib.load().zkhip_fri16_rowpaths_key_host(*shape, hw, int(view["pow_bits"]), int(view["W"]), *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)],
-                                                    C.byref(params), vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("rowpaths", view, params)
 
 
 def verify_fri16_rowpaths(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
@@ -1936,6 +1827,55 @@ def _fri16_head_arrays(view):
     pubs, opened = u(view["pubs"]), u(view["opened"])
     assert opened.size == 8 * (int(view["W"]) + 4)
     return pubs, opened
+
+
+# the fields of a whole fold-16 view in the order the prove entries take them (the library's fri16::View), and one row per kind of the machine: the entries' infix, the
+# shape words behind (R, F, log_blowup, queries[, inner hash width]), the fields the key entries take, and how many of the view's fields the prove entry takes.  The
+# lift machine's key takes the shape alone: fri16_lift_key, fri16_lift_key_host
+_FRI16_VIEW = ("betas", "final_poly", "indices", "values", "siblings", "roots", "paths", "capacity", "witness", "trows", "qrows", "consts", "tpaths", "qpaths", "troot", "qroot",
+               "pubs", "opened")
+_FRI16_KINDS = {
+    "layers": ("", (), _FRI16_VIEW[:5], 5),
+    "paths": ("_paths", (), ("final_poly", "indices", "values", "roots"), 7),
+    "indices": ("_indices", ("pow_bits",), ("final_poly", "values", "roots"), 9),
+    "openings": ("_openings", ("pow_bits", "W"), ("final_poly", "trows", "qrows", "roots"), 12),
+    "rowpaths": ("_rowpaths", ("pow_bits", "W"), ("final_poly", "roots", "troot", "qroot"), 16),
+    "head": ("_head", ("pow_bits", "W", "NP"), ("final_poly", "roots", "troot", "qroot"), 18),
+    "identity": ("_identity", ("pow_bits", "W", "NP"), ("final_poly", "roots", "troot", "qroot"), 18),
+    "lift": ("_lift", ("pow_bits", "W", "NP"), None, 18),
+}
+
+
+def _fri16_gather(view, kind, fields):
+    """a view and the fields an entry of this kind takes of it, each from the gatherer that has it (and checks its size) -> ((R, F, log_blowup, queries), (inner hash width,)
+    from the paths machine on, the kind's further shape words, the fields as the entry takes them: pointers to flat canonical arrays, the witness a word)"""
+    need, f = set(fields), {}
+    if kind == "layers":
+        shape, arrs = _fri16_arrays(view)
+    else:
+        shape, f["hash_width"], arrs, f["roots"], f["paths"] = _fri16_paths_arrays(view)
+    f.update(zip(_FRI16_VIEW[:5], arrs))
+    if need & {"trows", "qrows", "consts"}:
+        _, f["trows"], f["qrows"], f["consts"] = _fri16_openings_arrays(view)
+    if need & {"tpaths", "qpaths", "troot", "qroot"}:
+        f["tpaths"], f["qpaths"], f["troot"], f["qroot"] = _fri16_rowpaths_arrays(view)
+    if need & {"pubs", "opened"}:
+        f["pubs"], f["opened"] = _fri16_head_arrays(view)
+    if "capacity" in need:
+        f["capacity"], f["witness"] = np.ascontiguousarray(np.array(view["capacity"], dtype=np.uint32)), int(view["witness"])
+        assert f["capacity"].size == 8
+    words = {"pow_bits": lambda: int(view["pow_bits"]), "W": lambda: int(view["W"]), "NP": lambda: len(view["pubs"])}
+    return (shape, (f["hash_width"],) if kind != "layers" else (), tuple(words[w]() for w in _FRI16_KINDS[kind][1]),
+            [f[n] if n == "witness" else f[n].ctypes.data_as(u32p) for n in fields])
+
+
+def _fri16_key_host(kind, view, params):
+    params = params or Params(1, 100, 16)
+    infix, _, fields, _ = _FRI16_KINDS[kind]
+    shape, hw, more, args = _fri16_gather(view, kind, fields)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(getattr(_lib.load(), "zkhip_fri16%s_key_host" % infix)(*shape, *hw, *more, *args, C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
 
 
 def fri16_view_head(proof, log_n, width, public_values=(), params=None):
@@ -1957,15 +1897,9 @@ def fri16_head_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kin
     return _describe("fri16_head_describe", R, F, log_blowup, n_queries, pow_bits, W, NP, which=which, kind=kind)
 
 
-def fri16_head_key_host(view, params=None, _entry="zkhip_fri16_head_key_host"):
+def fri16_head_key_host(view, params=None):
     """zkhip_fri16_head_key_host: the fold-16 head machine's key of a view (with "pow_bits", "W", "troot", "qroot", "pubs"), without a GPU -> 8 canonical words"""
-    params = params or Params(1, 100, 16)
-    shape, hw, arrs, roots, _ = _fri16_paths_arrays(view)
-    _, _, troot, qroot = _fri16_rowpaths_arrays(view)
-    vk = np.zeros(8, dtype=np.uint32)
-    check(getattr(_lib.load(), _entry)(*shape, hw, int(view["pow_bits"]), int(view["W"]), len(view["pubs"]),
-                                       *[a.ctypes.data_as(u32p) for a in (arrs[1], roots, troot, qroot)], C.byref(params), vk.ctypes.data_as(u32p)))
-    return vk
+    return _fri16_key_host("head", view, params)
 
 
 def fri16_identity_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, kind):
@@ -1976,7 +1910,7 @@ def fri16_identity_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which,
 
 def fri16_identity_key_host(view, params=None):
     """zkhip_fri16_identity_key_host: the fold-16 identity machine's key of a head view, without a GPU -> 8 canonical words"""
-    return fri16_head_key_host(view, params, _entry="zkhip_fri16_identity_key_host")
+    return _fri16_key_host("identity", view, params)
 
 
 def verify_fri16_identity(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):
