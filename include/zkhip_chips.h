@@ -472,8 +472,7 @@ int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, 
  * zkhip_prove_fri16_lift_segment: segment proof in, lift proof out -- ONE pass of the host verifier over `proof` (log_n, width, public_values, inner_prm) with every
  * fold-16 view attached, then the lift prover under outer_prm.  It fails with the host verifier's code and message when the inner proof does not verify, and with
  * zkhip_fri16_view_head's message on a form that view does not take.
- * STILL OUTSIDE: the join of several lift proofs and the r0 host mirror's compress path (Risc0HipGuestProver::with_compress(), the Rust twin), lookups, version-7
- * and version-8 inner proofs, the wiring into shard_verifier.inl, a batch entry over the lock-step lanes. */
+ * STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the wiring into shard_verifier.inl, a batch entry over the lock-step lanes. */
 size_t zkhip_fri16_lift_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
                                  uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
 int zkhip_fri16_lift_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
@@ -493,6 +492,39 @@ int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int 
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
 int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
                                    size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len);
+
+/* ---- the JOIN of fold-16 lift proofs: N lift proofs of one shape -> ONE proof (RISC Zero: segments -> lift -> join) ----
+ * A lift proof is a version-11 proof of the thirteen-table lift machine and the lift key depends on the shape alone, so N lift proofs of one shape are N proofs of ONE
+ * keyed machine: machine mode (zkhip.h: zkhip_prove_machine_verifier) verifies them in-circuit.  These entries are a SHAPE CALL over it: each puts the
+ * zkhip_machine_desc together -- the lift machine's programs and tables as zkhip_fri16_lift_describe gives them (positions 0 .. 12), zkhip_fri16_lift_key_host's key
+ * as key_root, lift_prm's queries and proof-of-work bits, n_inner_public public values -- and calls the function behind the generic entry: the key, the size and the
+ * bytes are zkhip_machine_verifier_key_host's, _proof_size's and zkhip_prove_machine_verifier's on that description.  Shape arguments: zkhip_fri16_lift_key's
+ * (R, F, log_blowup, n_queries, inner_hash_width, inner_pow_bits, trace_width, n_inner_public); lift_prm: the outer parameters the lift proofs were made under;
+ * join_prm: the join's own.  public_values: n_proofs x n_inner_public words in proof order (n_public_total says how many; any other count is refused).
+ * zkhip_fri16_join_max_proofs: the most lift proofs of this shape one join takes (machine mode's bounds: 64 proofs, n_proofs x terms <= 2^22, 2^22 Poseidon2 rows);
+ * 0 (zkhip_last_error) for a shape the lift refuses.  n_proofs 0 or above it is refused by every entry with a message that names the bound; inner hash width 16
+ * with the lift's own message.
+ * zkhip_verify_fri16_join is host only and takes (shape, public values, key): no byte of a lift or segment proof.
+ * zkhip_prove_fri16_join_segments: segment proofs in, ONE proof out -- the lift proofs are made one after the other on ctx (zkhip_prove_fri16_lift_segment under
+ * lift_key), then joined under join_key.  A segment that does not verify fails with the host verifier's code and a message that names the segment.
+ * STILL OUTSIDE: a tree above the join for more than 64 segments, a lift batch over the lock-step lanes. */
+int zkhip_fri16_join_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, uint32_t vk[8]);
+int zkhip_fri16_join_setup(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                           uint32_t n_inner_public, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_join_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                   const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm);
+size_t zkhip_fri16_join_max_proofs(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                   const zkhip_params* lift_prm);
+int zkhip_prove_fri16_join(zkhip_ctx* ctx, const zkhip_machine_key* key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs, const size_t* lens, size_t n_proofs,
+                           const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len);
+int zkhip_verify_fri16_join(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                            const zkhip_params* lift_prm, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total, size_t n_proofs,
+                            const uint32_t vk[8], const zkhip_params* join_prm, int* reason);
+int zkhip_prove_fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key, const zkhip_machine_key* join_key, const uint8_t* const* segment_proofs,
+                                    const size_t* lens, size_t n_proofs, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public_total,
+                                    const zkhip_params* inner_prm, const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */
@@ -516,6 +548,15 @@ size_t zkhip_machine_verifier_describe(const zkhip_machine_desc* inner, size_t n
                                        uint32_t* pre_width);
 size_t zkhip_machine_verifier_host_tables(const zkhip_machine_desc* inner, const uint8_t* const* proofs, const size_t* proof_lens, size_t n_proofs, const uint32_t* public_values,
                                           size_t n_public, int which, uint32_t* out, size_t cap);
+/* machine mode's EVAL rows on the device (mrec_eval_rows_kernel) alone, one launch, for the row tests: n_terms raw terms chip by chip (chips[i] < n_chips
+ * non-decreasing, canonical coeffs[i], keys[3 i .. 3 i + 2] < kspan, firsts[i] 0 / 1), per proof a value table values[p][kspan][4] and alpha alphas[p][4]
+ * (canonical).  Key 0 is the extension one (the table's entry 0 is not read); keys 1 .. n_stream are read the way a proof's opened-value stream is (canonical words,
+ * Montgomery form made in the kernel), the keys behind them the way the public values and selectors are (the call's small block).  Out, canonical: rows
+ * [n_proofs n_terms][32] = F0 F1 F2 | M | TV | ACCIN | ACCO | ALPHA per term, accs [n_proofs n_chips][4] = ACCO of every (proof, chip)'s last term (zero: none).
+ * A device word of P or more is ZKHIP_ERR_INTERNAL. */
+int zkhip_machine_verifier_gen_eval_rows(zkhip_ctx* ctx, size_t n_terms, const uint32_t* chips, const uint32_t* coeffs, const uint32_t* keys, const uint32_t* firsts,
+                                         size_t n_chips, size_t n_proofs, size_t kspan, size_t n_stream, const uint32_t* values, const uint32_t* alphas, uint32_t* rows,
+                                         uint32_t* accs);
 int zkhip_ntt_pass(zkhip_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, size_t ld, int log_n,
                    uint32_t width, int which);
 int zkhip_last_prove_debug(zkhip_ctx* ctx, zkhip_prove_debug* out);
@@ -525,7 +566,8 @@ double zkhip_host_permutation_ns(int form);
 void zkhip_lockstep_stats(uint64_t out[6]);
 uint64_t zkhip_lockstep_stack_high_water(void);
 /* Where the recursion machines (zkhip_prove_shard_verifier[_air], zkhip_prove_machine_verifier, zkhip_prove_shard_tree) make their per-query witness tables -- ROWSUM,
- * QUERY, the fold rows, the queries' Poseidon2 rows: 0 (default) = device kernels over the inner proofs' words (round 6), 1 = the host's walk of rounds 4 - 5 (the same tables
+ * QUERY, the fold rows, the queries' Poseidon2 rows -- and machine mode its EVAL rows where that table has 2^15 rows or more (below, the host fills them under either
+ * setting: the kernel's fixed cost is then more than the upload it saves): 0 (default) = device kernels over the inner proofs' words (round 6), 1 = the host's walk of rounds 4 - 5 (the same tables
  * word for word: the fallback, and what tests/test_gpu_recursion_machine.py compares the kernels with).  Process-wide; returns the previous setting. */
 int zkhip_recursion_witnesses_on_host(int enable);
 

@@ -206,6 +206,26 @@ extern "C" {
     pub fn zkhip_shard_verifier_describe_air(program: *const u32, program_words: usize, log_n: c_int, width: u32, n_queries: usize, inner_pow_bits: c_int, n_public: usize,
                                              n_proofs: usize, which: c_int, kind: c_int, out: *mut u32, cap_words: usize, log_rows: *mut c_int, main_width: *mut u32,
                                              pre_width: *mut u32) -> usize;
+    /// RISC Zero's lift -> join (prover.rs:88-93): a segment proof -> a lift proof under the SHAPE's key, N lift proofs of one shape -> ONE proof (machine mode over
+    /// the lift machine).  Shape arguments: layers, log_final, log_blowup, queries, the segments' hash width (24), their grinding bits, trace width, public values.
+    pub fn zkhip_fri16_lift_key(ctx: *mut ZkhipCtx, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                n_inner_public: u32, prm: *const ZkhipParams, key: *mut *mut ZkhipMachineKey, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_join_setup(ctx: *mut ZkhipCtx, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                  n_inner_public: u32, lift_prm: *const ZkhipParams, n_proofs: usize, join_prm: *const ZkhipParams, key: *mut *mut ZkhipMachineKey,
+                                  vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_join_key_host(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                     n_inner_public: u32, lift_prm: *const ZkhipParams, n_proofs: usize, join_prm: *const ZkhipParams, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_join_proof_size(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                       n_inner_public: u32, lift_prm: *const ZkhipParams, n_proofs: usize, join_prm: *const ZkhipParams) -> usize;
+    pub fn zkhip_fri16_join_max_proofs(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                       n_inner_public: u32, lift_prm: *const ZkhipParams) -> usize;
+    pub fn zkhip_prove_fri16_join_segments(ctx: *mut ZkhipCtx, lift_key: *const ZkhipMachineKey, join_key: *const ZkhipMachineKey, segment_proofs: *const *const u8,
+                                           lens: *const usize, n_proofs: usize, log_n: c_int, width: u32, public_values: *const u32, n_public_total: usize,
+                                           inner_prm: *const ZkhipParams, lift_prm: *const ZkhipParams, join_prm: *const ZkhipParams, out: *mut u8, cap: usize,
+                                           len: *mut usize) -> c_int;
+    pub fn zkhip_verify_fri16_join(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                   n_inner_public: u32, lift_prm: *const ZkhipParams, proof: *const u8, len: usize, public_values: *const u32, n_public_total: usize,
+                                   n_proofs: usize, vk: *const u32, join_prm: *const ZkhipParams, reason: *mut c_int) -> c_int;
     pub fn zkhip_shard_verifier_max_proofs(log_n: c_int, width: u32, n_queries: usize, inner_pow_bits: c_int, n_public: usize, outer: *const ZkhipParams) -> usize;
     pub fn zkhip_prove_shard_verifier(ctx: *mut ZkhipCtx, key: *const ZkhipMachineKey, shard_proofs: *const *const u8, shard_proof_lens: *const usize, n_proofs: usize,
                                       log_n: c_int, width: u32, public_values: *const u32, n_public: usize, inner: *const ZkhipParams, outer: *const ZkhipParams,

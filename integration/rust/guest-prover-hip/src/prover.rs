@@ -460,6 +460,60 @@ pub fn verify_compressed(proof: &[u8], log_n: i32, width: u32, public_values: &[
     }, "zkhip_verify_shard_recursive")
 }
 
+/// The lift shape of RISC Zero-shape segment proofs over 2^log_n rows: (layers, log_final, log_blowup, queries, hash width, grinding bits), or an error where
+/// the parameters are not a fold-by-16 shape with a committed layer.
+fn segment_lift_shape(log_n: i32, inner: &ZkhipParams) -> Result<(i32, i32, i32, usize, i32, i32)> {
+    anyhow::ensure!(inner.log_fold == 4 && log_n > inner.log_final && (log_n - inner.log_final) % 4 == 0, "join_segments: not a fold-by-16 segment shape");
+    Ok(((log_n - inner.log_final) / 4, inner.log_final, inner.log_blowup, inner.num_queries as usize, inner.hash_width, inner.pow_bits))
+}
+
+/// RISC Zero's compress stage (prover.rs:88-93: segments -> lift -> join; the C++ mirror's `Risc0HipGuestProver::with_compress`): every segment proof lifted under the
+/// shape's key, the lift proofs joined into ONE proof.  `public_values`: `n_public` per segment, in segment order.  More segments than
+/// `zkhip_fri16_join_max_proofs` are refused (a tree above the join is not built).  Returns the joined proof and the join's key; `verify_joined_segments` then needs
+/// no byte of a segment or lift proof.
+pub fn join_segments(ctx: &Context, proofs: &[Vec<u8>], log_n: i32, width: u32, public_values: &[u32], n_public: usize, inner: &ZkhipParams, lift: &ZkhipParams,
+                     join: &ZkhipParams) -> Result<(Vec<u8>, [u32; 8])> {
+    anyhow::ensure!(!proofs.is_empty() && public_values.len() == proofs.len() * n_public, "join_segments: one public-value list per segment");
+    let (r, f, b, q, hw, pb) = segment_lift_shape(log_n, inner)?;
+    let n = proofs.len();
+    let most = unsafe { ffi::zkhip_fri16_join_max_proofs(r, f, b, q, hw, pb, width, n_public as u32, lift) };
+    anyhow::ensure!(most > 0, "join_segments: the lift does not take this shape");
+    anyhow::ensure!(n <= most, "join_segments: {} segments, one join takes at most {} (a tree above the join is not built)", n, most);
+    let (mut lift_key, mut join_key): (*mut ffi::ZkhipMachineKey, *mut ffi::ZkhipMachineKey) = (std::ptr::null_mut(), std::ptr::null_mut());
+    let (mut lift_vk, mut vk) = ([0u32; 8], [0u32; 8]);
+    check(unsafe { ffi::zkhip_fri16_lift_key(ctx.raw(), r, f, b, q, hw, pb, width, n_public as u32, lift, &mut lift_key, lift_vk.as_mut_ptr()) }, "zkhip_fri16_lift_key")?;
+    let rc = unsafe { ffi::zkhip_fri16_join_setup(ctx.raw(), r, f, b, q, hw, pb, width, n_public as u32, lift, n, join, &mut join_key, vk.as_mut_ptr()) };
+    if rc != 0 {
+        unsafe { ffi::zkhip_machine_key_destroy(lift_key) };
+        check(rc, "zkhip_fri16_join_setup")?;
+    }
+    let cap = unsafe { ffi::zkhip_fri16_join_proof_size(r, f, b, q, hw, pb, width, n_public as u32, lift, n, join) };
+    let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut out = vec![0u8; cap];
+    let mut len = 0usize;
+    let rc = unsafe {
+        ffi::zkhip_prove_fri16_join_segments(ctx.raw(), lift_key, join_key, ptrs.as_ptr(), lens.as_ptr(), n, log_n, width, public_values.as_ptr(), public_values.len(), inner, lift,
+                                             join, out.as_mut_ptr(), cap, &mut len)
+    };
+    unsafe { ffi::zkhip_machine_key_destroy(lift_key); ffi::zkhip_machine_key_destroy(join_key) };
+    check(rc, "zkhip_prove_fri16_join_segments")?;
+    out.truncate(len);
+    verify_joined_segments(&out, log_n, width, public_values, n_public, n, &vk, inner, lift, join)?;      // sp1.rs:120: the prover checks its own proof
+    Ok((out, vk))
+}
+
+/// Host-only check of `join_segments`' proof from (the segments' shape, their public values, the join's key -- `zkhip_fri16_join_key_host` derives it without a GPU).
+pub fn verify_joined_segments(proof: &[u8], log_n: i32, width: u32, public_values: &[u32], n_public: usize, n_proofs: usize, vk: &[u32; 8], inner: &ZkhipParams,
+                              lift: &ZkhipParams, join: &ZkhipParams) -> Result<()> {
+    let (r, f, b, q, hw, pb) = segment_lift_shape(log_n, inner)?;
+    let mut reason = 0;
+    check(unsafe {
+        ffi::zkhip_verify_fri16_join(r, f, b, q, hw, pb, width, n_public as u32, lift, proof.as_ptr(), proof.len(), public_values.as_ptr(), public_values.len(), n_proofs,
+                                     vk.as_ptr(), join, &mut reason)
+    }, "zkhip_verify_fri16_join")
+}
+
 
 // ---- shards in SP1's shard STRUCTURE (the C++ mirror's MachinePlan, zktls_amd/host/guest_prover_hip.hpp): chips of mixed heights, LogUp pairs inside and
 // across tables, preprocessed columns committed by setup -- every shard ONE keyed-machine proof (version 11), the compress stage in machine mode ----

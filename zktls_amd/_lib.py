@@ -65,6 +65,8 @@ EXPORTS = [
     "zkhip_prove_fri16_identity", "zkhip_verify_fri16_identity",
     "zkhip_fri16_lift_describe", "zkhip_fri16_lift_key_host", "zkhip_fri16_lift_key", "zkhip_fri16_lift_proof_size", "zkhip_fri16_lift_gen_tables",
     "zkhip_prove_fri16_lift", "zkhip_verify_fri16_lift", "zkhip_prove_fri16_lift_segment",
+    "zkhip_fri16_join_key_host", "zkhip_fri16_join_setup", "zkhip_fri16_join_proof_size", "zkhip_fri16_join_max_proofs", "zkhip_prove_fri16_join", "zkhip_verify_fri16_join",
+    "zkhip_prove_fri16_join_segments", "zkhip_machine_verifier_gen_eval_rows",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -447,6 +449,20 @@ def load():
     L.zkhip_verify_fri16_lift.argtypes = L.zkhip_verify_fri16_head.argtypes
     L.zkhip_prove_fri16_lift_segment.argtypes = [C.c_void_p, C.c_void_p, u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(Params), u8p,
                                                  C.c_size_t, C.POINTER(C.c_size_t)]
+    # the join of fold-16 lift proofs (machine mode over the lift machine of a shape): the lift key's shape arguments, the lift's outer parameters, n_proofs, the join's
+    fri16_jshape = fri16_hshape + [C.POINTER(Params)]
+    L.zkhip_fri16_join_key_host.argtypes = fri16_jshape + [C.c_size_t, C.POINTER(Params), u32p]
+    L.zkhip_fri16_join_setup.argtypes = [C.c_void_p] + fri16_jshape + [C.c_size_t, C.POINTER(Params), C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_join_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_join_proof_size.argtypes = fri16_jshape + [C.c_size_t, C.POINTER(Params)]
+    L.zkhip_fri16_join_max_proofs.restype = C.c_size_t
+    L.zkhip_fri16_join_max_proofs.argtypes = fri16_jshape
+    L.zkhip_prove_fri16_join.argtypes = [C.c_void_p, C.c_void_p] + fri16_jshape + [C.POINTER(u8p), szp, C.c_size_t, u32p, C.c_size_t, C.POINTER(Params), u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16_join.argtypes = fri16_jshape + [u8p, C.c_size_t, u32p, C.c_size_t, C.c_size_t, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
+    L.zkhip_prove_fri16_join_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(u8p), szp, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params),
+                                                  C.POINTER(Params), C.POINTER(Params), u8p, C.c_size_t, szp]
+    # machine mode's EVAL row kernel alone (the row tests)
+    L.zkhip_machine_verifier_gen_eval_rows.argtypes = [C.c_void_p, C.c_size_t, u32p, u32p, u32p, u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p, u32p, u32p, u32p]
     L.zkhip_sha256_air_chained.restype = C.c_size_t
     L.zkhip_sha256_air_chained.argtypes = [u32p, C.c_size_t]
     L.zkhip_sha256_gen_trace_chained.argtypes = [C.c_void_p, u32p, u8p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, u32p]

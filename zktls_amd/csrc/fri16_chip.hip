@@ -50,6 +50,8 @@
 //                                          (fri16_lift_tables_kernel) and pinned by the transcript chain alone.  The key is a function of the shape and the public-value
 //                                          count: ONE key per shape states "some valid segment proof of this shape with these public values exists" -- RISC Zero's lift.
 //                                          zkhip_prove_fri16_lift_segment is the call from segment proof to lift proof (tests/fri16_lift_air.py)
+//   JOIN     (zkhip_prove_fri16_join)      no machine of this file: N lift proofs of one shape are N proofs of ONE keyed machine, which machine mode
+//                                          (machine_verifier.inl) verifies in-circuit.  The entries at the end of the file describe the lift machine to it
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
 // table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
 // to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
@@ -971,7 +973,7 @@ int build_identity_key_tables(const Shape& s, const uint32_t* final_poly, const 
 // column, not a moved word.  Every multiplicity that gates a tuple with a moved word is preprocessed or constrained (DESIGN.md 3c has the table), and Fiat-Shamir pins
 // the values: the chain starts from zero and absorbs every root and coefficient over a bus.  So the key is a function of the SHAPE and NP alone: it states "some valid
 // segment proof of this shape with THESE public values exists".
-// STILL OUTSIDE: the join of several lift proofs and the r0 host mirror's compress path, lookups, version-7 and version-8 inner proofs, the wiring into
+// (The JOIN of several lift proofs is at the end of this file: a shape call over machine mode.)  STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the wiring into
 // shard_verifier.inl, a batch entry.  tests/fri16_lift_air.py writes it again.
 int build_lift_key_tables(const Shape& s, std::vector<uint32_t> pre[], const char* who) {
     const std::vector<uint32_t> no_coeffs((size_t)4 << s.F, 0u), no_roots(8 * (size_t)s.R, 0u);
@@ -2317,8 +2319,11 @@ int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int 
 
 // segment proof in, lift proof out: ONE pass of the host verifier with every fold-16 view sink attached (verifier.cpp: fri16_view_all -- it fails with the verifier's
 // code and message when the inner proof does not verify, and with the views' messages on a form they do not take), then the lift prover on what it left
-int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
-                                   size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len) {
+}  // extern "C"
+
+// (the body of zkhip_prove_fri16_lift_segment: the join's one-call entry makes its lift proofs with it)
+static int fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
+                              size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len) {
     CHECK_CTX(ctx);
     if (!key || !proof || !public_values || !inner_prm || !outer_prm || !out || !out_len) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: null argument");
     if (n_public > fri16::MAX_NP) return fail(ZKHIP_ERR_INVALID, "prove_fri16_lift_segment: more than 30 inner public values");
@@ -2330,5 +2335,203 @@ int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key,
     return fri16_prove({fri16::LIFT, f.R, f.F, inner_prm->log_blowup, (size_t)inner_prm->num_queries, inner_prm->pow_bits, width, (uint32_t)n_public}, "prove_fri16_lift", ctx, key,
                        v, outer_prm, out, cap, out_len);
 }
+
+// ---------------------------------------------------------------- JOIN: N lift proofs of one shape -> one proof
+// A lift proof is a version-11 proof of the thirteen-table lift machine, and the lift key depends on the shape alone: N lift proofs of one shape are N proofs of ONE keyed
+// machine, which machine mode (machine_verifier.inl) verifies in-circuit.  The entries below are a SHAPE CALL: they put the zkhip_machine_desc together from what
+// zkhip_fri16_lift_describe reads (the machine's programs and tables in machine order, the shape's key as key_root, the lift's queries and proof-of-work bits) and hand it
+// to the function behind the generic entry of the same name -- no second prover, the same bytes.
+namespace zk {
+namespace mrec {      // (machine_verifier.inl: the bodies of the zkhip_*machine_verifier* entries)
+int m_machine_verifier_setup(zkhip_ctx* ctx, const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, zkhip_machine_key** key, uint32_t vk[8]);
+int m_machine_verifier_key_host(const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, uint32_t vk[8]);
+size_t m_machine_verifier_proof_size(const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer);
+size_t m_machine_verifier_max_proofs(const zkhip_machine_desc* inner);
+int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const zkhip_machine_desc* inner, const uint8_t* const* proofs, const size_t* proof_lens, size_t n_proofs,
+                             const uint32_t* public_values, size_t n_public, const zkhip_params* outer, uint8_t* proof, size_t cap, size_t* len);
+int m_verify_machine_recursive(const zkhip_machine_desc* inner, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public, size_t n_proofs, const uint32_t vk[8],
+                               const zkhip_params* outer, int* reason);
+}  // namespace mrec
+}  // namespace zk
+
+namespace {
+struct JoinDesc { std::shared_ptr<const fri16::Machine> m; zkhip_machine_desc d; };      // (d points into m)
+// the shape's key is a host commitment of the thirteen tables' preprocessed columns, and every entry of a prove / verify pair asks for it again: kept per (shape, lift
+// parameters, Poseidon2 table set)
+std::mutex g_join_mu;
+std::map<std::array<uint64_t, 16>, std::array<uint32_t, 8>> g_join_roots;
+// the lift machine of a shape as machine mode takes it
+int fri16_join_desc(const fri16::ShapeArgs& a, int inner_hash_width, const zkhip_params* lift_prm, const char* who, JoinDesc& j) {
+    if (!lift_prm) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(a, s));
+    ZK_TRY(fri16::check_hash_width(inner_hash_width, who));
+    j.m = fri16::machine_of(s);
+    const keyed::KeyedMachine& km = j.m->km;
+    j.d = zkhip_machine_desc{};
+    j.d.n_chips = km.n; j.d.log_ns = km.log_ns; j.d.widths = km.widths; j.d.pre_widths = km.pre_widths;
+    j.d.programs = km.progs; j.d.program_words = km.prog_words; j.d.tables = km.tabs; j.d.table_words = km.tab_words;
+    j.d.num_queries = lift_prm->num_queries; j.d.pow_bits = lift_prm->pow_bits; j.d.n_public = a.NP;
+    const std::array<uint64_t, 16> id{(uint64_t)a.R, (uint64_t)a.F, (uint64_t)a.b, (uint64_t)a.Q, (uint64_t)a.pow_bits, (uint64_t)a.W, (uint64_t)a.NP,
+                                      (uint64_t)lift_prm->log_blowup, (uint64_t)lift_prm->num_queries, (uint64_t)lift_prm->pow_bits, (uint64_t)lift_prm->logup_pairs,
+                                      (uint64_t)lift_prm->log_fold, (uint64_t)lift_prm->log_final, (uint64_t)lift_prm->hash_width, (uint64_t)lift_prm->code_width,
+                                      zk::g_p2_generation.load()};
+    {
+        std::lock_guard<std::mutex> lk(g_join_mu);
+        const auto it = g_join_roots.find(id);
+        if (it != g_join_roots.end()) { std::memcpy(j.d.key_root, it->second.data(), 32); return ZKHIP_OK; }
+    }
+    fri16::View v;
+    v.hash_width = inner_hash_width;
+    ZK_TRY(fri16_key(a, who, nullptr, v, lift_prm, nullptr, j.d.key_root));
+    std::array<uint32_t, 8> root;
+    std::memcpy(root.data(), j.d.key_root, 32);
+    std::lock_guard<std::mutex> lk(g_join_mu);
+    if (g_join_roots.size() > 16) g_join_roots.clear();
+    g_join_roots.emplace(id, root);
+    return ZKHIP_OK;
+}
+// machine mode refused (rc, its message in zkhip_last_error): where n_proofs is what it did not take, the message names the bound -- found only now, on the way out, so
+// that a call that goes through builds the machine's shape once
+int fri16_join_refused(const JoinDesc& j, size_t n_proofs, const char* who, int rc) {
+    const std::string why = zkhip_last_error();
+    const size_t most = zk::mrec::m_machine_verifier_max_proofs(&j.d);
+    if (most && (n_proofs < 1 || n_proofs > most))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": 1 .. " + std::to_string(most) + " lift proofs of this shape go into one join, not " + std::to_string(n_proofs));
+    return fail(rc, why);
+}
+int fri16_join_check_public(const JoinDesc& j, size_t n_proofs, const uint32_t* public_values, size_t n_public_total, const char* who) {
+    if (!public_values || n_public_total != n_proofs * (size_t)j.d.n_public)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": public_values holds n_proofs x n_inner_public words in proof order (" + std::to_string(n_proofs * (size_t)j.d.n_public) +
+                                       " here), not " + std::to_string(n_public_total));
+    return ZKHIP_OK;
+}
+}  // namespace
+
+#define FRI16_JOIN_GUARD(expr, on_error)                                                                                     \
+    try { return expr; }                                                                                                     \
+    catch (const std::bad_alloc&) { (void)fail(ZKHIP_ERR_NOMEM, "fri16 join: out of host memory"); return on_error; }        \
+    catch (const std::exception& e) { (void)fail(ZKHIP_ERR_INTERNAL, std::string("fri16 join: ") + e.what()); return on_error; }
+
+static int fri16_join_key_host(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, uint32_t vk[8]) {
+    JoinDesc j;
+    ZK_TRY(fri16_join_desc(a, hw, lift_prm, "fri16_join_key_host", j));
+    const int rc = zk::mrec::m_machine_verifier_key_host(&j.d, n_proofs, join_prm, vk);
+    return rc == ZKHIP_ERR_INVALID ? fri16_join_refused(j, n_proofs, "fri16_join_key_host", rc) : rc;
+}
+static int fri16_join_setup(zkhip_ctx* ctx, const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, zkhip_machine_key** key,
+                            uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    JoinDesc j;
+    ZK_TRY(fri16_join_desc(a, hw, lift_prm, "fri16_join_setup", j));
+    const int rc = zk::mrec::m_machine_verifier_setup(ctx, &j.d, n_proofs, join_prm, key, vk);
+    return rc == ZKHIP_ERR_INVALID ? fri16_join_refused(j, n_proofs, "fri16_join_setup", rc) : rc;
+}
+static size_t fri16_join_proof_size(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm) {
+    JoinDesc j;
+    if (fri16_join_desc(a, hw, lift_prm, "fri16_join_proof_size", j) != ZKHIP_OK) return 0;
+    const size_t size = zk::mrec::m_machine_verifier_proof_size(&j.d, n_proofs, join_prm);
+    if (!size) (void)fri16_join_refused(j, n_proofs, "fri16_join_proof_size", ZKHIP_ERR_INVALID);
+    return size;
+}
+static size_t fri16_join_max_proofs(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm) {
+    JoinDesc j;
+    if (fri16_join_desc(a, hw, lift_prm, "fri16_join_max_proofs", j) != ZKHIP_OK) return 0;
+    return zk::mrec::m_machine_verifier_max_proofs(&j.d);
+}
+static int fri16_join_prove_desc(zkhip_ctx* ctx, const zkhip_machine_key* key, const JoinDesc& j, const uint8_t* const* lift_proofs, const size_t* lens, size_t n_proofs,
+                                 const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
+    ZK_TRY(fri16_join_check_public(j, n_proofs, public_values, n_public_total, "prove_fri16_join"));
+    const int rc = zk::mrec::m_prove_machine_verifier(ctx, key, &j.d, lift_proofs, lens, n_proofs, public_values, j.d.n_public, join_prm, out, cap, len);
+    return rc == ZKHIP_ERR_INVALID ? fri16_join_refused(j, n_proofs, "prove_fri16_join", rc) : rc;
+}
+static int fri16_join_prove(zkhip_ctx* ctx, const zkhip_machine_key* key, const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs,
+                            const size_t* lens, size_t n_proofs, const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm, uint8_t* out, size_t cap,
+                            size_t* len) {
+    CHECK_CTX(ctx);
+    JoinDesc j;
+    ZK_TRY(fri16_join_desc(a, hw, lift_prm, "prove_fri16_join", j));
+    return fri16_join_prove_desc(ctx, key, j, lift_proofs, lens, n_proofs, public_values, n_public_total, join_prm, out, cap, len);
+}
+static int fri16_join_verify(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total,
+                             size_t n_proofs, const uint32_t vk[8], const zkhip_params* join_prm, int* reason) {
+    JoinDesc j;
+    int rc = fri16_join_desc(a, hw, lift_prm, "verify_fri16_join", j);
+    if (rc == ZKHIP_OK) rc = fri16_join_check_public(j, n_proofs, public_values, n_public_total, "verify_fri16_join");
+    if (rc != ZKHIP_OK) { if (reason) *reason = 1; return rc; }
+    int why = 0;
+    rc = zk::mrec::m_verify_machine_recursive(&j.d, proof, len, public_values, j.d.n_public, n_proofs, vk, join_prm, &why);
+    if (reason) *reason = why;
+    return rc != ZKHIP_OK && why == 1 ? fri16_join_refused(j, n_proofs, "verify_fri16_join", rc) : rc;      // (reason 1: the arguments, the number of proofs among them)
+}
+static int fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key, const zkhip_machine_key* join_key, const uint8_t* const* segment_proofs, const size_t* lens,
+                               size_t n_proofs, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public_total, const zkhip_params* inner_prm,
+                               const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
+    const char* who = "prove_fri16_join_segments";
+    CHECK_CTX(ctx);
+    if (!lift_key || !join_key || !segment_proofs || !lens || !public_values || !inner_prm || !lift_prm || !join_prm || !out || !len) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (n_proofs < 1 || n_public_total % n_proofs)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": at least one segment proof, and public_values with the same number of words for every segment, in segment order");
+    if (inner_prm->log_fold != 4 || log_n <= inner_prm->log_final || (log_n - inner_prm->log_final) % 4)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": inner_prm is not a fold-by-16 shape with a committed layer at this height");
+    const size_t n_public = n_public_total / n_proofs;
+    // every segment has one shape -- the layers inner_prm gives at this height --, so the join's description, the number of proofs it takes and a lift proof's size are
+    // known before the first segment is lifted
+    const fri16::ShapeArgs a{fri16::LIFT, (log_n - inner_prm->log_final) / 4, inner_prm->log_final, inner_prm->log_blowup, (size_t)inner_prm->num_queries, inner_prm->pow_bits, width,
+                             (uint32_t)n_public};
+    JoinDesc j;
+    ZK_TRY(fri16_join_desc(a, inner_prm->hash_width, lift_prm, who, j));
+    if (!zk::mrec::m_machine_verifier_proof_size(&j.d, n_proofs, join_prm)) return fri16_join_refused(j, n_proofs, who, ZKHIP_ERR_INVALID);
+    const size_t room = fri16::proof_size(a, lift_prm);
+    // the lift proofs, one after the other on ctx
+    std::vector<std::vector<uint8_t>> lifted(n_proofs);
+    std::vector<const uint8_t*> ptrs(n_proofs);
+    std::vector<size_t> lift_lens(n_proofs);
+    for (size_t i = 0; i < n_proofs; i++) {
+        if (!segment_proofs[i]) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+        lifted[i].resize(room);
+        const int rc = fri16_lift_segment(ctx, lift_key, segment_proofs[i], lens[i], log_n, width, public_values + i * n_public, n_public, inner_prm, lift_prm, lifted[i].data(),
+                                          room, &lift_lens[i]);
+        if (rc != ZKHIP_OK) return fail(rc, std::string(who) + ": segment " + std::to_string(i) + ": " + zkhip_last_error());
+        ptrs[i] = lifted[i].data();
+    }
+    return fri16_join_prove_desc(ctx, join_key, j, ptrs.data(), lift_lens.data(), n_proofs, public_values, n_public_total, join_prm, out, cap, len);
+}
+
+extern "C" {
+int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
+                                   size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len) {
+    return fri16_lift_segment(ctx, key, proof, len, log_n, width, public_values, n_public, inner_prm, outer_prm, out, cap, out_len);
+}
+
+#define FRI16_JOIN_SHAPE int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public
+#define FRI16_JOIN_ARGS fri16::ShapeArgs{fri16::LIFT, R, F, log_blowup, n_queries, inner_pow_bits, trace_width, n_inner_public}, inner_hash_width
+int zkhip_fri16_join_key_host(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, uint32_t vk[8]) {
+    FRI16_JOIN_GUARD(fri16_join_key_host(FRI16_JOIN_ARGS, lift_prm, n_proofs, join_prm, vk), ZKHIP_ERR_NOMEM)
+}
+int zkhip_fri16_join_setup(zkhip_ctx* ctx, FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    FRI16_JOIN_GUARD(fri16_join_setup(ctx, FRI16_JOIN_ARGS, lift_prm, n_proofs, join_prm, key, vk), ZKHIP_ERR_NOMEM)
+}
+size_t zkhip_fri16_join_proof_size(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm) {
+    FRI16_JOIN_GUARD(fri16_join_proof_size(FRI16_JOIN_ARGS, lift_prm, n_proofs, join_prm), 0)
+}
+size_t zkhip_fri16_join_max_proofs(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm) { FRI16_JOIN_GUARD(fri16_join_max_proofs(FRI16_JOIN_ARGS, lift_prm), 0) }
+int zkhip_prove_fri16_join(zkhip_ctx* ctx, const zkhip_machine_key* key, FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs, const size_t* lens,
+                           size_t n_proofs, const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
+    FRI16_JOIN_GUARD(fri16_join_prove(ctx, key, FRI16_JOIN_ARGS, lift_prm, lift_proofs, lens, n_proofs, public_values, n_public_total, join_prm, out, cap, len), ZKHIP_ERR_NOMEM)
+}
+int zkhip_verify_fri16_join(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total, size_t n_proofs,
+                            const uint32_t vk[8], const zkhip_params* join_prm, int* reason) {
+    FRI16_JOIN_GUARD(fri16_join_verify(FRI16_JOIN_ARGS, lift_prm, proof, len, public_values, n_public_total, n_proofs, vk, join_prm, reason), ZKHIP_ERR_NOMEM)
+}
+int zkhip_prove_fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key, const zkhip_machine_key* join_key, const uint8_t* const* segment_proofs, const size_t* lens,
+                                    size_t n_proofs, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public_total, const zkhip_params* inner_prm,
+                                    const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
+    FRI16_JOIN_GUARD(fri16_join_segments(ctx, lift_key, join_key, segment_proofs, lens, n_proofs, log_n, width, public_values, n_public_total, inner_prm, lift_prm, join_prm, out, cap,
+                                         len), ZKHIP_ERR_NOMEM)
+}
+#undef FRI16_JOIN_SHAPE
+#undef FRI16_JOIN_ARGS
+#undef FRI16_JOIN_GUARD
 
 }  // extern "C"

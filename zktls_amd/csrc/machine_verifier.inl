@@ -1076,8 +1076,18 @@ struct WitPlan {
     int32_t inj_hi[32];                     // layer -> index in sh.hs of the height that joins there, -1: none
     uint32_t fri_off = 0;                   // a query's first FRI word relative to its first word
     int32_t c0[32];                         // per height index: the first chip of that height (whose zeta g the QUERY row takes)
+    bool eval_rows = false;                 // EVAL's rows are the device's too (mrec_eval_rows_kernel): from EVAL_DEVICE_MIN_ROWS rows on, see there
 };
-struct DevVals { std::vector<uint32_t> v; };    // [indices Q][betas 4 R][fa 4][zeta 4][per height: znx 4, yz 4, yn 4][pw 4 each], Montgomery except the indices
+struct DevVals {
+    std::vector<uint32_t> v;        // [indices Q][betas 4 R][fa 4][zeta 4][per height: znx 4, yz 4, yn 4][pw 4 each], Montgomery except the indices
+    std::vector<uint32_t> ev;       // what mrec_eval_rows_kernel reads beside the proof's words: [alpha 4][public values, 4 words each][per chip: the three selectors], Montgomery
+    std::vector<uint32_t> acc;      // [C][4]: every chip's EVAL accumulator as the host's pass leaves it (the kernel's hand-back is compared with it)
+};
+// EVAL's rows are made on the device when the table has at least this many (NP x terms).  The kernel replaces 128 bytes of upload and a row's writes per term, and costs a
+// launch, a tail memset, the term plan's upload and a wider read-back whatever the table's size: +0.26 ms on a join of sixteen headline shard proofs under the tree's top
+// (a few thousand terms) when it ran there, while on a join of four lift proofs (2^18 rows) 0.33 ms of kernel stand for 0.7 - 2.2 ms of upload.  At
+// 2^15 rows the table is 4 MB, whose upload alone is about what the fixed part costs
+constexpr size_t EVAL_DEVICE_MIN_ROWS = (size_t)1 << 15;
 inline size_t dv_words(const MShape& sh, const WitPlan& pl) { return (size_t)sh.Q + 4 * (size_t)sh.R + 8 + 12 * sh.hs.size() + 4 * pl.pw_keys.size(); }
 WitPlan build_wit_plan(const MShape& sh) {
     WitPlan pl;
@@ -1150,6 +1160,7 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
                const Transcript* pre = nullptr) {
     const MShape& sh = m.sh;
     const bool on_device = dplan != nullptr;               // the per-query tables (ROWSUM, QUERY, FOLD, the queries' Poseidon2 rows) are the device's: see top_finish
+    const bool eval_on_device = on_device && dplan->eval_rows;
     const int C = sh.C, Q = sh.Q, R = sh.R, H = sh.H;
     auto bad = [&](const char* what) { return fail(ZKHIP_ERR_VERIFY, std::string("prove_machine_verifier: proof ") + std::to_string(p) + " rejected: " + what); };
     Wit wt;
@@ -1271,18 +1282,31 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
     // ---- EVAL
     std::vector<Ext> acc_eval((size_t)C);
     {
+        // (device mode: the rows are mrec_eval_rows_kernel's; the pass stays, without a row written -- LOGUP's rows go on from its accumulators, and a chip whose
+        // constraints do not meet its quotient is refused below, before anything is proven)
         const size_t nt = sh.terms.size();
         Ext run = ext_zero();
         for (size_t i = 0; i < nt; i++) {
             const ETerm& e = sh.terms[i];
-            uint32_t* r = ht.evl.data() + (size_t)EV_MAIN * ((size_t)p * nt + i);
             if (i == sh.term0[e.chip]) run = ext_zero();
             const Ext f0 = value_of(e.key[0]), f1 = value_of(e.key[1]), f2 = value_of(e.key[2]);
             const Ext mm = ext_mul(f0, f1), tv = ext_mul_base(ext_mul(mm, f2), to_monty(e.coeff));
-            put_ext(r, EV_F0, f0); put_ext(r, EV_F0 + 4, f1); put_ext(r, EV_F0 + 8, f2); put_ext(r, EV_M, mm); put_ext(r, EV_TV, tv); put_ext(r, EV_ACCIN, run);
+            const Ext in = run;
             run = ext_add(e.first ? ext_mul(run, wt.alpha) : run, tv);
-            put_ext(r, EV_ACCO, run); put_ext(r, EV_ALPHA, wt.alpha);
             acc_eval[(size_t)e.chip] = run;
+            if (eval_on_device) continue;
+            uint32_t* r = ht.evl.data() + (size_t)EV_MAIN * ((size_t)p * nt + i);
+            put_ext(r, EV_F0, f0); put_ext(r, EV_F0 + 4, f1); put_ext(r, EV_F0 + 8, f2); put_ext(r, EV_M, mm); put_ext(r, EV_TV, tv); put_ext(r, EV_ACCIN, in);
+            put_ext(r, EV_ACCO, run); put_ext(r, EV_ALPHA, wt.alpha);
+        }
+        if (eval_on_device) {
+            std::vector<uint32_t>& ev = dvals->ev;
+            ev.clear();
+            auto pute = [&](const Ext& e) { ev.insert(ev.end(), e.c, e.c + 4); };
+            pute(wt.alpha);
+            for (uint32_t k = sh.NV + 1; k < sh.KSPAN; k++) pute(value_of(k));
+            dvals->acc.clear();
+            for (int ch = 0; ch < C; ch++) dvals->acc.insert(dvals->acc.end(), acc_eval[(size_t)ch].c, acc_eval[(size_t)ch].c + 4);
         }
     }
     sec("eval");
@@ -1841,6 +1865,97 @@ __global__ void __launch_bounds__(256) mrec_fold_pad_kernel(uint32_t* fold, uint
     if (r < rows) fold[(uint64_t)fw * r + frichip::T] = MONTY_R1;
 }
 
+
+// ---- EVAL's rows on the device: what fill_proof's EVAL section writes on the host, word for word.  One workgroup of 256 lanes per (proof, chip), the chip's terms 256
+// at a time, a lane per term: three values by key (the extension one; the opened-value stream, read from the proof's words; the public values and the chips' selectors
+// from the call's small block), M = F0 F1, TV = coeff M F2.  The running value is run <- (first ? run alpha : run) + TV: an inclusive scan of the affine maps
+// x -> a x + b with (a, b) = (first ? alpha : 1, TV), composition (a1, b1) then (a2, b2) = (a1 a2, b1 a2 + b2) -- over the wavefront by cross-lane moves, over the four
+// wavefronts through LDS, and the chunk's last value goes forward in registers.  No workgroup waits for another.  The arithmetic is exact, so the words do not depend on
+// how the maps are grouped.  Each lane stores its own 128-byte row as eight 16-byte stores.  acc receives ACCO of every (proof, chip)'s last term (zero: no term).
+struct EvalArgs {
+    const uint32_t* stream; uint64_t stream_stride;     // per proof: the value of key k in 1 .. NV at stream[4 (k - 1)], canonical words
+    const uint32_t* extra; uint32_t extra_stride;       // per proof: [alpha 4][the value of key NV + 1 + i at 4 + 4 i], Montgomery
+    const uint4* terms;                                 // per term: (key 0 | first << 31, key 1, key 2, coefficient (Montgomery))
+    const uint32_t* t0;                                 // chip c's terms: [t0[c], t0[c + 1])
+    uint32_t NV, C, n_terms;
+    uint32_t* rows;                                     // [NP n_terms][EV_MAIN]
+    uint32_t* acc;                                      // [NP C][4]
+};
+struct EvalMap { Ext a, b; };
+__device__ __forceinline__ EvalMap eval_then(const EvalMap& f, const EvalMap& g) { return EvalMap{ext_mul(f.a, g.a), ext_add(ext_mul(f.b, g.a), g.b)}; }      // g after f
+__device__ __forceinline__ Ext eval_shfl_up(const Ext& v, uint32_t d) {
+    return Ext{{(uint32_t)__shfl_up((int)v.c[0], d, 64), (uint32_t)__shfl_up((int)v.c[1], d, 64), (uint32_t)__shfl_up((int)v.c[2], d, 64), (uint32_t)__shfl_up((int)v.c[3], d, 64)}};
+}
+__device__ __forceinline__ Ext eval_value(const EvalArgs& a, const uint32_t* stream, const uint32_t* extra, uint32_t key) {
+    if (key == 0) return ext_one();
+    if (key <= a.NV) return w_ext_at(stream + 4u * (uint64_t)(key - 1u));
+    return w_ld4(extra + 4u + 4u * (key - 1u - a.NV));
+}
+__device__ __forceinline__ void eval_st4(uint32_t* r, const Ext& e) { *reinterpret_cast<uint4*>(r) = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]); }
+__global__ void __launch_bounds__(256) mrec_eval_rows_kernel(EvalArgs a) {
+    __shared__ uint32_t tot[4][8];                      // a wavefront's whole map (a, b)
+    __shared__ uint32_t last[4];                        // the chunk's last value
+    const uint32_t p = blockIdx.x / a.C, c = blockIdx.x % a.C, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t* stream = a.stream + (uint64_t)p * a.stream_stride;
+    const uint32_t* extra = a.extra + (uint64_t)p * a.extra_stride;
+    const Ext alpha = w_ld4(extra);
+    const uint32_t begin = a.t0[c], end = a.t0[c + 1];
+    Ext carry = ext_zero();                             // the running value in front of the chunk: zero at a chip's first term
+    for (uint32_t base = begin; base < end; base += 256u) {          // (uniform over the workgroup: every lane reaches every barrier)
+        const uint32_t i = base + tid;
+        const bool active = i < end;
+        Ext f0 = ext_zero(), f1 = ext_zero(), f2 = ext_zero(), mm = ext_zero(), tv = ext_zero();
+        EvalMap m{ext_one(), ext_zero()};                             // (a lane past the chip's terms: the identity)
+        if (active) {
+            const uint4 t = a.terms[i];
+            f0 = eval_value(a, stream, extra, t.x & 0x7FFFFFFFu); f1 = eval_value(a, stream, extra, t.y); f2 = eval_value(a, stream, extra, t.z);
+            mm = ext_mul(f0, f1); tv = ext_mul_base(ext_mul(mm, f2), t.w);
+            m = EvalMap{(t.x >> 31) ? alpha : ext_one(), tv};
+        }
+        for (uint32_t d = 1; d < 64u; d <<= 1) {                      // inclusive scan over the wavefront
+            const EvalMap before{eval_shfl_up(m.a, d), eval_shfl_up(m.b, d)};
+            if (lane >= d) m = eval_then(before, m);
+        }
+        if (lane == 63u) for (int j = 0; j < 4; j++) { tot[wave][j] = m.a.c[j]; tot[wave][4 + j] = m.b.c[j]; }
+        __syncthreads();
+        Ext in = carry;                                               // the value in front of this wavefront's first lane
+        for (uint32_t w = 0; w < wave; w++) in = ext_add(ext_mul(in, w_ld4(&tot[w][0])), w_ld4(&tot[w][4]));
+        const Ext acco = ext_add(ext_mul(in, m.a), m.b);
+        Ext accin = eval_shfl_up(acco, 1);
+        if (lane == 0) accin = in;
+        if (active) {
+            uint32_t* r = a.rows + (uint64_t)EV_MAIN * ((uint64_t)p * a.n_terms + i);
+            eval_st4(r + EV_F0, f0); eval_st4(r + EV_F0 + 4, f1); eval_st4(r + EV_F0 + 8, f2); eval_st4(r + EV_M, mm); eval_st4(r + EV_TV, tv);
+            eval_st4(r + EV_ACCIN, accin); eval_st4(r + EV_ACCO, acco); eval_st4(r + EV_ALPHA, alpha);
+        }
+        if (tid == 255u) for (int j = 0; j < 4; j++) last[j] = acco.c[j];
+        __syncthreads();                                              // (also: tot is written again by the next chunk)
+        carry = w_ld4(last);
+    }
+    if (tid == 0) eval_st4(a.acc + 4u * (uint64_t)blockIdx.x, carry);
+}
+// the term plan as the kernel reads it (a function of the shape alone)
+inline void eval_plan(const MShape& sh, std::vector<uint32_t>& terms, std::vector<uint32_t>& t0) {
+    terms.resize(4 * sh.terms.size());
+    t0.assign((size_t)sh.C + 1, 0u);
+    for (size_t i = 0; i < sh.terms.size(); i++) {
+        const ETerm& e = sh.terms[i];
+        terms[4 * i] = e.key[0] | (e.first << 31); terms[4 * i + 1] = e.key[1]; terms[4 * i + 2] = e.key[2]; terms[4 * i + 3] = to_monty(e.coeff);
+        t0[(size_t)e.chip + 1] = (uint32_t)(i + 1);
+    }
+    for (int c = 1; c <= sh.C; c++) if (t0[(size_t)c] < t0[(size_t)c - 1]) t0[(size_t)c] = t0[(size_t)c - 1];      // (a chip without terms: an empty range)
+}
+inline size_t eval_extra_words(const MShape& sh) { return 4 + 4 * ((size_t)sh.NPUB + 3 * (size_t)sh.C); }
+
+// the largest n_proofs make_mshape accepts for this description, 0 (zkhip_last_error) when it takes none: what it bounds grows with n_proofs
+size_t m_machine_verifier_max_proofs(const zkhip_machine_desc* inner) {
+    auto takes = [&](size_t n) { MShape sh; return make_mshape(inner, n, sh) == ZKHIP_OK; };
+    if (!takes(1)) return 0;
+    size_t lo = 1, hi = 64;
+    while (lo < hi) { const size_t mid = (lo + hi + 1) / 2; if (takes(mid)) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
 int m_machine_verifier_setup(zkhip_ctx* ctx, const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, zkhip_machine_key** key, uint32_t vk[8]) {
     CHECK_CTX(ctx);
     if (!outer || !key || !vk) return fail(ZKHIP_ERR_INVALID, "machine_verifier_setup: null argument");
@@ -1908,10 +2023,10 @@ int top_begin(const zkhip_machine_desc* inner, size_t n_proofs, size_t n_public,
     if ((int)n_public != sh.NPUB) return fail(ZKHIP_ERR_INVALID, "prove_machine_verifier: n_public is not the machine's");
     HostTabs& ht = s.ht;
     s.device = !rec_host_forced() && !t_batcher;            // (inside a lock-step batch the members' launches are merged: the witness kernels are launched directly, so there the host walks)
-    if (s.device) { s.plan = build_wit_plan(sh); s.vals.assign((size_t)sh.NP, DevVals{}); s.ptrs.assign((size_t)sh.NP, nullptr); }
+    if (s.device) { s.plan = build_wit_plan(sh); s.plan.eval_rows = (size_t)sh.NP * sh.terms.size() >= EVAL_DEVICE_MIN_ROWS; s.vals.assign((size_t)sh.NP, DevVals{}); s.ptrs.assign((size_t)sh.NP, nullptr); }
     ZeroedWords* tabs[N_CHIPS] = {nullptr, &ht.rs, &ht.fold, &ht.ts, &ht.q, &ht.op, &ht.sm, &ht.sc, &ht.evl, &ht.lgu};
     for (int c = 0; c < N_CHIPS; c++) {
-        if (!tabs[c] || (s.device && (c == C_ROWSUM || c == C_FOLD || c == C_QUERY))) continue;       // (device mode: those three never exist on the host)
+        if (!tabs[c] || (s.device && (c == C_ROWSUM || c == C_FOLD || c == C_QUERY || (c == C_EVAL && s.plan.eval_rows)))) continue;       // (device mode: those never exist on the host)
         if (!tabs[c]->reset((size_t)m.km.w_main[c] << m.km.height[c])) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory for the machine's tables");
     }
     if (!s.device) for (size_t r = 0; r < ((size_t)1 << m.km.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.km.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;      // (the fold chip's padding rows: T = 1)
@@ -2010,15 +2125,22 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
             size_t i = 0;
             for (int tr = 0; tr < N_TREES; tr++) { if (!sh.has_tree[tr]) continue; trees[i++].root_off = tr == T_E ? -1 : (int32_t)(tr == T_T ? o_troot : tr == T_P ? o_proot : o_qroot); }
         }
-        // one block of small things: [vals NP][rows][g0][hs][inj_hi][trees][src], then scratch [roh][pairs][pair_k][err]
+        // one block of small things: [vals NP][rows][g0][hs][inj_hi][trees][src][EVAL: per-proof block NP][terms][t0], then scratch [roh][pairs][pair_k][err][EVAL accumulators]
         auto rup = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const bool eval_rows = pl.eval_rows;
+        std::vector<uint32_t> eterms, et0;
+        if (eval_rows) eval_plan(sh, eterms, et0);
+        const size_t estride = eval_rows ? eval_extra_words(sh) : 0, n_terms = sh.terms.size();
         const size_t b_vals = rup(NPs * vstride * 4), b_rows = rup(nq * sizeof(WRow)), b_g0 = rup((nh + 1) * 4), b_hs = rup(nh * 4), b_inj = rup(32 * 4),
-                     b_trees = rup(trees.size() * sizeof(p2chip::MrecTreePlan)), b_src = rup(pl.src.size() * 4 + 4);
-        const size_t up_bytes = b_vals + b_rows + b_g0 + b_hs + b_inj + b_trees + b_src;
-        const size_t b_roh = rup(NPs * Q * nh * 16), b_pairs = rup(NPs * Q * R * 32), b_pk = rup(NPs * Q * R * 4), b_err = rup(NPs * 4);
+                     b_trees = rup(trees.size() * sizeof(p2chip::MrecTreePlan)), b_src = rup(pl.src.size() * 4 + 4), b_ev = rup(NPs * estride * 4), b_eterms = rup(eterms.size() * 4 + 16),
+                     b_et0 = rup(et0.size() * 4);
+        const size_t up_bytes = b_vals + b_rows + b_g0 + b_hs + b_inj + b_trees + b_src + b_ev + b_eterms + b_et0;
+        const size_t b_roh = rup(NPs * Q * nh * 16), b_pairs = rup(NPs * Q * R * 32), b_pk = rup(NPs * Q * R * 4), b_err = rup(NPs * 4), b_eacc = eval_rows ? rup(NPs * (size_t)sh.C * 16) : 0;
+        for (int p = 0; eval_rows && p < NP; p++)
+            if (s.vals[(size_t)p].ev.size() != estride || s.vals[(size_t)p].acc.size() != 4 * (size_t)sh.C) return fail(ZKHIP_ERR_INTERNAL, "prove_machine_verifier: a proof's EVAL block");
         void *dprf, *dblk, *hpin;
         ZK_TRY(ctx_reserve(ctx, S_WIT_A, NPs * s.proof_len, &dprf));
-        ZK_TRY(ctx_reserve(ctx, S_WIT_B, up_bytes + b_roh + b_pairs + b_pk + b_err, &dblk));
+        ZK_TRY(ctx_reserve(ctx, S_WIT_B, up_bytes + b_roh + b_pairs + b_pk + b_err + b_eacc, &dblk));
         ZK_TRY(ctx_host_pinned(ctx, NPs * s.proof_len + up_bytes, &hpin));
         uint8_t* hp = (uint8_t*)hpin;
         {   // the proofs into the pinned block side by side (a few threads: 60 MB for 64 transcript proofs), the small block behind them
@@ -2040,11 +2162,17 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
             std::memcpy(u + at, pl.inj_hi, 32 * 4); at += b_inj;
             std::memcpy(u + at, trees.data(), trees.size() * sizeof(p2chip::MrecTreePlan)); at += b_trees;
             if (!pl.src.empty()) std::memcpy(u + at, pl.src.data(), pl.src.size() * 4);
+            at += b_src;
+            for (int p = 0; eval_rows && p < NP; p++) std::memcpy(u + at + (size_t)p * estride * 4, s.vals[(size_t)p].ev.data(), estride * 4);
+            at += b_ev;
+            if (!eterms.empty()) std::memcpy(u + at, eterms.data(), eterms.size() * 4);
+            at += b_eterms;
+            if (!et0.empty()) std::memcpy(u + at, et0.data(), et0.size() * 4);
         }
         uint8_t* db = (uint8_t*)dblk;
         ZK_HIP(hipMemcpyAsync(dprf, hp, NPs * s.proof_len, hipMemcpyHostToDevice, ctx->stream));
         ZK_HIP(hipMemcpyAsync(db, hp + NPs * s.proof_len, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP(hipMemsetAsync(db + up_bytes, 0, b_roh + b_pairs + b_pk + b_err, ctx->stream));
+        ZK_HIP(hipMemsetAsync(db + up_bytes, 0, b_roh + b_pairs + b_pk + b_err + b_eacc, ctx->stream));
         ZK_HIP(hipMemsetAsync(dev[C_ROWSUM], 0, ((size_t)m.km.w_main[C_ROWSUM] << m.km.height[C_ROWSUM]) * 4, ctx->stream));
         ZK_HIP(hipMemsetAsync(dev[C_QUERY], 0, ((size_t)m.km.w_main[C_QUERY] << m.km.height[C_QUERY]) * 4, ctx->stream));
         ZK_HIP(hipMemsetAsync(dev[C_FOLD], 0, ((size_t)m.km.w_main[C_FOLD] << m.km.height[C_FOLD]) * 4, ctx->stream));
@@ -2055,13 +2183,26 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         a.rows = (const WRow*)(db + at); at += b_rows; a.g0 = (const uint32_t*)(db + at); at += b_g0; a.hs = (const int32_t*)(db + at); at += b_hs;
         a.inj_hi = (const int32_t*)(db + at); at += b_inj;
         const p2chip::MrecTreePlan* d_trees = (const p2chip::MrecTreePlan*)(db + at); at += b_trees;
-        const int32_t* d_src = (const int32_t*)(db + at);
+        const int32_t* d_src = (const int32_t*)(db + at); at += b_src;
+        EvalArgs ea{};
+        ea.stream = (const uint32_t*)dprf + o_qroot + 8; ea.stream_stride = pwords;              // (o_stream: the opened values stand behind the quotient root)
+        ea.extra = (const uint32_t*)(db + at); ea.extra_stride = (uint32_t)estride; at += b_ev;
+        ea.terms = (const uint4*)(db + at); at += b_eterms;
+        ea.t0 = (const uint32_t*)(db + at);
+        ea.NV = sh.NV; ea.C = (uint32_t)sh.C; ea.n_terms = (uint32_t)n_terms;
+        ea.rows = (uint32_t*)dev[C_EVAL]; ea.acc = (uint32_t*)(db + up_bytes + b_roh + b_pairs + b_pk + b_err);
         a.nh = (uint32_t)nh; a.nq = (uint32_t)nq; a.NP = (uint32_t)NP; a.Q = (uint32_t)Q; a.R = (uint32_t)R; a.H = (uint32_t)sh.H; a.NTREES = sh.NTREES;
         a.o_queries = (uint32_t)o_queries; a.per_query = (uint32_t)perq; a.o_final = (uint32_t)o_final; a.fri_off = pl.fri_off;
         a.rs = (uint32_t*)dev[C_ROWSUM]; a.qt = (uint32_t*)dev[C_QUERY]; a.fold = (uint32_t*)dev[C_FOLD]; a.fw = m.km.w_main[C_FOLD]; a.inj_col = frichip::width_of(sh.R, true, true);
         a.roh = (uint32_t*)(db + up_bytes); a.pairs = (uint32_t*)(db + up_bytes + b_roh); a.pair_k = (uint32_t*)(db + up_bytes + b_roh + b_pairs);
         a.err = (uint32_t*)(db + up_bytes + b_roh + b_pairs + b_pk);
         const unsigned gq = (unsigned)((NPs * Q * nh + 63) / 64), gf = (unsigned)((NPs * Q + 63) / 64);
+        if (eval_rows) {   // EVAL: a workgroup per (proof, chip) over the rows with a term; the rows behind them are zero
+            const size_t erows = (size_t)1 << m.km.height[C_EVAL], eused = NPs * n_terms;
+            if (eused > erows) return fail(ZKHIP_ERR_INTERNAL, "prove_machine_verifier: the EVAL table's height");
+            if (erows > eused) ZK_HIP(hipMemsetAsync(dev[C_EVAL] + (size_t)EV_MAIN * eused, 0, (erows - eused) * EV_MAIN * 4, ctx->stream));
+            hipLaunchKernelGGL(mrec_eval_rows_kernel, dim3((unsigned)(NPs * (size_t)sh.C)), dim3(256), 0, ctx->stream, ea);
+        }
         hipLaunchKernelGGL(mrec_rowsum_query_kernel, dim3(gq), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(mrec_rowsum_accin_kernel, dim3(gq), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(mrec_fold_kernel, dim3(gf), dim3(64), 0, ctx->stream, a);
@@ -2091,13 +2232,19 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         std::vector<uint32_t> trows(nt);
         for (size_t p = 0; p < NPs; p++) for (size_t T = 0; T < (size_t)sh.NT; T++) trows[p * (size_t)sh.NT + T] = (uint32_t)(p * sh.p2_rows + T);
         ZK_TRY(p2r_upload(trows));
-        std::vector<uint32_t> errs(NPs, 0u);
-        ZK_TRY(dev_d2h(ctx, errs.data(), a.err, NPs * 4));
+        // one read-back: the kernels' refusals and, behind them in the block, EVAL's accumulators
+        std::vector<uint32_t> back((b_err + b_eacc) / 4, 0u);
+        ZK_TRY(dev_d2h(ctx, back.data(), a.err, eval_rows ? b_err + NPs * (size_t)sh.C * 16 : NPs * 4));
+        const uint32_t* errs = back.data();
+        const uint32_t* eacc = back.data() + b_err / 4;
         for (size_t p = 0; p < NPs; p++) {
             if (!errs[p]) continue;
             const char* what = errs[p] == 1 ? "a FRI layer opening does not end in the layer's root" : errs[p] == 2 ? "a fold chain does not end in the final value" : "an opening does not end in its root";
             return fail(ZKHIP_ERR_VERIFY, "prove_machine_verifier: proof " + std::to_string(p) + " rejected: " + what);
         }
+        for (size_t p = 0; eval_rows && p < NPs; p++)
+            if (std::memcmp(eacc + p * (size_t)sh.C * 4, s.vals[p].acc.data(), (size_t)sh.C * 16) != 0)
+                return fail(ZKHIP_ERR_INTERNAL, "prove_machine_verifier: proof " + std::to_string(p) + ": the device's EVAL accumulators are not the host's");
     } else {   // the Poseidon2 rows: input states, bits, indices up; one launch fills the 360 columns of every row
         std::vector<uint32_t> trows(used);
         for (size_t r = 0; r < used; r++) trows[r] = (uint32_t)r;
@@ -2209,6 +2356,60 @@ size_t m_machine_verifier_host_tables(const zkhip_machine_desc* inner, const uin
     return n;
 }
 
+// mrec_eval_rows_kernel alone, for the row tests: one launch over raw terms and value tables.  Keys 1 .. n_stream are read as the kernel reads a proof's opened-value
+// stream (canonical words, Montgomery form made in the kernel), the keys behind them go up in the call's small block as the machine's public values and selectors do
+int m_machine_verifier_gen_eval_rows(zkhip_ctx* ctx, size_t n_terms, const uint32_t* chips, const uint32_t* coeffs, const uint32_t* keys, const uint32_t* firsts, size_t n_chips,
+                                     size_t n_proofs, size_t kspan, size_t n_stream, const uint32_t* values, const uint32_t* alphas, uint32_t* rows, uint32_t* accs) {
+    CHECK_CTX(ctx);
+    const char* who = "machine_verifier_gen_eval_rows";
+    if (!chips || !coeffs || !keys || !firsts || !values || !alphas || !rows || !accs) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (n_terms < 1 || n_terms > ((size_t)1 << 20) || n_chips < 1 || n_chips > (size_t)MAX_INNER_CHIPS || n_proofs < 1 || n_proofs > 64 || n_proofs * n_terms > ((size_t)1 << MAX_LOG_ROWS) ||
+        kspan < 1 || kspan > ((size_t)1 << 20) || n_stream >= kspan || n_proofs * kspan > ((size_t)1 << MAX_LOG_ROWS))
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": 1 .. 2^20 terms, 1 .. 16 chips, 1 .. 64 proofs, n_proofs x n_terms rows within the EVAL chip's bound (2^" +
+                                       std::to_string(MAX_LOG_ROWS) + "), 1 .. 2^20 keys of which fewer than all are stream values");
+    std::vector<uint32_t> terms(4 * n_terms), t0(n_chips + 1, 0u);
+    for (size_t i = 0; i < n_terms; i++) {
+        if (chips[i] >= n_chips || (i && chips[i] < chips[i - 1]) || coeffs[i] >= P || firsts[i] > 1 || keys[3 * i] >= kspan || keys[3 * i + 1] >= kspan || keys[3 * i + 2] >= kspan)
+            return fail(ZKHIP_ERR_INVALID, std::string(who) + ": terms chip by chip, canonical coefficients, first flags 0 / 1, keys below kspan");
+        terms[4 * i] = keys[3 * i] | (firsts[i] << 31); terms[4 * i + 1] = keys[3 * i + 1]; terms[4 * i + 2] = keys[3 * i + 2]; terms[4 * i + 3] = to_monty(coeffs[i]);
+        t0[chips[i] + 1] = (uint32_t)(i + 1);
+    }
+    for (size_t c = 1; c <= n_chips; c++) if (t0[c] < t0[c - 1]) t0[c] = t0[c - 1];
+    for (size_t i = 0; i < 4 * n_proofs * kspan; i++) if (values[i] >= P) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": values must be canonical");
+    for (size_t i = 0; i < 4 * n_proofs; i++) if (alphas[i] >= P) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": alpha must be canonical");
+    const size_t estride = 4 + 4 * (kspan - 1 - n_stream), sstride = 4 * n_stream + 4;
+    std::vector<uint32_t> extra(n_proofs * estride), stream(n_proofs * sstride, 0u);
+    for (size_t p = 0; p < n_proofs; p++) {
+        const uint32_t* v = values + 4 * p * kspan;
+        for (size_t j = 0; j < 4; j++) extra[p * estride + j] = to_monty(alphas[4 * p + j]);
+        for (size_t j = 0; j < 4 * (kspan - 1 - n_stream); j++) extra[p * estride + 4 + j] = to_monty(v[4 * (n_stream + 1) + j]);
+        std::memcpy(stream.data() + p * sstride, v + 4, 4 * n_stream * 4);                     // (the table's entry 0 is not read: key 0 is the extension one)
+    }
+    auto rup = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_terms = rup(terms.size() * 4), b_t0 = rup(t0.size() * 4), b_extra = rup(extra.size() * 4), b_stream = rup(stream.size() * 4), b_acc = rup(n_proofs * n_chips * 16),
+                 b_rows = n_proofs * n_terms * EV_MAIN * 4;
+    void* blk;
+    ZK_TRY(ctx_reserve(ctx, S_STAGE, b_terms + b_t0 + b_extra + b_stream + b_acc + b_rows, &blk));
+    uint8_t* d = (uint8_t*)blk;
+    ZK_TRY(dev_h2d(ctx, d, terms.data(), terms.size() * 4));
+    ZK_TRY(dev_h2d(ctx, d + b_terms, t0.data(), t0.size() * 4));
+    ZK_TRY(dev_h2d(ctx, d + b_terms + b_t0, extra.data(), extra.size() * 4));
+    ZK_TRY(dev_h2d(ctx, d + b_terms + b_t0 + b_extra, stream.data(), stream.size() * 4));
+    EvalArgs ea{};
+    ea.terms = (const uint4*)d; ea.t0 = (const uint32_t*)(d + b_terms); ea.extra = (const uint32_t*)(d + b_terms + b_t0); ea.extra_stride = (uint32_t)estride;
+    ea.stream = (const uint32_t*)(d + b_terms + b_t0 + b_extra); ea.stream_stride = sstride;
+    ea.NV = (uint32_t)n_stream; ea.C = (uint32_t)n_chips; ea.n_terms = (uint32_t)n_terms;
+    ea.acc = (uint32_t*)(d + b_terms + b_t0 + b_extra + b_stream); ea.rows = (uint32_t*)(d + b_terms + b_t0 + b_extra + b_stream + b_acc);
+    hipLaunchKernelGGL(mrec_eval_rows_kernel, dim3((unsigned)(n_proofs * n_chips)), dim3(256), 0, ctx->stream, ea);
+    ZK_HIP(hipGetLastError());
+    ZK_TRY(dev_d2h(ctx, rows, ea.rows, b_rows));
+    ZK_TRY(dev_d2h(ctx, accs, ea.acc, n_proofs * n_chips * 16));
+    // the device's words are Montgomery forms below P (a word of P or more would be a kernel that leaves its sums unreduced): canonical words go out
+    for (size_t i = 0; i < n_proofs * n_terms * EV_MAIN; i++) { if (rows[i] >= P) return fail(ZKHIP_ERR_INTERNAL, std::string(who) + ": the kernel left a row word of P or more"); rows[i] = from_monty(rows[i]); }
+    for (size_t i = 0; i < n_proofs * n_chips * 4; i++) { if (accs[i] >= P) return fail(ZKHIP_ERR_INTERNAL, std::string(who) + ": the kernel left an accumulator word of P or more"); accs[i] = from_monty(accs[i]); }
+    return ZKHIP_OK;
+}
+
 int m_verify_machine_recursive(const zkhip_machine_desc* inner, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public, size_t n_proofs, const uint32_t vk[8],
                                    const zkhip_params* outer, int* reason) {
     if (!proof || !vk || !outer || (n_public && !public_values)) { if (reason) *reason = 1; return fail(ZKHIP_ERR_VERIFY, "verify_machine_recursive: null argument"); }
@@ -2253,6 +2454,10 @@ int zkhip_prove_shard_tree(zkhip_ctx* ctx, const zkhip_machine_key* top_key, con
 size_t zkhip_machine_verifier_host_tables(const zkhip_machine_desc* inner, const uint8_t* const* proofs, const size_t* proof_lens, size_t n_proofs, const uint32_t* public_values,
                                           size_t n_public, int which, uint32_t* out, size_t cap) {
     ZK_MREC_GUARD(zk::mrec::m_machine_verifier_host_tables(inner, proofs, proof_lens, n_proofs, public_values, n_public, which, out, cap), 0)
+}
+int zkhip_machine_verifier_gen_eval_rows(zkhip_ctx* ctx, size_t n_terms, const uint32_t* chips, const uint32_t* coeffs, const uint32_t* keys, const uint32_t* firsts, size_t n_chips,
+                                         size_t n_proofs, size_t kspan, size_t n_stream, const uint32_t* values, const uint32_t* alphas, uint32_t* rows, uint32_t* accs) {
+    ZK_MREC_GUARD(zk::mrec::m_machine_verifier_gen_eval_rows(ctx, n_terms, chips, coeffs, keys, firsts, n_chips, n_proofs, kspan, n_stream, values, alphas, rows, accs), ZKHIP_ERR_NOMEM)
 }
 int zkhip_verify_machine_recursive(const zkhip_machine_desc* inner, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public, size_t n_proofs, const uint32_t vk[8],
                                    const zkhip_params* outer, int* reason) {

@@ -936,6 +936,67 @@ class Context:
                                                       C.byref(inner_params), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the JOIN of fold-16 lift proofs (machine mode over the lift machine of a shape): N lift proofs -> one proof
+    def fri16_join_setup(self, R, F, log_blowup, n_queries, pow_bits, W, NP, n_proofs, lift_params=None, params=None, hash_width=24):
+        """zkhip_fri16_join_setup: the key of the machine that verifies n_proofs lift proofs of this shape (made under lift_params) in-circuit -> MachineKey"""
+        lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        check(self.lib.zkhip_fri16_join_setup(self.handle, R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), n_proofs, C.byref(params),
+                                              C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def prove_fri16_join(self, key, R, F, log_blowup, n_queries, pow_bits, W, NP, lift_proofs, public_values, lift_params=None, params=None, hash_width=24):
+        """zkhip_prove_fri16_join: lift_proofs = a list of lift proofs of ONE shape, public_values one list of NP words per proof -> ONE proof, the bytes
+        prove_machine_verifier makes from the lift machine's description.  Refused by message: no proof or more than fri16_join_max_proofs, inner hash width 16,
+        another number of public values than len(lift_proofs) x NP"""
+        lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+        sps = [np.ascontiguousarray(sp, dtype=np.uint8) for sp in lift_proofs]
+        n = len(sps)
+        pv = np.ascontiguousarray(np.array([int(x) for v in public_values for x in v] or [0], dtype=np.uint32))
+        n_pub = sum(len(v) for v in public_values)
+        shape = (R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params))
+        size = self.lib.zkhip_fri16_join_proof_size(*shape, n, C.byref(params))
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        ptrs = (u8p * max(n, 1))(*[sp.ctypes.data_as(u8p) for sp in sps])
+        lens = (C.c_size_t * max(n, 1))(*[sp.size for sp in sps])
+        check(self.lib.zkhip_prove_fri16_join(self.handle, key.handle if key is not None else None, *shape, ptrs, lens, n, pv.ctypes.data_as(u32p), n_pub, C.byref(params),
+                                              buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
+    def prove_fri16_join_segments(self, lift_key, join_key, segment_proofs, log_n, width, public_values, inner_params, lift_params=None, params=None):
+        """zkhip_prove_fri16_join_segments: segment proofs in, ONE proof out -- each segment lifted on this context (prove_fri16_lift_segment under lift_key), then
+        prove_fri16_join under join_key.  A segment that does not verify raises with the host verifier's code and a message that names the segment"""
+        lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+        sps = [np.ascontiguousarray(sp, dtype=np.uint8) for sp in segment_proofs]
+        n = len(sps)
+        pv = np.ascontiguousarray(np.array([int(x) for v in public_values for x in v] or [0], dtype=np.uint32))
+        n_pub = sum(len(v) for v in public_values)
+        sh = _fri16_segment_shape(log_n, inner_params)
+        size = self.lib.zkhip_fri16_join_proof_size(sh[0], sh[1], sh[2], sh[3], int(inner_params.hash_width), int(inner_params.pow_bits), width, n_pub // max(n, 1),
+                                                    C.byref(lift_params), n, C.byref(params)) if sh else 0
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        ptrs = (u8p * max(n, 1))(*[sp.ctypes.data_as(u8p) for sp in sps])
+        lens = (C.c_size_t * max(n, 1))(*[sp.size for sp in sps])
+        check(self.lib.zkhip_prove_fri16_join_segments(self.handle, lift_key.handle, join_key.handle, ptrs, lens, n, log_n, width, pv.ctypes.data_as(u32p), n_pub,
+                                                       C.byref(inner_params), C.byref(lift_params), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
+        return buf[: got.value]
+
+    def machine_verifier_gen_eval_rows(self, chips, coeffs, keys, firsts, n_chips, values, alphas, n_stream):
+        """zkhip_machine_verifier_gen_eval_rows: machine mode's EVAL row kernel alone, one launch.  chips / coeffs / firsts [n_terms], keys [n_terms][3], values
+        [n_proofs][kspan][4] and alphas [n_proofs][4] canonical; keys 1 .. n_stream are read as a proof's opened-value stream, the rest as the call's small block
+        -> (rows [n_proofs n_terms][32], accs [n_proofs n_chips][4]), canonical words"""
+        u = lambda a: np.ascontiguousarray(np.array(a, dtype=np.uint32).reshape(-1))
+        ch, co, ke, fi, al = u(chips), u(coeffs), u(keys), u(firsts), u(alphas)
+        vals = np.ascontiguousarray(np.array(values, dtype=np.uint32))
+        n_terms, n_proofs, kspan = ch.size, vals.shape[0], vals.shape[1]
+        assert co.size == fi.size == n_terms and ke.size == 3 * n_terms and vals.shape[2] == 4 and al.size == 4 * n_proofs
+        rows, accs = np.zeros((n_proofs * n_terms, 32), dtype=np.uint32), np.zeros((n_proofs * n_chips, 4), dtype=np.uint32)
+        check(self.lib.zkhip_machine_verifier_gen_eval_rows(self.handle, n_terms, *[a.ctypes.data_as(u32p) for a in (ch, co, ke, fi)], n_chips, n_proofs, kspan, n_stream,
+                                                            vals.ctypes.data_as(u32p), al.ctypes.data_as(u32p), rows.ctypes.data_as(u32p), accs.ctypes.data_as(u32p)))
+        return rows, accs
+
     def shard_verifier_setup(self, log_n, width, n_queries, inner_pow_bits, n_public, params=None, n_proofs=1, program=None):
         """zkhip_shard_verifier_setup: the key of the shard-verifier machine for n_proofs inner proofs of this SHAPE (no inner proof involved);
         program: the inner proofs are version-7 proofs of that constraint program (zkhip_shard_verifier_setup_air)"""
@@ -1938,6 +1999,52 @@ def fri16_lift_key_host(R, F, log_blowup, n_queries, pow_bits, W, NP, params=Non
     vk = np.zeros(8, dtype=np.uint32)
     check(_lib.load().zkhip_fri16_lift_key_host(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(params), vk.ctypes.data_as(u32p)))
     return vk
+
+
+def fri16_lift_inner_machine(R, F, log_blowup, n_queries, pow_bits, W, NP, lift_params=None, hash_width=24):
+    """the lift machine of a shape as an InnerMachine for machine mode: fri16_lift_describe's thirteen positions, the shape's key, lift_params' queries and
+    proof-of-work bits -- what the fri16_join entries put together inside the library"""
+    lift_params = lift_params or Params(1, 100, 16)
+    chips = []
+    for which in range(13):
+        prog, ln, mw, pw, _ = fri16_lift_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, 0)
+        tab = fri16_lift_describe(R, F, log_blowup, n_queries, pow_bits, W, NP, which, 1)[0]
+        chips.append(dict(ln=ln, W=mw, Pw=pw, prog=prog, tab=tab))
+    root = fri16_lift_key_host(R, F, log_blowup, n_queries, pow_bits, W, NP, lift_params, hash_width)
+    return InnerMachine(chips, root, lift_params.num_queries, lift_params.pow_bits, NP)
+
+
+def fri16_join_key_host(R, F, log_blowup, n_queries, pow_bits, W, NP, n_proofs, lift_params=None, params=None, hash_width=24):
+    """zkhip_fri16_join_key_host: the join's key of (lift shape, lift parameters, n_proofs, join parameters), without a GPU -> 8 canonical words"""
+    lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_join_key_host(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), n_proofs, C.byref(params), vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def fri16_join_max_proofs(R, F, log_blowup, n_queries, pow_bits, W, NP, lift_params=None, hash_width=24):
+    """zkhip_fri16_join_max_proofs: the most lift proofs of this shape one join takes; 0 for a shape the lift refuses (last_error says why)"""
+    lift_params = lift_params or Params(1, 100, 16)
+    return int(_lib.load().zkhip_fri16_join_max_proofs(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params)))
+
+
+def fri16_join_proof_size(R, F, log_blowup, n_queries, pow_bits, W, NP, n_proofs, lift_params=None, params=None, hash_width=24):
+    lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    return int(_lib.load().zkhip_fri16_join_proof_size(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), n_proofs, C.byref(params)))
+
+
+def verify_fri16_join(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, NP, n_proofs, vk, lift_params=None, params=None, hash_width=24):
+    """zkhip_verify_fri16_join: the joined proof against (lift shape, the segments' public values in proof order -- one list per proof --, the join's key) -> (rc, reason);
+    host only, no byte of a lift or segment proof"""
+    lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    flat = [int(x) for v in public_values for x in v]
+    pv = np.ascontiguousarray(np.array(flat or [0], dtype=np.uint32))
+    k = np.ascontiguousarray(np.array(vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = _lib.load().zkhip_verify_fri16_join(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), pr.ctypes.data_as(u8p), pr.size,
+                                             pv.ctypes.data_as(u32p), len(flat), n_proofs, k.ctypes.data_as(u32p), C.byref(params), C.byref(reason))
+    return rc, reason.value
 
 
 def verify_fri16_lift(proof, inner_public, R, F, log_blowup, n_queries, pow_bits, W, vk, params=None):

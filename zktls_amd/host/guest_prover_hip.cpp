@@ -87,9 +87,11 @@ std::vector<Slot> g_slots;
 // headline shape): a function of the shape, so a prover that serves many requests of one plan keeps it -- parked like the contexts
 // (a machine key belongs to the context that made it: the pair is parked together)
 struct JoinKey { int device; int32_t log_n; uint32_t width; int32_t queries, pow_bits; uint32_t join; zkhip_ctx* ctx; zkhip_machine_key* key; uint32_t vk[8];
-                 uint64_t p2_generation; };          // the key commits with the Poseidon2 tables in effect when it was made (zkhip_load_poseidon2_params moves the counter)
+                 uint64_t p2_generation;             // the key commits with the Poseidon2 tables in effect when it was made (zkhip_load_poseidon2_params moves the counter)
+                 zkhip_machine_key* lift_key = nullptr; };      // the RISC Zero side (join_segment_proofs): key = the join's, lift_key = the segments' shape's; null: an SP1-shape pair
+void destroy_join_key(const JoinKey& k) { zkhip_machine_key_destroy(k.key); if (k.lift_key) zkhip_machine_key_destroy(k.lift_key); zkhip_ctx_destroy(k.ctx); }
 std::vector<JoinKey> g_join_keys;           // (under g_slots_mu)
-bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, JoinKey* out) {
+bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, JoinKey* out, bool r0 = false) {
     const uint64_t gen = zkhip_poseidon2_params_generation();
     std::vector<JoinKey> stale;
     bool found = false;
@@ -98,7 +100,7 @@ bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, Join
         for (size_t i = 0; i < g_join_keys.size();) {
             const JoinKey& k = g_join_keys[i];
             if (k.p2_generation != gen) { stale.push_back(k); g_join_keys.erase(g_join_keys.begin() + (long)i); continue; }     // made under other tables: a verifier would derive another key
-            if (!found && k.device == device && k.log_n == plan.log_n && k.width == plan.width && k.queries == plan.num_queries && k.pow_bits == plan.pow_bits && k.join == join) {
+            if (!found && k.device == device && k.log_n == plan.log_n && k.width == plan.width && k.queries == plan.num_queries && k.pow_bits == plan.pow_bits && k.join == join && (k.lift_key != nullptr) == r0) {
                 *out = k;
                 g_join_keys.erase(g_join_keys.begin() + (long)i);
                 found = true;
@@ -107,7 +109,7 @@ bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, Join
             i++;
         }
     }
-    for (auto& k : stale) { zkhip_machine_key_destroy(k.key); zkhip_ctx_destroy(k.ctx); }
+    for (auto& k : stale) destroy_join_key(k);
     return found;
 }
 void park_join_key(const JoinKey& k) {
@@ -115,8 +117,7 @@ void park_join_key(const JoinKey& k) {
         std::lock_guard<std::mutex> lk(g_slots_mu);
         if (g_join_keys.size() < 4 && k.p2_generation == zkhip_poseidon2_params_generation()) { g_join_keys.push_back(k); return; }
     }
-    zkhip_machine_key_destroy(k.key);
-    zkhip_ctx_destroy(k.ctx);
+    destroy_join_key(k);
 }
 // the pair taken for one compress stage: parked again when the stage went through, destroyed on every other way out (an exception included)
 struct JoinGuard {
@@ -127,6 +128,7 @@ struct JoinGuard {
         (void)zkhip_ctx_sync(jk.ctx);
         if (done) { park_join_key(jk); return; }
         if (jk.key) zkhip_machine_key_destroy(jk.key);
+        if (jk.lift_key) zkhip_machine_key_destroy(jk.lift_key);
         zkhip_ctx_destroy(jk.ctx);
     }
 };
@@ -313,6 +315,64 @@ static std::vector<uint8_t> compress_shard_proofs(const std::vector<int>& device
     std::memcpy(tail.data() + 32, &cnt, 4);
     entries.push_back(tail);
     return pack_shard_proofs(entries, BATCH_FLAG_SYNTHETIC | BATCH_FLAG_COMPRESSED | flags_extra);
+}
+
+// ---- RISC Zero's compress stage (prover.rs:88-93: segments -> lift -> join) ----
+// the lift shape of the plan's segment proofs (prm: the parameters prove_inner proves them under) and the outer parameters of the lift and the join proofs
+namespace {
+struct SegmentShape { int R, F, b; size_t Q; int hw, pb; uint32_t W; zkhip_params outer; };
+SegmentShape segment_shape(const ShardPlan& plan, const zkhip_params& prm) {
+    return SegmentShape{(plan.log_n - prm.log_final) / 4, prm.log_final, prm.log_blowup, (size_t)prm.num_queries, prm.hash_width, prm.pow_bits, plan.width,
+                        zkhip_params{1, plan.num_queries, plan.pow_bits, 0, 0, 0, 0, 0}};
+}
+// the parameters of the plan's segment proofs: RISC Zero's shape; the final polynomial shrinks for segments too small for 256 coefficients
+zkhip_params segment_params(const ShardPlan& plan) {
+    int lf = 8;
+    while (lf > plan.log_n || (plan.log_n - lf) % 4 != 0) lf--;
+    const bool defaults = plan.num_queries == 100 && plan.pow_bits == 16;
+    return zkhip_params{2, defaults ? 50 : plan.num_queries, defaults ? 0 : plan.pow_bits, 0, 4, lf, 24, 0};
+}
+}  // namespace
+// `proofs` = the plan's segment proofs, public values request digest | segment index: every one lifted under the shape's key, the lift proofs joined into ONE proof
+// (zkhip_prove_fri16_join_segments) on a pooled context that keeps both keys.  The blob: entry 0 = the joined proof, entry 1 = the join's key + the segment count.
+static std::vector<uint8_t> join_segment_proofs(int device, const ShardPlan& plan, const zkhip_params& prm, const std::vector<uint32_t>& digest,
+                                                const std::vector<std::vector<uint8_t>>& proofs) {
+    const SegmentShape sh = segment_shape(plan, prm);
+    const size_t n = plan.shards;
+    // (more segments than one join takes: the library's refusal names the bound; a tree above the join is not built)
+    const size_t cap = zkhip_fri16_join_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, n, &sh.outer);
+    if (cap == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error() + " (a tree above the join is not built)");
+    JoinGuard jg{JoinKey{device, plan.log_n, plan.width, plan.num_queries, plan.pow_bits, (uint32_t)n, nullptr, nullptr, {0}, zkhip_poseidon2_params_generation()}};
+    JoinKey& jk = jg.jk;
+    if (!take_join_key(device, plan, (uint32_t)n, &jk, true)) {
+        if (zkhip_ctx_create(device, nullptr, &jk.ctx) != ZKHIP_OK) { jk.ctx = nullptr; fail_zkhip("zkhip_ctx_create"); }
+        uint32_t lift_vk[8];
+        if (zkhip_fri16_lift_key(jk.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, &jk.lift_key, lift_vk) != ZKHIP_OK) { jk.lift_key = nullptr; fail_zkhip("zkhip_fri16_lift_key"); }
+        if (zkhip_fri16_join_setup(jk.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, n, &sh.outer, &jk.key, jk.vk) != ZKHIP_OK) { jk.key = nullptr; fail_zkhip("zkhip_fri16_join_setup"); }
+    }
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<size_t> lens(n);
+    std::vector<uint32_t> pvs;
+    for (size_t s = 0; s < n; s++) {
+        ptrs[s] = proofs[s].data(); lens[s] = proofs[s].size();
+        pvs.insert(pvs.end(), digest.begin(), digest.end());
+        pvs.push_back((uint32_t)s);
+    }
+    std::vector<uint8_t> joined(cap);
+    size_t len = 0;
+    if (zkhip_prove_fri16_join_segments(jk.ctx, jk.lift_key, jk.key, ptrs.data(), lens.data(), n, plan.log_n, plan.width, pvs.data(), pvs.size(), &prm, &sh.outer, &sh.outer, joined.data(),
+                                        cap, &len) != ZKHIP_OK)
+        fail_zkhip("zkhip_prove_fri16_join_segments");
+    joined.resize(len);
+    int reason = 0;
+    if (zkhip_verify_fri16_join(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, joined.data(), len, pvs.data(), pvs.size(), n, jk.vk, &sh.outer, &reason) != ZKHIP_OK)
+        fail_zkhip("zkhip_verify_fri16_join");          // sp1.rs:120: the prover checks its own proof
+    jg.done = true;
+    std::vector<uint8_t> tail(36);
+    std::memcpy(tail.data(), jk.vk, 32);
+    const uint32_t cnt = plan.shards;
+    std::memcpy(tail.data() + 32, &cnt, 4);
+    return pack_shard_proofs({std::move(joined), tail}, BATCH_FLAG_SYNTHETIC | BATCH_FLAG_COMPRESSED | BATCH_FLAG_R0_JOINED);
 }
 
 // ---- synthetic shards in SP1's shard STRUCTURE (MachinePlan): the keyed machine, its shard proofs, the machine-mode compress stage ----
@@ -1074,13 +1134,7 @@ ProveResult HipGuestProver::prove_inner(const GuestInput& input, const std::vect
     if (plan_.shards == 0) throw std::runtime_error("shard plan is empty");
     if (devices_.empty()) throw std::runtime_error("device list is empty");
     zkhip_params prm{1, plan_.num_queries, plan_.pow_bits, 0, 0, 0, 0, 0};
-    if (backend_ == Backend::Risc0) {
-        // RISC Zero's shape; the final polynomial shrinks for segments too small for 256 coefficients
-        int lf = 8;
-        while (lf > plan_.log_n || (plan_.log_n - lf) % 4 != 0) lf--;
-        const bool defaults = plan_.num_queries == 100 && plan_.pow_bits == 16;
-        prm = zkhip_params{2, defaults ? 50 : plan_.num_queries, defaults ? 0 : plan_.pow_bits, 0, 4, lf, 24, 0};
-    }
+    if (backend_ == Backend::Risc0) prm = segment_params(plan_);
     const size_t cap = zkhip_proof_size(plan_.log_n, plan_.width, &prm, 9);
     if (cap == 0) throw std::runtime_error(std::string("bad shard plan: ") + zkhip_last_error());
     uint64_t seed = 0;
@@ -1154,8 +1208,8 @@ ProveResult HipGuestProver::prove_inner(const GuestInput& input, const std::vect
     }
     if (failed.load()) throw std::runtime_error(first_error);
     if (compress_) {
-        if (backend_ != Backend::Sp1) throw std::runtime_error("with_compress: the shard verifier takes SP1-shape shard proofs");
-        r.proof = compress_shard_proofs(devices_, plan_, prm, digest, proofs);
+        // SP1: core -> compress (the shard verifier machine); RISC Zero: segments -> lift -> join (prover.rs:88-93), on the first device
+        r.proof = backend_ == Backend::Sp1 ? compress_shard_proofs(devices_, plan_, prm, digest, proofs) : join_segment_proofs(devices_[0], plan_, prm, digest, proofs);
         r.ok = true;
         return r;
     }
@@ -1186,6 +1240,18 @@ int verify_compressed_blob(const std::vector<uint8_t>& blob, const ShardPlan& pl
     uint32_t cnt = 0;
     std::memcpy(&cnt, entries.back().data() + 32, 4);
     if (cnt != plan.shards || cnt == 0 || std::memcmp(entries.back().data(), key, 32) != 0) return -1;        // (the key is the CALLER's: the blob's copy is informative)
+    if (flags & BATCH_FLAG_R0_JOINED) {
+        // segments -> lift -> join: ONE proof, checked from (the segments' shape, their public values, the join's key) -- no byte of a segment or lift proof
+        if (entries.size() != 2 || (flags & BATCH_FLAG_TREE)) return -1;
+        const SegmentShape sh = segment_shape(plan, segment_params(plan));
+        const std::vector<uint32_t> dg = request_digest(cbor, elf);
+        std::vector<uint32_t> pvs;
+        for (uint32_t s = 0; s < cnt; s++) { pvs.insert(pvs.end(), dg.begin(), dg.end()); pvs.push_back(s); }
+        int why = 0;
+        const int rc = zkhip_verify_fri16_join(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, entries[0].data(), entries[0].size(), pvs.data(), pvs.size(), cnt, key, &sh.outer, &why);
+        if (reason) *reason = why;
+        return rc == ZKHIP_OK ? 0 : -2;
+    }
     const uint32_t J = compress_join_size(plan), n_joins = (cnt + J - 1) / J;
     const std::vector<uint32_t> digest = request_digest(cbor, elf);
     const zkhip_params outer{1, plan.num_queries, plan.pow_bits, 0, 0, 0, 0, 0};
@@ -1237,6 +1303,12 @@ bool compress_key(int device, const ShardPlan& plan, uint32_t key_out[8], std::s
 }
 
 // the same key on the host's cores: no context, no device (zkhip_shard_verifier_key_host) -- what a verifier without a GPU calls
+bool r0_join_key_host(const ShardPlan& plan, uint32_t key_out[8], std::string* error) {
+    const SegmentShape sh = segment_shape(plan, segment_params(plan));
+    const bool ok = plan.shards && zkhip_fri16_join_key_host(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, plan.shards, &sh.outer, key_out) == ZKHIP_OK;
+    if (!ok && error) *error = plan.shards ? zkhip_last_error() : "shard plan is empty";
+    return ok;
+}
 bool compress_key_host(const ShardPlan& plan, uint32_t key_out[8], std::string* error) {
     const zkhip_params outer{1, plan.num_queries, plan.pow_bits, 0, 0, 0, 0, 0};
     const bool ok = zkhip_shard_verifier_key_host(plan.log_n, plan.width, (size_t)plan.num_queries, plan.pow_bits, 9, compress_join_size(plan), &outer, key_out) == ZKHIP_OK;
@@ -1276,7 +1348,7 @@ void release_cached() {
     { std::lock_guard<std::mutex> lk(g_slots_mu); all.swap(g_slots); }
     std::vector<JoinKey> keys;
     { std::lock_guard<std::mutex> lk(g_slots_mu); keys.swap(g_join_keys); }
-    for (auto& k : keys) { zkhip_machine_key_destroy(k.key); zkhip_ctx_destroy(k.ctx); }
+    for (auto& k : keys) destroy_join_key(k);
     std::vector<MachineJoinKey> mkeys;
     { std::lock_guard<std::mutex> lk(g_slots_mu); mkeys.swap(g_machine_join_keys); }
     for (auto& k : mkeys) { zkhip_machine_key_destroy(k.key); zkhip_ctx_destroy(k.ctx); }
@@ -1393,6 +1465,23 @@ int zktls_guest_prove_r0(int device, int mode, const zktls_shard_plan* plan, con
                          const uint8_t* elf, size_t elf_len, uint8_t** output, size_t* output_len, uint8_t** proof,
                          size_t* proof_len, char* err, size_t err_cap) {
     return guest_prove(zktls::Backend::Risc0, device, mode, plan, cbor, cbor_len, elf, elf_len, output, output_len, proof, proof_len, err, err_cap);
+}
+// ... with its compress stage behind it (Risc0HipGuestProver::with_compress; prover.rs:88-93: segments -> lift -> join): the blob carries ONE proof (flags
+// SYNTHETIC | COMPRESSED | R0_JOINED).  zktls_verify_compressed_blob checks it on the host from (plan, input, ELF, zktls_r0_join_key_host's key)
+int zktls_guest_prove_r0_compressed(int device, int mode, const zktls_shard_plan* plan, const uint8_t* cbor, size_t cbor_len, const uint8_t* elf, size_t elf_len,
+                                    uint8_t** output, size_t* output_len, uint8_t** proof, size_t* proof_len, char* err, size_t err_cap) {
+    if (!plan) { if (err && err_cap) { std::strncpy(err, "compress needs a shard plan", err_cap - 1); err[err_cap - 1] = 0; } return -1; }
+    return guest_prove(zktls::Backend::Risc0, device, mode, plan, cbor, cbor_len, elf, elf_len, output, output_len, proof, proof_len, err, err_cap, true);
+}
+// the join's key for the plan (its shape and segment count), on the host's cores: no device, no context
+int zktls_r0_join_key_host(const zktls_shard_plan* plan, uint32_t key[8], char* err, size_t err_cap) {
+    if (!plan || !key) { if (err && err_cap) { std::strncpy(err, "the join's key needs a shard plan", err_cap - 1); err[err_cap - 1] = 0; } return -1; }
+    zktls::ShardPlan sp;
+    sp.log_n = plan->log_n; sp.width = plan->width; sp.shards = plan->shards; sp.num_queries = plan->num_queries; sp.pow_bits = plan->pow_bits;
+    std::string e;
+    if (zktls::r0_join_key_host(sp, key, &e)) return 0;
+    if (err && err_cap) { std::strncpy(err, e.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
 }
 // the input-commitment guest (HipGuestProver::with_input_commitment): output = SHA-256 of the CBOR input, proof = a batch blob
 // flagged INPUT_SHA256 holding one SHA-256 chip proof; backend 0 SP1 shape, 1 RISC Zero shape

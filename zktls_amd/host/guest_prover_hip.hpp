@@ -128,6 +128,10 @@ public:
     // proof, entry 1 = 8 LE words of the shape's key + the shard count).  SP1 backend, synthetic shards, width a multiple of 8.  More shards
     // than one join holds (136 of the headline shape) take several joins of ONE shape (compress_join_size) and ONE more proof above them (the tree; blob flag TREE).  verify_compressed_blob checks
     // such a blob on the host from (plan, input, ELF, key): the shard proofs are gone.
+    // Backend::Risc0 (Risc0HipGuestProver): segments -> lift -> join (prover.rs:88-93) -- every segment proof is lifted under the shape's key and the lift proofs are
+    // joined into ONE proof (zkhip_prove_fri16_join_segments; the lift key and the join key are made once per (shape, segment count) on a pooled context), checked
+    // with zkhip_verify_fri16_join like sp1.rs:120; blob flags SYNTHETIC | COMPRESSED | R0_JOINED.  More segments than zkhip_fri16_join_max_proofs are refused with a
+    // message that names the bound (a tree above the join is not built).  verify_compressed_blob checks the blob from (plan, input, ELF, r0_join_key_host's key).
     // With with_input_commitment() and an input beyond one chip proof (1 MiB): the chain of SHA-256 shard proofs becomes ONE proof the same way
     // (zkhip_prove_sha256_compressed; blob flags INPUT_SHA256 | CHAINED | COMPRESSED) -- verify_commitment_blob checks it from (output, blob) alone.
     HipGuestProver& with_compress() { compress_ = true; return *this; }
@@ -184,6 +188,7 @@ uint32_t compress_join_size(const ShardPlan& plan);
 void set_compress_join_size(uint32_t shard_proofs_per_join);
 constexpr uint32_t BATCH_FLAG_TREE = 32u;            // with COMPRESSED: several joins were needed and were joined again: entry 0 = the ONE proof above them
 constexpr uint32_t BATCH_FLAG_MACHINE = 64u;         // with SYNTHETIC: every shard is a keyed-MACHINE proof (MachinePlan); with COMPRESSED the joins are machine-mode proofs and the last entry = the join's key (8 LE words) + the shard count
+constexpr uint32_t BATCH_FLAG_R0_JOINED = 128u;      // with SYNTHETIC | COMPRESSED: a joined r0 proof -- RISC Zero-shape segment proofs lifted and joined (entry 0; last entry = the join's key (8 LE words) + the segment count)
 constexpr uint32_t BATCH_FLAG_KEYED = 4u;            // with INPUT_SHA256: the proof is the keyed SHA-256 MACHINE's (chip + range table), checked against a vk
 // a consumer's check of an input-commitment blob on the CPU: the blob's proof(s) against the claimed output (SHA-256 of the input).
 // The caller says what it EXPECTS, the blob's own flags only have to agree: a 64-byte `vk` (from setup) means "a KEYED proof under this
@@ -207,6 +212,8 @@ ProveResult compress_blob(int device, const ShardPlan& plan, const std::vector<u
 bool compress_key(int device, const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
 // the same key computed on the host's cores (no device, no context): a verifier that owns no GPU checks a compressed blob with this and verify_compressed_blob
 bool compress_key_host(const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
+// the key of the join over the plan's segments (Risc0HipGuestProver::with_compress), on the host: zkhip_fri16_join_key_host on the plan's lift shape and segment count
+bool r0_join_key_host(const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
 // A MACHINE blob against the request it was made for, on the host: vk = the 64 bytes setup() / prove() returned (the machine key's root + the program's
 // digest, which must be request_digest("", elf)).  Plain: every shard proof under (the plan's machine, digest | s, the key).  COMPRESSED: the join's key
 // -- and with TREE the top's -- is DERIVED here from (the plan, the key's root, the shard count): no byte of a shard proof is needed.
