@@ -34,6 +34,9 @@ chain of two groups (n = 4) -- and for W % 4 != 0 are not live: test_shapes_belo
   ..._batch twins              the same inside a lock-step batch               whole proofs: W 8, 64, 132, 388, 48 (M 2118: terms<128>
                                                                                in the batch, wide<16> outside), 1024
 
+Pitched rows: chain<64,4>, chain<128,8>, terms<128>, terms<256> and wide<16> each once with ld = W + 4 (the form stays) and once with
+ld = W + 2 (rows off 16-byte boundaries: the same program must reach the interpreter).
+
 A reviewer can confirm one row with `rocprofv3 --kernel-trace --stats -- python -m pytest -m gpu <file>::<test>[<id>]` on a stage-level
 case (whole-proof cases are not run under the profiler: profiles/r04_segv.md).
 """
@@ -119,6 +122,14 @@ STAGE_CASES = [
     _case("wide<16>", 48, 6, counts=WIDE_C, lqd=2, pairs=PAIRS_C),
     _case("wide<16>", 48, 6, counts=WIDE_B, n_public=300, pairs=PAIRS_B),
     _case("wide<16>", 48, 6, saturated=(96, 1952)),
+    # ---- pitched rows under every term-parallel form and the wide form: ld = W + 4 keeps 16-byte aligned rows and the form (the
+    # padding holds the sentinel: a row step of W, or a read past the row's end, changes the result); ld = W + 2 must fall back to the
+    # interpreter (stark.hip launch_quotient_air `fits`, prover.cpp run_quotient_air `wide`)
+    _case("chain<64,4>", 20, 5, ld=24), _case("interpreter", 20, 5, ld=22),
+    _case("chain<128,8>", 388, 5, ld=392), _case("interpreter", 388, 5, ld=390),
+    _case("terms<128>", 48, 5, M=2048, ld=52), _case("interpreter", 48, 5, M=2048, ld=50),
+    _case("terms<256>", 48, 5, M=9000, ld=52), _case("interpreter", 48, 5, M=9000, ld=50),
+    _case("wide<16>", 48, 6, counts=WIDE_A, ld=52), _case("interpreter", 48, 6, counts=WIDE_A, ld=50),
 ]
 
 

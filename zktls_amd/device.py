@@ -67,6 +67,7 @@ class DeviceView:
     def __init__(self, buf, words):
         self.base = buf
         self.ptr = buf.ptr + 4 * int(words)
+        self.nwords = buf.nwords - int(words)       # to the end of the allocation: the wrappers that size a call by the buffer take a view too
 
 
 class Context:
@@ -119,24 +120,29 @@ class Context:
         return buf
 
     # ---- synthetic data
-    def fill_uniform(self, seed, log_n, width, out=None):
-        out = out or self.alloc(width << log_n)
-        check(self.lib.zkhip_fill_uniform(self.handle, seed, log_n, width, C.c_void_p(out.ptr), width))
+    # (ld / in_ld / out_ld below: a matrix's row pitch in words when it exceeds its width; matrices are DeviceBuffers or DeviceViews)
+    def fill_uniform(self, seed, log_n, width, out=None, ld=None):
+        ld = ld or width
+        out = out or self.alloc(ld << log_n)
+        check(self.lib.zkhip_fill_uniform(self.handle, seed, log_n, width, C.c_void_p(out.ptr), ld))
         return out
 
-    def gen_trace_logup_cross(self, seed, shard, partner_shard, log_n, width, partner_width, pairs, out=None):
-        out = out or self.alloc(width << log_n)
-        check(self.lib.zkhip_gen_trace_logup_cross(self.handle, seed, shard, partner_shard, log_n, width, partner_width, pairs, C.c_void_p(out.ptr), width))
+    def gen_trace_logup_cross(self, seed, shard, partner_shard, log_n, width, partner_width, pairs, out=None, ld=None):
+        ld = ld or width
+        out = out or self.alloc(ld << log_n)
+        check(self.lib.zkhip_gen_trace_logup_cross(self.handle, seed, shard, partner_shard, log_n, width, partner_width, pairs, C.c_void_p(out.ptr), ld))
         return out
 
-    def gen_trace(self, seed, shard, log_n, width, out=None):
-        out = out or self.alloc(width << log_n)
-        check(self.lib.zkhip_gen_trace(self.handle, seed, shard, log_n, width, C.c_void_p(out.ptr), width))
+    def gen_trace(self, seed, shard, log_n, width, out=None, ld=None):
+        ld = ld or width
+        out = out or self.alloc(ld << log_n)
+        check(self.lib.zkhip_gen_trace(self.handle, seed, shard, log_n, width, C.c_void_p(out.ptr), ld))
         return out
 
-    def gen_trace_logup(self, seed, shard, log_n, width, pairs, out=None):
-        out = out or self.alloc(width << log_n)
-        check(self.lib.zkhip_gen_trace_logup(self.handle, seed, shard, log_n, width, pairs, C.c_void_p(out.ptr), width))
+    def gen_trace_logup(self, seed, shard, log_n, width, pairs, out=None, ld=None):
+        ld = ld or width
+        out = out or self.alloc(ld << log_n)
+        check(self.lib.zkhip_gen_trace_logup(self.handle, seed, shard, log_n, width, pairs, C.c_void_p(out.ptr), ld))
         return out
 
     def perm_trace(self, trace, log_n, width, pairs, gamma, beta, out=None, ld=None):
@@ -149,9 +155,10 @@ class Context:
         return out
 
     # ---- NTT / LDE
-    def dft(self, src, log_n, width, inverse=False, bitrev_out=False, out=None):
-        out = out or self.alloc(width << log_n)
-        check(self.lib.zkhip_dft(self.handle, C.c_void_p(src.ptr), width, C.c_void_p(out.ptr), width, log_n, width,
+    def dft(self, src, log_n, width, inverse=False, bitrev_out=False, out=None, in_ld=None, out_ld=None):
+        in_ld, out_ld = in_ld or width, out_ld or width
+        out = out or self.alloc(out_ld << log_n)
+        check(self.lib.zkhip_dft(self.handle, C.c_void_p(src.ptr), in_ld, C.c_void_p(out.ptr), out_ld, log_n, width,
                                  int(inverse), int(bitrev_out)))
         return out
 
@@ -159,7 +166,7 @@ class Context:
         out_ld = out_ld or width
         in_ld = in_ld or width
         out = out or self.alloc(out_ld << (log_n + log_blowup))
-        check(self.lib.zkhip_coset_lde(self.handle, C.c_void_p(src.ptr), in_ld, out.offset(out_col), out_ld,
+        check(self.lib.zkhip_coset_lde(self.handle, C.c_void_p(src.ptr), in_ld, C.c_void_p(out.ptr + 4 * int(out_col)), out_ld,
                                        log_n, width, log_blowup, shift))
         return out
 
@@ -172,31 +179,33 @@ class Context:
     def poseidon2_permute(self, states):
         check(self.lib.zkhip_poseidon2_permute(self.handle, C.c_void_p(states.ptr), states.nwords // 16))
 
-    def _mat_args(self, mats):
+    def _mat_args(self, mats, n_fixed=2):
+        """mats: tuples of n_fixed entries (buffer or view, width, ...), each optionally followed by the row pitch (default: the width)"""
         n = len(mats)
         ptrs = (C.c_void_p * n)(*[m[0].ptr for m in mats])
-        lds = (C.c_size_t * n)(*[m[1] for m in mats])
+        lds = (C.c_size_t * n)(*[m[n_fixed] if len(m) > n_fixed else m[1] for m in mats])
         ws = (C.c_uint32 * n)(*[m[1] for m in mats])
         return ptrs, lds, ws
 
     def hash_rows(self, mats, height, out=None):
-        """mats: list of (DeviceBuffer, width) with contiguous rows"""
+        """mats: list of (buffer or view, width) with contiguous rows, or (buffer or view, width, ld)"""
         out = out or self.alloc(8 * height)
         ptrs, lds, ws = self._mat_args(mats)
         check(self.lib.zkhip_hash_rows(self.handle, ptrs, lds, ws, len(mats), height, C.c_void_p(out.ptr)))
         return out
 
     def merkle_commit(self, mats, log_h, out=None):
+        """mats: as for hash_rows"""
         out = out or self.alloc(8 * ((2 << log_h) - 1))
         ptrs, lds, ws = self._mat_args(mats)
         check(self.lib.zkhip_merkle_commit(self.handle, ptrs, lds, ws, len(mats), log_h, C.c_void_p(out.ptr)))
         return out
 
     def merkle_commit_mixed(self, mats, out=None):
-        """mats: list of (DeviceBuffer, width, log_height); tree sized for the tallest"""
+        """mats: list of (buffer or view, width, log_height) or (buffer or view, width, log_height, ld); tree sized for the tallest"""
         log_h = max(m[2] for m in mats)
         out = out or self.alloc(8 * ((2 << log_h) - 1))
-        ptrs, lds, ws = self._mat_args(mats)
+        ptrs, lds, ws = self._mat_args(mats, 3)
         lhs = (C.c_int * len(mats))(*[m[2] for m in mats])
         check(self.lib.zkhip_merkle_commit_mixed(self.handle, ptrs, lds, ws, lhs, len(mats), C.c_void_p(out.ptr)))
         return out
@@ -291,17 +300,17 @@ class Context:
         return buf
 
     # ---- STARK stages
-    def quotient_values(self, lde, log_n, width, alpha, out=None):
+    def quotient_values(self, lde, log_n, width, alpha, out=None, ld=None):
         out = out or self.alloc(4 << (log_n + 1))
         a = to_monty(np.asarray(alpha, dtype=np.uint32))
-        check(self.lib.zkhip_quotient_values(self.handle, C.c_void_p(lde.ptr), width, log_n, width,
+        check(self.lib.zkhip_quotient_values(self.handle, C.c_void_p(lde.ptr), ld or width, log_n, width,
                                              a.ctypes.data_as(u32p), C.c_void_p(out.ptr)))
         return out
 
-    def open_at(self, lde, log_n, log_blowup, width, points):
+    def open_at(self, lde, log_n, log_blowup, width, points, ld=None):
         pts = to_monty(np.ascontiguousarray(points, dtype=np.uint32).reshape(-1, 4))
         out = np.empty((pts.shape[0], width, 4), dtype=np.uint32)
-        check(self.lib.zkhip_open_at(self.handle, C.c_void_p(lde.ptr), width, log_n, log_blowup, width,
+        check(self.lib.zkhip_open_at(self.handle, C.c_void_p(lde.ptr), ld or width, log_n, log_blowup, width,
                                      pts.ctypes.data_as(u32p), pts.shape[0], out.ctypes.data_as(u32p)))
         return from_monty(out)
 
@@ -344,23 +353,23 @@ class Context:
         check(self.lib.zkhip_grind(self.handle, st.ctypes.data_as(u32p), int(slot), int(bits), int(base), int(count), C.byref(res)))
         return res.value
 
-    def commit(self, trace, log_n, width, log_blowup=1, hash_width=16):
+    def commit(self, trace, log_n, width, log_blowup=1, hash_width=16, ld=None):
         """coset LDE + Merkle tree + root in one call; returns (lde, tree, root[8] canonical)"""
         h = log_n + log_blowup
         lde, tree = self.alloc(width << h), self.alloc(8 * ((2 << h) - 1))
         root = np.zeros(8, dtype=np.uint32)
-        check(self.lib.zkhip_commit(self.handle, C.c_void_p(trace.ptr), width, log_n, width, log_blowup, hash_width,
+        check(self.lib.zkhip_commit(self.handle, C.c_void_p(trace.ptr), ld or width, log_n, width, log_blowup, hash_width,
                                     C.c_void_p(lde.ptr), C.c_void_p(tree.ptr), root.ctypes.data_as(u32p)))
         return lde, tree, root
 
     # ---- whole shard
-    def prove_shard(self, trace, log_n, width, public_values=(), params=None):
+    def prove_shard(self, trace, log_n, width, public_values=(), params=None, ld=None):
         params = params or Params(1, 100, 16, 0)
         pv = np.ascontiguousarray(np.array(public_values, dtype=np.uint32))
         size = self.lib.zkhip_proof_size(log_n, width, C.byref(params), pv.size)
         buf = np.empty(size, dtype=np.uint8)
         got = C.c_size_t(0)
-        check(self.lib.zkhip_prove_shard(self.handle, C.c_void_p(trace.ptr), width, log_n, width,
+        check(self.lib.zkhip_prove_shard(self.handle, C.c_void_p(trace.ptr), ld or width, log_n, width,
                                          pv.ctypes.data_as(u32p), pv.size, C.byref(params),
                                          buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
