@@ -472,7 +472,14 @@ int zkhip_verify_fri16_identity(const uint8_t* proof, size_t len, int R, int F, 
  * zkhip_prove_fri16_lift_segment: segment proof in, lift proof out -- ONE pass of the host verifier over `proof` (log_n, width, public_values, inner_prm) with every
  * fold-16 view attached, then the lift prover under outer_prm.  It fails with the host verifier's code and message when the inner proof does not verify, and with
  * zkhip_fri16_view_head's message on a form that view does not take.
- * STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the wiring into shard_verifier.inl, a batch entry over the lock-step lanes. */
+ * zkhip_prove_fri16_lift_batch: many segment proofs of ONE shape (log_n, width, n_public, inner_prm) lifted in one call -- what stands between the segments and the
+ * join.  Per job the views of its segment proof (host, on a small pool ahead of the device work) and the lift prover under the shape's key, which is made once per
+ * pooled context and kept with it; jobs are dealt over `devices` (NULL / 0: every visible device) like every batch of this library -- lock-step lanes
+ * (zkhip_set_lockstep) when there are at least two jobs per device, otherwise `in_flight_per_device` contexts per device.  Every proof is byte for byte
+ * zkhip_prove_fri16_lift_segment's; vk receives the shape's key (zkhip_fri16_lift_key_host's words).  A segment that does not verify fails ITS job with the host
+ * verifier's code and message and proof_len 0; the others are proven.  verify != 0: every proof is checked with zkhip_verify_fri16_lift right after it was made.
+ * Returns the status of the lowest failing job (every job still gets its own).
+ * STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the wiring into shard_verifier.inl. */
 size_t zkhip_fri16_lift_describe(int R, int F, int log_blowup, size_t n_queries, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public, int which, int kind,
                                  uint32_t* out, size_t cap_words, int* log_rows, uint32_t* main_width, uint32_t* pre_width, int* table);
 int zkhip_fri16_lift_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
@@ -492,6 +499,14 @@ int zkhip_verify_fri16_lift(const uint8_t* proof, size_t len, int R, int F, int 
                             uint32_t n_inner_public, const uint32_t* inner_public, const uint32_t vk[8], const zkhip_params* prm, int* reason);
 int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
                                    size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len);
+typedef struct {
+    const uint8_t* segment_proof; size_t segment_proof_len; /* in: a segment proof of this library (fold by 16) */
+    const uint32_t* public_values;                          /* in: n_public words */
+    uint8_t* proof; size_t proof_cap;                       /* in: >= zkhip_fri16_lift_proof_size */
+    size_t proof_len; int status;                           /* out */
+} zkhip_fri16_lift_job;
+int zkhip_prove_fri16_lift_batch(const int* devices, int n_devices, zkhip_fri16_lift_job* jobs, int n_jobs, int log_n, uint32_t width, size_t n_public,
+                                 const zkhip_params* inner_prm, const zkhip_params* outer_prm, int in_flight_per_device, int verify, uint32_t vk[8]);
 
 /* ---- the JOIN of fold-16 lift proofs: N lift proofs of one shape -> ONE proof (RISC Zero: segments -> lift -> join) ----
  * A lift proof is a version-11 proof of the thirteen-table lift machine and the lift key depends on the shape alone, so N lift proofs of one shape are N proofs of ONE
@@ -506,8 +521,9 @@ int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key,
  * with the lift's own message.
  * zkhip_verify_fri16_join is host only and takes (shape, public values, key): no byte of a lift or segment proof.
  * zkhip_prove_fri16_join_segments: segment proofs in, ONE proof out -- the lift proofs are made one after the other on ctx (zkhip_prove_fri16_lift_segment under
- * lift_key), then joined under join_key.  A segment that does not verify fails with the host verifier's code and a message that names the segment.
- * STILL OUTSIDE: a tree above the join for more than 64 segments, a lift batch over the lock-step lanes. */
+ * lift_key), then joined under join_key.  A segment that does not verify fails with the host verifier's code and a message that names the segment.  The faster
+ * route to the same bytes: zkhip_prove_fri16_lift_batch (the lifts side by side on the lock-step lanes), then zkhip_prove_fri16_join.
+ * STILL OUTSIDE: a tree above the join for more than 64 segments. */
 int zkhip_fri16_join_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
                               const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, uint32_t vk[8]);
 int zkhip_fri16_join_setup(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,

@@ -18,6 +18,18 @@ pub struct ZkhipShardJob {
     pub status: i32,
 }
 
+/// include/zkhip_chips.h `zkhip_fri16_lift_job`: one segment proof of `zkhip_prove_fri16_lift_batch`
+#[repr(C)]
+pub struct ZkhipFri16LiftJob {
+    pub segment_proof: *const u8,
+    pub segment_proof_len: usize,
+    pub public_values: *const u32,
+    pub proof: *mut u8,
+    pub proof_cap: usize,
+    pub proof_len: usize,
+    pub status: c_int,
+}
+
 #[repr(C)]
 pub struct ZkhipCtx {
     _private: [u8; 0],
@@ -210,6 +222,16 @@ extern "C" {
     /// the lift machine).  Shape arguments: layers, log_final, log_blowup, queries, the segments' hash width (24), their grinding bits, trace width, public values.
     pub fn zkhip_fri16_lift_key(ctx: *mut ZkhipCtx, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
                                 n_inner_public: u32, prm: *const ZkhipParams, key: *mut *mut ZkhipMachineKey, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_lift_proof_size(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_pow_bits: c_int, trace_width: u32, n_inner_public: u32,
+                                       prm: *const ZkhipParams) -> usize;
+    /// many segment proofs of one shape lifted in one call: dealt over `devices` (null + 0: every visible device) on the lock-step lanes, the shape's key with the
+    /// library's pooled contexts; every proof is zkhip_prove_fri16_lift_segment's bytes, `vk` the shape's lift key
+    pub fn zkhip_prove_fri16_lift_batch(devices: *const c_int, n_devices: c_int, jobs: *mut ZkhipFri16LiftJob, n_jobs: c_int, log_n: c_int, width: u32, n_public: usize,
+                                        inner_prm: *const ZkhipParams, outer_prm: *const ZkhipParams, in_flight_per_device: c_int, verify: c_int, vk: *mut u32) -> c_int;
+    pub fn zkhip_prove_fri16_join(ctx: *mut ZkhipCtx, key: *const ZkhipMachineKey, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int,
+                                  inner_pow_bits: c_int, trace_width: u32, n_inner_public: u32, lift_prm: *const ZkhipParams, lift_proofs: *const *const u8, lens: *const usize,
+                                  n_proofs: usize, public_values: *const u32, n_public_total: usize, join_prm: *const ZkhipParams, out: *mut u8, cap: usize,
+                                  len: *mut usize) -> c_int;
     pub fn zkhip_fri16_join_setup(ctx: *mut ZkhipCtx, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
                                   n_inner_public: u32, lift_prm: *const ZkhipParams, n_proofs: usize, join_prm: *const ZkhipParams, key: *mut *mut ZkhipMachineKey,
                                   vk: *mut u32) -> c_int;

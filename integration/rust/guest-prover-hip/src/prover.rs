@@ -470,34 +470,51 @@ fn segment_lift_shape(log_n: i32, inner: &ZkhipParams) -> Result<(i32, i32, i32,
 /// RISC Zero's compress stage (prover.rs:88-93: segments -> lift -> join; the C++ mirror's `Risc0HipGuestProver::with_compress`): every segment proof lifted under the
 /// shape's key, the lift proofs joined into ONE proof.  `public_values`: `n_public` per segment, in segment order.  More segments than
 /// `zkhip_fri16_join_max_proofs` are refused (a tree above the join is not built).  Returns the joined proof and the join's key; `verify_joined_segments` then needs
-/// no byte of a segment or lift proof.
-pub fn join_segments(ctx: &Context, proofs: &[Vec<u8>], log_n: i32, width: u32, public_values: &[u32], n_public: usize, inner: &ZkhipParams, lift: &ZkhipParams,
-                     join: &ZkhipParams) -> Result<(Vec<u8>, [u32; 8])> {
+/// no byte of a segment or lift proof.  The lifts are ONE call (`zkhip_prove_fri16_lift_batch`: side by side on the lock-step lanes of `devices` -- empty: every
+/// visible device --, the shape's lift key with the library's pooled contexts); the join runs on `ctx`.
+pub fn join_segments(ctx: &Context, devices: &[i32], proofs: &[Vec<u8>], log_n: i32, width: u32, public_values: &[u32], n_public: usize, inner: &ZkhipParams,
+                     lift: &ZkhipParams, join: &ZkhipParams) -> Result<(Vec<u8>, [u32; 8])> {
     anyhow::ensure!(!proofs.is_empty() && public_values.len() == proofs.len() * n_public, "join_segments: one public-value list per segment");
     let (r, f, b, q, hw, pb) = segment_lift_shape(log_n, inner)?;
     let n = proofs.len();
     let most = unsafe { ffi::zkhip_fri16_join_max_proofs(r, f, b, q, hw, pb, width, n_public as u32, lift) };
     anyhow::ensure!(most > 0, "join_segments: the lift does not take this shape");
     anyhow::ensure!(n <= most, "join_segments: {} segments, one join takes at most {} (a tree above the join is not built)", n, most);
-    let (mut lift_key, mut join_key): (*mut ffi::ZkhipMachineKey, *mut ffi::ZkhipMachineKey) = (std::ptr::null_mut(), std::ptr::null_mut());
-    let (mut lift_vk, mut vk) = ([0u32; 8], [0u32; 8]);
-    check(unsafe { ffi::zkhip_fri16_lift_key(ctx.raw(), r, f, b, q, hw, pb, width, n_public as u32, lift, &mut lift_key, lift_vk.as_mut_ptr()) }, "zkhip_fri16_lift_key")?;
-    let rc = unsafe { ffi::zkhip_fri16_join_setup(ctx.raw(), r, f, b, q, hw, pb, width, n_public as u32, lift, n, join, &mut join_key, vk.as_mut_ptr()) };
-    if rc != 0 {
-        unsafe { ffi::zkhip_machine_key_destroy(lift_key) };
-        check(rc, "zkhip_fri16_join_setup")?;
-    }
+    // the lifts: one job per segment, every lift proof in a buffer of its own
+    let room = unsafe { ffi::zkhip_fri16_lift_proof_size(r, f, b, q, pb, width, n_public as u32, lift) };
+    anyhow::ensure!(room > 0, "join_segments: the lift does not take this shape");
+    let mut lifted: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; room]).collect();
+    let mut jobs: Vec<ffi::ZkhipFri16LiftJob> = (0..n)
+        .map(|s| ffi::ZkhipFri16LiftJob {
+            segment_proof: proofs[s].as_ptr(),
+            segment_proof_len: proofs[s].len(),
+            public_values: public_values[s * n_public..].as_ptr(),
+            proof: lifted[s].as_mut_ptr(),
+            proof_cap: room,
+            proof_len: 0,
+            status: 0,
+        })
+        .collect();
+    let mut lift_vk = [0u32; 8];
+    let devs = if devices.is_empty() { std::ptr::null() } else { devices.as_ptr() };
+    check(unsafe {
+        ffi::zkhip_prove_fri16_lift_batch(devs, devices.len() as i32, jobs.as_mut_ptr(), n as i32, log_n, width, n_public, inner, lift, 0, 0, lift_vk.as_mut_ptr())
+    }, "zkhip_prove_fri16_lift_batch")?;
+    // the join of the lift proofs on ctx
+    let mut join_key: *mut ffi::ZkhipMachineKey = std::ptr::null_mut();
+    let mut vk = [0u32; 8];
+    check(unsafe { ffi::zkhip_fri16_join_setup(ctx.raw(), r, f, b, q, hw, pb, width, n_public as u32, lift, n, join, &mut join_key, vk.as_mut_ptr()) }, "zkhip_fri16_join_setup")?;
     let cap = unsafe { ffi::zkhip_fri16_join_proof_size(r, f, b, q, hw, pb, width, n_public as u32, lift, n, join) };
-    let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
-    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let ptrs: Vec<*const u8> = lifted.iter().map(|p| p.as_ptr()).collect();
+    let lens: Vec<usize> = jobs.iter().map(|j| j.proof_len).collect();
     let mut out = vec![0u8; cap];
     let mut len = 0usize;
     let rc = unsafe {
-        ffi::zkhip_prove_fri16_join_segments(ctx.raw(), lift_key, join_key, ptrs.as_ptr(), lens.as_ptr(), n, log_n, width, public_values.as_ptr(), public_values.len(), inner, lift,
-                                             join, out.as_mut_ptr(), cap, &mut len)
+        ffi::zkhip_prove_fri16_join(ctx.raw(), join_key, r, f, b, q, hw, pb, width, n_public as u32, lift, ptrs.as_ptr(), lens.as_ptr(), n, public_values.as_ptr(),
+                                    public_values.len(), join, out.as_mut_ptr(), cap, &mut len)
     };
-    unsafe { ffi::zkhip_machine_key_destroy(lift_key); ffi::zkhip_machine_key_destroy(join_key) };
-    check(rc, "zkhip_prove_fri16_join_segments")?;
+    unsafe { ffi::zkhip_machine_key_destroy(join_key) };
+    check(rc, "zkhip_prove_fri16_join")?;
     out.truncate(len);
     verify_joined_segments(&out, log_n, width, public_values, n_public, n, &vk, inner, lift, join)?;      // sp1.rs:120: the prover checks its own proof
     Ok((out, vk))

@@ -64,7 +64,7 @@ EXPORTS = [
     "zkhip_fri16_identity_describe", "zkhip_fri16_identity_key_host", "zkhip_fri16_identity_key", "zkhip_fri16_identity_proof_size", "zkhip_fri16_identity_gen_traces",
     "zkhip_prove_fri16_identity", "zkhip_verify_fri16_identity",
     "zkhip_fri16_lift_describe", "zkhip_fri16_lift_key_host", "zkhip_fri16_lift_key", "zkhip_fri16_lift_proof_size", "zkhip_fri16_lift_gen_tables",
-    "zkhip_prove_fri16_lift", "zkhip_verify_fri16_lift", "zkhip_prove_fri16_lift_segment",
+    "zkhip_prove_fri16_lift", "zkhip_verify_fri16_lift", "zkhip_prove_fri16_lift_segment", "zkhip_prove_fri16_lift_batch",
     "zkhip_fri16_join_key_host", "zkhip_fri16_join_setup", "zkhip_fri16_join_proof_size", "zkhip_fri16_join_max_proofs", "zkhip_prove_fri16_join", "zkhip_verify_fri16_join",
     "zkhip_prove_fri16_join_segments", "zkhip_machine_verifier_gen_eval_rows",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
@@ -108,6 +108,12 @@ class FriJob(C.Structure):
     _fields_ = [("shard_proof", u8p), ("shard_proof_len", C.c_size_t), ("public_values", u32p), ("n_public", C.c_size_t), ("proof", u8p),
                 ("proof_cap", C.c_size_t), ("proof_len", C.c_size_t), ("vk", C.c_uint32 * 8), ("final_value", C.c_uint32 * 4),
                 ("capacity", C.c_uint32 * 8), ("status", C.c_int32)]
+
+
+class Fri16LiftJob(C.Structure):
+    """zkhip_fri16_lift_job: one segment proof of zkhip_prove_fri16_lift_batch (include/zkhip_chips.h)"""
+    _fields_ = [("segment_proof", u8p), ("segment_proof_len", C.c_size_t), ("public_values", u32p), ("proof", u8p), ("proof_cap", C.c_size_t),
+                ("proof_len", C.c_size_t), ("status", C.c_int)]
 
 
 class ShardJob(C.Structure):
@@ -449,6 +455,9 @@ def load():
     L.zkhip_verify_fri16_lift.argtypes = L.zkhip_verify_fri16_head.argtypes
     L.zkhip_prove_fri16_lift_segment.argtypes = [C.c_void_p, C.c_void_p, u8p, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params), C.POINTER(Params), u8p,
                                                  C.c_size_t, C.POINTER(C.c_size_t)]
+    # ... and many of them in one call (the lock-step lanes; the shape's key with the pooled contexts)
+    L.zkhip_prove_fri16_lift_batch.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(Fri16LiftJob), C.c_int, C.c_int, C.c_uint32, C.c_size_t, C.POINTER(Params),
+                                               C.POINTER(Params), C.c_int, C.c_int, u32p]
     # the join of fold-16 lift proofs (machine mode over the lift machine of a shape): the lift key's shape arguments, the lift's outer parameters, n_proofs, the join's
     fri16_jshape = fri16_hshape + [C.POINTER(Params)]
     L.zkhip_fri16_join_key_host.argtypes = fri16_jshape + [C.c_size_t, C.POINTER(Params), u32p]

@@ -145,6 +145,11 @@ struct zkhip_ctx {
     zkhip_machine_key* rec_key = nullptr;
     std::vector<uint64_t> rec_key_sig;
     uint32_t rec_vk[8] = {0};
+    // the fold-16 lift machine's proving key made on this context by zkhip_prove_fri16_lift_batch, with what it is a function of (the shape, the outer
+    // parameters, the Poseidon2 table set)
+    zkhip_machine_key* lift_key = nullptr;
+    std::vector<uint64_t> lift_key_sig;
+    uint32_t lift_vk[8] = {0};
     // grow-only PINNED host block (ctx_host_pinned): work lists that a prover fills on host threads and uploads in one DMA
     void* host_pinned = nullptr;
     size_t host_pinned_bytes = 0;

@@ -49,7 +49,8 @@
 //   LIFT     (zkhip_prove_fri16_lift)      the roots and the final coefficients OUT of the key: they are main columns of ROOTS and COEFFS, made on the device
 //                                          (fri16_lift_tables_kernel) and pinned by the transcript chain alone.  The key is a function of the shape and the public-value
 //                                          count: ONE key per shape states "some valid segment proof of this shape with these public values exists" -- RISC Zero's lift.
-//                                          zkhip_prove_fri16_lift_segment is the call from segment proof to lift proof (tests/fri16_lift_air.py)
+//                                          zkhip_prove_fri16_lift_segment is the call from segment proof to lift proof (tests/fri16_lift_air.py);
+//                                          zkhip_prove_fri16_lift_batch is many of them in one call, side by side on the lock-step lanes (batch.h)
 //   JOIN     (zkhip_prove_fri16_join)      no machine of this file: N lift proofs of one shape are N proofs of ONE keyed machine, which machine mode
 //                                          (machine_verifier.inl) verifies in-circuit.  The entries at the end of the file describe the lift machine to it
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
@@ -63,6 +64,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <condition_variable>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -973,8 +975,8 @@ int build_identity_key_tables(const Shape& s, const uint32_t* final_poly, const 
 // column, not a moved word.  Every multiplicity that gates a tuple with a moved word is preprocessed or constrained (DESIGN.md 3c has the table), and Fiat-Shamir pins
 // the values: the chain starts from zero and absorbs every root and coefficient over a bus.  So the key is a function of the SHAPE and NP alone: it states "some valid
 // segment proof of this shape with THESE public values exists".
-// (The JOIN of several lift proofs is at the end of this file: a shape call over machine mode.)  STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the wiring into
-// shard_verifier.inl, a batch entry.  tests/fri16_lift_air.py writes it again.
+// (The JOIN of several lift proofs and the lift BATCH over the lock-step lanes are at the end of this file.)  STILL OUTSIDE: lookups, version-7 and version-8 inner proofs, the
+// wiring into shard_verifier.inl.  tests/fri16_lift_air.py writes it again.
 int build_lift_key_tables(const Shape& s, std::vector<uint32_t> pre[], const char* who) {
     const std::vector<uint32_t> no_coeffs((size_t)4 << s.F, 0u), no_roots(8 * (size_t)s.R, 0u);
     const uint32_t no_root[8] = {0};
@@ -2464,6 +2466,8 @@ static int fri16_join_verify(const fri16::ShapeArgs& a, int hw, const zkhip_para
     if (reason) *reason = why;
     return rc != ZKHIP_OK && why == 1 ? fri16_join_refused(j, n_proofs, "verify_fri16_join", rc) : rc;      // (reason 1: the arguments, the number of proofs among them)
 }
+// segment proofs in, one proof out, on ONE context: the lift proofs one after the other, then the join.  (The faster route to the same bytes is
+// zkhip_prove_fri16_lift_batch -- the lifts side by side on the lock-step lanes, the key with the pooled contexts -- followed by zkhip_prove_fri16_join.)
 static int fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key, const zkhip_machine_key* join_key, const uint8_t* const* segment_proofs, const size_t* lens,
                                size_t n_proofs, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public_total, const zkhip_params* inner_prm,
                                const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
@@ -2502,6 +2506,139 @@ extern "C" {
 int zkhip_prove_fri16_lift_segment(zkhip_ctx* ctx, const zkhip_machine_key* key, const uint8_t* proof, size_t len, int log_n, uint32_t width, const uint32_t* public_values,
                                    size_t n_public, const zkhip_params* inner_prm, const zkhip_params* outer_prm, uint8_t* out, size_t cap, size_t* out_len) {
     return fri16_lift_segment(ctx, key, proof, len, log_n, width, public_values, n_public, inner_prm, outer_prm, out, cap, out_len);
+}
+
+// ---- many segment proofs lifted in one call: what stands between the segments and the join (RISC Zero: segments -> lift -> join).  Per job: every fold-16 view of
+// the segment proof from ONE pass of the host verifier (on a small pool that runs ahead of the device work), then the lift prover -- fri16_prove at kind LIFT, the body
+// of zkhip_prove_fri16_lift_segment -- under the shape's key, which stays with the pooled context.  A lift proof is a few hundred launches over thirteen small
+// tables: the jobs are dealt over the lock-step lanes (batch.h) like every launch-bound batch of this library, one context per worker otherwise.  All jobs share
+// (log_n, width, n_public, inner_prm): one machine shape, one key.
+int zkhip_prove_fri16_lift_batch(const int* devices, int n_devices, zkhip_fri16_lift_job* jobs, int n_jobs, int log_n, uint32_t width, size_t n_public,
+                                 const zkhip_params* inner_prm, const zkhip_params* outer_prm, int in_flight_per_device, int verify, uint32_t vk[8]) {
+    const char* who = "prove_fri16_lift_batch";
+    if (!jobs || n_jobs < 0 || !inner_prm || !outer_prm || !vk) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": bad arguments");
+    for (int i = 0; i < n_jobs; i++) { jobs[i].status = ZKHIP_ERR_INVALID; jobs[i].proof_len = 0; }
+    std::memset(vk, 0, 32);
+    if (inner_prm->log_fold != 4 || log_n <= inner_prm->log_final || (log_n - inner_prm->log_final) % 4)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": inner_prm is not a fold-by-16 shape with a committed layer at this height");
+    if (n_public > fri16::MAX_NP) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": more than 30 inner public values");
+    const fri16::ShapeArgs a{fri16::LIFT, (log_n - inner_prm->log_final) / 4, inner_prm->log_final, inner_prm->log_blowup, (size_t)inner_prm->num_queries, inner_prm->pow_bits,
+                             width, (uint32_t)n_public};
+    fri16::Shape s;
+    ZK_TRY(fri16::shape_of(a, s));
+    const size_t need = fri16::proof_size(a, outer_prm);
+    if (!need) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": outer_prm gives the lift machine of this shape no proof");
+    std::vector<int> devs;
+    const int rc = resolve_devices(devices, n_devices, who, devs);
+    if (rc == ZKHIP_ERR_NO_DEVICE) {
+        for (int i = 0; i < n_jobs; i++) jobs[i].status = ZKHIP_ERR_NO_DEVICE;
+        return n_jobs == 0 ? ZKHIP_OK : rc;
+    }
+    if (rc != ZKHIP_OK) return rc;
+    if (n_jobs == 0) return ZKHIP_OK;
+    // which way the jobs are dealt, known first: the host threads of the views are what the lanes (or workers) leave of the sixteen CPUs a caller may count on
+    const auto m = fri16::machine_of(s);
+    uint64_t cells = 0;
+    for (int c = 0; c < m->km.n; c++) cells += ((uint64_t)(m->km.widths[c] + m->km.pre_widths[c])) << m->km.log_ns[c];
+    const int nd = (int)devs.size(), max_batch = lockstep_batch();
+    const bool lanes = max_batch > 1 && cells <= LOCKSTEP_MAX_CELLS && n_jobs >= 2 * nd;
+    const int busy = lanes ? lockstep_lanes() * nd : (in_flight_per_device > 0 ? in_flight_per_device : 4) * nd;
+    const int host_cpus = 16 - busy < 2 ? 2 : 16 - busy;
+    const int n_viewers = n_jobs < host_cpus ? n_jobs : (host_cpus > 8 ? 8 : host_cpus);
+    const int view_threads = host_cpus / n_viewers;              // (few jobs: each view's query checks spread over what is left)
+    const int check_threads = lanes ? 1 : (16 / busy < 1 ? 1 : 16 / busy);      // verify: one thread per check on the pool beside the lanes, a worker's share on its own thread
+    // (a) the views: one host pass over every segment proof, ahead of the device work (job i waits for view i only)
+    struct View { Fri16FullView f; int rc = ZKHIP_OK; std::string msg; std::mutex mu; std::condition_variable cv; bool done = false; };
+    std::vector<View> views((size_t)n_jobs);
+    HostPool viewers(n_viewers);
+    for (int i = 0; i < n_jobs; i++)
+        viewers.submit([&, i] {
+            View& v = views[(size_t)i];
+            const zkhip_fri16_lift_job& j = jobs[i];
+            t_query_threads_cap = view_threads;
+            try {
+                if (!j.segment_proof || !j.public_values) v.rc = fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+                else v.rc = fri16_view_all(j.segment_proof, j.segment_proof_len, log_n, width, j.public_values, n_public, inner_prm, v.f);
+                if (v.rc != ZKHIP_OK) v.msg = zkhip_last_error();
+            } catch (const std::bad_alloc&) { v.rc = ZKHIP_ERR_NOMEM; v.msg = std::string(who) + ": out of host memory"; }
+            catch (const std::exception& e) { v.rc = ZKHIP_ERR_INTERNAL; v.msg = std::string(who) + ": " + e.what(); }
+            t_query_threads_cap = 0;
+            { std::lock_guard<std::mutex> lk(v.mu); v.done = true; }
+            v.cv.notify_all();
+        });
+    // (b) the shape's key (once per context) and the proof per job on the devices
+    const std::vector<uint64_t> sig = {(uint64_t)a.R, (uint64_t)a.F, (uint64_t)a.b, (uint64_t)a.Q, (uint64_t)(uint32_t)a.pow_bits, a.W, a.NP, (uint64_t)(uint32_t)inner_prm->hash_width,
+                                       (uint64_t)(uint32_t)outer_prm->log_blowup, (uint64_t)(uint32_t)outer_prm->num_queries, (uint64_t)(uint32_t)outer_prm->pow_bits,
+                                       (uint64_t)(uint32_t)outer_prm->logup_pairs, (uint64_t)(uint32_t)outer_prm->log_fold, (uint64_t)(uint32_t)outer_prm->log_final,
+                                       (uint64_t)(uint32_t)outer_prm->hash_width, (uint64_t)(uint32_t)outer_prm->code_width, zk::g_p2_generation.load()};
+    std::mutex mu;
+    bool have_vk = false;
+    std::unique_ptr<HostPool> checkers;
+    std::vector<std::string> check_msg((size_t)n_jobs);
+    std::vector<char> ran;
+    auto run = [&](zkhip_ctx* ctx, int i) {
+        zkhip_fri16_lift_job& j = jobs[i];
+        View& v = views[(size_t)i];
+        { std::unique_lock<std::mutex> lk(v.mu); v.cv.wait(lk, [&] { return v.done; }); }
+        if (v.rc != ZKHIP_OK) { batch_leave(); j.status = v.rc; set_error(v.msg); return v.rc; }      // (nothing of this job reaches the device; the other members do not wait for it)
+        int r = j.proof && j.proof_cap >= need ? ZKHIP_OK : fail(ZKHIP_ERR_INVALID, std::string(who) + ": proof buffer too small (zkhip_fri16_lift_proof_size)");
+        if (r == ZKHIP_OK && ctx->lift_key && ctx->lift_key_sig != sig) { (void)dev_sync(ctx); zkhip_machine_key_destroy(ctx->lift_key); ctx->lift_key = nullptr; }
+        if (r == ZKHIP_OK && !ctx->lift_key) {
+            fri16::View kv;
+            kv.hash_width = inner_prm->hash_width;
+            r = fri16_key(a, who, ctx, kv, outer_prm, &ctx->lift_key, ctx->lift_vk);
+            if (r == ZKHIP_OK) ctx->lift_key_sig = sig;
+            else ctx->lift_key = nullptr;
+        }
+        if (r == ZKHIP_OK) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!have_vk) { std::memcpy(vk, ctx->lift_vk, 32); have_vk = true; }
+            else if (std::memcmp(vk, ctx->lift_vk, 32) != 0) r = fail(ZKHIP_ERR_INTERNAL, std::string(who) + ": two contexts disagree about the key of the shape");
+        }
+        size_t len = 0;
+        if (r == ZKHIP_OK) {
+            const Fri16FullView& f = v.f;
+            const fri16::View fv{f.hash_width, f.betas.data(), f.final_poly.data(), f.indices.data(), f.values.data(), f.siblings.data(), f.roots.data(), f.paths.data(),
+                                 f.transcript, f.transcript[9], f.trace_rows.data(), f.quotient_rows.data(), f.constants, f.trace_paths.data(), f.quotient_paths.data(),
+                                 f.trace_root, f.quotient_root, j.public_values, f.opened.data()};
+            r = fri16_prove(a, "prove_fri16_lift", ctx, ctx->lift_key, fv, outer_prm, j.proof, j.proof_cap, &len);
+        }
+        batch_leave();                                           // (lock-step batch: the rest is host work)
+        j.status = r;
+        j.proof_len = r == ZKHIP_OK ? len : 0;
+        if (r == ZKHIP_OK && verify) {
+            uint32_t key[8];
+            std::memcpy(key, ctx->lift_vk, 32);
+            auto check = [&jobs, &check_msg, i, len, a, n_public, p = *outer_prm, key, check_threads] {
+                zkhip_fri16_lift_job& jj = jobs[i];
+                const int cap_before = t_query_threads_cap;      // (the checks run beside the lanes or workers: the same budget as the views)
+                t_query_threads_cap = check_threads;
+                const int c = zkhip_verify_fri16_lift(jj.proof, len, a.R, a.F, a.b, a.Q, a.pow_bits, a.W, (uint32_t)n_public, jj.public_values, key, &p, nullptr);
+                t_query_threads_cap = cap_before;
+                if (c != ZKHIP_OK) { jj.status = c; jj.proof_len = 0; check_msg[(size_t)i] = zkhip_last_error(); }
+            };
+            if (checkers && t_batcher) checkers->submit(check);
+            else { check(); r = j.status; if (r != ZKHIP_OK) set_error(check_msg[(size_t)i]); }
+        }
+        return r;
+    };
+    int rcj;
+    if (lanes) {
+        if (verify) checkers.reset(new HostPool(host_cpus > 8 ? 8 : host_cpus));
+        std::vector<int> shape((size_t)n_jobs, 0);
+        rcj = deal_jobs_lockstep(devs.data(), nd, n_jobs, shape.data(), max_batch, lockstep_lanes(), run, ran,
+                                 cells << (outer_prm->log_blowup > 1 ? outer_prm->log_blowup - 1 : 0));
+    } else
+        rcj = deal_jobs(devs.data(), nd, n_jobs, in_flight_per_device, run, ran);
+    std::string msg = rcj != ZKHIP_OK ? zkhip_last_error() : "";
+    viewers.wait();                                              // (a failing call may return before every view was looked at)
+    if (checkers) {
+        checkers->wait();
+        for (int i = 0; i < n_jobs && rcj == ZKHIP_OK; i++)
+            if (!check_msg[(size_t)i].empty()) { rcj = jobs[i].status; msg = check_msg[(size_t)i]; }
+    }
+    if (rcj != ZKHIP_OK) set_error(msg);
+    return rcj;
 }
 
 #define FRI16_JOIN_SHAPE int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public

@@ -1444,6 +1444,38 @@ def prove_fri_indices_batch(shard_proofs, log_n, width, public_values, inner=Non
     return [(keep[i][2][: jobs[i].proof_len], list(jobs[i].vk), list(jobs[i].final_value), list(jobs[i].capacity)) for i in range(n)]
 
 
+def prove_fri16_lift_batch(devices, segments, log_n, width, public_values, inner, outer=None, in_flight=0, verify=False, raise_on_error=True, proof_caps=None):
+    """zkhip_prove_fri16_lift_batch: every segment proof of `segments` (one shape: log_n, width, the length of a public_values entry, inner) lifted in one call, dealt over
+    `devices` (None: every visible device) -> ([lift proof bytes, ...], [status, ...], vk [8]); each proof is prove_fri16_lift_segment's bytes.  A job that fails has an
+    empty proof and its own status; the call then raises with the lowest failing job's code and message unless raise_on_error is False (then the message is
+    zkhip_last_error's).  proof_caps: per job, the room it is given (default: zkhip_fri16_lift_proof_size)"""
+    lib = _lib.load()
+    outer = outer or Params(1, 100, 16)
+    n = len(segments)
+    pvs = [np.ascontiguousarray(np.array(v, dtype=np.uint32)) for v in public_values]
+    assert len(pvs) == n and all(v.size == pvs[0].size for v in pvs)
+    n_public = pvs[0].size if n else 0
+    sh = _fri16_segment_shape(log_n, inner)
+    size = lib.zkhip_fri16_lift_proof_size(*sh, int(inner.pow_bits), width, n_public, C.byref(outer)) if sh else 0
+    jobs = (_lib.Fri16LiftJob * max(n, 1))()
+    keep = []
+    for i, sp in enumerate(segments):
+        a = np.ascontiguousarray(sp, dtype=np.uint8)
+        cap = size if proof_caps is None else int(proof_caps[i])
+        buf = np.empty(max(cap, 1), dtype=np.uint8)
+        keep.append((a, buf))
+        jobs[i].segment_proof = a.ctypes.data_as(u8p); jobs[i].segment_proof_len = a.size
+        jobs[i].public_values = pvs[i].ctypes.data_as(u32p)
+        jobs[i].proof = buf.ctypes.data_as(u8p); jobs[i].proof_cap = cap
+    vk = np.zeros(8, dtype=np.uint32)
+    devs = (C.c_int * len(devices))(*devices) if devices else None
+    rc = lib.zkhip_prove_fri16_lift_batch(devs, len(devices) if devices else 0, jobs, n, log_n, width, n_public, C.byref(inner), C.byref(outer), in_flight, 1 if verify else 0,
+                                          vk.ctypes.data_as(u32p))
+    if raise_on_error:
+        check(rc)
+    return [keep[i][1][: jobs[i].proof_len] for i in range(n)], [int(jobs[i].status) for i in range(n)], vk
+
+
 def prove_shard_verifier_batch(shard_proofs, proofs_per_join, log_n, width, public_values, inner=None, outer=None, devices=None, in_flight=4, verify=False):
     """zkhip_prove_shard_verifier_batch: len(shard_proofs) / proofs_per_join joins of one shape, dealt over `devices`, `in_flight` at a time on each
     -> ([join proof bytes, ...], vk [8]); public_values: one list per shard proof"""

@@ -88,8 +88,8 @@ std::vector<Slot> g_slots;
 // (a machine key belongs to the context that made it: the pair is parked together)
 struct JoinKey { int device; int32_t log_n; uint32_t width; int32_t queries, pow_bits; uint32_t join; zkhip_ctx* ctx; zkhip_machine_key* key; uint32_t vk[8];
                  uint64_t p2_generation;             // the key commits with the Poseidon2 tables in effect when it was made (zkhip_load_poseidon2_params moves the counter)
-                 zkhip_machine_key* lift_key = nullptr; };      // the RISC Zero side (join_segment_proofs): key = the join's, lift_key = the segments' shape's; null: an SP1-shape pair
-void destroy_join_key(const JoinKey& k) { zkhip_machine_key_destroy(k.key); if (k.lift_key) zkhip_machine_key_destroy(k.lift_key); zkhip_ctx_destroy(k.ctx); }
+                 bool r0 = false; };      // the RISC Zero side (join_segment_proofs): key = the join of the segments' lift proofs (the lift keys live with the library's pooled contexts); false: an SP1-shape pair
+void destroy_join_key(const JoinKey& k) { zkhip_machine_key_destroy(k.key); zkhip_ctx_destroy(k.ctx); }
 std::vector<JoinKey> g_join_keys;           // (under g_slots_mu)
 bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, JoinKey* out, bool r0 = false) {
     const uint64_t gen = zkhip_poseidon2_params_generation();
@@ -100,7 +100,7 @@ bool take_join_key(int device, const zktls::ShardPlan& plan, uint32_t join, Join
         for (size_t i = 0; i < g_join_keys.size();) {
             const JoinKey& k = g_join_keys[i];
             if (k.p2_generation != gen) { stale.push_back(k); g_join_keys.erase(g_join_keys.begin() + (long)i); continue; }     // made under other tables: a verifier would derive another key
-            if (!found && k.device == device && k.log_n == plan.log_n && k.width == plan.width && k.queries == plan.num_queries && k.pow_bits == plan.pow_bits && k.join == join && (k.lift_key != nullptr) == r0) {
+            if (!found && k.device == device && k.log_n == plan.log_n && k.width == plan.width && k.queries == plan.num_queries && k.pow_bits == plan.pow_bits && k.join == join && k.r0 == r0) {
                 *out = k;
                 g_join_keys.erase(g_join_keys.begin() + (long)i);
                 found = true;
@@ -128,7 +128,6 @@ struct JoinGuard {
         (void)zkhip_ctx_sync(jk.ctx);
         if (done) { park_join_key(jk); return; }
         if (jk.key) zkhip_machine_key_destroy(jk.key);
-        if (jk.lift_key) zkhip_machine_key_destroy(jk.lift_key);
         zkhip_ctx_destroy(jk.ctx);
     }
 };
@@ -334,7 +333,7 @@ zkhip_params segment_params(const ShardPlan& plan) {
 }
 }  // namespace
 // `proofs` = the plan's segment proofs, public values request digest | segment index: every one lifted under the shape's key, the lift proofs joined into ONE proof
-// (zkhip_prove_fri16_join_segments) on a pooled context that keeps both keys.  The blob: entry 0 = the joined proof, entry 1 = the join's key + the segment count.
+// (zkhip_prove_fri16_lift_batch, then zkhip_prove_fri16_join on a pooled context that keeps the join's key).  The blob: entry 0 = the joined proof, entry 1 = the join's key + the segment count.
 static std::vector<uint8_t> join_segment_proofs(int device, const ShardPlan& plan, const zkhip_params& prm, const std::vector<uint32_t>& digest,
                                                 const std::vector<std::vector<uint8_t>>& proofs) {
     const SegmentShape sh = segment_shape(plan, prm);
@@ -342,27 +341,34 @@ static std::vector<uint8_t> join_segment_proofs(int device, const ShardPlan& pla
     // (more segments than one join takes: the library's refusal names the bound; a tree above the join is not built)
     const size_t cap = zkhip_fri16_join_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, n, &sh.outer);
     if (cap == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error() + " (a tree above the join is not built)");
-    JoinGuard jg{JoinKey{device, plan.log_n, plan.width, plan.num_queries, plan.pow_bits, (uint32_t)n, nullptr, nullptr, {0}, zkhip_poseidon2_params_generation()}};
+    JoinGuard jg{JoinKey{device, plan.log_n, plan.width, plan.num_queries, plan.pow_bits, (uint32_t)n, nullptr, nullptr, {0}, zkhip_poseidon2_params_generation(), true}};
     JoinKey& jk = jg.jk;
     if (!take_join_key(device, plan, (uint32_t)n, &jk, true)) {
         if (zkhip_ctx_create(device, nullptr, &jk.ctx) != ZKHIP_OK) { jk.ctx = nullptr; fail_zkhip("zkhip_ctx_create"); }
-        uint32_t lift_vk[8];
-        if (zkhip_fri16_lift_key(jk.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, &jk.lift_key, lift_vk) != ZKHIP_OK) { jk.lift_key = nullptr; fail_zkhip("zkhip_fri16_lift_key"); }
         if (zkhip_fri16_join_setup(jk.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, n, &sh.outer, &jk.key, jk.vk) != ZKHIP_OK) { jk.key = nullptr; fail_zkhip("zkhip_fri16_join_setup"); }
     }
-    std::vector<const uint8_t*> ptrs(n);
-    std::vector<size_t> lens(n);
+    // the lifts in ONE call, side by side on the library's lock-step lanes (the shape's lift key stays with its pooled contexts); then the join on the parked pair
     std::vector<uint32_t> pvs;
     for (size_t s = 0; s < n; s++) {
-        ptrs[s] = proofs[s].data(); lens[s] = proofs[s].size();
         pvs.insert(pvs.end(), digest.begin(), digest.end());
         pvs.push_back((uint32_t)s);
     }
+    const size_t room = zkhip_fri16_lift_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.pb, sh.W, 9, &sh.outer);
+    std::vector<std::vector<uint8_t>> lifted(n, std::vector<uint8_t>(room));
+    std::vector<zkhip_fri16_lift_job> jobs(n);
+    for (size_t s = 0; s < n; s++)
+        jobs[s] = zkhip_fri16_lift_job{proofs[s].data(), proofs[s].size(), pvs.data() + 9 * s, lifted[s].data(), room, 0, 0};
+    uint32_t lift_vk[8];
+    if (zkhip_prove_fri16_lift_batch(&device, 1, jobs.data(), (int)n, plan.log_n, plan.width, 9, &prm, &sh.outer, 0, 0, lift_vk) != ZKHIP_OK)
+        fail_zkhip("zkhip_prove_fri16_lift_batch");
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<size_t> lens(n);
+    for (size_t s = 0; s < n; s++) { ptrs[s] = lifted[s].data(); lens[s] = jobs[s].proof_len; }
     std::vector<uint8_t> joined(cap);
     size_t len = 0;
-    if (zkhip_prove_fri16_join_segments(jk.ctx, jk.lift_key, jk.key, ptrs.data(), lens.data(), n, plan.log_n, plan.width, pvs.data(), pvs.size(), &prm, &sh.outer, &sh.outer, joined.data(),
-                                        cap, &len) != ZKHIP_OK)
-        fail_zkhip("zkhip_prove_fri16_join_segments");
+    if (zkhip_prove_fri16_join(jk.ctx, jk.key, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, ptrs.data(), lens.data(), n, pvs.data(), pvs.size(), &sh.outer, joined.data(),
+                               cap, &len) != ZKHIP_OK)
+        fail_zkhip("zkhip_prove_fri16_join");
     joined.resize(len);
     int reason = 0;
     if (zkhip_verify_fri16_join(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, joined.data(), len, pvs.data(), pvs.size(), n, jk.vk, &sh.outer, &reason) != ZKHIP_OK)

@@ -129,7 +129,8 @@ public:
     // than one join holds (136 of the headline shape) take several joins of ONE shape (compress_join_size) and ONE more proof above them (the tree; blob flag TREE).  verify_compressed_blob checks
     // such a blob on the host from (plan, input, ELF, key): the shard proofs are gone.
     // Backend::Risc0 (Risc0HipGuestProver): segments -> lift -> join (prover.rs:88-93) -- every segment proof is lifted under the shape's key and the lift proofs are
-    // joined into ONE proof (zkhip_prove_fri16_join_segments; the lift key and the join key are made once per (shape, segment count) on a pooled context), checked
+    // joined into ONE proof (zkhip_prove_fri16_lift_batch: the lifts side by side, the lift key with the library's pooled contexts; then zkhip_prove_fri16_join under
+    // a join key made once per (shape, segment count) on a pooled context), checked
     // with zkhip_verify_fri16_join like sp1.rs:120; blob flags SYNTHETIC | COMPRESSED | R0_JOINED.  More segments than zkhip_fri16_join_max_proofs are refused with a
     // message that names the bound (a tree above the join is not built).  verify_compressed_blob checks the blob from (plan, input, ELF, r0_join_key_host's key).
     // With with_input_commitment() and an input beyond one chip proof (1 MiB): the chain of SHA-256 shard proofs becomes ONE proof the same way
