@@ -523,7 +523,7 @@ int zkhip_prove_fri16_lift_batch(const int* devices, int n_devices, zkhip_fri16_
  * zkhip_prove_fri16_join_segments: segment proofs in, ONE proof out -- the lift proofs are made one after the other on ctx (zkhip_prove_fri16_lift_segment under
  * lift_key), then joined under join_key.  A segment that does not verify fails with the host verifier's code and a message that names the segment.  The faster
  * route to the same bytes: zkhip_prove_fri16_lift_batch (the lifts side by side on the lock-step lanes), then zkhip_prove_fri16_join.
- * STILL OUTSIDE: a tree above the join for more than 64 segments. */
+ * More segments than one join takes: the tree below. */
 int zkhip_fri16_join_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
                               const zkhip_params* lift_prm, size_t n_proofs, const zkhip_params* join_prm, uint32_t vk[8]);
 int zkhip_fri16_join_setup(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
@@ -541,6 +541,56 @@ int zkhip_verify_fri16_join(int R, int F, int log_blowup, size_t n_queries, int 
 int zkhip_prove_fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key, const zkhip_machine_key* join_key, const uint8_t* const* segment_proofs,
                                     const size_t* lens, size_t n_proofs, int log_n, uint32_t width, const uint32_t* public_values, size_t n_public_total,
                                     const zkhip_params* inner_prm, const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len);
+
+/* ---- SEVERAL JOINS in one call, and the TREE above the join: more lift proofs than one join takes -> ONE proof (segments -> lift -> joins -> top) ----
+ * A join is a machine-mode proof, and machine mode verifies its own proofs: the top is machine mode over the JOIN machine of (shape, join size).  Again shape calls, no
+ * second prover and no second verifier.
+ * zkhip_prove_fri16_join_batch: n_proofs / proofs_per_join joins of ONE shape.  Join j takes the lift proofs [j J, (j + 1) J) and their public values, goes to
+ * devices[j mod n_devices] (NULL, 0: every visible device) and is proven on a pooled context that keeps the join's key, in_flight_per_device at a time on each (0: four);
+ * its proof goes to joined + j joined_stride (stride >= zkhip_fri16_join_proof_size), its length to joined_lens[j]; vk: the joins' key.  Every join is the bytes of
+ * zkhip_prove_fri16_join on the same inputs.  verify != 0: every join is checked by the host verifier on its worker's thread.  n_proofs that is not a positive multiple
+ * of proofs_per_join is refused by message; a failing join fails the call with machine mode's code and a message that names the join.  The joins in flight share the
+ * sixteen CPUs a caller may count on, whatever the machine shows.
+ * zkhip_fri16_tree_max_join: the largest join size whose join machine a top takes (machine mode's bounds on an INNER machine: chips of at most 2^21 rows, the public
+ * values, the terms), 0 (zkhip_last_error) if none.  zkhip_fri16_tree_max_joins: the most joins of that size one top takes.  Both are host only and computed from the
+ * machine's shape, never tabulated.
+ * zkhip_fri16_tree_key_host / _setup / _proof_size: join_vk is an INPUT -- what zkhip_fri16_join_key_host / _setup return for proofs_per_join -- and becomes key_root of
+ * the join machine's description (the ten chips zkhip_machine_verifier_describe gives over the lift machine at n_proofs = proofs_per_join, join_prm's queries and
+ * proof-of-work bits, proofs_per_join x n_inner_public public values).  The key, the size and the bytes are zkhip_machine_verifier_key_host's, _proof_size's and
+ * zkhip_prove_machine_verifier's on that description at n_proofs = n_joins.
+ * zkhip_prove_fri16_tree: the lift proofs -> joins (zkhip_prove_fri16_join_batch's way: dealt over `devices`, several in flight) -> ONE proof over the joins on ctx.  A
+ * join's tables for the top are filled on its worker's thread the moment the join exists.  n_proofs must be a positive multiple of proofs_per_join (the caller pads by
+ * repeating the last lift proof and its public values); a context whose join key is not join_vk fails the call by message before it proves.  joined / joined_stride
+ * (a multiple of 4) / joined_lens: the joins, as above.
+ * zkhip_verify_fri16_tree is host only and takes (shape, join size, the joins' key, the number of joins, every segment's public values in order, the top's key): no byte
+ * of a segment, lift or join proof.  n_public_total must be n_joins x proofs_per_join x n_inner_public.
+ * Every refusal names its entry and the bound it met; shapes the lift refuses keep the lift's message. */
+int zkhip_prove_fri16_join_batch(const int* devices, int n_devices, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                                 uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs, const size_t* lens,
+                                 size_t n_proofs, size_t proofs_per_join, const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm,
+                                 int in_flight_per_device, int verify, uint8_t* joined, size_t joined_stride, size_t* joined_lens, uint32_t vk[8]);
+size_t zkhip_fri16_tree_max_join(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                 const zkhip_params* lift_prm, const zkhip_params* join_prm);
+size_t zkhip_fri16_tree_max_joins(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                  const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm);
+int zkhip_fri16_tree_key_host(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                              const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                              const zkhip_params* top_prm, uint32_t vk[8]);
+int zkhip_fri16_tree_setup(zkhip_ctx* ctx, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width,
+                           uint32_t n_inner_public, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8],
+                           size_t n_joins, const zkhip_params* top_prm, zkhip_machine_key** key, uint32_t vk[8]);
+size_t zkhip_fri16_tree_proof_size(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                                   const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                                   const zkhip_params* top_prm);
+int zkhip_prove_fri16_tree(zkhip_ctx* ctx, const zkhip_machine_key* top_key, int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits,
+                           uint32_t trace_width, uint32_t n_inner_public, const zkhip_params* lift_prm, const int* devices, int n_devices,
+                           const uint8_t* const* lift_proofs, const size_t* lens, size_t n_proofs, size_t proofs_per_join, const uint32_t* public_values,
+                           size_t n_public_total, const zkhip_params* join_prm, const uint32_t join_vk[8], const zkhip_params* top_prm, int in_flight_per_device,
+                           uint8_t* joined, size_t joined_stride, size_t* joined_lens, uint8_t* out, size_t cap, size_t* len);
+int zkhip_verify_fri16_tree(int R, int F, int log_blowup, size_t n_queries, int inner_hash_width, int inner_pow_bits, uint32_t trace_width, uint32_t n_inner_public,
+                            const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                            const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total, const uint32_t top_vk[8],
+                            const zkhip_params* top_prm, int* reason);
 
 /* ---- chip programs, trace generators and machine descriptions whose statement-level entries are in zkhip.h (documented there, beside the prover that
  * uses them: the AIR-as-data section, the SHA-256 chip, the keyed SHA-256 machine, the shard verifier machines) ---- */

@@ -248,6 +248,35 @@ extern "C" {
     pub fn zkhip_verify_fri16_join(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
                                    n_inner_public: u32, lift_prm: *const ZkhipParams, proof: *const u8, len: usize, public_values: *const u32, n_public_total: usize,
                                    n_proofs: usize, vk: *const u32, join_prm: *const ZkhipParams, reason: *mut c_int) -> c_int;
+    /// several joins of one shape in one call (join j on devices[j mod n_devices], pooled contexts that keep the join's key), and the TREE above the join: the join
+    /// machine of (shape, join size) verified by machine mode one level up.  `join_vk` is an input: zkhip_fri16_join_key_host's / _setup's key for that join size
+    pub fn zkhip_prove_fri16_join_batch(devices: *const c_int, n_devices: c_int, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int,
+                                        inner_pow_bits: c_int, trace_width: u32, n_inner_public: u32, lift_prm: *const ZkhipParams, lift_proofs: *const *const u8,
+                                        lens: *const usize, n_proofs: usize, proofs_per_join: usize, public_values: *const u32, n_public_total: usize,
+                                        join_prm: *const ZkhipParams, in_flight_per_device: c_int, verify: c_int, joined: *mut u8, joined_stride: usize,
+                                        joined_lens: *mut usize, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_tree_max_join(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                     n_inner_public: u32, lift_prm: *const ZkhipParams, join_prm: *const ZkhipParams) -> usize;
+    pub fn zkhip_fri16_tree_max_joins(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                      n_inner_public: u32, lift_prm: *const ZkhipParams, proofs_per_join: usize, join_prm: *const ZkhipParams) -> usize;
+    pub fn zkhip_fri16_tree_key_host(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                     n_inner_public: u32, lift_prm: *const ZkhipParams, proofs_per_join: usize, join_prm: *const ZkhipParams, join_vk: *const u32,
+                                     n_joins: usize, top_prm: *const ZkhipParams, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_tree_setup(ctx: *mut ZkhipCtx, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                  n_inner_public: u32, lift_prm: *const ZkhipParams, proofs_per_join: usize, join_prm: *const ZkhipParams, join_vk: *const u32,
+                                  n_joins: usize, top_prm: *const ZkhipParams, key: *mut *mut ZkhipMachineKey, vk: *mut u32) -> c_int;
+    pub fn zkhip_fri16_tree_proof_size(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                       n_inner_public: u32, lift_prm: *const ZkhipParams, proofs_per_join: usize, join_prm: *const ZkhipParams, join_vk: *const u32,
+                                       n_joins: usize, top_prm: *const ZkhipParams) -> usize;
+    pub fn zkhip_prove_fri16_tree(ctx: *mut ZkhipCtx, top_key: *const ZkhipMachineKey, r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int,
+                                  inner_pow_bits: c_int, trace_width: u32, n_inner_public: u32, lift_prm: *const ZkhipParams, devices: *const c_int, n_devices: c_int,
+                                  lift_proofs: *const *const u8, lens: *const usize, n_proofs: usize, proofs_per_join: usize, public_values: *const u32,
+                                  n_public_total: usize, join_prm: *const ZkhipParams, join_vk: *const u32, top_prm: *const ZkhipParams, in_flight_per_device: c_int,
+                                  joined: *mut u8, joined_stride: usize, joined_lens: *mut usize, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn zkhip_verify_fri16_tree(r: c_int, f: c_int, log_blowup: c_int, n_queries: usize, inner_hash_width: c_int, inner_pow_bits: c_int, trace_width: u32,
+                                   n_inner_public: u32, lift_prm: *const ZkhipParams, proofs_per_join: usize, join_prm: *const ZkhipParams, join_vk: *const u32,
+                                   n_joins: usize, proof: *const u8, len: usize, public_values: *const u32, n_public_total: usize, top_vk: *const u32,
+                                   top_prm: *const ZkhipParams, reason: *mut c_int) -> c_int;
     pub fn zkhip_shard_verifier_max_proofs(log_n: c_int, width: u32, n_queries: usize, inner_pow_bits: c_int, n_public: usize, outer: *const ZkhipParams) -> usize;
     pub fn zkhip_prove_shard_verifier(ctx: *mut ZkhipCtx, key: *const ZkhipMachineKey, shard_proofs: *const *const u8, shard_proof_lens: *const usize, n_proofs: usize,
                                       log_n: c_int, width: u32, public_values: *const u32, n_public: usize, inner: *const ZkhipParams, outer: *const ZkhipParams,

@@ -469,7 +469,7 @@ fn segment_lift_shape(log_n: i32, inner: &ZkhipParams) -> Result<(i32, i32, i32,
 
 /// RISC Zero's compress stage (prover.rs:88-93: segments -> lift -> join; the C++ mirror's `Risc0HipGuestProver::with_compress`): every segment proof lifted under the
 /// shape's key, the lift proofs joined into ONE proof.  `public_values`: `n_public` per segment, in segment order.  More segments than
-/// `zkhip_fri16_join_max_proofs` are refused (a tree above the join is not built).  Returns the joined proof and the join's key; `verify_joined_segments` then needs
+/// `zkhip_fri16_join_max_proofs` are refused here: `join_segments_tree` takes them.  Returns the joined proof and the join's key; `verify_joined_segments` then needs
 /// no byte of a segment or lift proof.  The lifts are ONE call (`zkhip_prove_fri16_lift_batch`: side by side on the lock-step lanes of `devices` -- empty: every
 /// visible device --, the shape's lift key with the library's pooled contexts); the join runs on `ctx`.
 pub fn join_segments(ctx: &Context, devices: &[i32], proofs: &[Vec<u8>], log_n: i32, width: u32, public_values: &[u32], n_public: usize, inner: &ZkhipParams,
@@ -479,7 +479,7 @@ pub fn join_segments(ctx: &Context, devices: &[i32], proofs: &[Vec<u8>], log_n: 
     let n = proofs.len();
     let most = unsafe { ffi::zkhip_fri16_join_max_proofs(r, f, b, q, hw, pb, width, n_public as u32, lift) };
     anyhow::ensure!(most > 0, "join_segments: the lift does not take this shape");
-    anyhow::ensure!(n <= most, "join_segments: {} segments, one join takes at most {} (a tree above the join is not built)", n, most);
+    anyhow::ensure!(n <= most, "join_segments: {} segments, one join takes at most {} (join_segments_tree takes more)", n, most);
     // the lifts: one job per segment, every lift proof in a buffer of its own
     let room = unsafe { ffi::zkhip_fri16_lift_proof_size(r, f, b, q, pb, width, n_public as u32, lift) };
     anyhow::ensure!(room > 0, "join_segments: the lift does not take this shape");
@@ -531,6 +531,84 @@ pub fn verify_joined_segments(proof: &[u8], log_n: i32, width: u32, public_value
     }, "zkhip_verify_fri16_join")
 }
 
+/// THE TREE above the join (the C++ mirror's `join_segments_tree`): more segments than one join takes, or smaller joins asked for.  Every segment proof is lifted
+/// (`zkhip_prove_fri16_lift_batch` over `devices`), the lift proofs go into `ceil(n / proofs_per_join)` joins of ONE shape -- the last one repeating the last segment's
+/// lift proof and public values -- dealt over `devices`, four in flight on each, and ONE proof on `ctx` verifies the joins (`zkhip_prove_fri16_tree`).
+/// `proofs_per_join` must be at most `zkhip_fri16_tree_max_join` and the joins at most `zkhip_fri16_tree_max_joins`; the library's refusal names the bound.
+/// Returns (the top proof, the JOINS' key, the top's key); `verify_segment_tree` then needs no byte of a segment, lift or join proof.
+pub fn join_segments_tree(ctx: &Context, devices: &[i32], proofs: &[Vec<u8>], proofs_per_join: usize, log_n: i32, width: u32, public_values: &[u32], n_public: usize,
+                          inner: &ZkhipParams, lift: &ZkhipParams, join: &ZkhipParams, top: &ZkhipParams) -> Result<(Vec<u8>, [u32; 8], [u32; 8])> {
+    anyhow::ensure!(!proofs.is_empty() && proofs_per_join > 0 && public_values.len() == proofs.len() * n_public, "join_segments_tree: one public-value list per segment");
+    let (r, f, b, q, hw, pb) = segment_lift_shape(log_n, inner)?;
+    let (n, j) = (proofs.len(), proofs_per_join);
+    let np = n_public as u32;
+    let n_joins = (n + j - 1) / j;
+    let most = unsafe { ffi::zkhip_fri16_tree_max_joins(r, f, b, q, hw, pb, width, np, lift, j, join) };
+    anyhow::ensure!(most > 0, "join_segments_tree: {}", unsafe { std::ffi::CStr::from_ptr(ffi::zkhip_last_error()) }.to_string_lossy());
+    anyhow::ensure!(n_joins <= most, "join_segments_tree: {} segments need {} joins of {}, one top takes at most {} (a third tree level is not built)", n, n_joins, j, most);
+    let room = unsafe { ffi::zkhip_fri16_lift_proof_size(r, f, b, q, pb, width, np, lift) };
+    anyhow::ensure!(room > 0, "join_segments_tree: the lift does not take this shape");
+    let mut lifted: Vec<Vec<u8>> = (0..n).map(|_| vec![0u8; room]).collect();
+    let mut jobs: Vec<ffi::ZkhipFri16LiftJob> = (0..n)
+        .map(|s| ffi::ZkhipFri16LiftJob {
+            segment_proof: proofs[s].as_ptr(),
+            segment_proof_len: proofs[s].len(),
+            public_values: public_values[s * n_public..].as_ptr(),
+            proof: lifted[s].as_mut_ptr(),
+            proof_cap: room,
+            proof_len: 0,
+            status: 0,
+        })
+        .collect();
+    let mut lift_vk = [0u32; 8];
+    let devs = if devices.is_empty() { std::ptr::null() } else { devices.as_ptr() };
+    check(unsafe {
+        ffi::zkhip_prove_fri16_lift_batch(devs, devices.len() as i32, jobs.as_mut_ptr(), n as i32, log_n, width, n_public, inner, lift, 0, 0, lift_vk.as_mut_ptr())
+    }, "zkhip_prove_fri16_lift_batch")?;
+    // every join has J places: the last one repeats the last segment (one shape, one key)
+    let padded = n_joins * j;
+    let at = |s: usize| if s < n { s } else { n - 1 };
+    let ptrs: Vec<*const u8> = (0..padded).map(|s| lifted[at(s)].as_ptr()).collect();
+    let lens: Vec<usize> = (0..padded).map(|s| jobs[at(s)].proof_len).collect();
+    let pvs: Vec<u32> = (0..padded).flat_map(|s| public_values[at(s) * n_public..(at(s) + 1) * n_public].iter().copied()).collect();
+    let mut join_vk = [0u32; 8];
+    check(unsafe { ffi::zkhip_fri16_join_key_host(r, f, b, q, hw, pb, width, np, lift, j, join, join_vk.as_mut_ptr()) }, "zkhip_fri16_join_key_host")?;
+    let mut top_key: *mut ffi::ZkhipMachineKey = std::ptr::null_mut();
+    let mut top_vk = [0u32; 8];
+    check(unsafe { ffi::zkhip_fri16_tree_setup(ctx.raw(), r, f, b, q, hw, pb, width, np, lift, j, join, join_vk.as_ptr(), n_joins, top, &mut top_key, top_vk.as_mut_ptr()) },
+          "zkhip_fri16_tree_setup")?;
+    let jcap = unsafe { ffi::zkhip_fri16_join_proof_size(r, f, b, q, hw, pb, width, np, lift, j, join) };
+    let tcap = unsafe { ffi::zkhip_fri16_tree_proof_size(r, f, b, q, hw, pb, width, np, lift, j, join, join_vk.as_ptr(), n_joins, top) };
+    let mut joined = vec![0u8; n_joins * jcap];
+    let mut joined_lens = vec![0usize; n_joins];
+    let mut out = vec![0u8; tcap];
+    let mut len = 0usize;
+    let rc = unsafe {
+        ffi::zkhip_prove_fri16_tree(ctx.raw(), top_key, r, f, b, q, hw, pb, width, np, lift, devs, devices.len() as i32, ptrs.as_ptr(), lens.as_ptr(), padded, j, pvs.as_ptr(),
+                                    pvs.len(), join, join_vk.as_ptr(), top, 0, joined.as_mut_ptr(), jcap, joined_lens.as_mut_ptr(), out.as_mut_ptr(), tcap, &mut len)
+    };
+    unsafe { ffi::zkhip_machine_key_destroy(top_key) };
+    check(rc, "zkhip_prove_fri16_tree")?;
+    out.truncate(len);
+    verify_segment_tree(&out, log_n, width, public_values, n_public, n, j, &join_vk, &top_vk, inner, lift, join, top)?;      // sp1.rs:120: the prover checks its own proof
+    Ok((out, join_vk, top_vk))
+}
+
+/// Host-only check of `join_segments_tree`'s proof from (the segments' shape, THEIR public values -- `n_segments` x `n_public`, the padding is made here --, the join
+/// size, the joins' key and the top's key: `zkhip_fri16_join_key_host` and `zkhip_fri16_tree_key_host` derive them without a GPU).
+pub fn verify_segment_tree(proof: &[u8], log_n: i32, width: u32, public_values: &[u32], n_public: usize, n_segments: usize, proofs_per_join: usize, join_vk: &[u32; 8],
+                           top_vk: &[u32; 8], inner: &ZkhipParams, lift: &ZkhipParams, join: &ZkhipParams, top: &ZkhipParams) -> Result<()> {
+    anyhow::ensure!(n_segments > 0 && proofs_per_join > 0 && public_values.len() == n_segments * n_public, "verify_segment_tree: one public-value list per segment");
+    let (r, f, b, q, hw, pb) = segment_lift_shape(log_n, inner)?;
+    let n_joins = (n_segments + proofs_per_join - 1) / proofs_per_join;
+    let at = |s: usize| if s < n_segments { s } else { n_segments - 1 };
+    let pvs: Vec<u32> = (0..n_joins * proofs_per_join).flat_map(|s| public_values[at(s) * n_public..(at(s) + 1) * n_public].iter().copied()).collect();
+    let mut reason = 0;
+    check(unsafe {
+        ffi::zkhip_verify_fri16_tree(r, f, b, q, hw, pb, width, n_public as u32, lift, proofs_per_join, join, join_vk.as_ptr(), n_joins, proof.as_ptr(), proof.len(),
+                                     pvs.as_ptr(), pvs.len(), top_vk.as_ptr(), top, &mut reason)
+    }, "zkhip_verify_fri16_tree")
+}
 
 // ---- shards in SP1's shard STRUCTURE (the C++ mirror's MachinePlan, zktls_amd/host/guest_prover_hip.hpp): chips of mixed heights, LogUp pairs inside and
 // across tables, preprocessed columns committed by setup -- every shard ONE keyed-machine proof (version 11), the compress stage in machine mode ----

@@ -67,6 +67,8 @@ EXPORTS = [
     "zkhip_prove_fri16_lift", "zkhip_verify_fri16_lift", "zkhip_prove_fri16_lift_segment", "zkhip_prove_fri16_lift_batch",
     "zkhip_fri16_join_key_host", "zkhip_fri16_join_setup", "zkhip_fri16_join_proof_size", "zkhip_fri16_join_max_proofs", "zkhip_prove_fri16_join", "zkhip_verify_fri16_join",
     "zkhip_prove_fri16_join_segments", "zkhip_machine_verifier_gen_eval_rows",
+    "zkhip_prove_fri16_join_batch", "zkhip_fri16_tree_max_join", "zkhip_fri16_tree_max_joins", "zkhip_fri16_tree_key_host", "zkhip_fri16_tree_setup",
+    "zkhip_fri16_tree_proof_size", "zkhip_prove_fri16_tree", "zkhip_verify_fri16_tree",
     "zkhip_sha256_air", "zkhip_sha256_digest", "zkhip_sha256_pad", "zkhip_sha256_padding_publics", "zkhip_sha256_gen_trace", "zkhip_sha256_proof_size", "zkhip_prove_sha256", "zkhip_verify_sha256",
 ]
 
@@ -470,6 +472,22 @@ def load():
     L.zkhip_verify_fri16_join.argtypes = fri16_jshape + [u8p, C.c_size_t, u32p, C.c_size_t, C.c_size_t, u32p, C.POINTER(Params), C.POINTER(C.c_int)]
     L.zkhip_prove_fri16_join_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(u8p), szp, C.c_size_t, C.c_int, C.c_uint32, u32p, C.c_size_t, C.POINTER(Params),
                                                   C.POINTER(Params), C.POINTER(Params), u8p, C.c_size_t, szp]
+    # several joins in one call, and the tree above the join: the join's shape arguments, the join size, the join's parameters and key, the number of joins, the top's
+    PP, ip = C.POINTER(Params), C.POINTER(C.c_int)
+    L.zkhip_prove_fri16_join_batch.argtypes = [ip, C.c_int] + fri16_jshape + [C.POINTER(u8p), szp, C.c_size_t, C.c_size_t, u32p, C.c_size_t, PP, C.c_int, C.c_int, u8p,
+                                               C.c_size_t, szp, u32p]
+    L.zkhip_fri16_tree_max_join.restype = C.c_size_t
+    L.zkhip_fri16_tree_max_join.argtypes = fri16_jshape + [PP]
+    L.zkhip_fri16_tree_max_joins.restype = C.c_size_t
+    L.zkhip_fri16_tree_max_joins.argtypes = fri16_jshape + [C.c_size_t, PP]
+    fri16_tshape = fri16_jshape + [C.c_size_t, PP, u32p, C.c_size_t, PP]
+    L.zkhip_fri16_tree_key_host.argtypes = fri16_tshape + [u32p]
+    L.zkhip_fri16_tree_setup.argtypes = [C.c_void_p] + fri16_tshape + [C.POINTER(C.c_void_p), u32p]
+    L.zkhip_fri16_tree_proof_size.restype = C.c_size_t
+    L.zkhip_fri16_tree_proof_size.argtypes = fri16_tshape
+    L.zkhip_prove_fri16_tree.argtypes = [C.c_void_p, C.c_void_p] + fri16_jshape + [ip, C.c_int, C.POINTER(u8p), szp, C.c_size_t, C.c_size_t, u32p, C.c_size_t, PP, u32p, PP,
+                                         C.c_int, u8p, C.c_size_t, szp, u8p, C.c_size_t, szp]
+    L.zkhip_verify_fri16_tree.argtypes = fri16_jshape + [C.c_size_t, PP, u32p, C.c_size_t, u8p, C.c_size_t, u32p, C.c_size_t, u32p, PP, ip]
     # machine mode's EVAL row kernel alone (the row tests)
     L.zkhip_machine_verifier_gen_eval_rows.argtypes = [C.c_void_p, C.c_size_t, u32p, u32p, u32p, u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u32p, u32p, u32p, u32p]
     L.zkhip_sha256_air_chained.restype = C.c_size_t

@@ -53,6 +53,9 @@
 //                                          zkhip_prove_fri16_lift_batch is many of them in one call, side by side on the lock-step lanes (batch.h)
 //   JOIN     (zkhip_prove_fri16_join)      no machine of this file: N lift proofs of one shape are N proofs of ONE keyed machine, which machine mode
 //                                          (machine_verifier.inl) verifies in-circuit.  The entries at the end of the file describe the lift machine to it
+//   TREE     (zkhip_prove_fri16_tree)      no machine of this file either: a join is a machine-mode proof, and machine mode verifies its own proofs.  More lift
+//                                          proofs than one join takes go into several joins of one shape (zkhip_prove_fri16_join_batch: side by side, dealt over the
+//                                          devices) and ONE proof over the joins; the entries describe the JOIN machine of (shape, join size) to machine mode
 // The file in order: the chips' programs and each kind's key tables, section by section as the kinds came; then the one description -- Shape (flat: kind, the numbers, per
 // table number the height and widths), shape_of (every kind's validity checks), program_of and interactions_of (per TABLE, what each kind adds
 // to or changes in the kind before it), Machine and machine_of (one cache keyed by kind and shape; the machine order and the arrays by position are keyed_machine.h's) --
@@ -2353,6 +2356,12 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
                              const uint32_t* public_values, size_t n_public, const zkhip_params* outer, uint8_t* proof, size_t cap, size_t* len);
 int m_verify_machine_recursive(const zkhip_machine_desc* inner, const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public, size_t n_proofs, const uint32_t vk[8],
                                const zkhip_params* outer, int* reason);
+// (the tree above the join: a machine-mode machine as the description of the level above it, and the top over joins that the caller makes)
+using JoinSink = std::function<int(size_t, const uint8_t*, size_t)>;
+int m_machine_verifier_self_desc(const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, const uint32_t key_root[8], std::shared_ptr<const void>& keep,
+                                 zkhip_machine_desc& d);
+int m_prove_tree_top(zkhip_ctx* ctx, const zkhip_machine_key* top_key, const zkhip_machine_desc* join_machine, size_t n_joins, const uint32_t* public_values,
+                     const zkhip_params* top_outer, const std::function<int(const JoinSink&)>& run_joins, uint8_t* proof, size_t cap, size_t* len);
 }  // namespace mrec
 }  // namespace zk
 
@@ -2500,6 +2509,197 @@ static int fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lift_key
         ptrs[i] = lifted[i].data();
     }
     return fri16_join_prove_desc(ctx, join_key, j, ptrs.data(), lift_lens.data(), n_proofs, public_values, n_public_total, join_prm, out, cap, len);
+}
+
+// ---------------------------------------------------------------- SEVERAL JOINS, and the TREE above them: more than one join's worth of segments -> one proof
+// n_proofs / J joins of ONE shape (hence one key), zkhip_prove_shard_verifier_batch's way: join j takes the lift proofs [j J, (j + 1) J), goes to devices[j mod n_devices]
+// and is proven on a pooled context that keeps the join's key (the rec_key slot: the signature below starts with a tag no shard-verifier signature starts with and has
+// another length).  Every join is m_prove_machine_verifier on the lift machine's description: the bytes of zkhip_prove_fri16_join.  The joins in flight share the sixteen
+// CPUs a caller may count on: each is told its share (t_query_threads_cap), which bounds the pool that fills its lift proofs' tables and what every fill starts.
+// want_vk (the tree): the key every context must arrive at, checked before its first join is proven.  on_join: zk::mrec::JoinSink, run on the worker's thread right
+// after join j exists; its failure is the join's.
+static int fri16_join_batch(const char* who, const int* devices, int n_devices, const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs,
+                            const size_t* lens, size_t n_proofs, size_t J, const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm,
+                            int in_flight_per_device, int verify, uint8_t* joined, size_t joined_stride, size_t* joined_lens, uint32_t vk[8], const uint32_t* want_vk,
+                            const zk::mrec::JoinSink* on_join) {
+    const std::string me = who;
+    if (!lift_proofs || !lens || !public_values || !lift_prm || !join_prm || !joined || !joined_lens || !vk) return fail(ZKHIP_ERR_INVALID, me + ": null argument");
+    if (J == 0 || n_proofs == 0 || n_proofs % J != 0)
+        return fail(ZKHIP_ERR_INVALID, me + ": the number of lift proofs must be a positive multiple of proofs_per_join, not " + std::to_string(n_proofs) + " for joins of " +
+                                       std::to_string(J));
+    const size_t n_joins = n_proofs / J;
+    if (n_joins > (size_t)1 << 20) return fail(ZKHIP_ERR_INVALID, me + ": more than 2^20 joins");
+    JoinDesc j;
+    ZK_TRY(fri16_join_desc(a, hw, lift_prm, who, j));
+    ZK_TRY(fri16_join_check_public(j, n_proofs, public_values, n_public_total, who));
+    const size_t need = zk::mrec::m_machine_verifier_proof_size(&j.d, J, join_prm);
+    if (!need) return fri16_join_refused(j, J, who, ZKHIP_ERR_INVALID);
+    if (joined_stride < need) return fail(ZKHIP_ERR_INVALID, me + ": joined_stride is below zkhip_fri16_join_proof_size (" + std::to_string(need) + ")");
+    for (size_t k = 0; k < n_proofs; k++) if (!lift_proofs[k]) return fail(ZKHIP_ERR_INVALID, me + ": null argument");
+    for (size_t k = 0; k < n_joins; k++) joined_lens[k] = 0;
+    std::memset(vk, 0, 32);
+    std::vector<int> devs;
+    ZK_TRY(resolve_devices(devices, n_devices, who, devs));
+    std::vector<uint64_t> sig = {0x4A4F494E46523136ull /* "JOINFR16" */, (uint64_t)a.R, (uint64_t)a.F, (uint64_t)a.b, (uint64_t)a.Q, (uint64_t)(uint32_t)a.pow_bits, a.W, a.NP, (uint64_t)(uint32_t)hw, J};
+    for (const zkhip_params* p : {lift_prm, join_prm})
+        for (int v : {p->log_blowup, p->num_queries, p->pow_bits, p->logup_pairs, p->log_fold, p->log_final, p->hash_width, p->code_width}) sig.push_back((uint64_t)(uint32_t)v);
+    sig.push_back(zk::g_p2_generation.load());
+    const int nd = (int)devs.size();
+    const size_t workers = std::min<size_t>(n_joins, (size_t)(in_flight_per_device > 0 ? in_flight_per_device : 4) * (size_t)nd);
+    const int host_threads = workers >= 16 ? 1 : (int)(16 / workers);      // (a join's share of the sixteen CPUs, whatever the machine shows)
+    const size_t NP = j.d.n_public;
+    std::mutex mu;
+    bool have_vk = false;
+    std::vector<char> ran;
+    auto run = [&](zkhip_ctx* ctx, int k) {
+        int r = ZKHIP_OK;
+        const int cap_before = t_query_threads_cap;
+        t_query_threads_cap = host_threads;
+        if (ctx->rec_key && ctx->rec_key_sig != sig) { (void)dev_sync(ctx); zkhip_machine_key_destroy(ctx->rec_key); ctx->rec_key = nullptr; }
+        if (!ctx->rec_key) {
+            r = zk::mrec::m_machine_verifier_setup(ctx, &j.d, J, join_prm, &ctx->rec_key, ctx->rec_vk);
+            if (r == ZKHIP_OK) ctx->rec_key_sig = sig;
+            else ctx->rec_key = nullptr;
+        }
+        if (r == ZKHIP_OK && want_vk && std::memcmp(want_vk, ctx->rec_vk, 32) != 0)
+            r = fail(ZKHIP_ERR_INVALID, me + ": join_vk is not the key of joins of " + std::to_string(J) + " lift proofs of this shape (zkhip_fri16_join_key_host)");
+        if (r == ZKHIP_OK) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!have_vk) { std::memcpy(vk, ctx->rec_vk, 32); have_vk = true; }
+            else if (std::memcmp(vk, ctx->rec_vk, 32) != 0) r = fail(ZKHIP_ERR_INTERNAL, me + ": two contexts disagree about the key of the shape");
+        }
+        size_t len = 0;
+        uint8_t* const out = joined + (size_t)k * joined_stride;
+        const uint32_t* const pv = public_values + (size_t)k * J * NP;
+        if (r == ZKHIP_OK) {
+            r = zk::mrec::m_prove_machine_verifier(ctx, ctx->rec_key, &j.d, lift_proofs + (size_t)k * J, lens + (size_t)k * J, J, pv, NP, join_prm, out, joined_stride, &len);
+            if (r == ZKHIP_OK && verify) r = zk::mrec::m_verify_machine_recursive(&j.d, out, len, pv, NP, J, ctx->rec_vk, join_prm, nullptr);
+            if (r == ZKHIP_OK && on_join) r = (*on_join)((size_t)k, out, len);
+            if (r != ZKHIP_OK) r = fail(r, me + ": join " + std::to_string(k) + ": " + zkhip_last_error());      // (machine mode's code, the join's name)
+        }
+        joined_lens[(size_t)k] = r == ZKHIP_OK ? len : 0;
+        t_query_threads_cap = cap_before;
+        return r;
+    };
+    return deal_jobs(devs.data(), nd, (int)n_joins, in_flight_per_device, run, ran);          // (0: four)
+}
+
+// the join machine of (shape, join size) as machine mode takes it one level up: the ten chips of the machine-mode machine over the lift machine, join_vk as key_root,
+// join_prm's queries and proof-of-work bits, J x n_inner_public public values.  The lift's key is kept by fri16_join_desc and the machine by machine mode's own cache, per
+// (description, join size): a call that comes again builds neither
+namespace {
+struct TreeDesc { JoinDesc lift; std::shared_ptr<const void> m; zkhip_machine_desc d; size_t J = 0; };      // (d points into m)
+const uint32_t NO_KEY[8] = {0};                              // (the bounds do not depend on the key)
+int fri16_tree_desc(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm, const uint32_t* join_vk, const char* who, TreeDesc& t) {
+    if (!join_prm || !join_vk) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    ZK_TRY(fri16_join_desc(a, hw, lift_prm, who, t.lift));
+    t.J = J;
+    const int rc = zk::mrec::m_machine_verifier_self_desc(&t.lift.d, J, join_prm, join_vk, t.m, t.d);
+    return rc == ZKHIP_ERR_INVALID ? fri16_join_refused(t.lift, J, who, rc) : rc;
+}
+// the top refused (its message in zkhip_last_error): where the number of joins, or the join size, is what it did not take, the message names the bound
+int fri16_tree_refused(const TreeDesc& t, size_t n_joins, const char* who, int rc) {
+    const std::string why = zkhip_last_error();
+    const size_t most = zk::mrec::m_machine_verifier_max_proofs(&t.d);
+    if (!most)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": no top takes a join of " + std::to_string(t.J) + " lift proofs of this shape (zkhip_fri16_tree_max_join gives the largest): " +
+                                       zkhip_last_error());
+    if (n_joins < 1 || n_joins > most)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": 1 .. " + std::to_string(most) + " joins of " + std::to_string(t.J) + " lift proofs of this shape go under one top, not " +
+                                       std::to_string(n_joins));
+    return fail(rc, why);
+}
+int fri16_tree_check_public(const TreeDesc& t, size_t n_joins, const uint32_t* public_values, size_t n_public_total, const char* who) {
+    if (!public_values || n_public_total != n_joins * (size_t)t.d.n_public)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": public_values holds n_joins x proofs_per_join x n_inner_public words in segment order (" +
+                                       std::to_string(n_joins * (size_t)t.d.n_public) + " here), not " + std::to_string(n_public_total));
+    return ZKHIP_OK;
+}
+}  // namespace
+
+static size_t fri16_tree_max_joins(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm) {
+    TreeDesc t;
+    if (fri16_tree_desc(a, hw, lift_prm, J, join_prm, NO_KEY, "fri16_tree_max_joins", t) != ZKHIP_OK) return 0;
+    const size_t most = zk::mrec::m_machine_verifier_max_proofs(&t.d);
+    if (!most) (void)fri16_tree_refused(t, 1, "fri16_tree_max_joins", ZKHIP_ERR_INVALID);
+    return most;
+}
+// the largest join size whose join machine a top takes.  What machine mode bounds (the chips' heights, the public values per proof, the terms) grows with the join
+// size, so the sizes a top takes are 1 .. the answer: found by bisection below what one join takes
+static size_t fri16_tree_max_join(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, const zkhip_params* join_prm) {
+    const char* who = "fri16_tree_max_join";
+    if (!join_prm) { (void)fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument"); return 0; }
+    JoinDesc j;
+    if (fri16_join_desc(a, hw, lift_prm, who, j) != ZKHIP_OK) return 0;
+    const size_t most = zk::mrec::m_machine_verifier_max_proofs(&j.d);
+    if (!most) return 0;
+    auto takes = [&](size_t J) {
+        TreeDesc t;
+        return fri16_tree_desc(a, hw, lift_prm, J, join_prm, NO_KEY, who, t) == ZKHIP_OK && zk::mrec::m_machine_verifier_max_proofs(&t.d) >= 1;
+    };
+    if (!takes(1)) { (void)fail(ZKHIP_ERR_INVALID, std::string(who) + ": no top takes a join of this shape, not even a join of one: " + zkhip_last_error()); return 0; }
+    size_t lo = 1, hi = most;
+    while (lo < hi) { const size_t mid = (lo + hi + 1) / 2; if (takes(mid)) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+static int fri16_tree_key_host(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm, const uint32_t* join_vk, size_t n_joins,
+                               const zkhip_params* top_prm, uint32_t vk[8]) {
+    TreeDesc t;
+    ZK_TRY(fri16_tree_desc(a, hw, lift_prm, J, join_prm, join_vk, "fri16_tree_key_host", t));
+    const int rc = zk::mrec::m_machine_verifier_key_host(&t.d, n_joins, top_prm, vk);
+    return rc == ZKHIP_ERR_INVALID ? fri16_tree_refused(t, n_joins, "fri16_tree_key_host", rc) : rc;
+}
+static int fri16_tree_setup(zkhip_ctx* ctx, const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm, const uint32_t* join_vk,
+                            size_t n_joins, const zkhip_params* top_prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    CHECK_CTX(ctx);
+    TreeDesc t;
+    ZK_TRY(fri16_tree_desc(a, hw, lift_prm, J, join_prm, join_vk, "fri16_tree_setup", t));
+    const int rc = zk::mrec::m_machine_verifier_setup(ctx, &t.d, n_joins, top_prm, key, vk);
+    return rc == ZKHIP_ERR_INVALID ? fri16_tree_refused(t, n_joins, "fri16_tree_setup", rc) : rc;
+}
+static size_t fri16_tree_proof_size(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm, const uint32_t* join_vk, size_t n_joins,
+                                    const zkhip_params* top_prm) {
+    TreeDesc t;
+    if (fri16_tree_desc(a, hw, lift_prm, J, join_prm, join_vk, "fri16_tree_proof_size", t) != ZKHIP_OK) return 0;
+    const size_t size = zk::mrec::m_machine_verifier_proof_size(&t.d, n_joins, top_prm);
+    if (!size) (void)fri16_tree_refused(t, n_joins, "fri16_tree_proof_size", ZKHIP_ERR_INVALID);
+    return size;
+}
+// m_prove_shard_tree for this side: the top's session begun, the join batch whose sink fills a join's tables for the top on the worker's thread the moment the join
+// exists, the top finished on ctx -- the bytes of zkhip_prove_machine_verifier over the same joins
+static int fri16_tree_prove(zkhip_ctx* ctx, const zkhip_machine_key* top_key, const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, const int* devices, int n_devices,
+                            const uint8_t* const* lift_proofs, const size_t* lens, size_t n_proofs, size_t J, const uint32_t* public_values, size_t n_public_total,
+                            const zkhip_params* join_prm, const uint32_t* join_vk, const zkhip_params* top_prm, int in_flight_per_device, uint8_t* joined, size_t joined_stride,
+                            size_t* joined_lens, uint8_t* out, size_t cap, size_t* len) {
+    const char* who = "prove_fri16_tree";
+    CHECK_CTX(ctx);
+    if (!top_key || !top_prm || !out || !len || !join_vk) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": null argument");
+    if (J == 0 || n_proofs == 0 || n_proofs % J != 0)
+        return fail(ZKHIP_ERR_INVALID, std::string(who) + ": the number of lift proofs must be a positive multiple of proofs_per_join, not " + std::to_string(n_proofs) +
+                                       " for joins of " + std::to_string(J) + " (the caller pads by repeating the last)");
+    if (joined_stride % 4 != 0) return fail(ZKHIP_ERR_INVALID, std::string(who) + ": joined_stride must be a multiple of 4");
+    const size_t n_joins = n_proofs / J;
+    TreeDesc t;
+    ZK_TRY(fri16_tree_desc(a, hw, lift_prm, J, join_prm, join_vk, who, t));
+    ZK_TRY(fri16_tree_check_public(t, n_joins, public_values, n_public_total, who));
+    if (!zk::mrec::m_machine_verifier_proof_size(&t.d, n_joins, top_prm)) return fri16_tree_refused(t, n_joins, who, ZKHIP_ERR_INVALID);
+    uint32_t made_vk[8];
+    return zk::mrec::m_prove_tree_top(ctx, top_key, &t.d, n_joins, public_values, top_prm, [&](const zk::mrec::JoinSink& on_join) -> int {
+        return fri16_join_batch(who, devices, n_devices, a, hw, lift_prm, lift_proofs, lens, n_proofs, J, public_values, n_public_total, join_prm, in_flight_per_device, 0, joined,
+                                joined_stride, joined_lens, made_vk, join_vk, &on_join);
+    }, out, cap, len);
+}
+static int fri16_tree_verify(const fri16::ShapeArgs& a, int hw, const zkhip_params* lift_prm, size_t J, const zkhip_params* join_prm, const uint32_t* join_vk, size_t n_joins,
+                             const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total, const uint32_t* top_vk, const zkhip_params* top_prm, int* reason) {
+    const char* who = "verify_fri16_tree";
+    TreeDesc t;
+    int rc = fri16_tree_desc(a, hw, lift_prm, J, join_prm, join_vk, who, t);
+    if (rc == ZKHIP_OK) rc = fri16_tree_check_public(t, n_joins, public_values, n_public_total, who);
+    if (rc != ZKHIP_OK) { if (reason) *reason = 1; return rc; }
+    int why = 0;
+    rc = zk::mrec::m_verify_machine_recursive(&t.d, proof, len, public_values, t.d.n_public, n_joins, top_vk, top_prm, &why);
+    if (reason) *reason = why;
+    return rc != ZKHIP_OK && why == 1 ? fri16_tree_refused(t, n_joins, who, rc) : rc;      // (reason 1: the arguments, the number of joins among them)
 }
 
 extern "C" {
@@ -2666,6 +2866,44 @@ int zkhip_prove_fri16_join_segments(zkhip_ctx* ctx, const zkhip_machine_key* lif
                                     const zkhip_params* lift_prm, const zkhip_params* join_prm, uint8_t* out, size_t cap, size_t* len) {
     FRI16_JOIN_GUARD(fri16_join_segments(ctx, lift_key, join_key, segment_proofs, lens, n_proofs, log_n, width, public_values, n_public_total, inner_prm, lift_prm, join_prm, out, cap,
                                          len), ZKHIP_ERR_NOMEM)
+}
+// ---- several joins of one shape in one call, and the tree above them (the shape calls' bodies: fri16_join_batch, fri16_tree_* above)
+int zkhip_prove_fri16_join_batch(const int* devices, int n_devices, FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, const uint8_t* const* lift_proofs, const size_t* lens,
+                                 size_t n_proofs, size_t proofs_per_join, const uint32_t* public_values, size_t n_public_total, const zkhip_params* join_prm,
+                                 int in_flight_per_device, int verify, uint8_t* joined, size_t joined_stride, size_t* joined_lens, uint32_t vk[8]) {
+    FRI16_JOIN_GUARD(fri16_join_batch("prove_fri16_join_batch", devices, n_devices, FRI16_JOIN_ARGS, lift_prm, lift_proofs, lens, n_proofs, proofs_per_join, public_values,
+                                      n_public_total, join_prm, in_flight_per_device, verify, joined, joined_stride, joined_lens, vk, nullptr, nullptr), ZKHIP_ERR_NOMEM)
+}
+size_t zkhip_fri16_tree_max_join(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, const zkhip_params* join_prm) {
+    FRI16_JOIN_GUARD(fri16_tree_max_join(FRI16_JOIN_ARGS, lift_prm, join_prm), 0)
+}
+size_t zkhip_fri16_tree_max_joins(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm) {
+    FRI16_JOIN_GUARD(fri16_tree_max_joins(FRI16_JOIN_ARGS, lift_prm, proofs_per_join, join_prm), 0)
+}
+int zkhip_fri16_tree_key_host(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                              const zkhip_params* top_prm, uint32_t vk[8]) {
+    FRI16_JOIN_GUARD(fri16_tree_key_host(FRI16_JOIN_ARGS, lift_prm, proofs_per_join, join_prm, join_vk, n_joins, top_prm, vk), ZKHIP_ERR_NOMEM)
+}
+int zkhip_fri16_tree_setup(zkhip_ctx* ctx, FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8],
+                           size_t n_joins, const zkhip_params* top_prm, zkhip_machine_key** key, uint32_t vk[8]) {
+    FRI16_JOIN_GUARD(fri16_tree_setup(ctx, FRI16_JOIN_ARGS, lift_prm, proofs_per_join, join_prm, join_vk, n_joins, top_prm, key, vk), ZKHIP_ERR_NOMEM)
+}
+size_t zkhip_fri16_tree_proof_size(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                                   const zkhip_params* top_prm) {
+    FRI16_JOIN_GUARD(fri16_tree_proof_size(FRI16_JOIN_ARGS, lift_prm, proofs_per_join, join_prm, join_vk, n_joins, top_prm), 0)
+}
+int zkhip_prove_fri16_tree(zkhip_ctx* ctx, const zkhip_machine_key* top_key, FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, const int* devices, int n_devices,
+                           const uint8_t* const* lift_proofs, const size_t* lens, size_t n_proofs, size_t proofs_per_join, const uint32_t* public_values, size_t n_public_total,
+                           const zkhip_params* join_prm, const uint32_t join_vk[8], const zkhip_params* top_prm, int in_flight_per_device, uint8_t* joined, size_t joined_stride,
+                           size_t* joined_lens, uint8_t* out, size_t cap, size_t* len) {
+    FRI16_JOIN_GUARD(fri16_tree_prove(ctx, top_key, FRI16_JOIN_ARGS, lift_prm, devices, n_devices, lift_proofs, lens, n_proofs, proofs_per_join, public_values, n_public_total,
+                                      join_prm, join_vk, top_prm, in_flight_per_device, joined, joined_stride, joined_lens, out, cap, len), ZKHIP_ERR_NOMEM)
+}
+int zkhip_verify_fri16_tree(FRI16_JOIN_SHAPE, const zkhip_params* lift_prm, size_t proofs_per_join, const zkhip_params* join_prm, const uint32_t join_vk[8], size_t n_joins,
+                            const uint8_t* proof, size_t len, const uint32_t* public_values, size_t n_public_total, const uint32_t top_vk[8], const zkhip_params* top_prm,
+                            int* reason) {
+    FRI16_JOIN_GUARD(fri16_tree_verify(FRI16_JOIN_ARGS, lift_prm, proofs_per_join, join_prm, join_vk, n_joins, proof, len, public_values, n_public_total, top_vk, top_prm, reason),
+                     ZKHIP_ERR_NOMEM)
 }
 #undef FRI16_JOIN_SHAPE
 #undef FRI16_JOIN_ARGS

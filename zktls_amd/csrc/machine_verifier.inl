@@ -253,8 +253,9 @@ int make_mshape(const zkhip_machine_desc* d, size_t n_proofs, MShape& s) {
     if (s.terms.size() > ((size_t)1 << 20) || (size_t)s.NP * s.terms.size() > ((size_t)1 << MAX_LOG_ROWS))
         return fail(ZKHIP_ERR_INVALID, "machine verifier: too many program terms for the EVAL chip");
     if ((uint64_t)s.NP * s.KSPAN >= P / 2 || (uint64_t)s.NP * 32 * PWSPAN >= P / 2 || s.NV >= PWSPAN) return fail(ZKHIP_ERR_INVALID, "machine verifier: key space");
-    // the transcript table: one indicator column per (proof, sponge row with public values)
-    if (64u + (size_t)s.NP * s.pub_rows.size() > 1024) return fail(ZKHIP_ERR_INVALID, "machine verifier: too many proofs x public values for the transcript table");
+    // the transcript table: one indicator column per (proof, sponge row with public values) beside its 53 fixed preprocessed columns (ts_cols), rounded up to a multiple
+    // of four, and its TS_MAIN = 24 main ones -- within the 1024 columns a chip of a keyed machine may have
+    if (((53u + (size_t)s.NP * s.pub_rows.size() + 3u) & ~(size_t)3) + 24u > 1024) return fail(ZKHIP_ERR_INVALID, "machine verifier: too many proofs x public values for the transcript table");
     s.id = {(uint64_t)C, (uint64_t)s.Q, (uint64_t)s.PB, (uint64_t)s.NPUB, (uint64_t)s.NP};
     for (uint32_t v : s.head) s.id.push_back(v);
     return ZKHIP_OK;
@@ -1677,7 +1678,8 @@ int fill_proof(const Machine& m, int p, const uint8_t* inner, size_t inner_len, 
             }
             return 0;
         };
-        const int nth = sh.NP >= 16 ? 1 : 16 / sh.NP;
+        int nth = sh.NP >= 16 ? 1 : 16 / sh.NP;
+        if (t_query_threads_cap > 0 && nth > t_query_threads_cap) nth = t_query_threads_cap;      // (a caller that is itself one of many workers: the joins of a batch)
         if (x16) {
             for (int q = 0; q < Q; q++) qerr[(size_t)q] = fri_q(q);          // (the fold rows and the pairs: field arithmetic only)
             const int ng = (Q + 15) / 16;
@@ -2030,6 +2032,7 @@ int top_begin(const zkhip_machine_desc* inner, size_t n_proofs, size_t n_public,
         if (!tabs[c]->reset((size_t)m.km.w_main[c] << m.km.height[c])) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory for the machine's tables");
     }
     if (!s.device) for (size_t r = 0; r < ((size_t)1 << m.km.height[C_FOLD]); r++) ht.fold.data()[(size_t)m.km.w_main[C_FOLD] * r + frichip::T] = MONTY_R1;      // (the fold chip's padding rows: T = 1)
+    s.proof_len = proof_pos(sh).words * 4;                   // (the shape fixes it, and the fills run on several threads: set once, here; fill_proof refuses any other length)
     s.used = (size_t)sh.NP * sh.p2_rows;
     const size_t walked = s.device ? (size_t)sh.NP * (size_t)sh.NT : s.used;                          // Poseidon2 rows whose input states the host walks
     if (!ht.p2_in.reset(16 * walked) || !ht.p2_bit.reset(walked) || !ht.p2_kp.reset(walked)) return fail(ZKHIP_ERR_NOMEM, "prove_machine_verifier: no host memory");
@@ -2040,7 +2043,6 @@ int top_fill(TopSession& s, int p, const uint8_t* proof, size_t proof_len, const
     try {
         if (!proof) return fail(ZKHIP_ERR_INVALID, "prove_machine_verifier: null proof");
         if (s.device) {
-            if (s.proof_len == 0) s.proof_len = proof_len;                 // (every proof of one machine has one length: fill_proof checks it)
             s.ptrs[(size_t)p] = proof;
             return fill_proof(*s.mp, p, proof, proof_len, pubs, s.ht, &s.plan, &s.vals[(size_t)p], s.transcripts.empty() ? nullptr : &s.transcripts[(size_t)p]);
         }
@@ -2069,7 +2071,8 @@ void top_transcripts(TopSession& s, const uint8_t* const* proofs, const size_t* 
         try { if (n) walk_transcripts_x16(sh, n, ws, pubss, ps, stride, s.ht, out); } catch (...) { for (int i = 0; i < n; i++) out[i]->done = false; }
     };
     if (ng <= 1) { if (ng) group(0); return; }
-    HostPool pool(ng < 8 ? ng : 8);
+    const int gthr = t_query_threads_cap > 0 && t_query_threads_cap < 8 ? t_query_threads_cap : 8;
+    HostPool pool(ng < gthr ? ng : gthr);
     for (int g = 0; g < ng; g++) pool.submit([&group, g] { group(g); });
     pool.wait();
 }
@@ -2144,7 +2147,8 @@ int top_finish(zkhip_ctx* ctx, const zkhip_machine_key* key, TopSession& s, cons
         ZK_TRY(ctx_host_pinned(ctx, NPs * s.proof_len + up_bytes, &hpin));
         uint8_t* hp = (uint8_t*)hpin;
         {   // the proofs into the pinned block side by side (a few threads: 60 MB for 64 transcript proofs), the small block behind them
-            const int nthr = NP < 8 ? NP : 8;
+            int nthr = NP < 8 ? NP : 8;
+            if (t_query_threads_cap > 0 && nthr > t_query_threads_cap) nthr = t_query_threads_cap;
             if (nthr <= 1) for (int p = 0; p < NP; p++) std::memcpy(hp + (size_t)p * s.proof_len, s.ptrs[(size_t)p], s.proof_len);
             else {
                 HostPool pool(nthr);
@@ -2274,7 +2278,12 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
     {
         std::vector<int> rcs((size_t)NP, ZKHIP_OK);
         std::vector<std::string> msgs((size_t)NP);
+        // the host threads of this call: sixteen, or what a caller that runs several of these side by side leaves it (t_query_threads_cap: zkhip_prove_fri16_join_batch)
+        const int budget = t_query_threads_cap > 0 ? (t_query_threads_cap < 16 ? t_query_threads_cap : 16) : 0;
+        const int fillers = budget ? (NP < budget ? NP : budget) : (NP < 16 ? NP : 16);
         auto one = [&](int p) {
+            const int cap_before = t_query_threads_cap;
+            if (budget) t_query_threads_cap = budget / fillers;           // (a pool thread's own cap: what one fill may start)
 #ifdef ZKHIP_AB_HOOKS
             const auto tv = std::chrono::steady_clock::now();
 #endif
@@ -2284,10 +2293,11 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
 #endif
             rcs[(size_t)p] = r;
             if (r != ZKHIP_OK) msgs[(size_t)p] = zkhip_last_error();
+            t_query_threads_cap = cap_before;
         };
         if (NP == 1) one(0);
         else {
-            HostPool pool(NP < 16 ? NP : 16);
+            HostPool pool(fillers);
             for (int p = 0; p < NP; p++) pool.submit([&one, p] { one(p); });
             pool.wait();
         }
@@ -2295,6 +2305,21 @@ int m_prove_machine_verifier(zkhip_ctx* ctx, const zkhip_machine_key* key, const
     }
     lap("host: verify + witnesses + tables");
     const int prc = top_finish(ctx, key, s, public_values, n_public, outer, proof, cap, len, lap);
+    s.ht.release_later();
+    return prc;
+}
+
+// The top of a tree over joins that the caller makes: begin, then `run_joins`, which hands every join to the sink it is given the moment the join exists (on
+// whichever thread made it: the sink fills that join's tables for the top), then finish on ctx.  public_values: the joins' own, join after join.
+using JoinSink = std::function<int(size_t, const uint8_t*, size_t)>;
+int m_prove_tree_top(zkhip_ctx* ctx, const zkhip_machine_key* top_key, const zkhip_machine_desc* join_machine, size_t n_joins, const uint32_t* public_values,
+                     const zkhip_params* top_outer, const std::function<int(const JoinSink&)>& run_joins, uint8_t* proof, size_t cap, size_t* len) {
+    const size_t jpub = join_machine->n_public;
+    TopSession s;
+    ZK_TRY(top_begin(join_machine, n_joins, jpub, s));
+    const JoinSink on_join = [&](size_t j, const uint8_t* jp, size_t jl) { return top_fill(s, (int)j, jp, jl, public_values + j * jpub); };
+    ZK_TRY(run_joins(on_join));
+    const int prc = top_finish(ctx, top_key, s, public_values, jpub, top_outer, proof, cap, len, [](const char*) {});
     s.ht.release_later();
     return prc;
 }
@@ -2312,17 +2337,31 @@ int m_prove_shard_tree(zkhip_ctx* ctx, const zkhip_machine_key* top_key, const z
     if (joined_stride % 4 != 0) return fail(ZKHIP_ERR_INVALID, "prove_shard_tree: joined_stride must be a multiple of 4");
     const size_t J = proofs_per_join, n_joins = n_proofs / J, jpub = J * n_public;
     if (join_machine->n_public != jpub) return fail(ZKHIP_ERR_INVALID, "prove_shard_tree: the join machine's public values are not proofs_per_join x n_public");
-    TopSession s;
-    ZK_TRY(top_begin(join_machine, n_joins, jpub, s));
-    const std::function<int(size_t, const uint8_t*, size_t)> on_join = [&](size_t j, const uint8_t* jp, size_t jl) {
-        return top_fill(s, (int)j, jp, jl, public_values + j * jpub);
-    };
-    ZK_TRY(sv_prove_batch(devices, n_devices, shard_proofs, shard_proof_lens, n_proofs, J, log_n, width, public_values, n_public, inner, join_outer, in_flight_per_device, 0,
-                          joined, joined_stride, joined_lens, join_vk, &on_join));
-    if (std::memcmp(join_vk, join_machine->key_root, 32) != 0) return fail(ZKHIP_ERR_INVALID, "prove_shard_tree: the join machine's key is not the key of this shape");
-    const int prc = top_finish(ctx, top_key, s, public_values, jpub, top_outer, proof, cap, len, [](const char*) {});
-    s.ht.release_later();
-    return prc;
+    return m_prove_tree_top(ctx, top_key, join_machine, n_joins, public_values, top_outer, [&](const JoinSink& on_join) -> int {
+        ZK_TRY(sv_prove_batch(devices, n_devices, shard_proofs, shard_proof_lens, n_proofs, J, log_n, width, public_values, n_public, inner, join_outer, in_flight_per_device, 0,
+                              joined, joined_stride, joined_lens, join_vk, &on_join));
+        if (std::memcmp(join_vk, join_machine->key_root, 32) != 0) return fail(ZKHIP_ERR_INVALID, "prove_shard_tree: the join machine's key is not the key of this shape");
+        return ZKHIP_OK;
+    }, proof, cap, len);
+}
+
+// the machine-mode machine over (inner, n_proofs) AS a description, for the level above it: its ten chips in machine order, `key_root` (what
+// zkhip_machine_verifier_key_host / _setup return for it under `outer`) as the key, outer's queries and proof-of-work bits, n_proofs x inner->n_public public
+// values.  d points into what `keep` holds.
+int m_machine_verifier_self_desc(const zkhip_machine_desc* inner, size_t n_proofs, const zkhip_params* outer, const uint32_t key_root[8], std::shared_ptr<const void>& keep,
+                                 zkhip_machine_desc& d) {
+    if (!outer || !key_root) return fail(ZKHIP_ERR_INVALID, "machine verifier: null argument");
+    int rc = ZKHIP_OK;
+    const auto mp = machine_of(inner, n_proofs, &rc);
+    if (!mp) return rc;
+    keep = mp;
+    const keyed::KeyedMachine& km = mp->km;
+    d = zkhip_machine_desc{};
+    d.n_chips = km.n; d.log_ns = km.log_ns; d.widths = km.widths; d.pre_widths = km.pre_widths;
+    d.programs = km.progs; d.program_words = km.prog_words; d.tables = km.tabs; d.table_words = km.tab_words;
+    std::memcpy(d.key_root, key_root, 32);
+    d.num_queries = outer->num_queries; d.pow_bits = outer->pow_bits; d.n_public = mp->sh.npub_total();
+    return ZKHIP_OK;
 }
 
 // the machine's MAIN traces as the prover fills them on the host, for tests without a device: chip at position `which` (tallest first), canonical words,

@@ -992,6 +992,44 @@ class Context:
                                                        C.byref(inner_params), C.byref(lift_params), C.byref(params), buf.ctypes.data_as(u8p), size, C.byref(got)))
         return buf[: got.value]
 
+    # ---- the TREE above the join: more lift proofs than one join takes -> joins -> one proof
+    def fri16_tree_setup(self, R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params=None, join_params=None, params=None, hash_width=24):
+        """zkhip_fri16_tree_setup: the key of the top that verifies n_joins joins of proofs_per_join lift proofs each; join_vk: fri16_join_key_host's (or
+        fri16_join_setup's root) for that join size -> MachineKey"""
+        lift_params, join_params, params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16), params or Params(1, 100, 16)
+        handle, root = C.c_void_p(), np.zeros(8, dtype=np.uint32)
+        jvk = np.ascontiguousarray(np.array(join_vk, dtype=np.uint32))
+        check(self.lib.zkhip_fri16_tree_setup(self.handle, R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), proofs_per_join, C.byref(join_params),
+                                              jvk.ctypes.data_as(u32p), n_joins, C.byref(params), C.byref(handle), root.ctypes.data_as(u32p)))
+        return MachineKey(self, handle, root, None)
+
+    def prove_fri16_tree(self, top_key, R, F, log_blowup, n_queries, pow_bits, W, NP, lift_proofs, proofs_per_join, public_values, join_vk, lift_params=None, join_params=None,
+                         params=None, devices=None, in_flight=4, hash_width=24):
+        """zkhip_prove_fri16_tree: lift proofs of ONE shape -> joins of proofs_per_join (in flight, dealt over `devices`) -> ONE proof over the joins on this context
+        -> (top proof bytes, [join proof bytes, ...]); public_values: one list of NP words per lift proof.  len(lift_proofs) must be a positive multiple of
+        proofs_per_join (the caller pads by repeating the last)"""
+        lift_params, join_params, params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16), params or Params(1, 100, 16)
+        sps = [np.ascontiguousarray(sp, dtype=np.uint8) for sp in lift_proofs]
+        n = len(sps)
+        pv = np.ascontiguousarray(np.array([int(x) for v in public_values for x in v] or [0], dtype=np.uint32))
+        n_pub = sum(len(v) for v in public_values)
+        jvk = np.ascontiguousarray(np.array(join_vk, dtype=np.uint32))
+        shape = (R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params))
+        n_joins = n // proofs_per_join if proofs_per_join else 0
+        jsize = self.lib.zkhip_fri16_join_proof_size(*shape, max(proofs_per_join, 1), C.byref(join_params))
+        tsize = self.lib.zkhip_fri16_tree_proof_size(*shape, proofs_per_join, C.byref(join_params), jvk.ctypes.data_as(u32p), max(n_joins, 1), C.byref(params))
+        jbuf = np.empty((max(n_joins, 1), max(jsize, 4)), dtype=np.uint8)
+        jlens = (C.c_size_t * max(n_joins, 1))()
+        ptrs = (u8p * max(n, 1))(*[sp.ctypes.data_as(u8p) for sp in sps])
+        lens = (C.c_size_t * max(n, 1))(*[sp.size for sp in sps])
+        top = np.empty(max(tsize, 1), dtype=np.uint8)
+        got = C.c_size_t(0)
+        devs = (C.c_int * len(devices))(*devices) if devices else None
+        check(self.lib.zkhip_prove_fri16_tree(self.handle, top_key.handle if top_key is not None else None, *shape, devs, len(devices) if devices else 0, ptrs, lens, n,
+                                              proofs_per_join, pv.ctypes.data_as(u32p), n_pub, C.byref(join_params), jvk.ctypes.data_as(u32p), C.byref(params), in_flight,
+                                              jbuf.ctypes.data_as(u8p), jbuf.shape[1], jlens, top.ctypes.data_as(u8p), tsize, C.byref(got)))
+        return top[: got.value], [jbuf[j, : jlens[j]] for j in range(n_joins)]
+
     def machine_verifier_gen_eval_rows(self, chips, coeffs, keys, firsts, n_chips, values, alphas, n_stream):
         """zkhip_machine_verifier_gen_eval_rows: machine mode's EVAL row kernel alone, one launch.  chips / coeffs / firsts [n_terms], keys [n_terms][3], values
         [n_proofs][kspan][4] and alphas [n_proofs][4] canonical; keys 1 .. n_stream are read as a proof's opened-value stream, the rest as the call's small block
@@ -2085,6 +2123,80 @@ def verify_fri16_join(proof, public_values, R, F, log_blowup, n_queries, pow_bit
     reason = C.c_int(0)
     rc = _lib.load().zkhip_verify_fri16_join(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), pr.ctypes.data_as(u8p), pr.size,
                                              pv.ctypes.data_as(u32p), len(flat), n_proofs, k.ctypes.data_as(u32p), C.byref(params), C.byref(reason))
+    return rc, reason.value
+
+
+def prove_fri16_join_batch(lift_proofs, proofs_per_join, public_values, R, F, log_blowup, n_queries, pow_bits, W, NP, lift_params=None, params=None, devices=None, in_flight=4,
+                           verify=False, hash_width=24):
+    """zkhip_prove_fri16_join_batch: len(lift_proofs) / proofs_per_join joins of one shape, dealt over `devices`, `in_flight` at a time on each
+    -> ([join proof bytes, ...], vk [8]); public_values: one list of NP words per lift proof.  Every join is prove_fri16_join's bytes on the same inputs"""
+    lib = _lib.load()
+    lift_params, params = lift_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    sps = [np.ascontiguousarray(sp, dtype=np.uint8) for sp in lift_proofs]
+    n = len(sps)
+    pv = np.ascontiguousarray(np.array([int(x) for v in public_values for x in v] or [0], dtype=np.uint32))
+    n_pub = sum(len(v) for v in public_values)
+    shape = (R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params))
+    size = lib.zkhip_fri16_join_proof_size(*shape, max(proofs_per_join, 1), C.byref(params))
+    n_joins = n // proofs_per_join if proofs_per_join else 0
+    buf = np.empty((max(n_joins, 1), max(size, 4)), dtype=np.uint8)
+    lens = (C.c_size_t * max(n_joins, 1))()
+    ptrs = (u8p * max(n, 1))(*[sp.ctypes.data_as(u8p) for sp in sps])
+    plens = (C.c_size_t * max(n, 1))(*[sp.size for sp in sps])
+    vk = np.zeros(8, dtype=np.uint32)
+    devs = (C.c_int * len(devices))(*devices) if devices else None
+    check(lib.zkhip_prove_fri16_join_batch(devs, len(devices) if devices else 0, *shape, ptrs, plens, n, proofs_per_join, pv.ctypes.data_as(u32p), n_pub, C.byref(params), in_flight,
+                                           1 if verify else 0, buf.ctypes.data_as(u8p), buf.shape[1], lens, vk.ctypes.data_as(u32p)))
+    return [buf[j, : lens[j]] for j in range(n_joins)], vk
+
+
+def fri16_tree_max_join(R, F, log_blowup, n_queries, pow_bits, W, NP, lift_params=None, join_params=None, hash_width=24):
+    """zkhip_fri16_tree_max_join: the largest join size whose join machine a top takes; 0 if none (last_error says why)"""
+    lift_params, join_params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16)
+    return int(_lib.load().zkhip_fri16_tree_max_join(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), C.byref(join_params)))
+
+
+def fri16_tree_max_joins(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, lift_params=None, join_params=None, hash_width=24):
+    """zkhip_fri16_tree_max_joins: the most joins of proofs_per_join lift proofs one top takes; 0 if none (last_error says why)"""
+    lift_params, join_params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16)
+    return int(_lib.load().zkhip_fri16_tree_max_joins(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), proofs_per_join, C.byref(join_params)))
+
+
+def _fri16_tree_shape(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params, join_params, params, hash_width):
+    jvk = np.ascontiguousarray(np.array(join_vk, dtype=np.uint32))
+    return jvk, (R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), proofs_per_join, C.byref(join_params), jvk.ctypes.data_as(u32p), n_joins,
+                 C.byref(params))
+
+
+def fri16_tree_key_host(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params=None, join_params=None, params=None, hash_width=24):
+    """zkhip_fri16_tree_key_host: the top's key of (lift shape, lift parameters, join size, join parameters, the joins' key, n_joins, top parameters), without a GPU"""
+    lift_params, join_params, params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    _, shape = _fri16_tree_shape(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params, join_params, params, hash_width)
+    vk = np.zeros(8, dtype=np.uint32)
+    check(_lib.load().zkhip_fri16_tree_key_host(*shape, vk.ctypes.data_as(u32p)))
+    return vk
+
+
+def fri16_tree_proof_size(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params=None, join_params=None, params=None, hash_width=24):
+    lift_params, join_params, params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    _, shape = _fri16_tree_shape(R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, lift_params, join_params, params, hash_width)
+    return int(_lib.load().zkhip_fri16_tree_proof_size(*shape))
+
+
+def verify_fri16_tree(proof, public_values, R, F, log_blowup, n_queries, pow_bits, W, NP, proofs_per_join, join_vk, n_joins, top_vk, lift_params=None, join_params=None,
+                      params=None, hash_width=24):
+    """zkhip_verify_fri16_tree: the top proof against (lift shape, join size, the joins' key, n_joins, every segment's public values in order -- one list per segment --,
+    the top's key) -> (rc, reason); host only, no byte of a segment, lift or join proof"""
+    lift_params, join_params, params = lift_params or Params(1, 100, 16), join_params or Params(1, 100, 16), params or Params(1, 100, 16)
+    pr = np.ascontiguousarray(proof, dtype=np.uint8)
+    flat = [int(x) for v in public_values for x in v]
+    pv = np.ascontiguousarray(np.array(flat or [0], dtype=np.uint32))
+    jvk = np.ascontiguousarray(np.array(join_vk, dtype=np.uint32))
+    k = np.ascontiguousarray(np.array(top_vk, dtype=np.uint32))
+    reason = C.c_int(0)
+    rc = _lib.load().zkhip_verify_fri16_tree(R, F, log_blowup, n_queries, hash_width, pow_bits, W, NP, C.byref(lift_params), proofs_per_join, C.byref(join_params),
+                                             jvk.ctypes.data_as(u32p), n_joins, pr.ctypes.data_as(u8p), pr.size, pv.ctypes.data_as(u32p), len(flat), k.ctypes.data_as(u32p),
+                                             C.byref(params), C.byref(reason))
     return rc, reason.value
 
 

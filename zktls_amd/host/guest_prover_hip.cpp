@@ -332,15 +332,99 @@ zkhip_params segment_params(const ShardPlan& plan) {
     return zkhip_params{2, defaults ? 50 : plan.num_queries, defaults ? 0 : plan.pow_bits, 0, 4, lf, 24, 0};
 }
 }  // namespace
+// lift proofs per join for `plan` on the RISC Zero side: the plan's segments while ONE join takes them and set_compress_join_size is not below their number (everything
+// as without a tree); else equal joins of at most min(zkhip_fri16_tree_max_join, the cap) under ONE top.  0: no top takes a join of this shape (zkhip_last_error)
+uint32_t r0_join_size(const ShardPlan& plan) {
+    const uint32_t shards = plan.shards ? plan.shards : 1u;
+    const SegmentShape sh = segment_shape(plan, segment_params(plan));
+    const uint32_t most = (uint32_t)zkhip_fri16_join_max_proofs(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer);
+    const uint32_t cap = g_join_size.load();
+    if (most == 0 || (shards <= most && (cap == 0 || cap >= shards))) return shards;      // (a shape the lift refuses: the join itself says so)
+    uint32_t j0 = (uint32_t)zkhip_fri16_tree_max_join(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, &sh.outer);
+    if (j0 == 0) return 0;
+    if (cap && cap < j0) j0 = cap;
+    const uint32_t joins = (shards + j0 - 1u) / j0;
+    return (shards + joins - 1u) / joins;
+}
+// more segments than one join takes (or a smaller join size asked for): THE TREE -- the lifts in one call over the prover's devices, then zkhip_prove_fri16_tree: joins
+// of J dealt over the devices, four in flight on each, the last one repeating the last segment's lift proof and public values (one shape, one key), and ONE proof over
+// the joins.  The blob: entry 0 = the top, entry 1 = the JOINS' key + the segment count; whoever checks it derives the top's key from (plan, that key).
+static std::vector<uint8_t> join_segments_tree(const std::vector<int>& devices, const ShardPlan& plan, const zkhip_params& prm, const std::vector<uint32_t>& digest,
+                                               const std::vector<std::vector<uint8_t>>& proofs, uint32_t J) {
+    const SegmentShape sh = segment_shape(plan, prm);
+    const size_t n = plan.shards, n_joins = (n + J - 1) / J, padded = n_joins * J;
+    const size_t most = zkhip_fri16_tree_max_joins(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer);
+    if (most == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error());
+    if (n_joins > most)
+        throw std::runtime_error("with_compress: " + std::to_string(n) + " segments need " + std::to_string(n_joins) + " joins of " + std::to_string(J) +
+                                 " lift proofs; one top takes at most " + std::to_string(most) + " (zkhip_fri16_tree_max_joins; a third tree level is not built)");
+    std::vector<uint32_t> pvs;
+    for (size_t s = 0; s < padded; s++) {
+        pvs.insert(pvs.end(), digest.begin(), digest.end());
+        pvs.push_back((uint32_t)(s < n ? s : n - 1));
+    }
+    const size_t room = zkhip_fri16_lift_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.pb, sh.W, 9, &sh.outer);
+    std::vector<std::vector<uint8_t>> lifted(n, std::vector<uint8_t>(room));
+    std::vector<zkhip_fri16_lift_job> jobs(n);
+    for (size_t s = 0; s < n; s++) jobs[s] = zkhip_fri16_lift_job{proofs[s].data(), proofs[s].size(), pvs.data() + 9 * s, lifted[s].data(), room, 0, 0};
+    uint32_t lift_vk[8];
+    if (zkhip_prove_fri16_lift_batch(devices.data(), (int)devices.size(), jobs.data(), (int)n, plan.log_n, plan.width, 9, &prm, &sh.outer, 0, 0, lift_vk) != ZKHIP_OK)
+        fail_zkhip("zkhip_prove_fri16_lift_batch");
+    std::vector<const uint8_t*> ptrs(padded);
+    std::vector<size_t> lens(padded);
+    for (size_t s = 0; s < padded; s++) { const size_t k = s < n ? s : n - 1; ptrs[s] = lifted[k].data(); lens[s] = jobs[k].proof_len; }
+    // the top's context and key (the joins' own keys stay with the library's pooled contexts); the joins' key comes from a setup on this context
+    struct TopGuard {
+        zkhip_ctx* ctx = nullptr; zkhip_machine_key* jkey = nullptr; zkhip_machine_key* tkey = nullptr;
+        ~TopGuard() {
+            if (!ctx) return;
+            (void)zkhip_ctx_sync(ctx);
+            if (jkey) zkhip_machine_key_destroy(jkey);
+            if (tkey) zkhip_machine_key_destroy(tkey);
+            zkhip_ctx_destroy(ctx);
+        }
+    } g;
+    if (zkhip_ctx_create(devices[0], nullptr, &g.ctx) != ZKHIP_OK) { g.ctx = nullptr; fail_zkhip("zkhip_ctx_create"); }
+    uint32_t jvk[8], tvk[8];
+    if (zkhip_fri16_join_setup(g.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, &g.jkey, jvk) != ZKHIP_OK) { g.jkey = nullptr; fail_zkhip("zkhip_fri16_join_setup"); }
+    if (zkhip_fri16_tree_setup(g.ctx, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, jvk, n_joins, &sh.outer, &g.tkey, tvk) != ZKHIP_OK) {
+        g.tkey = nullptr;
+        fail_zkhip("zkhip_fri16_tree_setup");
+    }
+    const size_t jcap = zkhip_fri16_join_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer);
+    const size_t tcap = zkhip_fri16_tree_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, jvk, n_joins, &sh.outer);
+    if (jcap == 0 || tcap == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error());
+    std::vector<uint8_t> joined(n_joins * jcap), top(tcap);
+    std::vector<size_t> jlens(n_joins);
+    size_t tlen = 0;
+    if (zkhip_prove_fri16_tree(g.ctx, g.tkey, sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, devices.data(), (int)devices.size(), ptrs.data(), lens.data(), padded, J,
+                               pvs.data(), pvs.size(), &sh.outer, jvk, &sh.outer, 0, joined.data(), jcap, jlens.data(), top.data(), tcap, &tlen) != ZKHIP_OK)
+        fail_zkhip("zkhip_prove_fri16_tree");
+    top.resize(tlen);
+    int reason = 0;
+    if (zkhip_verify_fri16_tree(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, jvk, n_joins, top.data(), tlen, pvs.data(), pvs.size(), tvk, &sh.outer,
+                                &reason) != ZKHIP_OK)
+        fail_zkhip("zkhip_verify_fri16_tree");          // sp1.rs:120: the prover checks its own proof
+    std::vector<uint8_t> tail(36);
+    std::memcpy(tail.data(), jvk, 32);
+    const uint32_t cnt = plan.shards;
+    std::memcpy(tail.data() + 32, &cnt, 4);
+    return pack_shard_proofs({std::move(top), tail}, BATCH_FLAG_SYNTHETIC | BATCH_FLAG_COMPRESSED | BATCH_FLAG_R0_JOINED | BATCH_FLAG_TREE);
+}
 // `proofs` = the plan's segment proofs, public values request digest | segment index: every one lifted under the shape's key, the lift proofs joined into ONE proof
 // (zkhip_prove_fri16_lift_batch, then zkhip_prove_fri16_join on a pooled context that keeps the join's key).  The blob: entry 0 = the joined proof, entry 1 = the join's key + the segment count.
-static std::vector<uint8_t> join_segment_proofs(int device, const ShardPlan& plan, const zkhip_params& prm, const std::vector<uint32_t>& digest,
+// A plan that one join does not take (r0_join_size below the segment count) goes through the tree above.
+static std::vector<uint8_t> join_segment_proofs(const std::vector<int>& devices, const ShardPlan& plan, const zkhip_params& prm, const std::vector<uint32_t>& digest,
                                                 const std::vector<std::vector<uint8_t>>& proofs) {
+    if (devices.empty()) throw std::runtime_error("device list is empty");
+    const int device = devices[0];
     const SegmentShape sh = segment_shape(plan, prm);
     const size_t n = plan.shards;
-    // (more segments than one join takes: the library's refusal names the bound; a tree above the join is not built)
+    const uint32_t J = r0_join_size(plan);
+    if (J == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error());
+    if (J < n) return join_segments_tree(devices, plan, prm, digest, proofs, J);
     const size_t cap = zkhip_fri16_join_proof_size(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, n, &sh.outer);
-    if (cap == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error() + " (a tree above the join is not built)");
+    if (cap == 0) throw std::runtime_error(std::string("with_compress: ") + zkhip_last_error());
     JoinGuard jg{JoinKey{device, plan.log_n, plan.width, plan.num_queries, plan.pow_bits, (uint32_t)n, nullptr, nullptr, {0}, zkhip_poseidon2_params_generation(), true}};
     JoinKey& jk = jg.jk;
     if (!take_join_key(device, plan, (uint32_t)n, &jk, true)) {
@@ -1215,7 +1299,7 @@ ProveResult HipGuestProver::prove_inner(const GuestInput& input, const std::vect
     if (failed.load()) throw std::runtime_error(first_error);
     if (compress_) {
         // SP1: core -> compress (the shard verifier machine); RISC Zero: segments -> lift -> join (prover.rs:88-93), on the first device
-        r.proof = backend_ == Backend::Sp1 ? compress_shard_proofs(devices_, plan_, prm, digest, proofs) : join_segment_proofs(devices_[0], plan_, prm, digest, proofs);
+        r.proof = backend_ == Backend::Sp1 ? compress_shard_proofs(devices_, plan_, prm, digest, proofs) : join_segment_proofs(devices_, plan_, prm, digest, proofs);
         r.ok = true;
         return r;
     }
@@ -1248,10 +1332,24 @@ int verify_compressed_blob(const std::vector<uint8_t>& blob, const ShardPlan& pl
     if (cnt != plan.shards || cnt == 0 || std::memcmp(entries.back().data(), key, 32) != 0) return -1;        // (the key is the CALLER's: the blob's copy is informative)
     if (flags & BATCH_FLAG_R0_JOINED) {
         // segments -> lift -> join: ONE proof, checked from (the segments' shape, their public values, the join's key) -- no byte of a segment or lift proof
-        if (entries.size() != 2 || (flags & BATCH_FLAG_TREE)) return -1;
+        if (entries.size() != 2) return -1;
         const SegmentShape sh = segment_shape(plan, segment_params(plan));
         const std::vector<uint32_t> dg = request_digest(cbor, elf);
         std::vector<uint32_t> pvs;
+        const uint32_t J = r0_join_size(plan);
+        if (J == 0 || ((flags & BATCH_FLAG_TREE) != 0) != (J < cnt)) return -1;       // (the plan says whether one join takes it: prover and verifier agree)
+        if (flags & BATCH_FLAG_TREE) {
+            // segments -> lift -> joins -> top: ONE proof; `key` is the JOINS' key, the top's is derived here from (plan, that key) on the host's cores
+            const uint32_t n_joins = (cnt + J - 1) / J;
+            uint32_t tvk[8];
+            if (zkhip_fri16_tree_key_host(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, key, n_joins, &sh.outer, tvk) != ZKHIP_OK) return -1;
+            for (uint32_t s = 0; s < n_joins * J; s++) { pvs.insert(pvs.end(), dg.begin(), dg.end()); pvs.push_back(s < cnt ? s : cnt - 1); }      // the last join repeats the last segment
+            int why = 0;
+            const int rc = zkhip_verify_fri16_tree(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, key, n_joins, entries[0].data(), entries[0].size(), pvs.data(),
+                                                   pvs.size(), tvk, &sh.outer, &why);
+            if (reason) *reason = why;
+            return rc == ZKHIP_OK ? 0 : -2;
+        }
         for (uint32_t s = 0; s < cnt; s++) { pvs.insert(pvs.end(), dg.begin(), dg.end()); pvs.push_back(s); }
         int why = 0;
         const int rc = zkhip_verify_fri16_join(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, entries[0].data(), entries[0].size(), pvs.data(), pvs.size(), cnt, key, &sh.outer, &why);
@@ -1311,7 +1409,8 @@ bool compress_key(int device, const ShardPlan& plan, uint32_t key_out[8], std::s
 // the same key on the host's cores: no context, no device (zkhip_shard_verifier_key_host) -- what a verifier without a GPU calls
 bool r0_join_key_host(const ShardPlan& plan, uint32_t key_out[8], std::string* error) {
     const SegmentShape sh = segment_shape(plan, segment_params(plan));
-    const bool ok = plan.shards && zkhip_fri16_join_key_host(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, plan.shards, &sh.outer, key_out) == ZKHIP_OK;
+    const uint32_t J = plan.shards ? r0_join_size(plan) : 0;      // (one join: the segments' number; a tree: the joins' size -- the blob carries the joins' key)
+    const bool ok = J && zkhip_fri16_join_key_host(sh.R, sh.F, sh.b, sh.Q, sh.hw, sh.pb, sh.W, 9, &sh.outer, J, &sh.outer, key_out) == ZKHIP_OK;
     if (!ok && error) *error = plan.shards ? zkhip_last_error() : "shard plan is empty";
     return ok;
 }
@@ -1473,13 +1572,14 @@ int zktls_guest_prove_r0(int device, int mode, const zktls_shard_plan* plan, con
     return guest_prove(zktls::Backend::Risc0, device, mode, plan, cbor, cbor_len, elf, elf_len, output, output_len, proof, proof_len, err, err_cap);
 }
 // ... with its compress stage behind it (Risc0HipGuestProver::with_compress; prover.rs:88-93: segments -> lift -> join): the blob carries ONE proof (flags
-// SYNTHETIC | COMPRESSED | R0_JOINED).  zktls_verify_compressed_blob checks it on the host from (plan, input, ELF, zktls_r0_join_key_host's key)
+// SYNTHETIC | COMPRESSED | R0_JOINED; with | TREE where one join does not take the plan or zktls_set_compress_join_size asks for smaller joins: the proof above
+// the joins).  zktls_verify_compressed_blob checks either on the host from (plan, input, ELF, zktls_r0_join_key_host's key)
 int zktls_guest_prove_r0_compressed(int device, int mode, const zktls_shard_plan* plan, const uint8_t* cbor, size_t cbor_len, const uint8_t* elf, size_t elf_len,
                                     uint8_t** output, size_t* output_len, uint8_t** proof, size_t* proof_len, char* err, size_t err_cap) {
     if (!plan) { if (err && err_cap) { std::strncpy(err, "compress needs a shard plan", err_cap - 1); err[err_cap - 1] = 0; } return -1; }
     return guest_prove(zktls::Backend::Risc0, device, mode, plan, cbor, cbor_len, elf, elf_len, output, output_len, proof, proof_len, err, err_cap, true);
 }
-// the join's key for the plan (its shape and segment count), on the host's cores: no device, no context
+// the join's key for the plan (its shape and r0_join_size(plan): the segment count, or under a tree the size of one join), on the host's cores: no device, no context
 int zktls_r0_join_key_host(const zktls_shard_plan* plan, uint32_t key[8], char* err, size_t err_cap) {
     if (!plan || !key) { if (err && err_cap) { std::strncpy(err, "the join's key needs a shard plan", err_cap - 1); err[err_cap - 1] = 0; } return -1; }
     zktls::ShardPlan sp;

@@ -131,8 +131,11 @@ public:
     // Backend::Risc0 (Risc0HipGuestProver): segments -> lift -> join (prover.rs:88-93) -- every segment proof is lifted under the shape's key and the lift proofs are
     // joined into ONE proof (zkhip_prove_fri16_lift_batch: the lifts side by side, the lift key with the library's pooled contexts; then zkhip_prove_fri16_join under
     // a join key made once per (shape, segment count) on a pooled context), checked
-    // with zkhip_verify_fri16_join like sp1.rs:120; blob flags SYNTHETIC | COMPRESSED | R0_JOINED.  More segments than zkhip_fri16_join_max_proofs are refused with a
-    // message that names the bound (a tree above the join is not built).  verify_compressed_blob checks the blob from (plan, input, ELF, r0_join_key_host's key).
+    // with zkhip_verify_fri16_join like sp1.rs:120; blob flags SYNTHETIC | COMPRESSED | R0_JOINED.  More segments than one join takes (zkhip_fri16_join_max_proofs), or a
+    // smaller join size asked for with set_compress_join_size: THE TREE -- equal joins of r0_join_size(plan) lift proofs, dealt over the prover's devices, and ONE proof
+    // above them (zkhip_prove_fri16_tree; blob flags ... | R0_JOINED | TREE, entry 0 = the top, entry 1 = the JOINS' key + the segment count).  More joins than one top
+    // takes (zkhip_fri16_tree_max_joins) are refused with a message that names the bound.  verify_compressed_blob checks either blob from (plan, input, ELF,
+    // r0_join_key_host's key), deriving the top's key itself.
     // With with_input_commitment() and an input beyond one chip proof (1 MiB): the chain of SHA-256 shard proofs becomes ONE proof the same way
     // (zkhip_prove_sha256_compressed; blob flags INPUT_SHA256 | CHAINED | COMPRESSED) -- verify_commitment_blob checks it from (output, blob) alone.
     HipGuestProver& with_compress() { compress_ = true; return *this; }
@@ -187,7 +190,7 @@ uint32_t compress_join_size(const ShardPlan& plan);
 // ... or fewer per join (0: the most): an execution then takes several joins, and ONE more proof verifies the joins (machine mode of the shard
 // verifier machine, csrc/machine_verifier.inl): the blob carries that proof alone and the flag TREE
 void set_compress_join_size(uint32_t shard_proofs_per_join);
-constexpr uint32_t BATCH_FLAG_TREE = 32u;            // with COMPRESSED: several joins were needed and were joined again: entry 0 = the ONE proof above them
+constexpr uint32_t BATCH_FLAG_TREE = 32u;            // with COMPRESSED: several joins were needed and were joined again: entry 0 = the ONE proof above them (with R0_JOINED: the last entry = the JOINS' key + the segment count)
 constexpr uint32_t BATCH_FLAG_MACHINE = 64u;         // with SYNTHETIC: every shard is a keyed-MACHINE proof (MachinePlan); with COMPRESSED the joins are machine-mode proofs and the last entry = the join's key (8 LE words) + the shard count
 constexpr uint32_t BATCH_FLAG_R0_JOINED = 128u;      // with SYNTHETIC | COMPRESSED: a joined r0 proof -- RISC Zero-shape segment proofs lifted and joined (entry 0; last entry = the join's key (8 LE words) + the segment count)
 constexpr uint32_t BATCH_FLAG_KEYED = 4u;            // with INPUT_SHA256: the proof is the keyed SHA-256 MACHINE's (chip + range table), checked against a vk
@@ -213,7 +216,12 @@ ProveResult compress_blob(int device, const ShardPlan& plan, const std::vector<u
 bool compress_key(int device, const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
 // the same key computed on the host's cores (no device, no context): a verifier that owns no GPU checks a compressed blob with this and verify_compressed_blob
 bool compress_key_host(const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
-// the key of the join over the plan's segments (Risc0HipGuestProver::with_compress), on the host: zkhip_fri16_join_key_host on the plan's lift shape and segment count
+// lift proofs per join for `plan` on the RISC Zero side: the plan's segment count while one join takes it and set_compress_join_size is not below it (no tree: blob and
+// bytes as without this function); else J0 = min(zkhip_fri16_tree_max_join, the cap), ceil(segments / J0) joins of equal size J = ceil(segments / joins), the last
+// one repeating the last segment's lift proof and public values.  0: no top takes a join of this shape (zkhip_last_error)
+uint32_t r0_join_size(const ShardPlan& plan);
+// the key of the join(s) over the plan's segments (Risc0HipGuestProver::with_compress), on the host: zkhip_fri16_join_key_host on the plan's lift shape and
+// r0_join_size(plan) -- under a tree the key of ONE join; the top's key is derived from it by verify_compressed_blob
 bool r0_join_key_host(const ShardPlan& plan, uint32_t key[8], std::string* error = nullptr);
 // A MACHINE blob against the request it was made for, on the host: vk = the 64 bytes setup() / prove() returned (the machine key's root + the program's
 // digest, which must be request_digest("", elf)).  Plain: every shard proof under (the plan's machine, digest | s, the key).  COMPRESSED: the join's key
