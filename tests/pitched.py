@@ -157,26 +157,26 @@ def _mats_vec(mats):
     return len(mats) >= 1 and all(w > 0 and w % 4 == 0 and ld % 4 == 0 and off % 4 == 0 for w, ld, off in mats)
 
 
-def hash_rows_form(height, mats):
-    """hash.hip launch_hash_rows"""
-    if height <= COOP_MAX_NODES:
+def hash_rows_form(height, mats, bound=COOP_MAX_NODES):
+    """hash.hip launch_hash_rows; bound: coop_max_nodes(), lower inside a lock-step batch (lockstep_forms.coop_bound)"""
+    if height <= bound:
         return "hash_rows16"
     if len(mats) == 1 and mats[0][0] % 4 == 0 and mats[0][1] % 4 == 0 and mats[0][2] % 4 == 0:
         return "vec"
     return "mvec" if _mats_vec(mats) else "generic"
 
 
-def merkle_commit_form(log_h, mats):
+def merkle_commit_form(log_h, mats, bound=COOP_MAX_NODES):
     """context.cpp op_merkle_commit: medium trees hash their leaves inside the subtree launch"""
     count = 1 << log_h
-    if COOP_TOP_NODES < count <= COOP_MAX_NODES:
+    if COOP_TOP_NODES < count <= bound:
         return "hash_sub16"
-    return hash_rows_form(count, mats)
+    return hash_rows_form(count, mats, bound)
 
 
-def inject_form(height, mats):
+def inject_form(height, mats, bound=COOP_MAX_NODES):
     """hash.hip compress_inject_ok (context.cpp op_merkle_commit_mixed): one launch per injection level, or level + hash_rows + inject"""
-    return "compress_inject_mvec" if height > COOP_MAX_NODES and _mats_vec(mats) else "level+" + hash_rows_form(height, mats) + "+inject"
+    return "compress_inject_mvec" if height > bound and _mats_vec(mats) else "level+" + hash_rows_form(height, mats, bound) + "+inject"
 
 
 def quotient_form(log_n, width):

@@ -1122,9 +1122,9 @@ class Context:
                 for k, _ in ProveDebug._fields_}
 
 
-def prove_shards(traces, log_n, width, public_values_list, params=None, device=0, in_flight=4, host=False):
-    """zkhip_prove_shards: `traces` are DeviceBuffers (Montgomery, dense) or, with host=True, numpy arrays of canonical words.
-    Returns the list of proofs (numpy uint8 arrays)."""
+def prove_shards(traces, log_n, width, public_values_list, params=None, device=0, in_flight=4, host=False, lds=None):
+    """zkhip_prove_shards: `traces` are DeviceBuffers or DeviceViews (Montgomery; dense, or with lds[i] the row pitch of job i in words)
+    or, with host=True, numpy arrays of canonical words (dense).  Returns the list of proofs (numpy uint8 arrays)."""
     lib = _lib.load()
     params = params or Params(1, 100, 16, 0)
     n = len(traces)
@@ -1141,7 +1141,7 @@ def prove_shards(traces, log_n, width, public_values_list, params=None, device=0
         else:
             ptr = t.ptr
         pvs.append(pva); bufs.append(buf)
-        jobs[i].trace = ptr; jobs[i].ld = width; jobs[i].log_n = log_n; jobs[i].width = width
+        jobs[i].trace = ptr; jobs[i].ld = int(lds[i]) if lds is not None else width; jobs[i].log_n = log_n; jobs[i].width = width
         jobs[i].public_values = pva.ctypes.data_as(u32p); jobs[i].n_public = pva.size
         jobs[i].proof = buf.ctypes.data_as(u8p); jobs[i].proof_cap = size
     check(lib.zkhip_prove_shards(int(device), jobs, n, C.byref(params), int(in_flight), 1 if host else 0))
